@@ -10,9 +10,11 @@ A step = noising -> DiT forward -> MSE loss -> backward (incl. the per-group all
 reduce-scatter when N > 1) -> muP-AdamW step -> LR-schedule step, on one batch of synthetic
 OpenVid-shaped latents already resident in HBM.  Weak scaling: the per-GPU batch is fixed.
 
-Prints ONE JSON line on rank 0 (metric, value = whole-job samples/s, ms_per_step, roofline of the
-dominant kernel measured live with HIP events on the launch stream, cpu_baseline = the CPU oracle
-timed on the host cores on a bounded sample of the same workload).
+Prints ONE JSON line on rank 0 (metric, value = whole-job samples/s, ms_per_step).  A plain run only sets up,
+warms up, times the K steps and prints that line; `--full` adds everything else the line can carry: the roofline of
+the dominant kernel measured live with HIP events on the launch stream, the per-kernel breakdown, the `small_batch`
+and `secondary` (fp8) legs of c3b, and cpu_baseline = the CPU oracle timed on the host cores on a bounded sample of
+the same workload.  `--dump-outputs DIR` writes what the last timed step computed as .npy files (dump_outputs).
 """
 from __future__ import annotations
 
@@ -503,6 +505,29 @@ def comm_only(model, args, world, rank, device, desc, B):
         dist.destroy_process_group()
 
 
+DUMP_SAMPLE = 4096  # elements per parameter / gradient tensor written by --dump-outputs
+
+
+def dump_outputs(model, loss, out_dir):
+    """--dump-outputs: what the last timed step computed, as .npy files in out_dir -- `loss.npy` (float64, the loss the
+    step returned) and, per parameter, `param.<name>.npy` (after the optimizer step) and `grad.<name>.npy` (the gradient
+    that step consumed), float32.  Tensors larger than DUMP_SAMPLE elements are sampled at DUMP_SAMPLE indices drawn
+    from a fixed seed in parameter order, so two runs of the same workload write the same elements (DiT-XL: ~10 MB)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([float(loss.item())], dtype=np.float64))
+    gen = torch.Generator().manual_seed(0)
+    for name, p in model.named_parameters():
+        n = p.numel()
+        idx = None if n <= DUMP_SAMPLE else torch.randint(n, (DUMP_SAMPLE,), generator=gen).sort().values.to(p.device)
+        for kind, t in (("param", p), ("grad", p.grad)):
+            if t is None:
+                continue
+            flat = t.detach().reshape(-1)
+            np.save(os.path.join(out_dir, f"{kind}.{name}.npy"),
+                    (flat if idx is None else flat[idx]).float().cpu().numpy())
+
+
 def _flush_c_stdio():
     """RCCL prints its version banner through C stdio when a communicator is created; with stdout on a pipe that text sits in
     the C buffer until exit and would land BEHIND the JSON line.  Flushing it first keeps the JSON line last on stdout."""
@@ -541,11 +566,19 @@ def build_parser():
                     help="run with vds_set_deterministic(1): fixed-order reductions in every backward kernel (its cost on the step)")
     ap.add_argument("--no-fp8-cross-attention", action="store_true",
                     help="c5: keep the cross-attention products in bf16 (fp8 self-attention only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the live per-kernel timing (roofline, "
+                         "kernel_breakdown_ms), the c3b small_batch and secondary legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, sampled parameters and "
+                         "gradients) to DIR/<name>.npy")
     return ap
 
 
 def main():
     args = build_parser().parse_args()
+    if not (args.full or args.breakdown):  # a plain run times the steps only: no HIP events around the kernels
+        args.no_prof = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -619,6 +652,8 @@ def main():
     r = measure(step_fn, args.steps, args.warmup, world, kw, args, fs=fs, graphed=graphed)
     dt, median_ms, breakdown, dominant, dom, loss = r["dt"], r["median_ms"], r["breakdown"], r["dominant"], r["dom"], r["loss"]
     n_ag0, n_rs0 = r["n_ag0"], r["n_rs0"]
+    if args.dump_outputs and rank == 0:  # before the --full legs, which step the same model further
+        dump_outputs(model, loss, args.dump_outputs)
     comm_info = None
     if fs is not None:  # sharded run: what the communicator saw, per rank
         from video_diffusion_speedrun_amd import comm
@@ -686,18 +721,19 @@ def main():
                     rate = (f"{v['flops'] / v['ms'] / 1e9:8.1f} TFLOP/s" if v["flops"] > 0 else
                             f"{v['bytes'] / v['ms'] / 1e6:8.1f} GB/s")
                     print(f"[bench] {k:16s} {v['launches']:5d} launches {v['ms']:9.3f} ms  {rate}", file=sys.stderr)
-        # the companion legs must never cost the headline its JSON line: a failure is reported in their place
-        if world == 1 and args.workload == "c3b" and graphed is None and fs is None and not args.no_small_batch:
+        # the companion legs (--full) must never cost the headline its JSON line: a failure is reported in their place
+        legs = world == 1 and args.full
+        if legs and args.workload == "c3b" and graphed is None and fs is None and not args.no_small_batch:
             try:  # (before the secondary: that one switches the model to fp8)
                 out["small_batch"] = small_batch_leg(make_step, kw, args, flops, latent_shape, device, gen)
             except Exception as e:  # noqa: BLE001
                 out["small_batch"] = {"error": f"{type(e).__name__}: {e}"[:500]}
-        if world == 1 and args.workload == "c3b" and graphed is None and fs is None and not args.no_secondary:
+        if legs and args.workload == "c3b" and graphed is None and fs is None and not args.no_secondary:
             try:
                 out["secondary"] = secondary_c5(model, one_step, kw, args, B, flops)
             except Exception as e:  # noqa: BLE001
                 out["secondary"] = {"error": f"{type(e).__name__}: {e}"[:500]}
-        if world == 1 and not args.no_cpu_baseline:
+        if legs and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(kw, latent_shape, flops)
                 out["cpu_baseline"]["c1_measured"] = cpu_baseline_c1()

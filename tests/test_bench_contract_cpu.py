@@ -109,3 +109,40 @@ def test_c1_cpu_leg_and_line_helpers():
     assert r8["peak"] == 5000.0 and abs(r8["frac_of_practical_ceiling"] - r8["achieved"] / 3600.0) < 1e-9
     h = b.roofline_of("adamw", dict(flops=0.0, bytes=34e9, ms=6.6, launches=1), "c3b", 12)
     assert h["bound"] == "hbm" and "frac_of_practical_ceiling" not in h
+
+
+def test_plain_run_is_lean_and_full_is_opt_in():
+    """a plain `bench.py --gpus 1 --steps K --warmup W` times the steps only; the per-kernel timing, the companion legs
+    and the CPU baseline are behind --full, and --dump-outputs is off unless asked for"""
+    b = load_bench()
+    a = b.build_parser().parse_args(["--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and a.steps == 4 and a.warmup == 2
+    a = b.build_parser().parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_a_fixed_float_sample(tmp_path):
+    """--dump-outputs: loss as float64, every parameter and gradient as float32, tensors above DUMP_SAMPLE elements
+    sampled at the same indices in every run, the whole dump bounded by the sample size"""
+    import numpy as np
+    import torch
+    b = load_bench()
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(256, 64), torch.nn.Linear(64, 8, bias=False)).to(torch.bfloat16)
+    loss = m(torch.randn(4, 256, dtype=torch.bfloat16)).float().square().mean()
+    loss.backward()
+    m[1].weight.grad = None  # a parameter without a gradient writes no grad file
+    for d in ("a", "b"):
+        b.dump_outputs(m, loss, str(tmp_path / d))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) == ["grad.0.bias.npy", "grad.0.weight.npy", "loss.npy",
+                                                           "param.0.bias.npy", "param.0.weight.npy",
+                                                           "param.1.weight.npy"]
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == (np.float64 if n == "loss.npy" else np.float32) and np.array_equal(x, y)
+    assert np.load(tmp_path / "a" / "loss.npy")[0] == float(loss.detach())
+    w = m[0].weight.detach().float().flatten().numpy()
+    s = np.load(tmp_path / "a" / "param.0.weight.npy")
+    assert s.shape == (b.DUMP_SAMPLE,) and np.isin(s, w).all()          # 16384 elements -> a sample of them
+    assert np.array_equal(np.load(tmp_path / "a" / "param.1.weight.npy"), m[1].weight.detach().float().flatten().numpy())

@@ -16,10 +16,10 @@ if ! head -c 4 "$PY" | grep -q ELF; then
   exit 2
 fi
 # 1. per-kernel time of the bench command itself
-rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o c3b --output-format csv -- $PY bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-small-batch > "$OUT/bench_under_rocprof.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o c3b --output-format csv -- $PY bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-small-batch > "$OUT/bench_under_rocprof.log" 2>&1
 # 1b. the same command with 4 more steps: the difference of the two kernel_stats tables = launches per train step (what
 #     is left of torch's own kernels -- fills, copies, RNG -- in the step, as opposed to model / optimizer construction)
-rocprofv3 --kernel-trace --stats -d "$OUT/stats7" -o c3b7 --output-format csv -- $PY bench.py --steps 7 --warmup 1 --no-cpu-baseline --no-secondary --no-small-batch > "$OUT/bench7_under_rocprof.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$OUT/stats7" -o c3b7 --output-format csv -- $PY bench.py --full --steps 7 --warmup 1 --no-cpu-baseline --no-secondary --no-small-batch > "$OUT/bench7_under_rocprof.log" 2>&1
 find "$OUT/stats7" -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} "$OUT/c3b_7steps_kernel_stats.csv"
 # 1c. (round 5) HBM-side bytes of EVERY kernel class of the step: the bench command itself under the two PMC passes
 #     (FETCH_SIZE and WRITE_SIZE cannot share a pass), bf16 (c3b) and fp8 (c5) -> profiles/${TAG}_traffic.json, the file
@@ -50,7 +50,7 @@ for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA" \
 done
 # 4. (round 3) the fp8 configuration: kernel stats of the C5 bench, HBM bytes (B = 12) and SQ counters (B = 6) of the
 #    fp8 attention kernels
-rocprofv3 --kernel-trace --stats -d "$OUT/stats_c5" -o c5 --output-format csv -- $PY bench.py --workload c5 --steps 3 --warmup 3 --no-cpu-baseline > "$OUT/c5_bench_under_rocprof.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$OUT/stats_c5" -o c5 --output-format csv -- $PY bench.py --full --workload c5 --steps 3 --warmup 3 --no-cpu-baseline > "$OUT/c5_bench_under_rocprof.log" 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
   B=12 REPS=1 rocprofv3 --kernel-trace --pmc $c -d "$OUT/pmc8_$c" -o x --output-format csv -- $PY tools/prof_attn_fp8.py > "$OUT/pmc8_$c.log" 2>&1
 done
