@@ -389,6 +389,52 @@ int vds_adamw_multi_dev(const vds_adamw_tensor* desc_dev, const int32_t* chunk_t
                         const int64_t* chunk_start_dev, int32_t n_chunks, int32_t chunk_elems, float beta1,
                         float beta2, float eps, const float* scalars_dev, float grad_scale, vds_stream_t stream);
 
+/* ---- guarded step: global-norm clip, non-finite skip, weight EMA -- all decided on the device (no host
+ * synchronisation: the sequence below replays from a captured graph).
+ *
+ *   vds_grad_sumsq_multi      sum of squares of every gradient element of the chunk table   (+ finalize at world 1)
+ *   [all-reduce(sum) of that one float over the shard group, then vds_optim_guard_finalize -- sharded runs only]
+ *   vds_adamw_guarded_multi   the AdamW launch, reading the record
+ *
+ * The record the finalize leaves in device memory (caller-allocated, zeroed once; n_skipped accumulates): */
+typedef struct vds_optim_guard {
+  float norm;        /* global L2 norm of the gradients before clipping */
+  float coef;        /* what the step multiplies the gradients by: min(1, max_norm / (norm + 1e-6)), the arithmetic of
+                        torch.nn.utils.clip_grad_norm_; 1 when clipping is off */
+  int32_t skipped;   /* 1 = this step is skipped (norm not finite and skip_nonfinite set), 0 = applied */
+  int32_t n_skipped; /* running count of skipped steps */
+} vds_optim_guard;
+/* FIXED-ORDER two-stage reduction over the descriptor / chunk tables of vds_adamw_multi (only desc[i].g and .numel are
+ * read): one workgroup per chunk writes one fp32 partial into `workspace` (vds_grad_sumsq_workspace_floats(n_chunks)
+ * floats, caller-allocated, contents irrelevant), one workgroup adds the partials in index order and WRITES
+ * sumsq_out[0].  No floating-point atomics: bit-identical run to run, with or without vds_set_deterministic.  With
+ * guard != NULL the second stage also finalizes (below) from that sum -- the world-size-1 form, one launch fewer.
+ * max_norm <= 0 = clipping off; +inf is legal and gives coef == 1 exactly. */
+int64_t vds_grad_sumsq_workspace_floats(int32_t n_chunks);
+int vds_grad_sumsq_multi(const vds_adamw_tensor* desc_dev, const int32_t* chunk_tensor_dev,
+                         const int64_t* chunk_start_dev, int32_t n_chunks, int32_t chunk_elems, float* workspace,
+                         float* sumsq_out, float max_norm, int32_t skip_nonfinite, vds_optim_guard* guard_or_null,
+                         vds_stream_t stream);
+/* norm = sqrt(sumsq_dev[0] * sumsq_scale) (sumsq_scale: `world` after an averaging all-reduce, 1 after a sum), then
+ * coef / skipped / n_skipped as described at vds_optim_guard; ordinary stores of one thread. */
+int vds_optim_guard_finalize(const float* sumsq_dev, float sumsq_scale, float max_norm, int32_t skip_nonfinite,
+                             vds_optim_guard* guard, vds_stream_t stream);
+/* vds_adamw_multi / vds_adamw_multi_dev with the record: every gradient is multiplied by grad_scale * guard->coef;
+ * when guard->skipped every workgroup returns before its first store (p, m, v, the bf16 shadow and the EMA keep every
+ * bit).  ema_tab_dev (may be NULL = no EMA): device array of one fp32 pointer per descriptor (NULL entries allowed),
+ * parallel to desc_dev -- vds_adamw_tensor keeps its 56 bytes; ema = d * ema + (1 - d) * p_new in the same pass.
+ * d: ema_decay in [0, 1), or scalars_dev[3] for the _dev form (scalars_dev = { 1 - beta1^step,
+ * 1/sqrt(1 - beta2^step), lr_mult, ema_decay }: changing it between replays needs no new capture). */
+int vds_adamw_guarded_multi(const vds_adamw_tensor* desc_dev, const int32_t* chunk_tensor_dev,
+                            const int64_t* chunk_start_dev, int32_t n_chunks, int32_t chunk_elems, float beta1,
+                            float beta2, float eps, int32_t step, float lr_mult, float grad_scale,
+                            const vds_optim_guard* guard, float* const* ema_tab_dev, float ema_decay,
+                            vds_stream_t stream);
+int vds_adamw_guarded_multi_dev(const vds_adamw_tensor* desc_dev, const int32_t* chunk_tensor_dev,
+                                const int64_t* chunk_start_dev, int32_t n_chunks, int32_t chunk_elems, float beta1,
+                                float beta2, float eps, const float* scalars_dev, float grad_scale,
+                                const vds_optim_guard* guard, float* const* ema_tab_dev, vds_stream_t stream);
+
 /* ------------------------------------------- parameter / gradient sharding (model.py:512-542) ------
  * What the reference gets from FSDP2 `fully_shard` (apply_fsdp, model.py:512-542; mesh model.py:475-498): a bf16
  * all-gather of a shard group's parameters before use and an fp32 reduce-scatter-AVERAGE of its gradients after its
@@ -425,6 +471,9 @@ int vds_average_chunks_f32(const float* own, const float* staged, float* out, in
                            int32_t rank, vds_stream_t stream);
 /* utils.py:11-15 avg_scalar_across_ranks (loss logging): buf[i] = mean over ranks, in place */
 int vds_all_reduce_f32_avg(float* buf, int64_t n, vds_stream_t stream);
+/* buf[i] = sum over ranks, in place (the guarded optimizer step: every gradient element is owned by one rank, so the
+ * squared global norm is the sum of the ranks' local sums of squares) */
+int vds_all_reduce_f32_sum(float* buf, int64_t n, vds_stream_t stream);
 
 /* f32 -> bf16 cast (FSDP param_dtype cast before all-gather, model.py:516-518) */
 int vds_cast_f32_bf16(const float* src, void* dst, int64_t n, vds_stream_t stream);

@@ -69,6 +69,10 @@ class AdamWTensor(C.Structure):
                 ("numel", c_i64), ("lr", c_f32), ("wd", c_f32)]
 
 
+class OptimGuard(C.Structure):  # vds_optim_guard
+    _fields_ = [("norm", c_f32), ("coef", c_f32), ("skipped", c_i32), ("n_skipped", c_i32)]
+
+
 # name -> argtypes (restype is int unless noted).  Must list every symbol of include/vds.h.
 SIGNATURES = {
     "vds_version": [],
@@ -119,6 +123,12 @@ SIGNATURES = {
     "vds_cfg_euler_step": [c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_i64, c_vp],
     "vds_adamw_multi": [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_f32, c_i32, c_f32, c_f32, c_vp],
     "vds_adamw_multi_dev": [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp, c_f32, c_vp],
+    "vds_grad_sumsq_workspace_floats": [c_i32],
+    "vds_grad_sumsq_multi": [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_f32, c_i32, c_vp, c_vp],
+    "vds_optim_guard_finalize": [c_vp, c_f32, c_f32, c_i32, c_vp, c_vp],
+    "vds_adamw_guarded_multi": [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_f32, c_i32, c_f32, c_f32, c_vp, c_vp,
+                                c_f32, c_vp],
+    "vds_adamw_guarded_multi_dev": [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp, c_f32, c_vp, c_vp, c_vp],
     "vds_comm_available": [],
     "vds_comm_unique_id": [c_vp, C.c_size_t],
     "vds_comm_init": [c_i32, c_i32, c_vp, C.c_size_t],
@@ -130,6 +140,7 @@ SIGNATURES = {
     "vds_reduce_scatter_f32_avg": [c_vp, c_vp, c_i64, c_vp, C.c_size_t, c_vp],
     "vds_average_chunks_f32": [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp],
     "vds_all_reduce_f32_avg": [c_vp, c_i64, c_vp],
+    "vds_all_reduce_f32_sum": [c_vp, c_i64, c_vp],
     "vds_cast_f32_bf16": [c_vp, c_vp, c_i64, c_vp],
     "vds_cast_bf16_f32": [c_vp, c_vp, c_i64, c_vp],
     "vds_gemm_fp8": [C.POINTER(GemmArgs), c_vp, c_vp, c_i32, c_i32, c_vp, c_vp],

@@ -12,6 +12,9 @@ file (`model.pt`) and -- `dcp=True` -- as a torch.distributed.checkpoint directo
 the reference's own loader reads; a checkpoint directory written by the reference loads here.
 On top of the reference: each rank's optimizer shard (AdamW moments, step) goes to
 `optim_rank{r}_of{W}.pt`, so a run resumes exactly when world size and sharding are unchanged.
+When the optimizer carries a weight EMA (`MuAdamW(ema_decay=...)`), `model_ema.pt` holds it as full fp32 tensors
+under the same names -- `read_model_state(dir, ema=True)` -- ready for `load_state_dict` of a sampling model; the
+per-rank EMA shards travel in the optimizer file like the moments.
 """
 from __future__ import annotations
 
@@ -47,20 +50,43 @@ def save_checkpoint(path: str, model, optimizer=None, step: int = 0, dcp: bool =
         if dcp:
             import torch.distributed.checkpoint as dcp_mod
             dcp_mod.save(state, checkpoint_id=os.path.join(path, "dcp"), no_dist=True)
+    ema = _full_ema(model, optimizer)  # collective when sharded, like full_state_dict()
+    if ema is not None and rank == 0:
+        ema = {k: v.detach().to("cpu", torch.float32).contiguous() for k, v in ema.items()}
+        torch.save({"model": ema, "step": int(step)}, os.path.join(path, "model_ema.pt"))
     if optimizer is not None:
         torch.save({"optimizer": optimizer.state_dict(), "step": int(step), "rank": rank, "world": world},
                    os.path.join(path, f"optim_rank{rank}_of{world}.pt"))
     _barrier(model)
 
 
-def _read(path: str, model=None):
+def _full_ema(model, optimizer) -> Optional[Dict[str, torch.Tensor]]:
+    """the optimizer's weight EMA as full fp32 tensors keyed like the model's state dict (parameters without an EMA --
+    frozen ones -- keep their own value); None when the optimizer carries none"""
+    if optimizer is None or getattr(optimizer, "ema_decay", None) is None or not hasattr(optimizer, "ema_named"):
+        return None
+    pieces = optimizer.ema_named(model)
+    if not pieces:  # no step yet: the EMA would start as a copy of the weights
+        return None
+    groups = getattr(model, "_groups", None)
+    if groups is None:
+        return {n: pieces[n].detach().clone() if n in pieces else p.detach().clone() for n, p in model.named_parameters()}
+    out = {}
+    for g in groups:
+        out.update(g.full_tensors_of(pieces))
+    return out
+
+
+def _read(path: str, model=None, fname: str = "model.pt"):
     """(state dict of full fp32 tensors, stored step) from model.pt, a reference `temp.pt` (plain state
     dict) or a DCP directory (ours or the reference's).  Every file is read with weights_only=True: the
     stored objects are tensors, numbers, tuples, lists and dicts only."""
     if os.path.isfile(path):
         obj = torch.load(path, map_location="cpu", weights_only=True)
-    elif os.path.isfile(os.path.join(path, "model.pt")):
-        obj = torch.load(os.path.join(path, "model.pt"), map_location="cpu", weights_only=True)
+    elif os.path.isfile(os.path.join(path, fname)):
+        obj = torch.load(os.path.join(path, fname), map_location="cpu", weights_only=True)
+    elif fname != "model.pt":
+        raise FileNotFoundError(f"{os.path.join(path, fname)}: the checkpoint was written without a weight EMA")
     else:
         from torch.distributed.checkpoint.format_utils import dcp_to_torch_save
         d = os.path.join(path, "dcp") if os.path.isdir(os.path.join(path, "dcp")) else path
@@ -76,8 +102,9 @@ def _read(path: str, model=None):
     return {k.replace("module.", "").replace("_orig_mod.", ""): v for k, v in state.items() if torch.is_tensor(v)}, step
 
 
-def read_model_state(path: str) -> Dict[str, torch.Tensor]:
-    return _read(path)[0]
+def read_model_state(path: str, ema: bool = False) -> Dict[str, torch.Tensor]:
+    """the stored weights; ema=True: the weight EMA (`model_ema.pt`, written when the optimizer carried one)"""
+    return _read(path, fname="model_ema.pt" if ema else "model.pt")[0]
 
 
 def load_checkpoint(path: str, model, optimizer=None) -> int:

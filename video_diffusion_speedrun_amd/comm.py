@@ -151,3 +151,9 @@ def all_reduce_avg_(buf: torch.Tensor):
     assert buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous()
     _lib.check(_lib.load().vds_all_reduce_f32_avg(buf.data_ptr(), buf.numel(), _stream()), "vds_all_reduce_f32_avg")
     return buf
+
+
+def all_reduce_sum_(buf: torch.Tensor):
+    assert buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous()
+    _lib.check(_lib.load().vds_all_reduce_f32_sum(buf.data_ptr(), buf.numel(), _stream()), "vds_all_reduce_f32_sum")
+    return buf

@@ -256,3 +256,11 @@ extern "C" int vds_all_reduce_f32_avg(float* buf, int64_t n, vds_stream_t stream
   RCCL_TRY(R.AllReduce(buf, buf, (size_t)n, ncclFloat32, ncclAvg, g_comm, (hipStream_t)stream), "ncclAllReduce(f32, avg)");
   return VDS_OK;
 }
+
+extern "C" int vds_all_reduce_f32_sum(float* buf, int64_t n, vds_stream_t stream) {
+  vdserr::clear();
+  if (int e = need_comm("vds_all_reduce_f32_sum")) return e;
+  if (!buf || n <= 0) return VDS_ERR_ARG;
+  RCCL_TRY(R.AllReduce(buf, buf, (size_t)n, ncclFloat32, ncclSum, g_comm, (hipStream_t)stream), "ncclAllReduce(f32, sum)");
+  return VDS_OK;
+}

@@ -37,6 +37,7 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import params as _params
 from .params import FlatGroup
 
 
@@ -133,6 +134,16 @@ class ShardRuntime:
         with self._on_comm():
             g.reduce_grads(self.pg)
         self.n_reduce_scatter += 1
+
+    def all_reduce_scalar(self, buf: torch.Tensor):
+        """the guarded optimizer step's one float (local sum of squared gradients -> global): all-reduced on the
+        communication stream after everything queued on the compute stream, which then waits for it -- the
+        reduce-scatter's ordering; capturable like it"""
+        self._comm_waits_compute()
+        with self._on_comm():
+            _params.all_reduce_sum(buf, self.pg)
+        if self.cuda:
+            torch.cuda.current_stream().wait_stream(self.comm)
 
     # ---- forward --------------------------------------------------------------------------
     def _issue_gathers(self, upto: int):
@@ -373,4 +384,6 @@ def apply_fsdp(dit_model, param_dtype=torch.bfloat16, reduce_dtype=torch.float32
             reshard_after_forward = os.environ.get("VDS_FSDP_RESHARD", "0") == "1"
         rt = ReshardRuntime if (reshard_after_forward and len(groups) > 2) else ShardRuntime
         dit_model._fsdp = rt(dit_model, cast_fn, process_group)
+        for g in groups:
+            g.runtime = dit_model._fsdp
     return dit_model

@@ -10,7 +10,9 @@ in device memory rather than in kernel arguments:
   * the batch            -> static input buffers, refreshed with stream-ordered copies;
   * the RoPE offsets     -> device int32[3] read by `vds_rope_rows_dev` (drawn on the host from the
                             global CPU RNG exactly like the eager path, model.py:224-226);
-  * the AdamW bias corrections and LR multiplier -> device float[3] read by `vds_adamw_multi_dev`;
+  * the AdamW bias corrections, LR multiplier and EMA decay -> device float[4] read by `vds_adamw_multi_dev` /
+                            `vds_adamw_guarded_multi_dev`; the guarded step's norm, clip coefficient and skip flag never
+                            leave the device (optim.py): a replay fed a non-finite batch skips itself;
   * z / noise / caption-dropout draws -> torch's default device generator (graph-safe Philox: the
                             captured kernels take seed/offset from device memory).
 

@@ -6,9 +6,30 @@ Use exactly like the reference:
     groups, settings = dit.get_mup_setup(lr, 0.1, ["patch_proj", "context_kv", "positional_embedding"])
     opt = MuAdamW(groups, betas=(0.95, 0.99))
 It is a torch.optim.Optimizer, so HF / torch LR schedulers drive `param_groups[i]["lr"]` as usual.
+
+Guarded step (all three options default to off; with them off `step()` issues exactly the one launch above):
+    opt = MuAdamW(groups, betas=(0.95, 0.99), max_grad_norm=1.0, skip_nonfinite=True, ema_decay=0.9999)
+`step()` then runs, on the current stream and without reading anything on the host: a fixed-order sum of squares of
+every gradient (`vds_grad_sumsq_multi`) -> when sharded, an all-reduce of that one float over the shard group -> a
+finalize that leaves norm / coefficient / skipped flag / skipped count in a device record -> the guarded AdamW launch
+that reads the record (and updates the EMA in the same pass).  So the whole thing replays from a captured graph.
+
+  * max_grad_norm: global L2 clip with the arithmetic of `torch.nn.utils.clip_grad_norm_`
+    (coefficient min(1, max_norm / (norm + 1e-6))).  The coefficient is applied INSIDE the kernel: `p.grad` is not
+    modified.  `float("inf")` is legal (coefficient exactly 1: only the norm is measured).
+  * skip_nonfinite: a step whose global gradient norm is inf / NaN writes nothing -- parameters, both moments, the
+    bf16 shadows and the EMA keep every bit -- and the device count behind `skipped_steps()` goes up by one.
+    UNLIKE torch's GradScaler, a skipped step STILL COUNTS as a step for the bias corrections and for the LR schedule:
+    the host cannot know that it was skipped without a synchronisation, and a replayed step must not depend on it.
+  * ema_decay: `state[p]["ema"]` (fp32, the shape of `p` -- the shard under sharding), initialised to a copy of `p`
+    the first time `step()` sees the parameter (before that step's update), then ema = d * ema + (1 - d) * p_new.
+    `opt.ema_decay = d` may be changed at any time, also between graph replays.  `swap_ema()` /
+    `with opt.ema_weights():` exchange parameters and EMA in place (sampling, evaluation, `model_ema.pt`).
+  * `opt.grad_norm`: 0-d DEVICE tensor, the pre-clip global norm of the last step (`.item()` it at logging time only).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import List
 
@@ -20,21 +41,106 @@ CHUNK = 1 << 16
 
 
 class MuAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.95, 0.99), eps=1e-8, weight_decay=1e-2, fused=True):
+    def __init__(self, params, lr=1e-3, betas=(0.95, 0.99), eps=1e-8, weight_decay=1e-2, fused=True,
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:  # also refuses NaN
+            raise ValueError(f"MuAdamW: max_grad_norm must be > 0 (inf allowed) or None, got {max_grad_norm}")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self._step = 0
         self._table_key = None
         self._chunk_key = None
         self._dev = {}
-        self._dev_scalars = None  # device float[3]: see use_device_scalars
+        self._dev_scalars = None  # device float[4]: see use_device_scalars
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._ema_decay = None
+        self.ema_decay = ema_decay
+        self._guard = None        # device record of the guarded step: float32[4] = vds_optim_guard
+        self._skipped_seed = 0    # skipped count to start from (load_state_dict before the record exists)
+        self._ema_swapped = False
+
+    # ---- guarded step: options and what it leaves behind ---------------------------------------
+    @property
+    def ema_decay(self):
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, d):
+        if d is not None and not 0.0 <= float(d) < 1.0:
+            raise ValueError(f"MuAdamW: ema_decay must be in [0, 1) or None, got {d}")
+        if (d is None) != (self._ema_decay is None):
+            self._table_key = None  # the EMA pointer table appears / disappears
+        self._ema_decay = None if d is None else float(d)
+
+    @property
+    def guarded(self) -> bool:
+        return self.max_grad_norm is not None or self.skip_nonfinite or self._ema_decay is not None
+
+    @property
+    def grad_norm(self):
+        """0-d device tensor: global L2 norm of the gradients of the last `step()`, before clipping (None before the
+        first guarded step).  Reading it on the host synchronises: do that at logging time only."""
+        return None if self._guard is None else self._guard[0]
+
+    def skipped_steps(self) -> int:
+        """number of steps `skip_nonfinite` has skipped so far (reads the device count: synchronises)"""
+        if self._guard is None:
+            return self._skipped_seed
+        return int(self._guard.view(torch.int32)[3].item())
+
+    def _guard_record(self, device):
+        if self._guard is None:
+            rec = torch.zeros(4, dtype=torch.int32, device=device)
+            rec[3] = self._skipped_seed
+            self._guard = rec.view(torch.float32)
+            self._dev["sumsq"] = torch.zeros(1, dtype=torch.float32, device=device)
+        return self._guard
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """exchange every parameter with its EMA, in place (pointers stay: a captured step keeps working), and void the
+        bf16 compute copies so that the next forward -- eager or replayed -- re-casts.  Twice = every bit restored."""
+        groups = {}
+        for group in self.param_groups:
+            for p in group["params"]:
+                ema = self.state.get(p, {}).get("ema")
+                if ema is None or ema.numel() != p.numel():
+                    continue
+                tmp = p.data.clone()
+                p.data.copy_(ema.view_as(p.data))
+                ema.copy_(tmp.view_as(ema))
+                g = getattr(p, "_vds_group", None)
+                if g is not None:
+                    groups[id(g)] = g
+        for g in groups.values():
+            g.invalidate_shadow()
+        self._ema_swapped = not self._ema_swapped
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with opt.ema_weights(): sample / evaluate`: the model computes with the EMA inside the block"""
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
+    def ema_named(self, model):
+        """{parameter name: this rank's EMA piece} for the parameters of `model` that carry one"""
+        out = {}
+        for n, p in model.named_parameters():
+            ema = self.state.get(p, {}).get("ema")
+            if ema is not None and ema.numel() == p.numel():
+                out[n] = ema
+        return out
 
     def use_device_scalars(self, device):
         """Keep the per-step scalars (bias corrections, LR multiplier) in device memory instead of kernel
         arguments, so that a captured step can be replayed (graph.py).  `step()` refreshes them with a
         stream-ordered copy unless the stream is capturing; a replay driver calls `advance()` itself."""
         if self._dev_scalars is None:
-            self._dev_scalars = torch.zeros(3, dtype=torch.float32, device=device)
+            self._dev_scalars = torch.zeros(4, dtype=torch.float32, device=device)
         return self._dev_scalars
 
     def _scalars(self, mult):
@@ -43,7 +149,9 @@ class MuAdamW(torch.optim.Optimizer):
         one, st = np.float32(1), np.float32(self._step)
         bc1 = one - np.power(b1, st)
         bc2 = one - np.power(b2, st)
-        return torch.tensor([bc1, one / np.sqrt(bc2), np.float32(mult)], dtype=torch.float32)
+        # [3]: the EMA decay of the guarded step (read by vds_adamw_guarded_multi_dev only)
+        return torch.tensor([bc1, one / np.sqrt(bc2), np.float32(mult), np.float32(self._ema_decay or 0.0)],
+                            dtype=torch.float32)
 
     def advance(self):
         """host half of one captured step: count it and push its scalars (call before the replay)"""
@@ -68,6 +176,9 @@ class MuAdamW(torch.optim.Optimizer):
         self._dev["ct"] = torch.tensor(chunk_t, dtype=torch.int32, device=device)
         self._dev["cs"] = torch.tensor(chunk_s, dtype=torch.int64, device=device)
         self._dev["n"] = len(chunk_t)
+        if self.guarded:  # the partials of the fixed-order sum of squares: one float per chunk
+            nws = int(_lib.load().vds_grad_sumsq_workspace_floats(len(chunk_t)))
+            self._dev["ws"] = torch.empty(nws, dtype=torch.float32, device=device)
 
     def _lr_plan(self, plist):
         """(per-param base lr list, common multiplier): LR schedulers scale every group's lr by the same
@@ -101,15 +212,25 @@ class MuAdamW(torch.optim.Optimizer):
             d.numel = p.numel()
             d.lr, d.wd = lrs[i], float(group["weight_decay"])
         self._dev["desc"] = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(device)
+        # the EMA pointers travel as a parallel array indexed by tensor (the descriptor keeps its 56 bytes)
+        self._dev["ema"] = None
+        if self._ema_decay is not None:
+            self._dev["ema"] = torch.tensor([self.state[p]["ema"].data_ptr() for p, _ in plist],
+                                            dtype=torch.int64).to(device)
 
     def state_dict(self):
         d = super().state_dict()
         d["vds_step"] = self._step
+        if self.guarded:
+            d["vds_skipped"] = self.skipped_steps()
         return d
 
     def load_state_dict(self, state_dict):
         state_dict = dict(state_dict)
         self._step = int(state_dict.pop("vds_step", 0))
+        self._skipped_seed = int(state_dict.pop("vds_skipped", 0))
+        if self._guard is not None:
+            self._guard.view(torch.int32)[3] = self._skipped_seed
         super().load_state_dict(state_dict)
         self._table_key = self._chunk_key = None  # moments were replaced: rebuild the descriptor table
 
@@ -130,18 +251,31 @@ class MuAdamW(torch.optim.Optimizer):
             return None
         self._step += 1
         device = plist[0][0].device
+        if self._ema_decay is not None:
+            if self._ema_swapped:
+                raise RuntimeError("MuAdamW.step() while the EMA is swapped in: leave ema_weights() / swap_ema() back first")
+            for p, _ in plist:  # first sight of a parameter: its EMA starts as a copy of it, before this step's update
+                st = self.state[p]
+                if "ema" not in st or st["ema"].numel() != p.numel():
+                    st["ema"] = p.data.detach().clone()
+                    self._table_key = None
         ckey = tuple(p.numel() for p, _ in plist)
         if ckey != self._chunk_key:
             self._build_chunks(plist, device)
             self._chunk_key, self._table_key = ckey, None
         lrs, mult = self._lr_plan(plist)
         key = tuple((p.data.data_ptr(), p.grad.data_ptr(), lr, g["weight_decay"]) for (p, g), lr in zip(plist, lrs))
+        if self.guarded and "ws" not in self._dev:  # an option was switched on after the chunk table was built
+            self._build_chunks(plist, device)
         if key != self._table_key:  # pointers or the base lr changed: refresh the descriptors
             self._build_descs(plist, device, lrs)
             self._table_key = key
         b1, b2 = self.param_groups[0]["betas"]
         eps = self.param_groups[0]["eps"]
-        if self._dev_scalars is not None:
+        fresh_before = ()
+        if self.guarded:
+            fresh_before = self._step_guarded(plist, device, mult, b1, b2, eps)
+        elif self._dev_scalars is not None:
             if not torch.cuda.is_current_stream_capturing():
                 self._dev_scalars.copy_(self._scalars(mult))
             _lib.check(_lib.load().vds_adamw_multi_dev(self._dev["desc"].data_ptr(), self._dev["ct"].data_ptr(),
@@ -154,6 +288,45 @@ class MuAdamW(torch.optim.Optimizer):
                                                    self._step, mult, 1.0, ops._stream()), "vds_adamw_multi")
         # the bf16 shadows of these flat groups are now current: the next forward skips its cast pass
         for g in {id(getattr(p, "_vds_group", None)): getattr(p, "_vds_group", None) for p, _ in plist}.values():
-            if g is not None:
+            if g is not None and (not self.skip_nonfinite or id(g) in fresh_before):
                 g.mark_shadow_fresh()
         return None
+
+    def _step_guarded(self, plist, device, mult, b1, b2, eps):
+        """sum of squares -> (all-reduce over the shard group) -> finalize -> guarded AdamW, all on the current stream.
+        Returns the ids of the flat groups whose bf16 shadow was current before the step: a step that may have been
+        skipped has written no shadow, so it can only keep that claim, not establish it."""
+        lib, stream = _lib.load(), ops._stream()
+        rec = self._guard_record(device)
+        ss, d = self._dev["sumsq"], self._dev
+        max_norm = 0.0 if self.max_grad_norm is None else self.max_grad_norm  # 0 = clipping off
+        skip = 1 if self.skip_nonfinite else 0
+        shard = None  # the flat group whose communicator spans the ranks that own the other gradient elements
+        fresh_before = set()
+        for g in {id(getattr(p, "_vds_group", None)): getattr(p, "_vds_group", None) for p, _ in plist}.values():
+            if g is None:
+                continue
+            if shard is None and (g.world > 1 or g.runtime is not None):
+                shard = g
+            if g.shadow_fresh:
+                fresh_before.add(id(g))
+        _lib.check(lib.vds_grad_sumsq_multi(d["desc"].data_ptr(), d["ct"].data_ptr(), d["cs"].data_ptr(), d["n"], CHUNK,
+                                            d["ws"].data_ptr(), ss.data_ptr(), max_norm, skip,
+                                            None if shard is not None else rec.data_ptr(), stream),
+                   "vds_grad_sumsq_multi")
+        if shard is not None:
+            shard.all_reduce_scalar(ss)
+            _lib.check(lib.vds_optim_guard_finalize(ss.data_ptr(), 1.0, max_norm, skip, rec.data_ptr(), stream),
+                       "vds_optim_guard_finalize")
+        ema = d["ema"].data_ptr() if d.get("ema") is not None else None
+        if self._dev_scalars is not None:
+            if not torch.cuda.is_current_stream_capturing():
+                self._dev_scalars.copy_(self._scalars(mult))
+            _lib.check(lib.vds_adamw_guarded_multi_dev(d["desc"].data_ptr(), d["ct"].data_ptr(), d["cs"].data_ptr(), d["n"],
+                                                       CHUNK, b1, b2, eps, self._dev_scalars.data_ptr(), 1.0,
+                                                       rec.data_ptr(), ema, stream), "vds_adamw_guarded_multi_dev")
+        else:
+            _lib.check(lib.vds_adamw_guarded_multi(d["desc"].data_ptr(), d["ct"].data_ptr(), d["cs"].data_ptr(), d["n"],
+                                                   CHUNK, b1, b2, eps, self._step, mult, 1.0, rec.data_ptr(), ema,
+                                                   self._ema_decay or 0.0, stream), "vds_adamw_guarded_multi")
+        return fresh_before

@@ -59,6 +59,7 @@ class FlatGroup:
         self.master = self.shadow = self.full = self.gfull = self.gshard = None
         self.gathered = False
         self._fresh_versions = None  # see mark_shadow_fresh
+        self.runtime = None  # fsdp.ShardRuntime when the group's collectives run on a communication stream
 
     # ---- layout -------------------------------------------------------------------------
     def local_range(self, name: str) -> Tuple[int, int]:
@@ -181,6 +182,16 @@ class FlatGroup:
         if self.world > 1 or (self.gshard is not self.gfull):
             reduce_scatter_avg(self.gshard, self.gfull, group)
 
+    def all_reduce_scalar(self, buf: torch.Tensor):
+        """sum `buf` (fp32, the optimizer's local sum of squared gradients) over the ranks of the shard group, ordered
+        against the current stream like the reduce-scatter: on the runtime's communication stream between two waits"""
+        if self.world == 1 and self.runtime is None:
+            return
+        if self.runtime is not None:
+            self.runtime.all_reduce_scalar(buf)
+        else:
+            all_reduce_sum(buf, self.pg)
+
     def publish_grads(self):
         """point `.grad` of every trainable parameter at its slice of the reduced gradient shard (frozen parameters --
         `requires_grad_(False)` -- get none: no optimizer would ever clear it again)"""
@@ -231,6 +242,23 @@ class FlatGroup:
             return self.params[name].data.detach().clone()
         return self.full_tensors([name])[name]
 
+    def full_tensors_of(self, pieces: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """full fp32 tensors of per-parameter state laid out like the parameters themselves (`pieces[name]`: this
+        rank's piece, the size of `params[name]`; the weight EMA of MuAdamW): ONE all-gather when sharded, like
+        `full_tensors`.  Names without a piece take the parameter's own value."""
+        if self.world == 1:
+            return {n: pieces[n].detach().reshape(self.shapes[n]).clone() if n in pieces else
+                    self.params[n].data.detach().clone() for n in self.names}
+        flat = self.master.clone()
+        for n in self.names:
+            lo, hi = self.local_range(n)
+            if n in pieces and hi > lo:
+                flat[lo:hi].copy_(pieces[n].reshape(-1))
+        full = torch.empty(self.padded, dtype=torch.float32, device=self.device)
+        all_gather_flat(full, flat, self.pg)
+        return {n: full[self.offsets[n]:self.offsets[n] + _numel(self.shapes[n])].view(self.shapes[n]).clone()
+                for n in self.names}
+
     def full_tensors(self, names: Optional[Sequence[str]] = None) -> Dict[str, torch.Tensor]:
         """fp32 full values of the group's parameters with ONE all-gather of the master shards (on the
         group's own communicator)."""
@@ -275,3 +303,14 @@ def reduce_scatter_avg(out: torch.Tensor, inp: torch.Tensor, group=None):
         out.copy_(tmp.view(w, -1)[r] / w)
     else:
         dist.reduce_scatter_tensor(out, inp, op=dist.ReduceOp.AVG, group=group)
+
+
+def all_reduce_sum(buf: torch.Tensor, group=None):
+    """buf <- sum over the ranks of the shard group, in place, fp32: the one float of the guarded optimizer step (every
+    gradient element is owned by exactly one rank, so the squared global norm is the sum of the ranks' local sums of
+    squares).  One replaceable function, like the two above: the emulated-rank tests substitute it."""
+    from . import comm
+    if buf.is_cuda and comm.active_for(group):
+        comm.all_reduce_sum_(buf)
+    else:
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)

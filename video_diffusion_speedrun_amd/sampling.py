@@ -36,6 +36,16 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
                      inference_steps: int = 50, cfg_scale: float = 6.0, height: int = 512, width: int = 512,
                      seed: int = 42, latents: Optional[torch.Tensor] = None,
                      rope_starts: Optional[Sequence[Tuple[int, int, int]]] = None, device="cuda") -> torch.Tensor:
+    """Samples whatever weights the model holds.  To sample the weight EMA of a training run
+    (`MuAdamW(..., ema_decay=0.9999)`), either swap it in for the duration of the call
+
+        with opt.ema_weights():
+            acc = generate_latents(dit, prompt_embeds, seed=42)
+
+    or build a sampling model from the EMA file a checkpoint carries:
+
+        dit.load_state_dict(checkpoint.read_model_state(ckpt_dir, ema=True))
+    """
     dev = torch.device(device)
     prompt_embeds = prompt_embeds.to(dev, bf16)
     guided = cfg_scale > 1
