@@ -48,6 +48,11 @@ const char* vds_last_error(void);
  *   VDS_EPI_DGELU      C = bf16(acc * gelu'(aux[m,n]))           (backward of model.py:85)
  *   VDS_EPI_F32        C(f32) = acc; a K split (vds_gemm_args.split_k) runs over blockIdx.y and accumulates
  *                      atomically into the pre-zeroed C; the accumulate forms let several calls sum into one C
+ * Single-output forms of the two-output epilogues (a forward pass that keeps nothing for a backward: no_grad, and
+ * the first forward of a recomputing model): with C == NULL and C2 != NULL, VDS_EPI_BIAS_GELU stores only the
+ * activation and VDS_EPI_GATE_RES only the new residual stream, in every tiling and in the partial tiles; what is
+ * stored is bit-identical to the two-output launch.  C == NULL with any other epilogue, or with C2 == NULL too, is
+ * VDS_ERR_ARG.
  * Requirements: K % 8 == 0 for NT / NN (any K for TN); N % 8 == 0 (TN: M % 8 == 0 too);
  * ld* % 8 == 0; every tensor < 4 GiB. */
 enum { VDS_NT = 0, VDS_NN = 1, VDS_TN = 2 };

@@ -307,7 +307,7 @@ __device__ __forceinline__ void epilogue_64x64(const GemmP& p, float* stg, int r
         if constexpr (LUT) o2[e] = f2_to_bf2(bf2_to_f2(o[e]) * lut_pair(lut, o[e]));  // as epilogue_full
         else o2[e] = pack_bf2(gelu_f(a), gelu_f(b));
       }
-      *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(p.C) + grow * p.ldc + gcol) = o;
+      if (p.C) *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(p.C) + grow * p.ldc + gcol) = o;  // (NULL: act only)
       if (p.C2) *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(p.C2) + grow * p.ldc2 + gcol) = o2;
       if constexpr (EMIT) ev = o2;
     } else if constexpr (EPI == VDS_EPI_GATE_RES) {
@@ -500,6 +500,7 @@ __device__ __forceinline__ bool epilogue_full_dispatch(const GemmP& p, const flo
     return true;
   } else if constexpr (EPI == VDS_EPI_BIAS_GELU) {
     if (c1 && c2 && !eany) { VDS_FULL(EPI, 0, true, true, false, false); return true; }
+    if (!c1 && c2 && !eany) { VDS_FULL(EPI, 0, false, true, false, false); return true; }  // no-grad forward: act only
     if constexpr (EMIT) {
       if (c1 && !c2 && eq && !csum && p.e_fmt == 0) { VDS_FULL(EPI, 0, true, false, true, false); return true; }
     }
@@ -1499,7 +1500,8 @@ extern "C" int vds_gemm_bf16(const vds_gemm_args* a, vds_stream_t stream) {
   p.b_bytes = (unsigned)bbytes;
   hipStream_t s = (hipStream_t)stream;
   if (p.atomic && !(a->layout == VDS_TN && a->epilogue == VDS_EPI_F32)) return VDS_ERR_ARG;
-  if (!a->C && a->epilogue != VDS_EPI_GATE_RES) return VDS_ERR_ARG;
+  // C == NULL: the two-output epilogues store their second output only (GATE_RES: x_new, BIAS_GELU: the activation)
+  if (!a->C && !((a->epilogue == VDS_EPI_GATE_RES || a->epilogue == VDS_EPI_BIAS_GELU) && a->C2)) return VDS_ERR_ARG;
   const bool det = vdscfg::geti(vdscfg::DETERMINISTIC) != 0;
   // deterministic mode: the fc1 bias gradient is a separate fixed-order column sum, not the epilogue's per-tile atomics
   const float* fused_colsum = det ? nullptr : a->colsum;

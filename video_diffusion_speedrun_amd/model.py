@@ -325,13 +325,19 @@ class DiTBlock(nn.Module):
                                     rope[1] if rope is not None else None, *params)
 
     # ---- the kernel sequence of one block (used by DiT's whole-model autograd node and by `forward`) ----
-    def _fwd(self, G, pre, X, ctx2d, cvec, v0, cos, sin, B, L, Lc, save, fp8=None, mod=None):
+    def _fwd(self, G, pre, X, ctx2d, cvec, v0, cos, sin, B, L, Lc, save, fp8=None, mod=None, keep=None, replay=None):
         """X [B*L, D] bf16 token buffer -> (X_out, v [B,H,L,hdp], saved).  G: the FlatGroup holding this block's
         parameters under the name prefix `pre`; cvec f32 [B, D]; v0: block 0's v in the padded head-major layout
-        or None; cos / sin f32 [L, hd/2]; fp8 = (AmaxHistory | None, block index) when the fp8 linears are on."""
+        or None; cos / sin f32 [L, hd/2]; fp8 = (AmaxHistory | None, block index) when the fp8 linears are on.
+        Activation recomputation (DiT.enable_recompute): with save=False, keep = "full" | "selective" returns as `saved`
+        only what the replay needs (X, mod; selective: attn, lse1 too).  replay = that object, with save=True: the run
+        before the block's `_bwd` -- the self-attention forward is not launched when attn / lse1 were kept, and the
+        new residual stream after the MLP is not stored (X_out is None: the next block's kept X already holds it)."""
         D, H, hd = self.hidden_size, self.num_heads, self.head_dim
         hdp = HDP_OF[hd]
         use_fp8 = fp8 is not None
+        if use_fp8 and (keep is not None or replay is not None):
+            raise ValueError("activation recomputation does not cover the fp8 path")
         fp8_hist, i, fp8_attn, fp8_lin, q_ctx = fp8 if use_fp8 else (None, 0, 0, False, None)
         W = lambda n: G.w(pre + n)
         Wo = lambda n: G.w(pre + n) if G.has(pre + n) else None
@@ -363,8 +369,12 @@ class DiTBlock(nn.Module):
         else:
             qkv = ops.linear_fwd(xn1, W("qkv.weight"), Wo("qkv.bias"))
         mix = self.residual_v and v0 is not None
-        attn = torch.empty(B * L, D, dtype=bf16, device=dev)
-        lse1 = torch.empty(B, H, L, dtype=f32, device=dev)
+        kept_attn = replay is not None and getattr(replay, "attn", None) is not None
+        if kept_attn:
+            attn, lse1 = replay.attn, replay.lse1
+        else:
+            attn = torch.empty(B * L, D, dtype=bf16, device=dev)
+            lse1 = torch.empty(B, H, L, dtype=f32, device=dev)
         # fp8 attention (csrc/attention_fp8.hip): delayed scaling only -- q, k, v leave the RoPE kernel as e4m3 scaled by
         # the previous step's amax; until a complete step has been recorded the bf16 kernels run and the amax is taken
         a8_on = use_fp8 and fp8_attn and ops.attn_fp8_supported(hd)
@@ -384,8 +394,9 @@ class DiTBlock(nn.Module):
         else:
             q, k, v = ops.qkv_rope_fwd(qkv, cos, sin, v0 if mix else None, W("lambda_param") if mix else None, B, L, H,
                                        hd, hdp)
-            ops.attn_fwd(q[..., :hd], k[..., :hd], v[..., :hd], ops.heads_view(attn, B, L, H, hd), lse1,
-                         kv_pad_ones=(hdp - hd) >= 8)
+            if not kept_attn:
+                ops.attn_fwd(q[..., :hd], k[..., :hd], v[..., :hd], ops.heads_view(attn, B, L, H, hd), lse1,
+                             kv_pad_ones=(hdp - hd) >= 8)
             if a8_on and save:  # first steps: record the amax the next step quantises with
                 for j, t in enumerate((q, k, v)):
                     ops.absmax(t.view(B * H * L, hdp)[:, :hd], fp8_hist.cur(F8.ROWS * i + F8.ROW_Q + j))
@@ -397,7 +408,7 @@ class DiTBlock(nn.Module):
             q_wap = F8.Q(W("attn_proj.weight"), F8.E4M3, True, save, hist, R0 + F8.ROW_W + 1, weight=True, remeasure=moved)
             y_sa, X1 = F8.fwd_gate_res(q_attn, q_wap, None, mod, 2 * D, X, L)
         else:
-            y_sa, X1 = ops.linear_fwd_gate_res(attn, W("attn_proj.weight"), None, mod, 2 * D, X, L)
+            y_sa, X1 = ops.linear_fwd_gate_res(attn, W("attn_proj.weight"), None, mod, 2 * D, X, L, want_y=save)
         # --- cross attention (model.py:142-160)
         has_cross = G.has(pre + "q_cross.weight")
         if has_cross:
@@ -457,7 +468,7 @@ class DiTBlock(nn.Module):
                 q_wcp = F8.Q(W("cross_proj.weight"), F8.E4M3, True, save, hist, R0 + F8.ROW_W + 4, weight=True, remeasure=moved)
                 y_ca, X2 = F8.fwd_gate_res(q_catt, q_wcp, None, mod, 5 * D, X1, L)
             else:
-                y_ca, X2 = ops.linear_fwd_gate_res(catt, W("cross_proj.weight"), None, mod, 5 * D, X1, L)
+                y_ca, X2 = ops.linear_fwd_gate_res(catt, W("cross_proj.weight"), None, mod, 5 * D, X1, L, want_y=save)
         else:
             X2 = X1
             f8c = False
@@ -483,9 +494,17 @@ class DiTBlock(nn.Module):
             if hist is not None:
                 G.recast = False  # every weight of the block has recorded its current amax
         else:
-            hpre, hact = ops.linear_fwd_gelu(xn3, W("mlp.0.weight"), W("mlp.0.bias"))
-            y_mlp, X3 = ops.linear_fwd_gate_res(hact, W("mlp.2.weight"), W("mlp.2.bias"), mod, 8 * D, X2, L)
+            hpre, hact = ops.linear_fwd_gelu(xn3, W("mlp.0.weight"), W("mlp.0.bias"), want_pre=save)
+            if replay is not None:  # the backward reads y_mlp only: the store epilogue writes the same bits
+                y_mlp, X3 = ops.linear_fwd(hact, W("mlp.2.weight"), W("mlp.2.bias")), None
+            else:
+                y_mlp, X3 = ops.linear_fwd_gate_res(hact, W("mlp.2.weight"), W("mlp.2.bias"), mod, 8 * D, X2, L,
+                                                    want_y=save)
         bs = None
+        if keep is not None and not save:
+            bs = _Saved()
+            bs.X, bs.mod = X, mod
+            bs.attn, bs.lse1 = (attn, lse1) if keep == "selective" else (None, None)
         if save:
             bs = _Saved()
             bs.mod, bs.X, bs.X1, bs.X2 = mod, X, X1, X2
@@ -713,6 +732,50 @@ class _Saved:
     pass
 
 
+RECOMPUTE_MODES = ("none", "full", "selective")
+_FP8_RECOMPUTE = ("enable_fp8() and enable_recompute() cannot be combined: the fp8 producers write amax-history rows "
+                  "during the forward pass, which a replayed forward would write a second time")
+
+
+def activation_bytes(dit, B: int, latent_shape, Lc: int, mode: str = "none") -> Dict[str, int]:
+    """Bytes of the tensors a grad-enabled forward of `dit` keeps inside its blocks for the backward pass, from their
+    shapes alone (no GPU): latent_shape = (T, H, W) of the input latents, Lc = context length.
+      per_block   what ONE block keeps in `mode`
+      kept        depth x per_block (+ nothing else: the root-level saves are the same in every mode)
+      transient   one block's full set of intermediates -- what a replay holds between a block's second `_fwd` and
+                  the end of its `_bwd` (0 in mode "none", whose `kept` already is depth x that)
+    bf16 fp8-free path; the lists mirror the `bs.*` assignments of DiTBlock._fwd."""
+    if mode not in RECOMPUTE_MODES:
+        raise ValueError(f"activation_bytes: mode must be one of {RECOMPUTE_MODES}, got {mode!r}")
+    D, H, hd = dit.hidden_size, dit.num_heads, dit.head_dim
+    hdp = HDP_OF[hd]
+    T, Hh, Ww = latent_shape
+    L = (T // dit.time_patch_size) * (Hh // dit.patch_size) * (Ww // dit.patch_size) + N_REG
+    R = B * L
+    Dm = int(D * dit.mlp_ratio)
+    cross = dit.cross_attn_input_size is not None
+    mod = 4 * B * 9 * D
+    lse = 4 * B * H * L
+    full = 2 * R * D * 3                 # X, X1, X2 (X1 is X2 without cross-attention: one tensor)
+    full += 2 * R * D + 4 * R            # xn1, rstd1
+    full += 2 * R * 3 * D                # qkv
+    full += 2 * 3 * B * H * L * hdp      # q, k, v (head-major, rows padded to hdp)
+    full += 2 * R * D + lse              # attn, lse1
+    full += 2 * R * D                    # y_sa
+    if cross:
+        full += 2 * R * D * 4 + 4 * R + lse  # xn2, qc, catt, y_ca, rstd2, lse2
+        full += 2 * B * Lc * 2 * D           # ckv
+    else:
+        full -= 2 * R * D                # (no X2 of its own)
+    full += 2 * R * D + 4 * R            # xn3, rstd3
+    full += 2 * R * Dm * 2               # hpre, hact
+    full += 2 * R * D                    # y_mlp
+    full += mod
+    per_block = {"none": full, "full": 2 * R * D + mod, "selective": 2 * R * D + mod + 2 * R * D + lse}[mode]
+    return {"per_block": per_block, "kept": dit.depth * per_block, "transient": 0 if mode == "none" else full,
+            "rows": R}
+
+
 def _offsets(groups):
     off = 0
     for g in groups:
@@ -776,6 +839,7 @@ class DiT(nn.Module):
         self.fp8 = False   # enable_fp8(): qkv / mlp GEMMs on the fp8 MFMA path (fp8.py; BASELINE config 5)
         self.fp8_attn = 0  # ... and the attention products (1: self-attention, 2: cross-attention too)
         self.fp8_lin = False   # ... and the four remaining linears of a block
+        self.recompute = "none"  # enable_recompute(): what the forward keeps for the backward ("none" | "full" | "selective")
 
     def enable_fp8(self, on: bool = True, attention: bool = True, all_linears: bool = True,
                    cross_attention: bool = True):
@@ -785,10 +849,29 @@ class DiT(nn.Module):
         `cross_attention=False` keeps the cross-attention products (L x 512 context keys) on the bf16 kernels: in fp8
         they are 1.1 % of the step faster at the C3b shape and leave the 200-step loss curve where it was, at a
         cross-attention output 4.6 % instead of 0.3 % from the fp32 oracle."""
+        if on and self.recompute != "none":
+            raise ValueError(_FP8_RECOMPUTE)
         self.fp8 = bool(on)
         self.fp8_attn = (2 if cross_attention else 1) if (on and attention) else 0  # 0 none, 1 self, 2 self + cross
         self.fp8_lin = bool(on and all_linears)  # attn_proj, q_cross, context_kv, cross_proj too (qkv / MLP always)
         self._fp8_hist = None  # fp8.AmaxHistory: 6 rows per block (gelu(fc1), d fc2-in, xn1, xn3, d mlp-out, d qkv)
+        return self
+
+    def enable_recompute(self, mode: str = "selective"):
+        """Activation recomputation: what the forward pass keeps per block for the hand-written backward.
+          "none"       every intermediate of `_fwd` (27 D bf16 elements per token row and block);
+          "full"       the block's input token buffer and its modulation row; `_backward_impl` runs the block's `_fwd`
+                       again right before its `_bwd`, so only ONE block's intermediates exist at a time;
+          "selective"  additionally the self-attention output and its log-sum-exp (2 D per row): the replay does not
+                       launch the self-attention forward, the one kernel that dominates a long clip's forward.
+        The replay launches the forward's own fixed-order kernels on the same inputs: gradients are bit-identical to
+        "none" in deterministic mode.  Not together with enable_fp8() (the fp8 producers record amax rows
+        during the forward; a replay would record them twice).  Returns self."""
+        if mode not in RECOMPUTE_MODES:
+            raise ValueError(f"enable_recompute: mode must be one of {RECOMPUTE_MODES}, got {mode!r}")
+        if mode != "none" and self.fp8:
+            raise ValueError(_FP8_RECOMPUTE)
+        self.recompute = mode
         return self
 
     # --------------------------------------------------------------------- parameters ----
@@ -946,12 +1029,14 @@ class DiT(nn.Module):
             wt, bt, _, _ = self._adaln_tables()
             mods = ops.small_linear_fwd_batched(cvec, wt, bt, self.depth, 9 * D, 1)
         v0 = None
+        keep = self.recompute if (save and self.recompute != "none") else None  # blocks keep their inputs, not their work
         for i in range(self.depth):
             if fs is not None:
                 fs.pre_forward_block(i)
             X, v, bs = self.blocks[i]._fwd(self.block_group(i), f"blocks.{i}.", X, ctx2d, cvec, v0, cos, sin, B, L, Lc,
-                                           save, (self._fp8_hist, i, self.fp8_attn, self.fp8_lin, q_ctx) if self.fp8 else None,
-                                           mods[i] if mods is not None else None)
+                                           save and keep is None,
+                                           (self._fp8_hist, i, self.fp8_attn, self.fp8_lin, q_ctx) if self.fp8 else None,
+                                           mods[i] if mods is not None else None, keep=keep)
             if v0 is None:
                 v0 = v
             if save:
@@ -962,6 +1047,7 @@ class DiT(nn.Module):
             sv.v0 = v0
             sv.x_last = X
             sv.batched_adaln = mods is not None
+            sv.recompute = keep is not None
 
         # final layer (model.py:386-401)
         fmod = ops.small_linear_fwd(cvec, R.w("final_modulation.1.weight"), R.w("final_modulation.1.bias"), 1)
@@ -1016,10 +1102,17 @@ class DiT(nn.Module):
         for i in reversed(range(self.depth)):
             if fs is not None:
                 fs.pre_backward_block(i)
-            dX = self.blocks[i]._bwd(self.block_group(i), f"blocks.{i}.", sv.blocks[i], dX, sv, dc, dv0, B, L, Lc,
+            bs = sv.blocks[i]
+            if sv.recompute:
+                # replay: the block's forward kernels once more, on its kept input and the same conditioning / RoPE rows /
+                # block-0 v (sv.v0 stays the v handed out in the first forward; block 0 makes its own copy again)
+                _, _, bs = self.blocks[i]._fwd(self.block_group(i), f"blocks.{i}.", bs.X, sv.ctx2d, sv.cvec,
+                                               sv.v0 if i > 0 else None, sv.cos, sv.sin, B, L, Lc, True, None, bs.mod,
+                                               replay=bs)
+            dX = self.blocks[i]._bwd(self.block_group(i), f"blocks.{i}.", bs, dX, sv, dc, dv0, B, L, Lc,
                                      i == 0, (self._fp8_hist, i, self.fp8_attn, self.fp8_lin, sv.q_ctx) if self.fp8 else None,
                                      dmods[i] if dmods is not None else None)
-            sv.blocks[i] = None
+            sv.blocks[i] = bs = None
             if fs is not None:
                 fs.post_backward_block(i)
         if dmods is not None:  # adaLN weight / bias gradients of all blocks and their fan-in to dc: one launch each

@@ -110,22 +110,24 @@ def linear_fwd(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = 
     return y
 
 
-def linear_fwd_gelu(x, W, bias):
-    """(pre, act) = (x W^T + b, gelu_erf(pre))   (model.py:84-85)."""
+def linear_fwd_gelu(x, W, bias, want_pre: bool = True):
+    """(pre, act) = (x W^T + b, gelu_erf(pre))   (model.py:84-85).  want_pre=False: only `act` is stored (a forward
+    that keeps nothing for a backward); `pre` comes back as None and `act` has the same bits."""
     M, K = x.shape
     N = W.shape[0]
-    pre = torch.empty(M, N, dtype=bf16, device=x.device)
+    pre = torch.empty(M, N, dtype=bf16, device=x.device) if want_pre else None
     act = torch.empty(M, N, dtype=bf16, device=x.device)
     gemm(VDS_NT, EPI_BIAS_GELU, M, N, K, x, x.stride(0), W, W.stride(0), pre, N, act, N, bias=bias)
     return pre, act
 
 
-def linear_fwd_gate_res(x, W, bias, mod, gate_col: int, res, rows_per_batch: int):
+def linear_fwd_gate_res(x, W, bias, mod, gate_col: int, res, rows_per_batch: int, want_y: bool = True):
     """y = x W^T + b ; x_new = res + y * gate[b]  (model.py:138-139,159-160,165).
-    mod: f32 [B, 9D] modulation table, gate at column gate_col."""
+    mod: f32 [B, 9D] modulation table, gate at column gate_col.  want_y=False: only `x_new` is stored (`y` is read by
+    the backward pass alone); `y` comes back as None and `x_new` has the same bits."""
     M, K = x.shape
     N = W.shape[0]
-    y = torch.empty(M, N, dtype=bf16, device=x.device)
+    y = torch.empty(M, N, dtype=bf16, device=x.device) if want_y else None
     xn = torch.empty(M, N, dtype=bf16, device=x.device)
     gate = mod[:, gate_col:]
     gemm(VDS_NT, EPI_GATE_RES, M, N, K, x, x.stride(0), W, W.stride(0), y, N, xn, N, bias=bias, aux=res,
