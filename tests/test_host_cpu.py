@@ -86,3 +86,31 @@ def test_use_rope_false_keeps_the_reference_state_dict_key():
     import pytest
     with pytest.raises((AttributeError, RuntimeError)):
         m(torch.zeros(1, 16, 4, 8, 8), torch.zeros(1, 4, 4096), torch.zeros(1))
+
+
+def test_set_deterministic_keeps_its_flag_when_the_library_refuses(monkeypatch):
+    """ops.set_deterministic(True) with a library handle that rejects the call (a negative return code): the error is
+    raised and `is_deterministic()` stays False -- the model must not assume fixed-order sums the library did not switch
+    on.  An accepted call sets it."""
+    import pytest
+    from video_diffusion_speedrun_amd import _lib, ops
+
+    class Stub:
+        def __init__(self, rc):
+            self.rc, self.calls = rc, []
+
+        def vds_set_deterministic(self, on, ws, nbytes):
+            self.calls.append((on, bool(ws), nbytes))
+            return self.rc
+
+    monkeypatch.setattr(ops, "_det_ws", [None])
+    refuse = Stub(-1)
+    monkeypatch.setattr(_lib, "load", lambda: refuse)
+    with pytest.raises(ValueError):
+        ops.set_deterministic(True, 4096, device="cpu")
+    assert refuse.calls == [(1, True, 4096)]
+    assert ops.is_deterministic() is False
+    accept = Stub(0)
+    monkeypatch.setattr(_lib, "load", lambda: accept)
+    assert ops.set_deterministic(True, 4096, device="cpu") is False  # (returns the previous mode)
+    assert ops.is_deterministic() is True

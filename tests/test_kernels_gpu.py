@@ -4,10 +4,15 @@ C ABI (ctypes) -- nothing here can pass on a silent fallback because there is no
 import math
 import os
 
+import sys
+
 import pytest
 import torch
 
 from oracle import dit_oracle as O
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import residual_v_cases as RV  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -950,6 +955,64 @@ def test_dv0_reduce_equals_the_per_block_accumulation(ops, hd, hdp, n):
     ops.dv0_reduce([b[2] for b in blocks[:1]], [b[4] for b in blocks[:1]], out, B, H, L, hd, hdp, accumulate=True)
     want = acc[..., :hd] + (1.0 - blocks[0][4].float()) * blocks[0][2][..., :hd].float()
     close("dv0.accumulate", out[..., :hd], want, 1e-6)
+
+
+@pytest.mark.parametrize("hd,hdp", RV.DV0_HEADS)
+@pytest.mark.parametrize("n", RV.DV0_N)
+def test_dv0_reduce_matches_float64_reference_with_distinct_lambdas(ops, parity_log, n, hd, hdp):
+    """vds_dv0_reduce as DiTBlock._bwd calls it, against plain float64 torch on the CPU (not against another kernel):
+    want = sum_i (1 - lam_i) dv_i[..., :hd] with lambdas that are distinct in bf16, not symmetric about 0.5, one below 0
+    and some above 1, and dv_i scaled by 1 + i, so that a lambda taken from the wrong pointer moves the result by far more
+    than rounding (tests/helpers/residual_v_cases.py).  n sits on both sides of the model's chunk of 9 and of the 32
+    pointers one launch takes; 148 rows end inside a workgroup; the pad columns of every dv_i hold NaN (never read) and
+    those of the output a sentinel (never written).
+
+    Bound, per element: the kernel forms each term in fp32 and adds the n of them in fp32 -- one rounding for 1 - lam, one
+    per product, one per addition -- so |got - want| <= (n + 2) 2^-24 sum_i |(1 - lam_i) dv_i|; asserted with a factor 2.
+    Detection power: the same reference with the lambdas rotated by one position breaks that bound at more than half of
+    the elements (at all of them, for every n here), so no wrong pairing passes.
+
+    Two forms: one call over the whole list, and the model's chunks -- nine entries at a time from the end of the list
+    downwards, the first overwriting the accumulator, the rest adding to it.  The kernel adds its terms one after the other
+    in pointer order onto an accumulator that starts at zero or at the fp32 value in `out`, and a launch boundary (32
+    pointers, or a chunk) only stores that fp32 accumulator and loads it again: the order of the additions is the order
+    of the list, however it is cut.  The one call is therefore given the list in the order the chunks walk it, and the
+    two results must be the same bits; a third call in ascending block order (another summation order) is held to the
+    bound alone."""
+    B, H, L = RV.DV0_DIMS
+    dvs, lams = RV.dv0_inputs(n, hd, hdp)
+    want, scale = RV.dv0_reference(dvs, lams, hd)
+    bound = RV.dv0_bound(n, scale)
+    if n > 1:
+        wrong, _ = RV.dv0_reference(dvs, RV.dv0_rotated(lams), hd)
+        assert ((wrong - want).abs() > bound).double().mean().item() > 0.5
+    dvd, lamd = [t.cuda() for t in dvs], [t.cuda() for t in lams]
+    chunks = RV.dv0_chunks(n)
+    walk = [i for c in chunks for i in c]
+
+    def fresh():
+        return torch.full((B, H, L, hdp), RV.DV0_SENTINEL, dtype=f32, device="cuda")
+
+    one, asc, chunked = fresh(), fresh(), fresh()
+    ops.dv0_reduce([dvd[i] for i in walk], [lamd[i] for i in walk], one, B, H, L, hd, hdp)
+    ops.dv0_reduce(dvd, lamd, asc, B, H, L, hd, hdp)
+    for k, c in enumerate(chunks):
+        ops.dv0_reduce([dvd[i] for i in c], [lamd[i] for i in c], chunked, B, H, L, hd, hdp, accumulate=k > 0)
+    torch.cuda.synchronize()
+    worst = {}
+    for name, got in (("one_call", one), ("ascending", asc), ("chunked", chunked)):
+        g = got.cpu()
+        worst[name] = ((g[..., :hd].double() - want).abs() / bound).max().item()
+    parity_log("dv0_reduce_vs_float64", n=n, hd=hd, err_over_bound=worst)
+    print(f"dv0_reduce n={n} hd={hd}: worst |got - want| / bound {worst}")
+    for name, got in (("one_call", one), ("ascending", asc), ("chunked", chunked)):
+        g = got.cpu()
+        assert torch.isfinite(g).all(), name
+        if hdp > hd:
+            assert bool((g[..., hd:] == RV.DV0_SENTINEL).all()), name  # pad columns untouched
+        bad = (g[..., :hd].double() - want).abs() > bound
+        assert not bool(bad.any()), (name, int(bad.sum()), worst[name])
+    assert torch.equal(one, chunked)
 
 
 # ------------------------------------------------------------------ deterministic mode ----

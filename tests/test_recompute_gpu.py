@@ -232,8 +232,8 @@ def test_three_optimizer_steps_are_bit_equal(vds, deterministic, accumulate):
 def test_shard_runtime_on_one_gpu_is_bit_equal(vds, deterministic, monkeypatch):
     """apply_fsdp forced on with a 1-rank communicator (as test_shard_runtime_on_one_gpu_matches_unsharded does), resident
     and reshard_after_forward: the replay sits between pre_backward_block and post_backward_block, where the block's
-    weights are gathered.  Every lambda_param stays at its initial 0.5 (the reshard runtime's deferred dv0 reduction reads
-    lambda through a view that can go stale beyond the slot count: a known open defect this test does not depend on)."""
+    weights are gathered.  Five blocks on the ring's three buffers, every mixing block with a lambda of its own: a buffer
+    is refilled while the deferred dv0 reduction is pending, and a lambda read from it would show in block 0's gradients."""
     import torch.distributed as dist
     from video_diffusion_speedrun_amd.fsdp import apply_fsdp
     from video_diffusion_speedrun_amd import comm
@@ -243,10 +243,11 @@ def test_shard_runtime_on_one_gpu_is_bit_equal(vds, deterministic, monkeypatch):
         os.environ.setdefault("MASTER_PORT", "29541")
         dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
     try:
-        cfg = O.DiTConfig(in_channels=16, hidden_size=128, depth=4, num_heads=2, cross_attn_input_size=64,
+        cfg = O.DiTConfig(in_channels=16, hidden_size=128, depth=5, num_heads=2, cross_attn_input_size=64,
                           residual_v=True, train_bias_and_rms=False)
         P = O.init_params(cfg, seed=31, randomize_zero_init=True, init_std_factor=1.0)
-        assert all(float(P[f"blocks.{i}.lambda_param"]) == 0.5 for i in range(cfg.depth))
+        for i in range(1, cfg.depth):
+            P[f"blocks.{i}.lambda_param"] = torch.tensor([0.2 + 0.15 * i])
         g = torch.Generator().manual_seed(6)
         x = torch.randn(2, 16, 4, 8, 8, generator=g).to(bf16).cuda()
         c = torch.randn(2, 16, 64, generator=g).to(bf16).cuda()

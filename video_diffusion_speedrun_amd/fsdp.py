@@ -67,6 +67,10 @@ class ShardRuntime:
     """Stream / event choreography of the per-group collectives around DiT's explicit
     forward / backward kernel sequences (model.py hooks `pre_forward_*` ... `post_backward_*`)."""
 
+    # a block's gathered weights stay valid from its backward to the end of the pass (model.py keeps views of them:
+    # the lambdas of the deferred residual-V reduction); ReshardRuntime hands the buffer to another block instead
+    releases_params = False
+
     def __init__(self, model, cast_fn, process_group=None):
         self.model = model
         self.cast_fn = cast_fn
@@ -184,6 +188,11 @@ class ShardRuntime:
     def post_forward_root(self):
         pass
 
+    def capture_ended(self):
+        """GraphedTrainStep: the step just recorded into a graph launched nothing; events recorded while capturing
+        belong to the graph and must not be waited for by eager work"""
+        self.gather_ev = [None] * len(self.gather_ev)
+
     # ---- backward -------------------------------------------------------------------------
     def pre_backward_root(self):
         for gi in range(len(self.model._groups)):  # no-grad forwards may have left events unconsumed
@@ -218,6 +227,8 @@ class ReshardRuntime(ShardRuntime):
     A buffer is handed to the next gather with an event recorded on the compute stream at release: the communication
     stream waits for it, so a gather never overwrites weights a queued kernel still reads.  The root group (patch
     embedding, time MLP, final layer: used at both ends of both passes) stays resident."""
+
+    releases_params = True
 
     def __init__(self, model, cast_fn, process_group=None):
         super().__init__(model, cast_fn, process_group)
@@ -277,6 +288,20 @@ class ReshardRuntime(ShardRuntime):
         g = self.model._groups[gi]
         g.full = None
         g.gathered = False
+
+    def capture_ended(self):
+        """the captured step released every block; the release events it left in `slot_free_ev` were recorded into the
+        graph, and the next eager gather (a validation or sampling forward between replays) would wait on one.  They
+        are dropped: that gather is ordered behind everything on the compute stream, the replays included, by
+        pre_forward_root's `_comm_waits_compute`.  The ring goes back to its initial state."""
+        super().capture_ended()
+        for gi in range(1, len(self.model._groups)):
+            if self.slot_of[gi] is not None:
+                g = self.model._groups[gi]
+                g.full, g.gathered = None, False
+                self.slot_of[gi] = None
+        self.slot_free_ev = [None] * self.n_slots
+        self.free_slots = list(range(self.n_slots))
 
     # ---- forward --------------------------------------------------------------------------
     def pre_forward_root(self):

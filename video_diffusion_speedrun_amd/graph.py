@@ -111,6 +111,7 @@ class GraphedTrainStep:
                 # what one step issues (the memory-bounded runtime gathers most blocks twice): replays count it
                 self._per_step = (fs.n_all_gather - counts[0], fs.n_reduce_scatter - counts[1])
                 fs.n_all_gather, fs.n_reduce_scatter = counts  # the capture launched nothing
+                fs.capture_ended()  # (drops the events recorded into the graph: an eager forward may follow a replay)
         self.opt._step = step0  # the capture launched nothing: `advance()` counts the step at replay time
         self.graph, self.loss = g, loss
 

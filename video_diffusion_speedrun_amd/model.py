@@ -689,7 +689,15 @@ class DiTBlock(nn.Module):
         defer = getattr(sv, "dv_terms", None)  # DiT.backward: [(dv, lambda)] of the mixed blocks, summed at block 0
         mix_mode = (2 if defer is not None else 1) if bs.mix else 0
         if mix_mode == 2:
-            defer.append((dv, W("lambda_param")))  # (keeps dv alive until the next reduction)
+            lam = W("lambda_param")
+            snap = getattr(sv, "lam_snap", None)
+            if snap is not None:
+                # the gathered copy this view points into is released behind this block and refilled with another block's
+                # weights before the reduction runs (fsdp.ReshardRuntime): the reduction reads a copy of the value instead
+                k, sv.lam_used = sv.lam_used, sv.lam_used + 1
+                snap[k:k + 1].copy_(lam)
+                lam = snap[k:k + 1]
+            defer.append((dv, lam))  # (keeps dv alive until the next reduction)
         # summed every _DV0_CHUNK blocks (and at block 0): at most that many dv tensors stay alive (DiT-XL, B = 12: 9 x 303 MB
         # instead of 27 x 303 MB = 8 GB), for one more read-modify-write of the fp32 accumulator per chunk
         if dv0 is not None and defer and (first or len(defer) >= _DV0_CHUNK):
@@ -1099,6 +1107,10 @@ class DiT(nn.Module):
         hdp = HDP_OF[hd]
         dv0 = torch.zeros(B, H, L, hdp, dtype=f32, device=dev) if (self.residual_v and self.depth > 1) else None
         sv.dv_terms = [] if (_DV0_DEFER and dv0 is not None) else None
+        # one bf16 lambda per deferred block, copied when the block defers: only where the runtime releases a block's
+        # gathered weights before the deferred reduction reads them (resident and unsharded weights stay where they are)
+        snap = sv.dv_terms is not None and fs is not None and fs.releases_params
+        sv.lam_snap, sv.lam_used = (torch.empty(self.depth, dtype=bf16, device=dev) if snap else None), 0
         for i in reversed(range(self.depth)):
             if fs is not None:
                 fs.pre_backward_block(i)

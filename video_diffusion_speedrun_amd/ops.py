@@ -90,13 +90,15 @@ def set_deterministic(on: bool, workspace_bytes: int = 1 << 30, device="cuda") -
     if on:
         ws = torch.empty(int(workspace_bytes), dtype=torch.uint8, device=device)
         prev = lib.vds_set_deterministic(1, ws.data_ptr(), ws.numel())
+        if prev < 0:  # rejected: the library's mode and workspace are what they were, and so is is_deterministic()
+            raise ValueError("vds_set_deterministic")
         _det_ws[0] = ws
     else:
         torch.cuda.synchronize()
         prev = lib.vds_set_deterministic(0, None, 0)
+        if prev < 0:
+            raise ValueError("vds_set_deterministic")
         _det_ws[0] = None
-    if prev < 0:
-        raise ValueError("vds_set_deterministic")
     return bool(prev)
 
 
