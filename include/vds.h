@@ -206,6 +206,15 @@ typedef struct vds_attn_args {
 
 int vds_attn_fwd(const vds_attn_args* args, vds_stream_t stream);
 int vds_attn_bwd(const vds_attn_args* args, vds_stream_t stream);
+/* The same two calls with per-sample key counts: kv_lens = device pointer to B int32, each in [0, Lk] (values outside
+ * are clamped); the kernels read it, never the host, so a captured graph replays with new lengths.  Sample b attends
+ * keys 0 .. kv_lens[b]-1 only: o, lse and dq are those of that restricted attention, rows < kv_lens[b] of dk / dv get
+ * its gradient and rows kv_lens[b] .. Lk-1 are WRITTEN as exact zeros.  kv_lens[b] == 0 means "no context": o, dq,
+ * dk, dv = 0 and lse = 0 for that sample, no NaN.  Key tiles past the count are skipped, not computed and masked; the
+ * launch geometry and the workspace (vds_attn_bwd_workspace_bytes) stay functions of Lk.  kv_lens == NULL forwards to
+ * vds_attn_fwd / vds_attn_bwd.  kv_pad_ones 0 and 2 (cross-attention); kv_pad_ones == 1 with lengths: VDS_ERR_ARG. */
+int vds_attn_fwd_kvlen(const vds_attn_args* args, const int32_t* kv_lens, vds_stream_t stream);
+int vds_attn_bwd_kvlen(const vds_attn_args* args, const int32_t* kv_lens, vds_stream_t stream);
 /* K / V of a cross-attention, token-major bf16 rows [B*Lk, ld] with head h of K at columns k_col0 + h*hd and of V at
  * v_col0 + h*hd (the context_kv output, model.py:150-156), copied into head-major padded rows kp, vp [B,H,Lk,hdp]
  * (hdp >= hd + 8, multiples of 8) with the ones columns of vds_attn_args.kv_pad_ones and zeros in the rest of the pad. */

@@ -57,7 +57,17 @@ struct AttnP {
   float* dkv_part;
   // 16-byte row stores in the 16x16x32 kernels' epilogues (store_block_bf16_t): rows 16-byte aligned
   int wide_o, wide_dq, wide_dkv;
+  // per-sample key counts (vds_attn_*_kvlen): B int32 on the device, read by the KVLEN instances of the kernels only
+  const int* kv_lens;
 };
+
+// Keys of sample b.  KVLEN: kv_lens[b] clamped to [0, Lk] -- b is the same for the whole workgroup, so this is one
+// scalar load; every bound, tile count and mask of the kernel then uses it in place of the launch-wide Lk.
+template <bool KVLEN>
+__device__ __forceinline__ int kv_len_of(const AttnP& p, int b) {
+  if constexpr (KVLEN) return min(max(p.kv_lens[b], 0), p.Lk);
+  else return p.Lk;
+}
 
 // ---- LDS image (a): rows x HDP bf16, 8x32 sub-tiles of 512 B -------------------------------
 template <int HDP>
@@ -180,8 +190,28 @@ __device__ __forceinline__ void store_rows_f32(float* rowp, const f32x16 (&acc)[
         *reinterpret_cast<f32x4*>(rowp + d) = f32x4{acc[db][4 * rg], acc[db][4 * rg + 1], acc[db][4 * rg + 2], acc[db][4 * rg + 3]};
     }
 }
+// zero rows in the two store forms above and below (KVLEN instances: a sample without keys, key rows past its length)
+template <int NDB>
+__device__ __forceinline__ void store_zero_rows(bf16_t* rowp, int hd, int h) {
+  f32x16 z[NDB];
+#pragma unroll
+  for (int i = 0; i < NDB; ++i) z[i] = zero16();
+  store_rows<NDB>(rowp, z, 0.0f, hd, h);
+}
+// (all 64 lanes must call: the wide form of store_block_bf16_t exchanges lanes)
+__device__ __forceinline__ void store_zero_block(bf16_t* row, int hd, int g, bool valid, bool wide) {
+  float z[5][4];
+#pragma unroll
+  for (int db = 0; db < 5; ++db)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) z[db][e] = 0.f;
+  store_block_bf16_t(z, 0.0f, row, hd, g, valid, wide);
+}
 // dk / dv (bf16, strided) = sum over the q_split partials; one thread = 4 consecutive head-dim columns of one
 // (b, h, key, dk | dv) row; dk is scaled by the softmax scale here (the bf16 path does it in store_rows)
+// KVLEN: rows at or past kv_lens[b] are written as zeros and their partials -- which skipped workgroups never wrote --
+// are not read.
+template <bool KVLEN = false>
 __global__ __launch_bounds__(256) void dkv_reduce_kernel(AttnP p) {
   const int hq = p.hd >> 2;
   const long n = (long)p.B * p.H * p.Lk * 2 * hq;
@@ -194,8 +224,11 @@ __global__ __launch_bounds__(256) void dkv_reduce_kernel(AttnP p) {
   const int bh = (int)(row / p.Lk), b = bh / p.H, hh = bh % p.H;
   const long stride = (long)p.B * p.H * p.Lk * 2 * p.hd;
   const float* src = p.dkv_part + (row * 2 + which) * p.hd + 4 * c;
-  f32x4 a = *reinterpret_cast<const f32x4*>(src);
-  for (int sp = 1; sp < p.q_split; ++sp) a += *reinterpret_cast<const f32x4*>(src + sp * stride);
+  f32x4 a = {0.f, 0.f, 0.f, 0.f};
+  if (!KVLEN || key < kv_len_of<KVLEN>(p, b)) {
+    a = *reinterpret_cast<const f32x4*>(src);
+    for (int sp = 1; sp < p.q_split; ++sp) a += *reinterpret_cast<const f32x4*>(src + sp * stride);
+  }
   const float mul = which == 0 ? p.scale : 1.0f;
   bf16_t* dst = which == 0 ? p.dk + b * p.dk_sb + hh * p.dk_sh + (long)key * p.dk_sl
                            : p.dv + b * p.dv_sb + hh * p.dv_sh + (long)key * p.dv_sl;
@@ -316,7 +349,9 @@ struct DmaStage {
 };
 
 // ---- forward kernel: lazy softmax + LDS-DMA staging (PIPE: explicit fragment prefetch) ---------
-template <int HDP, int HDQ, int WPS, bool PIPE>
+// KVLEN (all forward kernels): sample b attends its first kv_lens[b] keys; the K / V bounds, the tile count and the
+// ragged-tile mask follow that count, and a sample without keys gets O = 0, lse = 0 before anything is staged.
+template <int HDP, int HDQ, int WPS, bool PIPE, bool KVLEN = false>
 __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, TILE = 64 * HDP * 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -326,10 +361,20 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qrow = qt * 128 + wave * 32 + (lane & 31);
+  const int Lk = kv_len_of<KVLEN>(p, b);
+  if constexpr (KVLEN) {
+    if (Lk == 0) {  // no context: O = 0, lse = 0
+      if (qrow < p.Lq) {
+        store_zero_rows<NDB>(p.o + b * p.o_sb + hh * p.o_sh + (long)qrow * p.o_sl, p.hd, h);
+        if (h == 0) p.lse[((long)b * p.H + hh) * p.Lq + qrow] = 0.0f;
+      }
+      return;
+    }
+  }
 
   const __amdgpu_buffer_rsrc_t rq = slice_rsrc(p.q + b * p.q_sb + hh * p.q_sh, p.q_sl, p.Lq, p.hd);
-  const srd_t rk = slice_srd(p.k + b * p.k_sb + hh * p.k_sh, p.k_sl, p.Lk, p.hd);
-  const srd_t rv = slice_srd(p.v + b * p.v_sb + hh * p.v_sh, p.v_sl, p.Lk, p.hd);
+  const srd_t rk = slice_srd(p.k + b * p.k_sb + hh * p.k_sh, p.k_sl, Lk, p.hd);
+  const srd_t rv = slice_srd(p.v + b * p.v_sb + hh * p.v_sh, p.v_sl, Lk, p.hd);
 
   DmaStage<64, HDP> dk, dv;
   dk.init(p.k_sl, p.hd, wave, lane);
@@ -352,7 +397,7 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   for (int i = 0; i < NDB; ++i) o[i] = zero16();
   float m = -1e30f, l = 0.f;
   const float c = p.scale * LOG2E;
-  const int nkt = (p.Lk + 63) / 64;
+  const int nkt = (Lk + 63) / 64;
 #pragma unroll
   for (int ks = 0; ks < KSQ; ++ks) retire(qf[ks]);
   VDS_WAIT_VM(0);
@@ -367,7 +412,7 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
     }
     const char* kt = smem + par * 2 * TILE;
     const char* vt = kt + TILE;
-    const bool ragged = (j == nkt - 1) && (p.Lk & 63);
+    const bool ragged = (j == nkt - 1) && (Lk & 63);
     if constexpr (PIPE) {
       bf16x8 k0[KSQ], k1[KSQ];
       load_kfrags<HDP, KSQ>(k0, kt, 0, lane);
@@ -382,8 +427,8 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
       if (ragged) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          if (j * 64 + acc_row(r, h) >= p.Lk) s0[r] = -INFINITY;
-          if (j * 64 + 32 + acc_row(r, h) >= p.Lk) s1[r] = -INFINITY;
+          if (j * 64 + acc_row(r, h) >= Lk) s0[r] = -INFINITY;
+          if (j * 64 + 32 + acc_row(r, h) >= Lk) s1[r] = -INFINITY;
         }
       }
       bf16x8 pf[2];
@@ -409,7 +454,7 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
         if (ragged) {
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            if (j * 64 + kb * 32 + acc_row(r, h) >= p.Lk) s[r] = -INFINITY;
+            if (j * 64 + kb * 32 + acc_row(r, h) >= Lk) s[r] = -INFINITY;
         }
         bf16x8 pf[2];
         lazy_softmax<NDB>(s, c, m, l, o, pf);
@@ -482,7 +527,7 @@ __device__ __forceinline__ void ones_softmax(f32x16& s, float& m, bf16x8& q_ones
   pf[1] = acc_frag(s, 1);
 }
 
-template <int HDP, int HDQ, bool ONES>
+template <int HDP, int HDQ, bool ONES, bool KVLEN = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_wide_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, TILE = 64 * HDP * 2;
   static_assert(!ONES || (HDP == 96 && HDQ == 80), "ones columns: head_dim 72 layout");
@@ -494,10 +539,24 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_wide_kernel(AttnP p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qrow0 = qt * 256 + wave * 64 + (lane & 31);  // query of block 0; block 1 = + 32
   const int hd_kv = ONES ? p.hd + 8 : p.hd;               // columns of K / V rows that are fetched
+  const int Lk = kv_len_of<KVLEN>(p, b);
+  if constexpr (KVLEN) {
+    if (Lk == 0) {  // no context: O = 0, lse = 0
+#pragma unroll
+      for (int qb = 0; qb < 2; ++qb) {
+        const int qrow = qrow0 + 32 * qb;
+        if (qrow < p.Lq) {
+          store_zero_rows<NDB>(p.o + b * p.o_sb + hh * p.o_sh + (long)qrow * p.o_sl, p.hd, h);
+          if (h == 0) p.lse[((long)b * p.H + hh) * p.Lq + qrow] = 0.0f;
+        }
+      }
+      return;
+    }
+  }
 
   const __amdgpu_buffer_rsrc_t rq = slice_rsrc(p.q + b * p.q_sb + hh * p.q_sh, p.q_sl, p.Lq, p.hd);
-  const srd_t rk = slice_srd(p.k + b * p.k_sb + hh * p.k_sh, p.k_sl, p.Lk, hd_kv);
-  const srd_t rv = slice_srd(p.v + b * p.v_sb + hh * p.v_sh, p.v_sl, p.Lk, hd_kv);
+  const srd_t rk = slice_srd(p.k + b * p.k_sb + hh * p.k_sh, p.k_sl, Lk, hd_kv);
+  const srd_t rv = slice_srd(p.v + b * p.v_sb + hh * p.v_sh, p.v_sl, Lk, hd_kv);
 
   DmaStage<64, HDP> dk, dv;
   dk.init(p.k_sl, hd_kv, wave, lane);
@@ -536,7 +595,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_wide_kernel(AttnP p) {
     for (int i = 0; i < NDB; ++i) o[qb][i] = zero16();
   float m[2], l[2] = {0.f, 0.f};
   m[0] = m[1] = ONES ? 0.f : -1e30f;
-  const int nkt = (p.Lk + 63) / 64;
+  const int nkt = (Lk + 63) / 64;
   VDS_WAIT_VM(0);
   __syncthreads();
 
@@ -551,7 +610,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_wide_kernel(AttnP p) {
     }
     const char* kt = smem + par * 2 * TILE;
     const char* vt = kt + TILE;
-    const bool ragged = (j == nkt - 1) && (p.Lk & 63);
+    const bool ragged = (j == nkt - 1) && (Lk & 63);
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
       bf16x8 kfr[KSQ];
@@ -568,7 +627,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_wide_kernel(AttnP p) {
         if (ragged) {
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            if (j * 64 + kb * 32 + acc_row(r, h) >= p.Lk) { s0[r] = -INFINITY; s1[r] = -INFINITY; }
+            if (j * 64 + kb * 32 + acc_row(r, h) >= Lk) { s0[r] = -INFINITY; s1[r] = -INFINITY; }
         }
       }
       bf16x8 vfr[2][NDB];
@@ -705,7 +764,8 @@ __global__ __launch_bounds__(256) void attn_delta_tokmajor_kernel(AttnP p) {
 // columns hd, hd+1 (K holds 1.0 there), dO carries -delta as a (hi, lo) pair at columns hd, hd+4 (V holds
 // 1.0 there): S' = log2 P and dP - delta come straight out of the two MFMA chains, leaving
 // exp2, one multiply and the bf16 pack per element.  Keys past Lk need no mask in either mode.
-template <int HDP, int HDQ, bool ONES>
+// KVLEN (all dQ kernels): the sweep covers the first kv_lens[b] keys of sample b; without keys dQ = 0.
+template <int HDP, int HDQ, bool ONES, bool KVLEN = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, TILE = 64 * HDP * 2;
   static_assert(!ONES || (HDP == 96 && HDQ == 80), "ones columns: head_dim 72 layout");
@@ -717,11 +777,18 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qrow = qt * 128 + wave * 32 + (lane & 31);
   const int hd_kv = ONES ? p.hd + 8 : p.hd;
+  const int Lk = kv_len_of<KVLEN>(p, b);
+  if constexpr (KVLEN) {
+    if (Lk == 0) {  // no context: dQ = 0
+      if (qrow < p.Lq) store_zero_rows<NDB>(p.dq + b * p.dq_sb + hh * p.dq_sh + (long)qrow * p.dq_sl, p.hd, h);
+      return;
+    }
+  }
 
   const __amdgpu_buffer_rsrc_t rq = slice_rsrc(p.q + b * p.q_sb + hh * p.q_sh, p.q_sl, p.Lq, p.hd);
   const __amdgpu_buffer_rsrc_t rdo = slice_rsrc(p.d_o + b * p.do_sb + hh * p.do_sh, p.do_sl, p.Lq, p.hd);
-  const srd_t rk = slice_srd(p.k + b * p.k_sb + hh * p.k_sh, p.k_sl, p.Lk, hd_kv);
-  const srd_t rv = slice_srd(p.v + b * p.v_sb + hh * p.v_sh, p.v_sl, p.Lk, hd_kv);
+  const srd_t rk = slice_srd(p.k + b * p.k_sb + hh * p.k_sh, p.k_sl, Lk, hd_kv);
+  const srd_t rv = slice_srd(p.v + b * p.v_sb + hh * p.v_sh, p.v_sl, Lk, hd_kv);
 
   DmaStage<64, HDP> dk, dv;
   dk.init(p.k_sl, hd_kv, wave, lane);
@@ -767,7 +834,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   f32x16 dq[NDB];
 #pragma unroll
   for (int i = 0; i < NDB; ++i) dq[i] = zero16();
-  const int nkt = (p.Lk + 63) / 64;
+  const int nkt = (Lk + 63) / 64;
   VDS_WAIT_VM(0);
   __syncthreads();  // tile 0 landed
 
@@ -831,7 +898,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
 // ONES (kv_pad_ones, head_dim 72): Q rows are staged WITH their pad, which the delta preprocess filled
 // with -lse*log2(e) (hi, lo); the K fragments are pre-multiplied by scale*log2(e) and hold 1.0 in those
 // two columns, so S comes out of the MFMA as log2 P: no multiply-add and no lse reads per element.
-template <int HDP, int HDQ, bool ONES>
+// KVLEN: rows at or past kv_lens[b] of dK / dV are zeros.  A workgroup whose 128 keys all lie there stores them and
+// leaves (query split: it leaves at once -- dkv_reduce_kernel<true> writes the zeros without reading its partial); the
+// workgroup that holds the boundary runs as usual and clears the accumulators of the rows past it before the store.
+template <int HDP, int HDQ, bool ONES, bool KVLEN = false>
 __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void attn_bwd_dkv_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, Q_TILE = 64 * HDP * 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -853,12 +923,22 @@ __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void att
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int key0 = kt_idx * 128;
   const int krow = key0 + wave * 32 + (lane & 31);
+  const int Lk = kv_len_of<KVLEN>(p, b);
+  if constexpr (KVLEN) {
+    if (key0 >= Lk) {  // no key of this tile is attended
+      if (p.q_split == 1 && krow < p.Lk) {
+        store_zero_rows<NDB>(p.dk + b * p.dk_sb + hh * p.dk_sh + (long)krow * p.dk_sl, p.hd, h);
+        store_zero_rows<NDB>(p.dv + b * p.dv_sb + hh * p.dv_sh + (long)krow * p.dv_sl, p.hd, h);
+      }
+      return;
+    }
+  }
 
   const int hd_q = ONES ? p.hd + 8 : p.hd;  // Q row columns that are staged
   const srd_t rq = slice_srd(p.q + b * p.q_sb + hh * p.q_sh, p.q_sl, p.Lq, hd_q);
   const srd_t rdo = slice_srd(p.d_o + b * p.do_sb + hh * p.do_sh, p.do_sl, p.Lq, p.hd);
-  const __amdgpu_buffer_rsrc_t rk = slice_rsrc(p.k + b * p.k_sb + hh * p.k_sh, p.k_sl, p.Lk, p.hd);
-  const __amdgpu_buffer_rsrc_t rv = slice_rsrc(p.v + b * p.v_sb + hh * p.v_sh, p.v_sl, p.Lk, p.hd);
+  const __amdgpu_buffer_rsrc_t rk = slice_rsrc(p.k + b * p.k_sb + hh * p.k_sh, p.k_sl, Lk, p.hd);
+  const __amdgpu_buffer_rsrc_t rv = slice_rsrc(p.v + b * p.v_sb + hh * p.v_sh, p.v_sl, Lk, p.hd);
   const long nrows = (long)p.B * p.H * p.Lq;
   const long srow0 = ((long)b * p.H + hh) * p.Lq;
   // statistics of this head: delta rows then lse2 rows, each bounded to the head's Lq entries
@@ -979,6 +1059,12 @@ __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void att
     q_tile(j, std::integral_constant<int, 0>{});
     if (j + 1 < j1) q_tile(j + 1, std::integral_constant<int, 1>{});
   }
+  if constexpr (KVLEN) {
+    if (krow >= Lk) {  // P of a zero key row is not zero: its sums are dropped here
+#pragma unroll
+      for (int i = 0; i < NDB; ++i) { dk[i] = zero16(); dv[i] = zero16(); }
+    }
+  }
   if (krow < p.Lk) {
     if (p.q_split > 1) {  // fp32 partial of this query range (an empty range stores zeros); dkv_reduce_kernel finishes
       float* part = p.dkv_part + ((((long)sp * p.B * p.H + bh) * p.Lk + krow) * 2) * p.hd;
@@ -1036,7 +1122,8 @@ __device__ __forceinline__ bf16x8 pack2(const f32x4& a, const f32x4& b) {
 // QPAD = false (round 5, cross-attention: vds_attn_args.kv_pad_ones = 2): the q rows carry no annotated pad (token-major
 // views of a linear layer's output), so only head_dim columns of a q row are staged and the S accumulators START from
 // -lse2 of their queries, read from the statistics this kernel stages beside -delta anyway.
-template <int HDP, bool QPAD = true>
+// KVLEN: as in attn_bwd_dkv_kernel; 16-key blocks past kv_lens[b] are not computed at all (NKB).
+template <int HDP, bool QPAD = true, bool KVLEN = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv16_kernel(AttnP p) {
   static_assert(HDP == 96, "head_dim 72 layout (ones columns at 72, 73)");
   constexpr int KS = HDP / 32, NDB = 5, Q_TILE = 64 * HDP * 2;
@@ -1049,12 +1136,24 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv16_kernel(AttnP p) {
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int key0 = kt_idx * 128 + wave * 32;
+  const int Lk = kv_len_of<KVLEN>(p, b);
+  if constexpr (KVLEN) {
+    if (kt_idx * 128 >= Lk) {  // no key of this tile is attended (all 64 lanes call the store: it exchanges lanes)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) {
+        const int krow = key0 + cb * 16 + (lane & 15);
+        store_zero_block(p.dk + b * p.dk_sb + hh * p.dk_sh + (long)krow * p.dk_sl, p.hd, g, krow < p.Lk, p.wide_dkv);
+        store_zero_block(p.dv + b * p.dv_sb + hh * p.dv_sh + (long)krow * p.dv_sl, p.hd, g, krow < p.Lk, p.wide_dkv);
+      }
+      return;
+    }
+  }
 
   const int hd_q = QPAD ? p.hd + 8 : p.hd;  // QPAD: Q rows are staged with their pad: -lse*log2(e) as (hi, lo) at columns hd, hd+1
   const srd_t rq = slice_srd(p.q + b * p.q_sb + hh * p.q_sh, p.q_sl, p.Lq, hd_q);
   const srd_t rdo = slice_srd(p.d_o + b * p.do_sb + hh * p.do_sh, p.do_sl, p.Lq, p.hd);
-  const __amdgpu_buffer_rsrc_t rk = slice_rsrc(p.k + b * p.k_sb + hh * p.k_sh, p.k_sl, p.Lk, p.hd);
-  const __amdgpu_buffer_rsrc_t rv = slice_rsrc(p.v + b * p.v_sb + hh * p.v_sh, p.v_sl, p.Lk, p.hd);
+  const __amdgpu_buffer_rsrc_t rk = slice_rsrc(p.k + b * p.k_sb + hh * p.k_sh, p.k_sl, Lk, p.hd);
+  const __amdgpu_buffer_rsrc_t rv = slice_rsrc(p.v + b * p.v_sb + hh * p.v_sh, p.v_sl, Lk, p.hd);
   const long nrows = (long)p.B * p.H * p.Lq;
   const long srow0 = ((long)b * p.H + hh) * p.Lq;
   const srd_t rdl = make_srd(p.delta + srow0, (unsigned)(p.Lq * 4));
@@ -1187,7 +1286,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv16_kernel(AttnP p) {
       if (j + 1 < nqt) q_tile(j + 1, std::integral_constant<int, 1>{}, NKBT);
     }
   };
-  const int nkb = min(2, max(0, (p.Lk - key0 + 15) >> 4));  // wave-uniform
+  const int nkb = min(2, max(0, (Lk - key0 + 15) >> 4));  // wave-uniform
   if (nkb == 2) run(std::integral_constant<int, 2>{});
   else if (nkb == 1) run(std::integral_constant<int, 1>{});
   else run(std::integral_constant<int, 0>{});
@@ -1199,6 +1298,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv16_kernel(AttnP p) {
     for (int db = 0; db < NDB; ++db)
 #pragma unroll
       for (int e = 0; e < 4; ++e) { vk[db][e] = dk[db][cb][e]; vv[db][e] = dv[db][cb][e]; }
+    if constexpr (KVLEN) {
+      if (krow >= Lk) {  // P of a zero key row is not zero: its sums are dropped here
+#pragma unroll
+        for (int db = 0; db < NDB; ++db)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { vk[db][e] = 0.f; vv[db][e] = 0.f; }
+      }
+    }
     store_block_bf16_t(vk, p.scale, p.dk + b * p.dk_sb + hh * p.dk_sh + (long)krow * p.dk_sl, p.hd, g, krow < p.Lk, p.wide_dkv);
     store_block_bf16_t(vv, 1.0f, p.dv + b * p.dv_sb + hh * p.dv_sh + (long)krow * p.dv_sl, p.hd, g, krow < p.Lk, p.wide_dkv);
   }
@@ -1220,7 +1327,7 @@ __device__ __forceinline__ float max_over_lane_groups(float x) {  // max over th
   return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
 }
 
-template <int HDP>
+template <int HDP, bool KVLEN = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
   static_assert(HDP == 96, "head_dim 72 layout (ones columns at 72, 73 / 72, 76)");
   constexpr int KS = HDP / 32, NDB = 5, TILE = 64 * HDP * 2;
@@ -1232,10 +1339,22 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qrow0 = qt * 256 + wave * 64 + (lane & 15);  // query of block 0; block cb = + 16 cb
   const int hd_kv = p.hd + 8;
+  const int Lk = kv_len_of<KVLEN>(p, b);
+  if constexpr (KVLEN) {
+    if (Lk == 0) {  // no context: O = 0, lse = 0 (all 64 lanes call the store: it exchanges lanes)
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) {
+        const int qrow = qrow0 + 16 * cb;
+        store_zero_block(p.o + b * p.o_sb + hh * p.o_sh + (long)qrow * p.o_sl, p.hd, g, qrow < p.Lq, p.wide_o);
+        if (qrow < p.Lq && g == 0) p.lse[((long)b * p.H + hh) * p.Lq + qrow] = 0.0f;
+      }
+      return;
+    }
+  }
 
   const __amdgpu_buffer_rsrc_t rq = slice_rsrc(p.q + b * p.q_sb + hh * p.q_sh, p.q_sl, p.Lq, p.hd);
-  const srd_t rk = slice_srd(p.k + b * p.k_sb + hh * p.k_sh, p.k_sl, p.Lk, hd_kv);
-  const srd_t rv = slice_srd(p.v + b * p.v_sb + hh * p.v_sh, p.v_sl, p.Lk, hd_kv);
+  const srd_t rk = slice_srd(p.k + b * p.k_sb + hh * p.k_sh, p.k_sl, Lk, hd_kv);
+  const srd_t rv = slice_srd(p.v + b * p.v_sb + hh * p.v_sh, p.v_sl, Lk, hd_kv);
   DmaStage<64, HDP, 1> dk, dv;
   dk.init(p.k_sl, hd_kv, wave, lane);
   dv.init(p.v_sl, hd_kv, wave, lane);
@@ -1265,7 +1384,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) o[db][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m[4] = {0.f, 0.f, 0.f, 0.f};
-  const int nkt = (p.Lk + 63) / 64;
+  const int nkt = (Lk + 63) / 64;
   VDS_WAIT_VM(0);
   __syncthreads();
 
@@ -1396,7 +1515,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
 // two cross-lane adds), writes -delta and lse * log2(e) to the workspace and the (hi, lo) pair of -lse2 into the pad of its
 // Q row -- what attn_delta_*_kernel did in a pass of its own over O and dO (6.5 ms per C3b step).  The host then runs this
 // kernel BEFORE the dK/dV kernel, which reads those statistics.
-template <int HDP, bool FOLD = false>
+template <int HDP, bool FOLD = false, bool KVLEN = false>
 __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
   static_assert(HDP == 96, "head_dim 72 layout");
   constexpr int KS = HDP / 32, NDB = 5, TILE = 64 * HDP * 2, NQ = 2;
@@ -1408,11 +1527,24 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qrow0 = qt * (64 * NQ) + wave * (16 * NQ) + (lane & 15);  // query of column block 0; block cb = + 16 cb
   const int hd_kv = p.hd + 8;
+  const int Lk = kv_len_of<KVLEN>(p, b);
+  if constexpr (KVLEN) {
+    // no context: dQ = 0.  (FOLD: the statistics of this sample stay unwritten -- every dK/dV workgroup of a sample
+    // without keys leaves before it reads them)
+    if (Lk == 0) {
+#pragma unroll
+      for (int cb = 0; cb < NQ; ++cb) {
+        const int qrow = qrow0 + 16 * cb;
+        store_zero_block(p.dq + b * p.dq_sb + hh * p.dq_sh + (long)qrow * p.dq_sl, p.hd, g, qrow < p.Lq, p.wide_dq);
+      }
+      return;
+    }
+  }
 
   const __amdgpu_buffer_rsrc_t rq = slice_rsrc(p.q + b * p.q_sb + hh * p.q_sh, p.q_sl, p.Lq, p.hd);
   const __amdgpu_buffer_rsrc_t rdo = slice_rsrc(p.d_o + b * p.do_sb + hh * p.do_sh, p.do_sl, p.Lq, p.hd);
-  const srd_t rk = slice_srd(p.k + b * p.k_sb + hh * p.k_sh, p.k_sl, p.Lk, hd_kv);
-  const srd_t rv = slice_srd(p.v + b * p.v_sb + hh * p.v_sh, p.v_sl, p.Lk, hd_kv);
+  const srd_t rk = slice_srd(p.k + b * p.k_sb + hh * p.k_sh, p.k_sl, Lk, hd_kv);
+  const srd_t rv = slice_srd(p.v + b * p.v_sb + hh * p.v_sh, p.v_sl, Lk, hd_kv);
   DmaStage<64, HDP, 1> dk, dv;
   dk.init(p.k_sl, hd_kv, wave, lane);
   dv.init(p.v_sl, hd_kv, wave, lane);
@@ -1479,7 +1611,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
   for (int db = 0; db < NDB; ++db)
 #pragma unroll
     for (int cb = 0; cb < NQ; ++cb) dq[db][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int nkt = (p.Lk + 63) / 64;
+  const int nkt = (Lk + 63) / 64;
   VDS_WAIT_VM(0);
   __syncthreads();  // tile 0 landed
 
@@ -1586,6 +1718,7 @@ AttnP to_p(const vds_attn_args* a) {
   p.kv_pad_ones = a->kv_pad_ones;
   p.q_split = 1;
   p.dkv_part = nullptr;
+  p.kv_lens = nullptr;
   const bool wide_on = vdscfg::geti(vdscfg::ATTN_WIDE_STORES) != 0;  // A/B knob
   p.wide_o = wide_on && p.hd > 64 && rows16(p.o, p.o_sb, p.o_sh, p.o_sl);
   p.wide_dq = wide_on && p.hd > 64 && rows16(p.dq, p.dq_sb, p.dq_sh, p.dq_sl);
@@ -1629,15 +1762,17 @@ static int tail_last_for(int L, int tile) {
   return (vdscfg::geti(vdscfg::ATTN_TAIL_LAST) && L > tile && (L % tile) != 0) ? 1 : 0;
 }
 
-template <int HDP, int HDQ>
+// KVLEN (vds_attn_*_kvlen): the same choices and launch geometry -- functions of Lk, never of the device-side lengths --
+// on the kernel instances that read p.kv_lens
+template <int HDP, int HDQ, bool KVLEN = false>
 int run_fwd(AttnP p, hipStream_t s) {
   constexpr int LDS = 4 * 64 * HDP * 2;
   static bool once = false;
   if (!once) {
-    set_lds(attn_fwd_kernel<HDP, HDQ, 2, true>, LDS);
-    if constexpr (HDP <= 96) set_lds(attn_fwd_wide_kernel<HDP, HDQ, false>, LDS);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd_wide_kernel<HDP, HDQ, true>, LDS);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd16_kernel<HDP>, LDS);
+    set_lds(attn_fwd_kernel<HDP, HDQ, 2, true, KVLEN>, LDS);
+    if constexpr (HDP <= 96) set_lds(attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN>, LDS);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd_wide_kernel<HDP, HDQ, true, KVLEN>, LDS);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd16_kernel<HDP, KVLEN>, LDS);
     once = true;
   }
   const int wide = vdscfg::geti(vdscfg::ATTN_FWD_WIDE);  // 0 / 1 forces (experiments); 2 (default): head_dim 64 / 72, long query sequences
@@ -1647,6 +1782,8 @@ int run_fwd(AttnP p, hipStream_t s) {
   p.n_rt = cdiv(p.Lq, use_wide ? 256 : 128);
   p.tail_last = tail_last_for(p.Lq, use_wide ? 256 : 128);
   const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
+  // (KVLEN: the host does not know the lengths -- the profiler credits the work of all Lk keys, here and in run_bwd, so
+  // its FLOP/s and byte rates of a masked call are overstated by Lk / mean length)
   const double fl = 4.0 * p.B * p.H * (double)p.Lq * p.Lk * p.hd;
   const bool ones_fwd = HDP == 96 && HDQ == 80 && use_wide && p.kv_pad_ones && p.hd == 72;
   // (kv_pad_ones == 2: cross-attention on the ones-column kernels -- keeps its own profiler class)
@@ -1654,7 +1791,7 @@ int run_fwd(AttnP p, hipStream_t s) {
                     2.0 * p.B * p.H * p.hd * (2.0 * p.Lq + 2.0 * p.Lk));
   if constexpr (HDP == 64) {
     if (use_wide) {
-      hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, false>), dim3(grid), dim3(256), LDS, s, p);
+      hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN>), dim3(grid), dim3(256), LDS, s, p);
       return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
     }
   }
@@ -1665,16 +1802,16 @@ int run_fwd(AttnP p, hipStream_t s) {
         if (p.kv_pad_ones && p.hd == 72) {
           // (round 5 measured a form of this kernel software-pipelined inside the wave: +9.5 % slower, removed in round 6;
           // profiles/r05/attn_fwd_software_pipelined.log)
-          if (attn_variant() & 4) hipLaunchKernelGGL((attn_fwd16_kernel<HDP>), dim3(grid), dim3(256), LDS, s, p);
-          else hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, true>), dim3(grid), dim3(256), LDS, s, p);
+          if (attn_variant() & 4) hipLaunchKernelGGL((attn_fwd16_kernel<HDP, KVLEN>), dim3(grid), dim3(256), LDS, s, p);
+          else hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, true, KVLEN>), dim3(grid), dim3(256), LDS, s, p);
           done = true;
         }
       }
-      if (!done) hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, false>), dim3(grid), dim3(256), LDS, s, p);
+      if (!done) hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN>), dim3(grid), dim3(256), LDS, s, p);
       return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
     }
   }
-  hipLaunchKernelGGL((attn_fwd_kernel<HDP, HDQ, 2, true>), dim3(grid), dim3(256), LDS, s, p);
+  hipLaunchKernelGGL((attn_fwd_kernel<HDP, HDQ, 2, true, KVLEN>), dim3(grid), dim3(256), LDS, s, p);
   return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
 }
 
@@ -1689,20 +1826,20 @@ int dkv_qsplit(int B, int H, int Lq, int Lk) {
   return (int)(sp < 1 ? 1 : sp > 16 ? 16 : sp);
 }
 
-template <int HDP, int HDQ>
+template <int HDP, int HDQ, bool KVLEN = false>
 int run_bwd(AttnP p, hipStream_t s, size_t ws_floats) {
   constexpr int LDS_DQ = 4 * 64 * HDP * 2;
   constexpr int LDS_DKV = 4 * 64 * HDP * 2 + 2 * 128 * 4;
   static bool once = false;
   if (!once) {
-    set_lds(attn_bwd_dq_kernel<HDP, HDQ, false>, LDS_DQ);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dq_kernel<HDP, HDQ, true>, LDS_DQ);
-    set_lds(attn_bwd_dkv_kernel<HDP, HDQ, false>, LDS_DKV);
+    set_lds(attn_bwd_dq_kernel<HDP, HDQ, false, KVLEN>, LDS_DQ);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dq_kernel<HDP, HDQ, true, KVLEN>, LDS_DQ);
+    set_lds(attn_bwd_dkv_kernel<HDP, HDQ, false, KVLEN>, LDS_DKV);
     if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dkv_kernel<HDP, HDQ, true>, LDS_DKV);
     if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dkv16_kernel<HDP>, LDS_DKV);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dkv16_kernel<HDP, false>, LDS_DKV);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dq16_kernel<HDP>, LDS_DQ);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dq16_kernel<HDP, true>, LDS_DQ);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dkv16_kernel<HDP, false, KVLEN>, LDS_DKV);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dq16_kernel<HDP, false, KVLEN>, LDS_DQ);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dq16_kernel<HDP, true, KVLEN>, LDS_DQ);
     once = true;
   }
   const long rows = (long)p.B * p.H * p.Lq;
@@ -1726,13 +1863,13 @@ int run_bwd(AttnP p, hipStream_t s, size_t ws_floats) {
       // (48 queries per wave -- every fragment read feeds 3 MFMAs, two waves per SIMD instead of three -- measured 2-6 %
       // slower in round 5, removed in round 6; profiles/r05/attn_dq_three_blocks_per_wave.log)
       if (fold)
-        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, true>), dim3(grid), dim3(256), LDS_DQ, s, p);
+        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, true, KVLEN>), dim3(grid), dim3(256), LDS_DQ, s, p);
       else if (ones && (attn_variant() & 2))
-        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP>), dim3(grid), dim3(256), LDS_DQ, s, p);
+        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, false, KVLEN>), dim3(grid), dim3(256), LDS_DQ, s, p);
       else if (ones)
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, HDQ, true>), dim3(grid), dim3(256), LDS_DQ, s, p);
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, HDQ, true, KVLEN>), dim3(grid), dim3(256), LDS_DQ, s, p);
     }
-    if (!ones) hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, HDQ, false>), dim3(grid), dim3(256), LDS_DQ, s, p);
+    if (!ones) hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, HDQ, false, KVLEN>), dim3(grid), dim3(256), LDS_DQ, s, p);
   };
   if (fold) launch_dq();
   else {
@@ -1770,7 +1907,7 @@ int run_bwd(AttnP p, hipStream_t s, size_t ws_floats) {
       // the query-range split below exists in the plain kernel only): the 16x16x32 kernel with S started from -lse2
       const int x16 = vdscfg::geti(vdscfg::CROSS_DKV16);  // 0 = plain kernel, 1 = rule, 2 = also for small grids (tests)
       if (!ones_kv && p.kv_pad_ones == 2 && p.hd == 72 && x16 && ((long)grid >= 512 || x16 == 2) && (attn_variant() & 1)) {
-        hipLaunchKernelGGL((attn_bwd_dkv16_kernel<HDP, false>), dim3(grid), dim3(256), LDS_DKV, s, p);
+        hipLaunchKernelGGL((attn_bwd_dkv16_kernel<HDP, false, KVLEN>), dim3(grid), dim3(256), LDS_DKV, s, p);
         done16 = true;
       }
     }
@@ -1788,13 +1925,13 @@ int run_bwd(AttnP p, hipStream_t s, size_t ws_floats) {
         p.dkv_part = p.delta + 2 * rows;
         p.tail_last = 0;
         const int g2 = cdiv(p.B * p.H, 8) * 8 * p.n_rt * split;
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, false>), dim3(g2), dim3(256), LDS_DKV, s, p);
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, false, KVLEN>), dim3(g2), dim3(256), LDS_DKV, s, p);
         const long n = (long)p.B * p.H * p.Lk * 2 * (p.hd >> 2);
-        hipLaunchKernelGGL(dkv_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(dkv_reduce_kernel<KVLEN>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
         p.q_split = 1;
         p.dkv_part = nullptr;
       } else {
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, false>), dim3(grid), dim3(256), LDS_DKV, s, p);
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, false, KVLEN>), dim3(grid), dim3(256), LDS_DKV, s, p);
       }
     }
   }
@@ -1862,6 +1999,26 @@ extern "C" int vds_attn_fwd(const vds_attn_args* a, vds_stream_t stream) {
   }
 }
 
+// per-sample key counts: the same checks, then the KVLEN instances (kv_lens == NULL: the calls above, unchanged)
+extern "C" int vds_attn_fwd_kvlen(const vds_attn_args* a, const int32_t* kv_lens, vds_stream_t stream) {
+  if (!a) return VDS_ERR_ARG;
+  if (!kv_lens) return vds_attn_fwd(a, stream);
+  if (a->kv_pad_ones == 1) return VDS_ERR_ARG;  // self-attention on annotated q rows: no lengths
+  if (!a->q || !a->k || !a->v || !a->o || !a->lse || a->Lq <= 0 || a->Lk <= 0) return VDS_ERR_ARG;
+  if (!strides_ok(a, false)) return VDS_ERR_ARG;
+  AttnP p = to_p(a);
+  p.kv_lens = kv_lens;
+  hipStream_t s = (hipStream_t)stream;
+  switch (kernel_instance(a->head_dim)) {
+    case 32: return run_fwd<32, 32, true>(p, s);
+    case 64: return run_fwd<64, 64, true>(p, s);
+    case 80: return run_fwd<96, 80, true>(p, s);
+    case 96: return run_fwd<96, 96, true>(p, s);
+    case 128: return run_fwd<128, 128, true>(p, s);
+    default: return VDS_ERR_UNSUPPORTED;
+  }
+}
+
 extern "C" size_t vds_attn_bwd_workspace_bytes(const vds_attn_args* a) {
   if (!a || a->B <= 0 || a->H <= 0 || a->Lq <= 0) return 0;
   size_t fl = (size_t)2 * a->B * a->H * a->Lq;
@@ -1884,6 +2041,28 @@ extern "C" int vds_attn_bwd(const vds_attn_args* a, vds_stream_t stream) {
     case 80: return run_bwd<96, 80>(p, s, ws);
     case 96: return run_bwd<96, 96>(p, s, ws);
     case 128: return run_bwd<128, 128>(p, s, ws);
+    default: return VDS_ERR_UNSUPPORTED;
+  }
+}
+
+extern "C" int vds_attn_bwd_kvlen(const vds_attn_args* a, const int32_t* kv_lens, vds_stream_t stream) {
+  if (!a) return VDS_ERR_ARG;
+  if (!kv_lens) return vds_attn_bwd(a, stream);
+  if (a->kv_pad_ones == 1) return VDS_ERR_ARG;
+  if (!a->q || !a->k || !a->v || !a->o || !a->lse || !a->d_o || !a->dq || !a->dk || !a->dv || !a->delta || a->Lq <= 0 ||
+      a->Lk <= 0)
+    return VDS_ERR_ARG;
+  if (!strides_ok(a, true)) return VDS_ERR_ARG;
+  AttnP p = to_p(a);
+  p.kv_lens = kv_lens;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t ws = a->ws_floats > 0 ? (size_t)a->ws_floats : (size_t)2 * a->B * a->H * a->Lq;
+  switch (kernel_instance(a->head_dim)) {
+    case 32: return run_bwd<32, 32, true>(p, s, ws);
+    case 64: return run_bwd<64, 64, true>(p, s, ws);
+    case 80: return run_bwd<96, 80, true>(p, s, ws);
+    case 96: return run_bwd<96, 96, true>(p, s, ws);
+    case 128: return run_bwd<128, 128, true>(p, s, ws);
     default: return VDS_ERR_UNSUPPORTED;
   }
 }

@@ -7,7 +7,8 @@ MI355X-first: nothing is traced or re-generated.  The explicit kernel sequence o
 into a HIP graph and replayed with one launch per step.  That needs every per-step value to live
 in device memory rather than in kernel arguments:
 
-  * the batch            -> static input buffers, refreshed with stream-ordered copies;
+  * the batch            -> static input buffers, refreshed with stream-ordered copies (latent, context and, when the
+                            first batch carries it, the int32 `context_lens` the attention kernels read on the device);
   * the RoPE offsets     -> device int32[3] read by `vds_rope_rows_dev` (drawn on the host from the
                             global CPU RNG exactly like the eager path, model.py:224-226);
   * the AdamW bias corrections, LR multiplier and EMA decay -> device float[4] read by `vds_adamw_multi_dev` /
@@ -35,7 +36,8 @@ could run is the capture of RCCL collectives across several PROCESSES; RCCL supp
 the same sequence.
 
 A captured graph bakes in device pointers (static batch buffers, the fp8 amax tables, the activation buffers the
-allocator handed out): `step()` refuses a batch whose latent / context shape differs from the captured one.
+allocator handed out): `step()` refuses a batch whose latent / context shape differs from the captured one, or that adds or drops
+`context_lens`.
 """
 from __future__ import annotations
 
@@ -72,14 +74,23 @@ class GraphedTrainStep:
     def _stage(self, batch):
         """copy the batch into the static buffers (allocating them on first use)"""
         lat, ctx = batch["latent"], batch["context"]
+        lens = batch.get("context_lens")
         if not self.static:
             self.static["latent"] = torch.empty(lat.shape, dtype=bf16, device=self.device)
             self.static["context"] = torch.empty(ctx.shape, dtype=bf16, device=self.device)
+            if lens is not None:  # masked and unmasked steps are different kernel sequences: decided by the first batch
+                self.static["context_lens"] = torch.empty(lat.shape[0], dtype=torch.int32, device=self.device)
+        if (lens is not None) != ("context_lens" in self.static):
+            raise ValueError("GraphedTrainStep was set up " + ("with" if "context_lens" in self.static else "without") +
+                             " context_lens; every batch must " + ("carry" if "context_lens" in self.static else "omit") + " it")
         for k, src in (("latent", lat), ("context", ctx)):
             dst = self.static[k]
             if tuple(src.shape) != tuple(dst.shape):
                 raise ValueError(f"GraphedTrainStep was captured for {k} {tuple(dst.shape)}, got {tuple(src.shape)}")
             dst.copy_(src, non_blocking=True)
+        if lens is not None:
+            from .model import check_context_lens
+            self.static["context_lens"].copy_(check_context_lens(lens, ctx.shape[0], ctx.shape[1]), non_blocking=True)
 
     def _draw_rope(self):
         st = self.model.rope.draw_start(self._thw(self.static["latent"]))

@@ -262,6 +262,39 @@ class ThreeDimRotary(nn.Module):
         return cos[None, None], sin[None, None]
 
 
+def check_context_lens(context_lens, B: int, Lc: int) -> torch.Tensor:
+    """Per-sample context lengths as an int32 tensor of shape [B].  A sequence of ints or a CPU integer tensor is checked
+    here, on the host (B entries, each in [0, Lc]; ValueError otherwise) and comes back as a CPU tensor; a CUDA integer
+    tensor is only checked for its shape and dtype and stays on the device -- no host sync, so a captured graph can
+    replay it with new contents (the kernels clamp what they read to [0, Lc])."""
+    if isinstance(context_lens, torch.Tensor):
+        t = context_lens
+        if t.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise ValueError(f"context_lens: integer tensor expected, got {t.dtype}")
+        if tuple(t.shape) != (B,):
+            raise ValueError(f"context_lens: shape [{B}] expected (one length per sample), got {tuple(t.shape)}")
+        if t.is_cuda:
+            return t.to(torch.int32).contiguous()
+        vals = [int(v) for v in t.tolist()]
+    else:
+        try:
+            vals = list(context_lens)
+        except TypeError:
+            raise ValueError("context_lens: a sequence of ints or an integer tensor expected") from None
+        if any(isinstance(v, bool) or not isinstance(v, int) for v in vals):
+            raise ValueError("context_lens: a sequence of ints expected")
+        if len(vals) != B:
+            raise ValueError(f"context_lens: {B} entries expected (one length per sample), got {len(vals)}")
+    bad = [v for v in vals if v < 0 or v > Lc]
+    if bad:
+        raise ValueError(f"context_lens: every length must be in [0, {Lc}] (the context has {Lc} rows), got {bad}")
+    return torch.tensor(vals, dtype=torch.int32)
+
+
+_FP8_CONTEXT_LENS = ("context_lens is not implemented for the fp8 cross-attention kernels: call "
+                     "enable_fp8(cross_attention=False) to keep the cross-attention products on the bf16 kernels")
+
+
 class DiTBlock(nn.Module):
     """model.py:44-167.  `forward(x, context, c, v_0=None, rope=None) -> (x, v)` has the reference's signature and
     runs the block's HIP kernel sequence (`_fwd`) under one autograd node whose backward is `_bwd`; DiT.forward
@@ -313,29 +346,41 @@ class DiTBlock(nn.Module):
         self._own_group = g
         return g, ""
 
-    def forward(self, x, context, c, v_0=None, rope=None):
+    def forward(self, x, context, c, v_0=None, rope=None, context_lens=None):
         """x [B,L,D], context [B,Lc,Cc] (None without cross-attention), c [B,D] conditioning, v_0 [B,H,L,hd] (block
         0's v; None in block 0), rope = (cos, sin) each [1,1,L,hd/2] or None -> (x [B,L,D], v [B,H,L,hd]) in bf16.
         Gradients flow to x, c, v_0 and the block's parameters (fp32 .grad); `context` is data (the frozen text
-        encoder's output, train.py:70-87) and gets none."""
+        encoder's output, train.py:70-87) and gets none.  context_lens (see DiT.forward): sample b attends its first
+        context_lens[b] context rows only."""
+        kv_lens = None
+        if context_lens is not None:
+            if context is None:
+                raise ValueError("DiTBlock: context_lens given to a block without cross-attention")
+            kv_lens = check_context_lens(context_lens, x.shape[0], context.shape[1])
         _need_gpu(x, "DiTBlock")
+        if kv_lens is not None:
+            kv_lens = kv_lens.to(x.device)
         params = [p for p in self.parameters()]
         save = torch.is_grad_enabled()  # (always off inside an autograd.Function's forward: decided here)
         return _BlockFunction.apply(self, save, x, context, c, v_0, rope[0] if rope is not None else None,
-                                    rope[1] if rope is not None else None, *params)
+                                    rope[1] if rope is not None else None, kv_lens, *params)
 
     # ---- the kernel sequence of one block (used by DiT's whole-model autograd node and by `forward`) ----
-    def _fwd(self, G, pre, X, ctx2d, cvec, v0, cos, sin, B, L, Lc, save, fp8=None, mod=None, keep=None, replay=None):
+    def _fwd(self, G, pre, X, ctx2d, cvec, v0, cos, sin, B, L, Lc, save, fp8=None, mod=None, keep=None, replay=None,
+             kv_lens=None):
         """X [B*L, D] bf16 token buffer -> (X_out, v [B,H,L,hdp], saved).  G: the FlatGroup holding this block's
         parameters under the name prefix `pre`; cvec f32 [B, D]; v0: block 0's v in the padded head-major layout
         or None; cos / sin f32 [L, hd/2]; fp8 = (AmaxHistory | None, block index) when the fp8 linears are on.
         Activation recomputation (DiT.enable_recompute): with save=False, keep = "full" | "selective" returns as `saved`
         only what the replay needs (X, mod; selective: attn, lse1 too).  replay = that object, with save=True: the run
         before the block's `_bwd` -- the self-attention forward is not launched when attn / lse1 were kept, and the
-        new residual stream after the MLP is not stored (X_out is None: the next block's kept X already holds it)."""
+        new residual stream after the MLP is not stored (X_out is None: the next block's kept X already holds it).
+        kv_lens: int32 device tensor [B] or None -- per-sample key counts of the cross-attention (bf16 kernels only)."""
         D, H, hd = self.hidden_size, self.num_heads, self.head_dim
         hdp = HDP_OF[hd]
         use_fp8 = fp8 is not None
+        if kv_lens is not None and use_fp8 and fp8[2] >= 2:
+            raise NotImplementedError(_FP8_CONTEXT_LENS)
         if use_fp8 and (keep is not None or replay is not None):
             raise ValueError("activation recomputation does not cover the fp8 path")
         fp8_hist, i, fp8_attn, fp8_lin, q_ctx = fp8 if use_fp8 else (None, 0, 0, False, None)
@@ -452,13 +497,15 @@ class DiTBlock(nn.Module):
                     # round 5: forward (and dQ) of the cross-attention on the ones-column 16x16x32 kernels of the
                     # self-attention: K / V get head-major padded copies with the ones columns (512 context rows: a 38 MB
                     # copy), the queries stay token-major (the kernels keep them in registers and set their pad columns there)
+                    # (with kv_lens the copy is still of all Lc rows: the kernels bound what they read)
                     kp, vp = ops.kv_pad_ones(ckv, B, Lc, H, hd, hdp, 0, D)
                     ops.attn_fwd(ops.heads_view(qc, B, L, H, hd), kp[..., :hd], vp[..., :hd],
-                                 ops.heads_view(catt, B, L, H, hd), lse2, kv_pad_ones=2)
+                                 ops.heads_view(catt, B, L, H, hd), lse2, kv_pad_ones=2, kv_lens=kv_lens)
                     del kp, vp  # (the backward pass makes them again from ckv: 12 us, nothing extra saved)
                 else:
                     ops.attn_fwd(ops.heads_view(qc, B, L, H, hd), ops.heads_view(ckv, B, Lc, H, hd, 0),
-                                 ops.heads_view(ckv, B, Lc, H, hd, D), ops.heads_view(catt, B, L, H, hd), lse2)
+                                 ops.heads_view(ckv, B, Lc, H, hd, D), ops.heads_view(catt, B, L, H, hd), lse2,
+                                 kv_lens=kv_lens)
                 if c8_on and save:
                     for j, t in enumerate((qc, ckv[:, :D], ckv[:, D:])):
                         ops.absmax(t, fp8_hist.cur(R0 + F8.ROW_QC + j))
@@ -636,7 +683,7 @@ class DiTBlock(nn.Module):
                 ops.attn_bwd(ops.heads_view(bs.qc, B, L, H, hd), kvw, vvw, ops.heads_view(bs.catt, B, L, H, hd), bs.lse2,
                              ops.heads_view(dcatt, B, L, H, hd), ops.heads_view(dqc, B, L, H, hd),
                              ops.heads_view(dckv, B, Lc, H, hd, 0), ops.heads_view(dckv, B, Lc, H, hd, D), None,
-                             kv_pad_ones=ones)
+                             kv_pad_ones=ones, kv_lens=sv.kv_lens)
                 if bs.c8_on:
                     ops.absmax(dcatt, fp8_hist.cur(R0 + F8.ROW_DOC))
             if G.has(pre + "context_kv.bias"):
@@ -950,8 +997,19 @@ class DiT(nn.Module):
                 g.gfull.zero_()
 
     # ------------------------------------------------------------------------ forward ----
-    def forward(self, x, context, timesteps, rope_start: Optional[Tuple[int, int, int]] = None):
-        """x [B,C,T,H,W], context [B,Lc,Cc], timesteps [B] -> [B,C,T,H,W] bf16 (model.py:358-402)."""
+    def forward(self, x, context, timesteps, rope_start: Optional[Tuple[int, int, int]] = None, context_lens=None):
+        """x [B,C,T,H,W], context [B,Lc,Cc], timesteps [B] -> [B,C,T,H,W] bf16 (model.py:358-402).
+        context_lens: per-sample context lengths -- sample b cross-attends its first context_lens[b] context rows only, 0
+        = no context at all (the cross-attention adds nothing for that sample).  A sequence of ints or a CPU integer tensor
+        [B] is validated on the host and uploaded once; a CUDA integer tensor [B] is used as it is, without a host sync.
+        None (the default, the reference's behaviour): all Lc rows of every sample are attended."""
+        kv_lens = None
+        if context_lens is not None:
+            if self.cross_attn_input_size is None:
+                raise ValueError("DiT: context_lens given to a model without cross-attention (cross_attn_input_size=None)")
+            kv_lens = check_context_lens(context_lens, x.shape[0], context.shape[1])
+            if self.fp8 and self.fp8_attn >= 2:
+                raise NotImplementedError(_FP8_CONTEXT_LENS)
         if not x.is_cuda:
             raise RuntimeError("video_diffusion_speedrun_amd.DiT runs on the GPU only (no CPU fallback)")
         if not self.use_rope:
@@ -967,9 +1025,11 @@ class DiT(nn.Module):
         self._ensure_groups(x.device)
         params = [p for p in self.parameters() if p.requires_grad]
         need_grad = torch.is_grad_enabled() and len(params) > 0
+        if kv_lens is not None:
+            kv_lens = kv_lens.to(x.device)
         if need_grad:
-            return _DiTFunction.apply(self, x, context, timesteps, rope_start, *params)
-        out, _ = self._forward_impl(x, context, timesteps, rope_start, save=False)
+            return _DiTFunction.apply(self, x, context, timesteps, rope_start, kv_lens, *params)
+        out, _ = self._forward_impl(x, context, timesteps, rope_start, save=False, kv_lens=kv_lens)
         return out
 
     def _gather_all(self):
@@ -979,7 +1039,7 @@ class DiT(nn.Module):
         for g in self._groups:
             g.gather(ops.cast_f32_bf16, None)
 
-    def _forward_impl(self, x, context, timesteps, rope_start, save: bool):
+    def _forward_impl(self, x, context, timesteps, rope_start, save: bool, kv_lens=None):
         D, H, hd = self.hidden_size, self.num_heads, self.head_dim
         pt, p = self.time_patch_size, self.patch_size
         B, C, T, Hh, Ww = x.shape
@@ -1028,6 +1088,7 @@ class DiT(nn.Module):
             sv.patches, sv.temb, sv.h1, sv.cvec, sv.cos, sv.sin = patches, temb, h1, cvec, cos, sin
             sv.dims = (B, C, T, Hh, Ww, t, h, w, N, L, Lc, Cc)
             sv.ctx2d = ctx2d
+            sv.kv_lens = kv_lens
             sv.blocks = []
 
         # adaLN modulation of every block in ONE launch (K4 of SURVEY 2.3): all blocks read the same conditioning vector.
@@ -1044,7 +1105,7 @@ class DiT(nn.Module):
             X, v, bs = self.blocks[i]._fwd(self.block_group(i), f"blocks.{i}.", X, ctx2d, cvec, v0, cos, sin, B, L, Lc,
                                            save and keep is None,
                                            (self._fp8_hist, i, self.fp8_attn, self.fp8_lin, q_ctx) if self.fp8 else None,
-                                           mods[i] if mods is not None else None, keep=keep)
+                                           mods[i] if mods is not None else None, keep=keep, kv_lens=kv_lens)
             if v0 is None:
                 v0 = v
             if save:
@@ -1120,7 +1181,7 @@ class DiT(nn.Module):
                 # block-0 v (sv.v0 stays the v handed out in the first forward; block 0 makes its own copy again)
                 _, _, bs = self.blocks[i]._fwd(self.block_group(i), f"blocks.{i}.", bs.X, sv.ctx2d, sv.cvec,
                                                sv.v0 if i > 0 else None, sv.cos, sv.sin, B, L, Lc, True, None, bs.mod,
-                                               replay=bs)
+                                               replay=bs, kv_lens=sv.kv_lens)
             dX = self.blocks[i]._bwd(self.block_group(i), f"blocks.{i}.", bs, dX, sv, dc, dv0, B, L, Lc,
                                      i == 0, (self._fp8_hist, i, self.fp8_attn, self.fp8_lin, sv.q_ctx) if self.fp8 else None,
                                      dmods[i] if dmods is not None else None)
@@ -1211,7 +1272,7 @@ class _BlockFunction(torch.autograd.Function):
     """DiTBlock.forward as one autograd node (see DiTBlock.forward for the contract)."""
 
     @staticmethod
-    def forward(ctx, block, need, x, context, c, v_0, cos, sin, *params):
+    def forward(ctx, block, need, x, context, c, v_0, cos, sin, kv_lens, *params):
         B, L, D = x.shape
         H, hd = block.num_heads, block.head_dim
         hdp = HDP_OF[hd]
@@ -1242,10 +1303,10 @@ class _BlockFunction(torch.autograd.Function):
             else:
                 v0p = torch.zeros(B, H, L, hdp, dtype=bf16, device=dev)
                 v0p[..., :hd].copy_(v_0)
-        Xo, v, bs = block._fwd(G, pre, X, ctx2d, cvec, v0p, cos2, sin2, B, L, Lc, need)
+        Xo, v, bs = block._fwd(G, pre, X, ctx2d, cvec, v0p, cos2, sin2, B, L, Lc, need, kv_lens=kv_lens)
         if need:
             sv = _Saved()
-            sv.cos, sv.sin, sv.v0, sv.ctx2d, sv.cvec = cos2, sin2, v0p, ctx2d, cvec
+            sv.cos, sv.sin, sv.v0, sv.ctx2d, sv.cvec, sv.kv_lens = cos2, sin2, v0p, ctx2d, cvec, kv_lens
             ctx.state = (block, G, pre, bs, sv, (B, L, Lc, D, H, hd, hdp), x.dtype, c.dtype,
                          v_0.dtype if v_0 is not None else None)
         ctx.set_materialize_grads(False)
@@ -1275,7 +1336,7 @@ class _BlockFunction(torch.autograd.Function):
         G.add_held(held)
         gv0 = dv0[..., :hd].to(v0dt) if (bs.mix and v0dt is not None) else None
         n_params = len(list(block.parameters()))
-        return (None, None, dX0.view(B, L, D).to(xdt), None, dc.to(cdt), gv0, None, None) + (None,) * n_params
+        return (None, None, dX0.view(B, L, D).to(xdt), None, dc.to(cdt), gv0, None, None, None) + (None,) * n_params
 
 
 class _DiTFunction(torch.autograd.Function):
@@ -1283,8 +1344,8 @@ class _DiTFunction(torch.autograd.Function):
     parameter gradients are written into the flat fp32 gradient buffers that p.grad aliases."""
 
     @staticmethod
-    def forward(ctx, model, x, context, timesteps, rope_start, *params):
-        out, sv = model._forward_impl(x, context, timesteps, rope_start, save=True)
+    def forward(ctx, model, x, context, timesteps, rope_start, kv_lens, *params):
+        out, sv = model._forward_impl(x, context, timesteps, rope_start, save=True, kv_lens=kv_lens)
         ctx.model, ctx.sv = model, sv
         return out
 
@@ -1293,4 +1354,4 @@ class _DiTFunction(torch.autograd.Function):
         model, sv = ctx.model, ctx.sv
         ctx.sv = None
         model._backward_impl(sv, dout)
-        return (None,) * (5 + len([p for p in model.parameters() if p.requires_grad]))
+        return (None,) * (6 + len([p for p in model.parameters() if p.requires_grad]))

@@ -242,9 +242,18 @@ def _st(t):
     return t.stride(0), t.stride(1), t.stride(2)
 
 
-def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False):
+def _kv_lens_ptr(kv_lens, B: int) -> int:
+    """device pointer of a per-sample key-count tensor: int32, CUDA, shape [B], contiguous -- anything else is an error"""
+    if not (isinstance(kv_lens, torch.Tensor) and kv_lens.is_cuda and kv_lens.dtype == torch.int32
+            and tuple(kv_lens.shape) == (B,) and kv_lens.is_contiguous()):
+        raise ValueError(f"kv_lens must be a contiguous int32 CUDA tensor of shape [{B}]")
+    return kv_lens.data_ptr()
+
+
+def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None):
     """q [B,H,Lq,hd], k/v [B,H,Lk,hd], o [B,H,Lq,hd] strided views (last dim contiguous); lse f32 [B,H,Lq].
-    kv_pad_ones: k / v are views into qkv_rope_fwd outputs whose pad carries the ones columns."""
+    kv_pad_ones: k / v are views into qkv_rope_fwd outputs whose pad carries the ones columns.
+    kv_lens: int32 CUDA tensor [B]; sample b attends its first kv_lens[b] keys only (vds_attn_fwd_kvlen)."""
     B, H, Lq, hd = q.shape
     Lk = k.shape[2]
     a = AttnArgs()
@@ -255,7 +264,11 @@ def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False):
     a.o, (a.o_sb, a.o_sh, a.o_sl) = _p(o), _st(o)
     a.lse = _p(lse)
     a.kv_pad_ones = int(kv_pad_ones)  # (True = 1: self-attention layout; 2: ones in k / v only, cross-attention)
-    check(_lib.load().vds_attn_fwd(C.byref(a), _stream()), f"vds_attn_fwd(B={B},H={H},Lq={Lq},Lk={Lk},hd={hd})")
+    if kv_lens is None:
+        check(_lib.load().vds_attn_fwd(C.byref(a), _stream()), f"vds_attn_fwd(B={B},H={H},Lq={Lq},Lk={Lk},hd={hd})")
+    else:
+        check(_lib.load().vds_attn_fwd_kvlen(C.byref(a), _kv_lens_ptr(kv_lens, B), _stream()),
+              f"vds_attn_fwd_kvlen(B={B},H={H},Lq={Lq},Lk={Lk},hd={hd})")
 
 
 def kv_pad_ones(kv: torch.Tensor, B: int, Lk: int, H: int, hd: int, hdp: int, k_col0: int, v_col0: int):
@@ -276,9 +289,10 @@ def attn_bwd_workspace_floats(B, H, Lq, Lk, hd, kv_pad_ones: bool = False) -> in
     return _lib.load().vds_attn_bwd_workspace_bytes(C.byref(a)) // 4
 
 
-def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = False):
+def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = False, kv_lens=None):
     """delta: f32 workspace of 2*B*H*Lq elements (rowsum(dO*O), then lse*log2 e); allocated here when None
-    (size from vds_attn_bwd_workspace_bytes)."""
+    (size from vds_attn_bwd_workspace_bytes).
+    kv_lens: as in attn_fwd; rows kv_lens[b].. of dk[b] / dv[b] are written as zeros (vds_attn_bwd_kvlen)."""
     B, H, Lq, hd = q.shape
     assert lse.is_contiguous()
     Lk = k.shape[2]
@@ -300,7 +314,11 @@ def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = Fa
     a.dv, (a.dv_sb, a.dv_sh, a.dv_sl) = _p(dv), _st(dv)
     a.delta = _p(delta)
     a.kv_pad_ones = int(kv_pad_ones)
-    check(_lib.load().vds_attn_bwd(C.byref(a), _stream()), f"vds_attn_bwd(B={B},H={H},Lq={Lq},Lk={Lk},hd={hd})")
+    if kv_lens is None:
+        check(_lib.load().vds_attn_bwd(C.byref(a), _stream()), f"vds_attn_bwd(B={B},H={H},Lq={Lq},Lk={Lk},hd={hd})")
+    else:
+        check(_lib.load().vds_attn_bwd_kvlen(C.byref(a), _kv_lens_ptr(kv_lens, B), _stream()),
+              f"vds_attn_bwd_kvlen(B={B},H={H},Lq={Lq},Lk={Lk},hd={hd})")
 
 
 # ---------------------------------------------------------------------- fp8 attention ----

@@ -35,8 +35,13 @@ def shifted_times(i: int, steps: int) -> Tuple[float, float]:
 def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Optional[torch.Tensor] = None,
                      inference_steps: int = 50, cfg_scale: float = 6.0, height: int = 512, width: int = 512,
                      seed: int = 42, latents: Optional[torch.Tensor] = None,
-                     rope_starts: Optional[Sequence[Tuple[int, int, int]]] = None, device="cuda") -> torch.Tensor:
-    """Samples whatever weights the model holds.  To sample the weight EMA of a training run
+                     rope_starts: Optional[Sequence[Tuple[int, int, int]]] = None, device="cuda",
+                     prompt_lens=None, negative_lens=None) -> torch.Tensor:
+    """prompt_lens / negative_lens ([B] ints, DiT.forward's context_lens): the number of real tokens of the prompt / the
+    negative prompt; if either is given every model call passes lengths, a side without them attends all its rows, and
+    `negative_embeds=None` with prompt_lens means an EMPTY negative prompt (length 0: no context), not 512 zero rows.
+
+    Samples whatever weights the model holds.  To sample the weight EMA of a training run
     (`MuAdamW(..., ema_decay=0.9999)`), either swap it in for the duration of the call
 
         with opt.ema_weights():
@@ -49,6 +54,18 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
     dev = torch.device(device)
     prompt_embeds = prompt_embeds.to(dev, bf16)
     guided = cfg_scale > 1
+    lens_c = lens_u = None
+    if prompt_lens is not None or negative_lens is not None:
+        from .model import check_context_lens
+        nb, Lc = prompt_embeds.shape[0], prompt_embeds.shape[1]
+        lens_c = check_context_lens(prompt_lens if prompt_lens is not None else [Lc] * nb, nb, Lc).to(dev)
+        if guided:
+            if negative_lens is None:
+                negative_lens = [0] * nb if negative_embeds is None else [negative_embeds.shape[1]] * nb
+            lens_u = check_context_lens(negative_lens, nb, Lc if negative_embeds is None else negative_embeds.shape[1]).to(dev)
+            lens_cu = torch.cat([lens_c, lens_u])
+    kw_c = {} if lens_c is None else {"context_lens": lens_c}
+    kw_u = {} if lens_u is None else {"context_lens": lens_u}
     if guided and negative_embeds is None:
         negative_embeds = torch.zeros_like(prompt_embeds)  # sample.py:105
     if latents is None:
@@ -67,17 +84,18 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
             if s_c == s_u:  # one batched forward: [cond, uncond]
                 tt = torch.tensor([t, t], device=dev).to(bf16)
                 out = model(torch.cat([lat, lat]), torch.cat([prompt_embeds, negative_embeds.to(dev, bf16)]), tt,
-                            **({"rope_start": s_c} if s_c is not None else {}))
+                            **({"rope_start": s_c} if s_c is not None else {}),
+                            **({} if lens_c is None else {"context_lens": lens_cu}))
                 cond, uncond = out[0:1].contiguous(), out[1:2].contiguous()
             else:
                 tt = torch.tensor([t], device=dev).to(bf16)
-                cond = model(lat, prompt_embeds, tt, rope_start=s_c)
-                uncond = model(lat, negative_embeds.to(dev, bf16), tt, rope_start=s_u)
+                cond = model(lat, prompt_embeds, tt, rope_start=s_c, **kw_c)
+                uncond = model(lat, negative_embeds.to(dev, bf16), tt, rope_start=s_u, **kw_u)
         else:
             tt = torch.tensor([t], device=dev).to(bf16)
             s_c = tuple(rope_starts[call]) if rope_starts is not None else None
             call += 1
-            cond = model(lat, prompt_embeds, tt, **({"rope_start": s_c} if s_c is not None else {}))
+            cond = model(lat, prompt_embeds, tt, **({"rope_start": s_c} if s_c is not None else {}), **kw_c)
             uncond = None
         ops.cfg_euler_step(cond, uncond, acc, lat, cfg_scale, dt)
     return acc

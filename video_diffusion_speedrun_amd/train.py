@@ -7,7 +7,8 @@ the loop body of train.py:431-434, on the HIP path.
 
 `batch` = {"latent": Tensor[B,C,T,H,W], "prompt": list[str]}; the text encoder is the caller's
 (frozen, third-party; out of scope) -- for synthetic runs pass `batch["context"]` (a pre-encoded
-[B,Lc,Cc] tensor) and text_encoder=None.
+[B,Lc,Cc] tensor) and text_encoder=None.  Optional `batch["context_lens"]` ([B] ints: the number of real caption tokens
+of each sample, `lens_from_mask(attention_mask)`) restricts the cross-attention to those rows (DiT.forward).
 """
 from __future__ import annotations
 
@@ -22,10 +23,26 @@ bf16, f32 = torch.bfloat16, torch.float32
 ALPHA = 8.0  # time shift, train.py:95
 
 
+def lens_from_mask(attention_mask) -> torch.Tensor:
+    """Tokenizer attention mask [B, Lc] (0/1 or bool, right-padded) -> int32 [B] on the CPU: the number of leading ones of
+    every row.  A mask with a one after a zero is not a prefix and cannot be expressed as a length: ValueError."""
+    m = torch.as_tensor(attention_mask).cpu()
+    if m.dim() != 2:
+        raise ValueError(f"lens_from_mask: a [B, Lc] mask expected, got shape {tuple(m.shape)}")
+    m = m != 0
+    lens = m.sum(dim=1)
+    prefix = torch.arange(m.shape[1]).unsqueeze(0) < lens.unsqueeze(1)
+    if not torch.equal(m, prefix):
+        bad = [b for b in range(m.shape[0]) if not torch.equal(m[b], prefix[b])]
+        raise ValueError(f"lens_from_mask: the mask of sample(s) {bad} is not a prefix (a one follows a zero)")
+    return lens.to(torch.int32)
+
+
 def encode_prompt_with_t5(text_encoder, tokenizer, max_sequence_length=512, prompt=None, device=None,
-                          return_index=-1):
+                          return_index=-1, return_lengths=False):
     """Caption -> encoder hidden states [B, max_sequence_length, C] in the encoder's dtype, same call contract as
-    the reference's helper (utils.py:38-80).  The encoder is the caller's frozen third-party model: host glue only."""
+    the reference's helper (utils.py:38-80).  The encoder is the caller's frozen third-party model: host glue only.
+    return_lengths=True: (states, lens) with lens = lens_from_mask(the tokenizer's attention_mask), int32 [B] on the CPU."""
     prompts = [prompt] if isinstance(prompt, str) else list(prompt)
     tokens = tokenizer(prompts, padding="max_length", max_length=max_sequence_length, truncation=True,
                        return_length=False, return_overflowing_tokens=False, return_tensors="pt")
@@ -33,7 +50,10 @@ def encode_prompt_with_t5(text_encoder, tokenizer, max_sequence_length=512, prom
     chosen = states[return_index]
     if return_index != -1:  # an inner layer: finish it the way the encoder finishes its last one
         chosen = text_encoder.encoder.dropout(text_encoder.encoder.final_layer_norm(chosen))
-    return chosen.to(device=device, dtype=text_encoder.dtype)
+    chosen = chosen.to(device=device, dtype=text_encoder.dtype)
+    if return_lengths:
+        return chosen, lens_from_mask(tokens.attention_mask)
+    return chosen
 
 
 class _FlowLoss(torch.autograd.Function):
@@ -81,13 +101,20 @@ def forward(dit_model, batch, text_encoder, tokenizer, device, global_step, mast
         # (capturable) and without writing into the caller's batch["context"]
         caption_encoded = torch.where(do_zero_out[:, None, None], torch.zeros((), dtype=bf16, device=device),
                                       caption_encoded)
+        context_lens = batch.get("context_lens")
+        if context_lens is not None:
+            # a dropped caption is no context at all: its length goes to 0 as its rows go to zero (on the device: capturable)
+            from .model import check_context_lens
+            context_lens = check_context_lens(context_lens, caption_encoded.shape[0], caption_encoded.shape[1]).to(device)
+            context_lens = torch.where(do_zero_out, torch.zeros((), dtype=torch.int32, device=device), context_lens)
     B = vae_latent.size(0)
     z = torch.randn(B, device=device, dtype=bf16, generator=generator)
     t = time_shift_from_normal(z)
     noise = torch.randn(vae_latent.shape, device=device, dtype=bf16, generator=generator)
     z_t, v_objective = ops.noise_latents(vae_latent.contiguous(), noise, t.to(f32))
-    output = dit_model(z_t, caption_encoded, t, rope_start=rope_start) if rope_start is not None \
-        else dit_model(z_t, caption_encoded, t)
+    kw = {} if context_lens is None else {"context_lens": context_lens}
+    output = dit_model(z_t, caption_encoded, t, rope_start=rope_start, **kw) if rope_start is not None \
+        else dit_model(z_t, caption_encoded, t, **kw)
     diffusion_loss, _per = flow_loss(output, v_objective)
     total_loss = diffusion_loss
     if master_process:
