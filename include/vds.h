@@ -449,6 +449,45 @@ int vds_adamw_guarded_multi_dev(const vds_adamw_tensor* desc_dev, const int32_t*
                                 float beta2, float eps, const float* scalars_dev, float grad_scale,
                                 const vds_optim_guard* guard, float* const* ema_tab_dev, vds_stream_t stream);
 
+/* ---- Muon for the 2-D hidden matrices: momentum, orthogonalised by a Newton-Schulz iteration (csrc/muon.hip; the
+ * reference knows AdamW only).  Every call works on a GROUP of nmat matrices of ONE shape [rows, cols] (row-major fp32,
+ * contiguous), each given by one descriptor of a device array -- the row slices of qkv.weight / context_kv.weight are
+ * matrices at pointer offsets.  rows, cols: multiples of 8, <= 2^20, rows * cols <= 2^28; 1 <= nmat <= 65535; anything
+ * else is VDS_ERR_ARG.  The three calls share one caller-allocated workspace of vds_muon_workspace_bytes(nmat, rows,
+ * cols) bytes (16-byte aligned; contents irrelevant before vds_muon_momentum; 0 for a bad shape) in which a matrix is
+ * held as bf16 [m, n], m = min(rows, cols), n = max(rows, cols): transposed on the way in and back on the way out when
+ * rows > cols.  All launches go to `stream`, nothing is read on the host, no atomics and no split-K: results are
+ * bit-identical run to run, in either deterministic mode.
+ *
+ *   vds_muon_momentum       g' = coef g;  buf = mu buf + g';  u = nesterov ? g' + mu buf : buf  (fp32), u stored as bf16
+ *                           [nmat, m, n], and sum u^2 per matrix left in the workspace by a fixed-order two-stage
+ *                           reduction.  guard (may be NULL: coef = 1, never skipped): the record of
+ *                           vds_optim_guard_finalize; coef = guard->coef, and with guard->skipped nothing is written
+ *                           (buf keeps every bit).  0 <= mu < 1.
+ *   vds_muon_orthogonalize  X = u / (||u||_F + 1e-7), then `steps` (0 .. 64; Muon uses 5) times  A = X X^T,
+ *                           B = b A + c A A,  X = a X + B X  with (a, b, c) = (3.4445, -4.7750, 2.0315); X, A, B stored as
+ *                           bf16, fp32 accumulation on the MFMA.  The result O replaces u.
+ *   vds_muon_update         p = p (1 - lr wd) - lr sqrt(max(1, rows / cols)) O;  p_bf16 = bf16(p) and
+ *                           ema = d ema + (1 - d) p where the descriptor has them.  lr = the base `lr` x lr_mult, d =
+ *                           ema_decay; with scalars_dev != NULL (the float[4] of vds_adamw_guarded_multi_dev) lr_mult =
+ *                           scalars_dev[2] and d = scalars_dev[3] instead, so that a captured step follows the schedule.
+ *                           With guard->skipped nothing is written. */
+typedef struct vds_muon_mat {
+  float* p; const float* g; float* buf; void* p_bf16; float* ema; /* p_bf16, ema: may be NULL */
+} vds_muon_mat;
+size_t vds_muon_workspace_bytes(int32_t nmat, int32_t rows, int32_t cols);
+/* byte offsets of the workspace's sections (tests, tools): offsets6 = HOST int64[6] = { x0, x1, a, b, sumsq, partials }:
+ * x0 / x1 bf16 [nmat, m, n] (x0: u after the momentum call, O after the orthogonalisation), a / b bf16 [nmat, m, m],
+ * sumsq f32 [nmat], partials f32 [nmat, ceil(rows / 64) * ceil(cols / 64)] */
+int vds_muon_workspace_layout(int32_t nmat, int32_t rows, int32_t cols, int64_t* offsets6);
+int vds_muon_momentum(const vds_muon_mat* mats_dev, int32_t nmat, int32_t rows, int32_t cols, float mu,
+                      int32_t nesterov, const vds_optim_guard* guard_or_null, void* workspace, vds_stream_t stream);
+int vds_muon_orthogonalize(void* workspace, int32_t nmat, int32_t rows, int32_t cols, int32_t steps,
+                           vds_stream_t stream);
+int vds_muon_update(const vds_muon_mat* mats_dev, int32_t nmat, int32_t rows, int32_t cols, float lr,
+                    float weight_decay, float lr_mult, float ema_decay, const float* scalars_dev,
+                    const vds_optim_guard* guard_or_null, const void* workspace, vds_stream_t stream);
+
 /* ------------------------------------------- parameter / gradient sharding (model.py:512-542) ------
  * What the reference gets from FSDP2 `fully_shard` (apply_fsdp, model.py:512-542; mesh model.py:475-498): a bf16
  * all-gather of a shard group's parameters before use and an fp32 reduce-scatter-AVERAGE of its gradients after its

@@ -73,6 +73,10 @@ class OptimGuard(C.Structure):  # vds_optim_guard
     _fields_ = [("norm", c_f32), ("coef", c_f32), ("skipped", c_i32), ("n_skipped", c_i32)]
 
 
+class MuonMat(C.Structure):  # vds_muon_mat
+    _fields_ = [("p", c_vp), ("g", c_vp), ("buf", c_vp), ("p_bf16", c_vp), ("ema", c_vp)]
+
+
 # name -> argtypes (restype is int unless noted).  Must list every symbol of include/vds.h.
 SIGNATURES = {
     "vds_version": [],
@@ -131,6 +135,11 @@ SIGNATURES = {
     "vds_adamw_guarded_multi": [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_f32, c_i32, c_f32, c_f32, c_vp, c_vp,
                                 c_f32, c_vp],
     "vds_adamw_guarded_multi_dev": [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp, c_f32, c_vp, c_vp, c_vp],
+    "vds_muon_workspace_bytes": [c_i32, c_i32, c_i32],
+    "vds_muon_workspace_layout": [c_i32, c_i32, c_i32, c_vp],
+    "vds_muon_momentum": [c_vp, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp, c_vp, c_vp],
+    "vds_muon_orthogonalize": [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp],
+    "vds_muon_update": [c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp],
     "vds_comm_available": [],
     "vds_comm_unique_id": [c_vp, C.c_size_t],
     "vds_comm_init": [c_i32, c_i32, c_vp, C.c_size_t],

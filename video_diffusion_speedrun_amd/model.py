@@ -1241,6 +1241,51 @@ class DiT(nn.Module):
             table[name] = {"lr": lr, "wd": wd, "shape": info["shape"]}
         return list(buckets.values()), table
 
+    # Muon: which parameters of a DiTBlock it manages (name suffix -> how many row slices the tensor is made of)
+    MUON_MATRICES = {"qkv.weight": 3, "attn_proj.weight": 1, "q_cross.weight": 1, "context_kv.weight": 2,
+                     "cross_proj.weight": 1, "mlp.0.weight": 1, "mlp.2.weight": 1}
+
+    def get_muon_setup(self, learning_rate, weight_decay, constant_param_classes, muon_lr=0.02, muon_weight_decay=0.0,
+                       momentum=0.95, nesterov=True, ns_steps=5):
+        """`get_mup_setup` for `optim.MuonAdamW`: the 2-D matrices of every DiTBlock -- qkv (three row slices: q, k, v
+        are orthogonalised separately), attn_proj, q_cross, context_kv (two slices), cross_proj and the two MLP weights
+        -- leave the AdamW groups and form Muon groups (`use_muon=True`, `muon_split` = 1 | 2 | 3, lr `muon_lr`,
+        `weight_decay` `muon_weight_decay`, plus `momentum`, `nesterov`, `ns_steps`); biases, norms, lambda_param, the
+        adaLN modulation, patch embedding, timestep MLP, registers and the final layer keep exactly the (lr, wd) of
+        `get_mup_setup`.  Returns (groups, table); Muon entries of the table carry "muon": True and "split"."""
+        if not float(muon_lr) > 0.0:
+            raise ValueError(f"get_muon_setup: muon_lr must be > 0, got {muon_lr}")
+        if not float(muon_weight_decay) >= 0.0:
+            raise ValueError(f"get_muon_setup: muon_weight_decay must be >= 0, got {muon_weight_decay}")
+        if not 0.0 <= float(momentum) < 1.0:
+            raise ValueError(f"get_muon_setup: momentum must be in [0, 1), got {momentum}")
+        if int(ns_steps) != ns_steps or not 0 <= ns_steps <= 64:
+            raise ValueError(f"get_muon_setup: ns_steps must be an integer in [0, 64], got {ns_steps}")
+        groups, table = self.get_mup_setup(learning_rate, weight_decay, constant_param_classes)
+        split_of = {}
+        for name, p in self.named_parameters():
+            name = name.replace("_fsdp_wrapped_module.", "")
+            if name not in table or not name.startswith("blocks."):
+                continue
+            suffix = name.split(".", 2)[2]
+            if suffix in self.MUON_MATRICES:
+                split_of[id(p)] = (self.MUON_MATRICES[suffix], name, p)
+        out = []
+        for g in groups:
+            keep = [p for p in g["params"] if id(p) not in split_of]
+            if keep:
+                out.append(dict(g, params=keep))
+        for split in (1, 2, 3):
+            ps = [p for s_, _, p in split_of.values() if s_ == split]
+            if ps:
+                out.append({"params": ps, "lr": float(muon_lr), "weight_decay": float(muon_weight_decay),
+                            "use_muon": True, "muon_split": split, "momentum": float(momentum),
+                            "nesterov": bool(nesterov), "ns_steps": int(ns_steps)})
+        for split, name, _ in split_of.values():
+            table[name] = {"lr": float(muon_lr), "wd": float(muon_weight_decay), "shape": table[name]["shape"],
+                           "muon": True, "split": split}
+        return out, table
+
     # --------------------------------------------------------------- state / copies ----
     def invalidate_compute_copy(self):
         """Force the next forward to re-cast the fp32 masters into the bf16 compute copies.  In-place writes

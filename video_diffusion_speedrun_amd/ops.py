@@ -718,6 +718,52 @@ def cfg_euler_step(cond, uncond, acc, latents, cfg_scale: float, dt: float):
                                          _stream()), "vds_cfg_euler_step")
 
 
+# ------------------------------------------------------------------------------- Muon ----
+def muon_workspace_bytes(nmat: int, rows: int, cols: int) -> int:
+    n = int(_lib.load().vds_muon_workspace_bytes(nmat, rows, cols))
+    if n == 0:
+        raise ValueError(f"Muon: unsupported group ({nmat} matrices of [{rows}, {cols}]): dimensions must be multiples of 8")
+    return n
+
+
+def muon_views(ws: torch.Tensor, nmat: int, rows: int, cols: int):
+    """the sections of a Muon workspace (uint8 tensor) as tensors: x0 / x1 bf16 [nmat, m, n], a / b bf16 [nmat, m, m],
+    sumsq f32 [nmat]; m = min(rows, cols), n = max(rows, cols)"""
+    off = (C.c_int64 * 6)()
+    check(_lib.load().vds_muon_workspace_layout(nmat, rows, cols, C.addressof(off)), "vds_muon_workspace_layout")
+    m, n = min(rows, cols), max(rows, cols)
+
+    def sec(o, shape, dt):
+        numel = 1
+        for d in shape:
+            numel *= d
+        return ws[o:o + numel * dt.itemsize].view(dt).view(shape)
+    return {"x0": sec(off[0], (nmat, m, n), bf16), "x1": sec(off[1], (nmat, m, n), bf16),
+            "a": sec(off[2], (nmat, m, m), bf16), "b": sec(off[3], (nmat, m, m), bf16), "sumsq": sec(off[4], (nmat,), f32)}
+
+
+def muon_table(mats, device) -> torch.Tensor:
+    """device array of vds_muon_mat from (p, g, buf, p_bf16 | None, ema | None) tuples of data pointers"""
+    descs = (_lib.MuonMat * len(mats))()
+    for d, (pp, g, buf, pb, ema) in zip(descs, mats):
+        d.p, d.g, d.buf, d.p_bf16, d.ema = pp, g, buf, pb, ema
+    return torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(device)
+
+
+def muon_momentum(table_ptr: int, nmat, rows, cols, mu, nesterov, guard_ptr, ws: torch.Tensor):
+    check(_lib.load().vds_muon_momentum(table_ptr, nmat, rows, cols, mu, 1 if nesterov else 0, guard_ptr, _p(ws),
+                                        _stream()), "vds_muon_momentum")
+
+
+def muon_orthogonalize(ws: torch.Tensor, nmat, rows, cols, steps: int = 5):
+    check(_lib.load().vds_muon_orthogonalize(_p(ws), nmat, rows, cols, steps, _stream()), "vds_muon_orthogonalize")
+
+
+def muon_update(table_ptr: int, nmat, rows, cols, lr, wd, lr_mult, ema_decay, scalars_ptr, guard_ptr, ws: torch.Tensor):
+    check(_lib.load().vds_muon_update(table_ptr, nmat, rows, cols, lr, wd, lr_mult, ema_decay, scalars_ptr, guard_ptr,
+                                      _p(ws), _stream()), "vds_muon_update")
+
+
 def cast_f32_bf16(src, dst):
     check(_lib.load().vds_cast_f32_bf16(_p(src), _p(dst), src.numel(), _stream()), "vds_cast_f32_bf16")
 

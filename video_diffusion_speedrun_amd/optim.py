@@ -330,3 +330,260 @@ class MuAdamW(torch.optim.Optimizer):
                                                    CHUNK, b1, b2, eps, self._step, mult, 1.0, rec.data_ptr(), ema,
                                                    self._ema_decay or 0.0, stream), "vds_adamw_guarded_multi")
         return fresh_before
+
+
+# ---------------------------------------------------------------------------------------------- Muon ----
+MUON_SLICE_BYTES = 256 << 20  # a bucket larger than this much workspace runs in slices of whole matrices
+
+
+class MuonAdamW(MuAdamW):
+    """Muon -- momentum, orthogonalised by a Newton-Schulz iteration (csrc/muon.hip) -- for the parameter groups that carry
+    `use_muon=True`, `MuAdamW` for every other group:
+
+        groups, table = dit.get_muon_setup(lr, 0.1, ["patch_proj", "context_kv", "positional_embedding"], muon_lr=0.02)
+        opt = MuonAdamW(groups, betas=(0.95, 0.99))
+
+    A Muon group holds 2-D parameters; `muon_split` = s says that each is s matrices stacked along its rows (qkv: 3,
+    context_kv: 2), which are orthogonalised separately.  Group keys: `lr`, `weight_decay`, `momentum` (0.95), `nesterov`
+    (True), `ns_steps` (5).  Per step and matrix W [rows, cols] with gradient G (coef = the clip coefficient, 1 without):
+        buf = momentum * buf + coef * G;   u = coef * G + momentum * buf  (nesterov)  |  buf
+        O = NewtonSchulz(u / (||u||_F + 1e-7), ns_steps)
+        W = W * (1 - lr * weight_decay) - lr * sqrt(max(1, rows / cols)) * O
+    The matrices are bucketed by (split) shape and every bucket runs momentum -> orthogonalize -> update as batched
+    launches on the current stream, nothing read on the host: the step replays from a captured graph and follows the LR
+    schedule through the device scalars of `use_device_scalars`.  `max_grad_norm`, `skip_nonfinite` and `ema_decay` work
+    as documented for `MuAdamW`: the sum of squares covers EVERY gradient, Muon's included, and the Muon kernels read the
+    same device record (a skipped step leaves parameters, momentum, shadows and EMA untouched).
+    `state[p]["momentum_buffer"]` is fp32 in the shape of `p`.
+
+    Whole matrices only: a parameter that is a shard of an `apply_fsdp`-wrapped model raises ValueError."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.95, 0.99), eps=1e-8, weight_decay=1e-2, fused=True,
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, fused=fused,
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay)
+        for group in self.param_groups:
+            if not group.get("use_muon"):
+                continue
+            group.setdefault("momentum", 0.95)
+            group.setdefault("nesterov", True)
+            group.setdefault("ns_steps", 5)
+            split = group.setdefault("muon_split", 1)
+            if split not in (1, 2, 3):
+                raise ValueError(f"MuonAdamW: muon_split must be 1, 2 or 3, got {split}")
+            if not 0.0 <= float(group["momentum"]) < 1.0:
+                raise ValueError(f"MuonAdamW: momentum must be in [0, 1), got {group['momentum']}")
+            if int(group["ns_steps"]) != group["ns_steps"] or not 0 <= group["ns_steps"] <= 64:
+                raise ValueError(f"MuonAdamW: ns_steps must be an integer in [0, 64], got {group['ns_steps']}")
+            for p in group["params"]:
+                g = getattr(p, "_vds_group", None)
+                full = tuple(getattr(p, "_vds_full_shape", p.shape))
+                if (g is not None and g.world > 1) or tuple(p.shape) != full:
+                    raise ValueError("MuonAdamW: Muon needs whole matrices (the Newton-Schulz iteration multiplies a "
+                                     f"matrix with its transpose); this parameter is a shard of a {full} tensor of an "
+                                     "apply_fsdp-wrapped model")
+                if p.dim() != 2:
+                    raise ValueError(f"MuonAdamW: a Muon group takes 2-D parameters, got shape {tuple(p.shape)}")
+                rows, cols = p.shape[0] // split, p.shape[1]
+                if p.shape[0] % split or rows % 8 or cols % 8 or rows == 0:
+                    raise ValueError(f"MuonAdamW: shape {tuple(p.shape)} with muon_split={split}: every matrix needs "
+                                     "rows and columns that are multiples of 8")
+        self._muon = {}        # bucket key -> dict(table, nmat, rows, cols, ...)
+        self._muon_key = None
+        self._muon_ws = None
+        self._all = {}         # descriptor / chunk tables over EVERY gradient: the guarded step's sum of squares
+        self._all_key = None
+        self._guard_done = False
+        self._muon_active = False
+
+    # ---- the AdamW half sees the groups without `use_muon` only -------------------------------------
+    @contextlib.contextmanager
+    def _adam_groups_only(self):
+        every = self.param_groups
+        self.param_groups = [g for g in every if not g.get("use_muon")]
+        try:
+            yield
+        finally:
+            self.param_groups = every
+
+    def _muon_plist(self):
+        return [(p, g) for g in self.param_groups if g.get("use_muon") for p in g["params"]
+                if p.grad is not None and p.numel() > 0]
+
+    def _adam_plist(self):
+        return [(p, g) for g in self.param_groups if not g.get("use_muon") for p in g["params"]
+                if p.grad is not None and p.numel() > 0]
+
+    def _muon_lr_plan(self, mlist):
+        """(base lr per Muon parameter, multiplier): the AdamW half's plan when the Muon groups follow the same
+        schedule (every scheduler of train.get_schedule does), else the current lr with multiplier 1 -- which a captured
+        step cannot follow, since it reads the AdamW half's multiplier from the device scalars"""
+        alist = self._adam_plist()
+        lrs, mult = self._lr_plan(alist + mlist)  # (the AdamW half first: its ratio is the common multiplier, to the bit)
+        if alist and self._dev_scalars is not None and self._lr_plan(alist)[1] != mult:
+            raise RuntimeError("MuonAdamW: the Muon groups and the AdamW groups follow different LR schedules; a step "
+                               "with device scalars (graph replay) needs one common multiplier")
+        return lrs[len(alist):], mult
+
+    def advance(self):
+        mlist = self._muon_plist()
+        if mlist and self._muon_key is not None:
+            lrs, _ = self._muon_lr_plan(mlist)
+            if tuple(lrs) != self._muon_key[1]:
+                raise RuntimeError("MuonAdamW: the base learning rates changed under a captured step; capture again")
+        if self._adam_plist():
+            with self._adam_groups_only():
+                super().advance()
+        else:
+            self._step += 1
+            self._dev_scalars.copy_(self._scalars(self._muon_lr_plan(mlist)[1]))
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._muon_key = self._all_key = None  # momentum buffers / EMAs were replaced
+
+    # ---- tables ---------------------------------------------------------------------------------------
+    def _build_all(self, plist, device):
+        """descriptor + chunk tables over every gradient (only .g and .numel are read)"""
+        descs = (_lib.AdamWTensor * len(plist))()
+        chunk_t: List[int] = []
+        chunk_s: List[int] = []
+        for i, (p, _) in enumerate(plist):
+            descs[i].g, descs[i].numel = p.grad.data_ptr(), p.numel()
+            chunk_t.extend([i] * ((p.numel() + CHUNK - 1) // CHUNK))
+            chunk_s.extend(range(0, p.numel(), CHUNK))
+        nws = int(_lib.load().vds_grad_sumsq_workspace_floats(len(chunk_t)))
+        self._all = {"desc": torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(device),
+                     "ct": torch.tensor(chunk_t, dtype=torch.int32, device=device),
+                     "cs": torch.tensor(chunk_s, dtype=torch.int64, device=device), "n": len(chunk_t),
+                     "ws": torch.empty(nws, dtype=torch.float32, device=device)}
+
+    def _build_muon(self, mlist, lrs, device):
+        buckets = {}
+        for (p, group), lr in zip(mlist, lrs):
+            st = self.state[p]
+            split = group["muon_split"]
+            rows, cols = p.shape[0] // split, p.shape[1]
+            key = (rows, cols, lr, float(group["weight_decay"]), float(group["momentum"]), bool(group["nesterov"]),
+                   int(group["ns_steps"]))
+            shadow = getattr(p, "_vds_shadow", None)
+            if shadow is not None and shadow.numel() != p.numel():
+                shadow = None
+            ema = st.get("ema") if self._ema_decay is not None else None
+            for k in range(split):
+                o = k * rows * cols
+                buckets.setdefault(key, []).append((p.data.data_ptr() + 4 * o, p.grad.data_ptr() + 4 * o,
+                                                    st["momentum_buffer"].data_ptr() + 4 * o,
+                                                    None if shadow is None else shadow.data_ptr() + 2 * o,
+                                                    None if ema is None else ema.data_ptr() + 4 * o))
+        self._muon, ws_bytes = {}, 0
+        for key, mats in buckets.items():
+            rows, cols = key[0], key[1]
+            per = max(1, MUON_SLICE_BYTES // ops.muon_workspace_bytes(1, rows, cols))
+            slices = [(i, min(per, len(mats) - i)) for i in range(0, len(mats), per)]
+            ws_bytes = max(ws_bytes, ops.muon_workspace_bytes(slices[0][1], rows, cols))
+            self._muon[key] = {"table": ops.muon_table(mats, device), "slices": slices}
+        if self._muon_ws is None or self._muon_ws.numel() < ws_bytes or self._muon_ws.device != device:
+            self._muon_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+
+    # ---- the step -----------------------------------------------------------------------------------------
+    def _guard_all(self, device):
+        """sum of squares over EVERY gradient -> (all-reduce over the shard group) -> record; once per step"""
+        lib, stream = _lib.load(), ops._stream()
+        rec = self._guard_record(device)
+        d, ss = self._all, self._dev["sumsq"]
+        max_norm = 0.0 if self.max_grad_norm is None else self.max_grad_norm
+        skip = 1 if self.skip_nonfinite else 0
+        _lib.check(lib.vds_grad_sumsq_multi(d["desc"].data_ptr(), d["ct"].data_ptr(), d["cs"].data_ptr(), d["n"], CHUNK,
+                                            d["ws"].data_ptr(), ss.data_ptr(), max_norm, skip, rec.data_ptr(), stream),
+                   "vds_grad_sumsq_multi")
+        self._guard_done = True
+        return rec
+
+    def _step_guarded(self, plist, device, mult, b1, b2, eps):
+        """the inherited guarded AdamW launch over the AdamW half, behind a record that covers every gradient"""
+        if not self._muon_active:  # no Muon gradient this step: exactly the inherited sequence
+            return super()._step_guarded(plist, device, mult, b1, b2, eps)
+        lib, stream, d = _lib.load(), ops._stream(), self._dev
+        rec = self._guard_all(device)
+        fresh_before = {id(g) for g in {id(getattr(p, "_vds_group", None)): getattr(p, "_vds_group", None)
+                                        for p, _ in plist}.values() if g is not None and g.shadow_fresh}
+        ema = d["ema"].data_ptr() if d.get("ema") is not None else None
+        if self._dev_scalars is not None:
+            if not torch.cuda.is_current_stream_capturing():
+                self._dev_scalars.copy_(self._scalars(mult))
+            _lib.check(lib.vds_adamw_guarded_multi_dev(d["desc"].data_ptr(), d["ct"].data_ptr(), d["cs"].data_ptr(), d["n"],
+                                                       CHUNK, b1, b2, eps, self._dev_scalars.data_ptr(), 1.0,
+                                                       rec.data_ptr(), ema, stream), "vds_adamw_guarded_multi_dev")
+        else:
+            _lib.check(lib.vds_adamw_guarded_multi(d["desc"].data_ptr(), d["ct"].data_ptr(), d["cs"].data_ptr(), d["n"],
+                                                   CHUNK, b1, b2, eps, self._step, mult, 1.0, rec.data_ptr(), ema,
+                                                   self._ema_decay or 0.0, stream), "vds_adamw_guarded_multi")
+        return fresh_before
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        assert closure is None
+        mlist = self._muon_plist()
+        self._muon_active = bool(mlist)
+        if not mlist:
+            with self._adam_groups_only():
+                return super().step()
+        alist = self._adam_plist()
+        for p, _ in mlist:
+            if not p.is_cuda:
+                raise RuntimeError("MuonAdamW is a HIP kernel: parameters must be on the GPU")
+            assert p.dtype == torch.float32 and p.grad.dtype == torch.float32
+            assert p.data.is_contiguous() and p.grad.is_contiguous()
+        device = mlist[0][0].device
+        if self._ema_decay is not None and self._ema_swapped:
+            raise RuntimeError("MuonAdamW.step() while the EMA is swapped in: leave ema_weights() / swap_ema() back first")
+        for p, _ in mlist:  # first sight of a parameter: zero momentum; its EMA starts as a copy of it
+            st = self.state[p]
+            if "momentum_buffer" not in st or st["momentum_buffer"].shape != p.shape:
+                st["momentum_buffer"] = torch.zeros_like(p.data, memory_format=torch.contiguous_format)
+                self._muon_key = None
+            if self._ema_decay is not None and ("ema" not in st or st["ema"].numel() != p.numel()):
+                st["ema"] = p.data.detach().clone()
+                self._muon_key = None
+        groups = {id(getattr(p, "_vds_group", None)): getattr(p, "_vds_group", None) for p, _ in mlist}
+        fresh_before = {i for i, g in groups.items() if g is not None and g.shadow_fresh}
+        if self.guarded:
+            akey = tuple((p.grad.data_ptr(), p.numel()) for p, _ in alist + mlist)
+            if akey != self._all_key:
+                self._build_all(alist + mlist, device)
+                self._all_key = akey
+        # ---- AdamW half (computes the guard record over every gradient on its way: _step_guarded above)
+        self._guard_done = False
+        if alist:
+            with self._adam_groups_only():
+                super().step()
+        else:
+            self._step += 1
+        lrs, mult = self._muon_lr_plan(mlist)
+        if not alist and self._dev_scalars is not None and not torch.cuda.is_current_stream_capturing():
+            self._dev_scalars.copy_(self._scalars(mult))
+        rec = None
+        if self.guarded:
+            rec = (self._guard_record(device) if self._guard_done else self._guard_all(device)).data_ptr()
+        # ---- Muon half
+        mkey = (tuple((p.data.data_ptr(), p.grad.data_ptr(), self.state[p]["momentum_buffer"].data_ptr(),
+                       g["muon_split"], g["weight_decay"], g["momentum"], g["nesterov"], g["ns_steps"],
+                       self._ema_decay is not None) for p, g in mlist), tuple(lrs))
+        if mkey != self._muon_key:
+            self._build_muon(mlist, lrs, device)
+            self._muon_key = mkey
+        sc = None if self._dev_scalars is None else self._dev_scalars.data_ptr()
+        ws = self._muon_ws
+        for (rows, cols, lr, wd, mu, nesterov, ns_steps), b in self._muon.items():
+            for first, n in b["slices"]:
+                tab = b["table"].data_ptr() + first * C.sizeof(_lib.MuonMat)
+                ops.muon_momentum(tab, n, rows, cols, mu, nesterov, rec, ws)
+                ops.muon_orthogonalize(ws, n, rows, cols, ns_steps)
+                ops.muon_update(tab, n, rows, cols, lr, wd, mult, self._ema_decay or 0.0, sc, rec, ws)
+        # the bf16 shadows of the Muon matrices are current again (same rule as the AdamW half: a step that may have
+        # been skipped can only keep that claim, not establish it)
+        for i, g in groups.items():
+            if g is not None and (not self.skip_nonfinite or i in fresh_before):
+                g.mark_shadow_fresh()
+        return None
