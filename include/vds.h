@@ -275,6 +275,24 @@ int vds_qkv_rope_bwd(const void* dq, const void* dk, const void* dv, const float
                      const float* sinb, const void* qkv_raw, const void* v0, const void* lam,
                      float* dv0_acc, float* dlam, void* dqkv, int32_t mix, int32_t add_dv0, int32_t B,
                      int32_t L, int32_t H, int32_t hd, int32_t hdp, vds_stream_t stream);
+/* QK-norm: the two calls above with a weightless RMSNorm on every head row of q and k before the rotation
+ * (self-attention only; v, residual-V, the pad and the ones columns are those of the plain calls, bit for bit).
+ *   forward:  q_n = bf16(q * rsqrt(mean_d(q^2) + eps)) over the hd data columns (fp32 math), then the rotation of q_n
+ *             exactly as in vds_qkv_rope_fwd (fp32 math, one rounding); the same for k.
+ *   backward: with g = the inverse rotation of dq (fp32), r recomputed from the raw row of qkv_raw and y = q r (fp32):
+ *             dq_raw = bf16(r (g - y mean_d(g y))) -- one rounding, at the store; the same for k.  qkv_raw (the forward's
+ *             qkv) is required in every call, not only when mix is set.
+ * A zero row gives r = eps^-1/2, output 0 and a finite gradient.  No atomics are added: both calls are as reproducible as
+ * the plain ones (dlam: see vds_set_deterministic).  Argument checks and kernel selection (token-tile / wave-per-token form
+ * under the same conditions and knobs, the element-wise form otherwise) are those of the plain calls, plus eps > 0 and
+ * qkv_raw != NULL (VDS_ERR_ARG).  The plain calls launch none of the normed kernel instances. */
+int vds_qkv_rope_norm_fwd(const void* qkv, const float* cosb, const float* sinb, const void* v0,
+                          const void* lam, void* q, void* k, void* v, int32_t B, int32_t L, int32_t H,
+                          int32_t hd, int32_t hdp, float eps, vds_stream_t stream);
+int vds_qkv_rope_norm_bwd(const void* dq, const void* dk, const void* dv, const float* cosb,
+                          const float* sinb, const void* qkv_raw, const void* v0, const void* lam,
+                          float* dv0_acc, float* dlam, void* dqkv, int32_t mix, int32_t add_dv0, int32_t B,
+                          int32_t L, int32_t H, int32_t hd, int32_t hdp, float eps, vds_stream_t stream);
 /* residual-V (/root/reference/model.py:129-130, backward): out[b,h,l,:hd] (f32 [B,H,L,hdp]; + its old value when
  * accumulate != 0) = sum_i (1 - lam_i) dv_i[b,h,l,:hd] over n blocks.  dv / lam: HOST arrays of n DEVICE pointers (dv_i bf16
  * [B,H,L,hdp] contiguous, 16-byte aligned; lam_i one bf16).  Columns >= hd of out are not touched. */

@@ -481,10 +481,14 @@ __global__ __launch_bounds__(256) void det_finish_scalar_kernel(const float* par
 // ------------------------------------------------- qkv split + RoPE + residual-V (fwd) ---
 // model.py:126-134,266-275.  One thread = 4 elements d..d+3 of the first half of one head of
 // one token and their rotation partners d+hd/2.. (hd/2 is a multiple of 4 for 64/72/128).
+// NORM (QK-norm, vds_qkv_rope_norm_fwd): q and k head rows go through a weightless RMSNorm first -- x * rsqrt(mean_d x^2
+// + eps) in fp32, rounded to bf16 -- and the rotation takes that.  Every thread of a head sums the head row's squares
+// itself, in column order (this is the fallback form: the token-tile kernel below shares the sums through LDS).
+template <bool NORM = false>
 __global__ __launch_bounds__(256) void qkv_rope_fwd_kernel(const bf16_t* qkv, const float* cosb, const float* sinb,
                                                            const bf16_t* v0, const bf16_t* lamp, bf16_t* q,
                                                            bf16_t* k, bf16_t* v, int B, int L, int H, int hd,
-                                                           int hdp) {
+                                                           int hdp, float eps) {
   const int upt = H * (hd >> 3);
   const long gid = (long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long)B * L * upt) return;
@@ -501,8 +505,22 @@ __global__ __launch_bounds__(256) void qkv_rope_fwd_kernel(const bf16_t* qkv, co
   for (int which = 0; which < 2; ++which) {
     const u32x2 lo = *reinterpret_cast<const u32x2*>(src + which * D);
     const u32x2 hi = *reinterpret_cast<const u32x2*>(src + which * D + half);
-    const float x1[4] = {bflo(lo[0]), bfhi(lo[0]), bflo(lo[1]), bfhi(lo[1])};
-    const float x2[4] = {bflo(hi[0]), bfhi(hi[0]), bflo(hi[1]), bfhi(hi[1])};
+    float x1[4] = {bflo(lo[0]), bfhi(lo[0]), bflo(lo[1]), bfhi(lo[1])};
+    float x2[4] = {bflo(hi[0]), bfhi(hi[0]), bflo(hi[1]), bfhi(hi[1])};
+    if constexpr (NORM) {
+      const bf16_t* row = qkv + tok * 3 * D + which * D + hh * hd;
+      float ss = 0.f;
+      for (int d = 0; d < hd; d += 4) {
+        const u32x2 w = *reinterpret_cast<const u32x2*>(row + d);
+        ss += bflo(w[0]) * bflo(w[0]) + bfhi(w[0]) * bfhi(w[0]) + bflo(w[1]) * bflo(w[1]) + bfhi(w[1]) * bfhi(w[1]);
+      }
+      const float r = rsqrtf(ss / (float)hd + eps);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        x1[e] = bf2f(f2bf(x1[e] * r));
+        x2[e] = bf2f(f2bf(x2[e] * r));
+      }
+    }
     float y1[4], y2[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -556,10 +574,14 @@ __global__ __launch_bounds__(256) void qkv_rope_fwd_kernel(const bf16_t* qkv, co
 // Token-tile form of the kernel above (rope_stage.h): T consecutive tokens per workgroup, qkv rows copied to LDS by
 // LDS-DMA, q / k rotated in place there, every global access 16 bytes wide and every (tensor, head) written as a run of T
 // complete head rows.  Same arithmetic and rounding points.
-template <int HD, int HDP, int T>
+// NORM (QK-norm): the nt * 2H values rsqrt(mean_d x^2 + eps) of the staged q / k head rows are computed from LDS into a
+// small array behind the rows (ropestage::row_rstd), and the rotation pass scales and rounds each element before it
+// rotates: no byte more of global traffic than the plain instance.
+template <int HD, int HDP, int T, bool NORM = false>
 __global__ __launch_bounds__(256) void qkv_rope_fwd_tile_kernel(const bf16_t* qkv, const float* cosb, const float* sinb,
                                                                 const bf16_t* v0, const bf16_t* lamp, bf16_t* q,
-                                                                bf16_t* k, bf16_t* v, long ntok, int L, int H) {
+                                                                bf16_t* k, bf16_t* v, long ntok, int L, int H,
+                                                                float eps) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -574,7 +596,14 @@ __global__ __launch_bounds__(256) void qkv_rope_fwd_tile_kernel(const bf16_t* qk
   }
   VDS_WAIT_VM(0);
   __syncthreads();
-  ropestage::rotate_rows<HD>(smem, cosb, sinb, tok0, nt, L, H, row_b, tid);
+  if constexpr (NORM) {
+    float* rs = reinterpret_cast<float*>(smem + ropestage::lds_bytes(T, D));
+    ropestage::row_rstd<HD>(smem, rs, nt, H, row_b, eps, tid);
+    __syncthreads();
+    ropestage::rotate_rows<HD, true>(smem, cosb, sinb, tok0, nt, L, H, row_b, tid, rs);
+  } else {
+    ropestage::rotate_rows<HD>(smem, cosb, sinb, tok0, nt, L, H, row_b, tid);
+  }
   __syncthreads();
   constexpr int CPR = HDP >> 3, DCH = HD >> 3;
   constexpr bool ONES = (HDP - HD) >= 8;
@@ -636,12 +665,16 @@ __global__ __launch_bounds__(256) void rope_apply_kernel(const bf16_t* x, long x
 }
 
 // backward of the above
+// NORM (QK-norm, vds_qkv_rope_norm_bwd): with g = the inverse rotation of dq (fp32), x = the raw q row of qkv_raw,
+// r = rsqrt(mean_d x^2 + eps) and y = x r, the kernel writes bf16(r (g - y mean_d(g y))) -- one rounding; the same for k.
+// Every thread of a head walks the whole head row for the two sums, in column order (fallback form).
+template <bool NORM = false>
 __global__ __launch_bounds__(256) void qkv_rope_bwd_kernel(const bf16_t* dq, const bf16_t* dk, const bf16_t* dv,
                                                            const float* cosb, const float* sinb,
                                                            const bf16_t* qkv_raw, const bf16_t* v0,
                                                            const bf16_t* lamp, float* dv0_acc, float* dlam,
                                                            bf16_t* dqkv, int mix, int add_dv0, int B, int L, int H,
-                                                           int hd, int hdp, float* det) {
+                                                           int hd, int hdp, float* det, float eps) {
   __shared__ float red[4];
   const int upt = H * (hd >> 3);
   const long gid = (long)blockIdx.x * 256 + threadIdx.x;
@@ -668,6 +701,36 @@ __global__ __launch_bounds__(256) void qkv_rope_bwd_kernel(const bf16_t* dq, con
       for (int e = 0; e < 4; ++e) {
         d1[e] = g1[e] * c4[e] - g2[e] * s4[e];
         d2[e] = g1[e] * s4[e] + g2[e] * c4[e];
+      }
+      if constexpr (NORM) {
+        const bf16_t* xrow = qkv_raw + tok * 3 * D + which * D + hh * hd;
+        const bf16_t* grow = (which == 0 ? dq : dk) + (((long)b * H + hh) * L + l) * hdp;
+        float ss = 0.f, gx = 0.f;
+        for (int d = 0; d < half; d += 4) {
+          const f32x4 cc = *reinterpret_cast<const f32x4*>(cosb + (long)l * half + d);
+          const f32x4 sn = *reinterpret_cast<const f32x4*>(sinb + (long)l * half + d);
+          const u32x2 ga = *reinterpret_cast<const u32x2*>(grow + d), gb = *reinterpret_cast<const u32x2*>(grow + d + half);
+          const u32x2 xa = *reinterpret_cast<const u32x2*>(xrow + d), xb = *reinterpret_cast<const u32x2*>(xrow + d + half);
+          const float a1[4] = {bflo(ga[0]), bfhi(ga[0]), bflo(ga[1]), bfhi(ga[1])};
+          const float a2[4] = {bflo(gb[0]), bfhi(gb[0]), bflo(gb[1]), bfhi(gb[1])};
+          const float z1[4] = {bflo(xa[0]), bfhi(xa[0]), bflo(xa[1]), bfhi(xa[1])};
+          const float z2[4] = {bflo(xb[0]), bfhi(xb[0]), bflo(xb[1]), bfhi(xb[1])};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            ss += z1[e] * z1[e] + z2[e] * z2[e];
+            gx += (a1[e] * cc[e] - a2[e] * sn[e]) * z1[e] + (a1[e] * sn[e] + a2[e] * cc[e]) * z2[e];
+          }
+        }
+        const float r = rsqrtf(ss / (float)hd + eps);
+        const float m = r * r * gx / (float)hd;  // mean_d(g y) r: what multiplies x below
+        const u32x2 xa = *reinterpret_cast<const u32x2*>(xrow + 4 * i), xb = *reinterpret_cast<const u32x2*>(xrow + 4 * i + half);
+        const float z1[4] = {bflo(xa[0]), bfhi(xa[0]), bflo(xa[1]), bfhi(xa[1])};
+        const float z2[4] = {bflo(xb[0]), bfhi(xb[0]), bflo(xb[1]), bfhi(xb[1])};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          d1[e] = r * (d1[e] - z1[e] * m);
+          d2[e] = r * (d2[e] - z2[e] * m);
+        }
       }
       u32x2 w1 = {pack_bf2(d1[0], d1[1]), pack_bf2(d1[2], d1[3])};
       u32x2 w2 = {pack_bf2(d2[0], d2[1]), pack_bf2(d2[2], d2[3])};
@@ -735,13 +798,20 @@ __global__ __launch_bounds__(256) void qkv_rope_bwd_kernel(const bf16_t* dq, con
 // Measured on the DiT-XL step (B = 12, same box): 18.8 ms per step against 22.2 ms.  The same restructuring of
 // the FORWARD kernel was slower (14.3 against 13.4 ms: its scattered 144-byte head-row stores gain nothing from
 // 16-byte lanes and it pays the LDS exchange) and is not in the tree.
-template <int NI, int QF = -1>
+// NORM (QK-norm; bf16 output only): a first pass over the wave's items rotates dq / dk back (g, kept in registers), loads
+// the raw q / k chunks of qkv_raw (16 bytes per lane) and forms each chunk's partial sums of x^2 and g x.  A head owns
+// hd/8 chunks -- 9 at head_dim 72, not a power-of-two lane group -- so the partials meet in LDS, not in a butterfly: they
+// overwrite the wave's dq copy (16 bytes per chunk: the same D * 2 bytes; every partner read is done by then), and each
+// lane adds the hd/8 partials of its head in chunk order.  The result r (g - x r^2 mean_d(g x)) is rounded once.
+template <int NI, int QF = -1, bool NORM = false>
 __global__ __launch_bounds__(256) void qkv_rope_bwd_tok_kernel(const bf16_t* dq, const bf16_t* dk, const bf16_t* dv,
                                                                const float* cosb, const float* sinb,
                                                                const bf16_t* qkv_raw, const bf16_t* v0,
                                                                const bf16_t* lamp, float* dv0_acc, float* dlam,
                                                                bf16_t* dqkv, int mix, int add_dv0, int B, int L,
-                                                               int H, int hd, int hdp, QOut qo, float* det) {
+                                                               int H, int hd, int hdp, QOut qo, float* det,
+                                                               float eps) {
+  static_assert(!NORM || QF < 0, "the normed backward writes bf16");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ float red[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -779,6 +849,65 @@ __global__ __launch_bounds__(256) void qkv_rope_bwd_tok_kernel(const bf16_t* dq,
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
       const float lam = mix ? bf2f(*lamp) : 0.f, oml = 1.0f - lam;
+    float nq[NORM ? NI : 1][8], nk[NORM ? NI : 1][8];  // NORM: g = the inverse rotation of dq / dk
+    u32x4 xq[NORM ? NI : 1], xk[NORM ? NI : 1];        // NORM: the raw q / k chunks
+    if constexpr (NORM) {
+      f32x4 part[NI];
+#pragma unroll
+      for (int i = 0; i < NI; ++i) {
+        const int c = lane + 64 * i;
+        if (c >= nch) continue;
+        const int hh = c / cph, j = c % cph;
+        float gq[8], gk[8];
+        unpack8(rq[i], gq);
+        unpack8(rk[i], gk);
+#pragma unroll
+        for (int g4 = 0; g4 < 2; ++g4) {
+          const int d0 = 8 * j + 4 * g4;
+          const bool first = d0 < half;
+          const int pd = first ? d0 + half : d0 - half, ci = first ? d0 : d0 - half;
+          const u32x2 pq = *reinterpret_cast<const u32x2*>(wq + (hh * hd + pd) * 2);
+          const u32x2 pk = *reinterpret_cast<const u32x2*>(wk + (hh * hd + pd) * 2);
+          const f32x4 c4 = *reinterpret_cast<const f32x4*>(wc + ci);
+          const f32x4 s4 = *reinterpret_cast<const f32x4*>(wsn + ci);
+          const float pqf[4] = {bflo(pq[0]), bfhi(pq[0]), bflo(pq[1]), bfhi(pq[1])};
+          const float pkf[4] = {bflo(pk[0]), bfhi(pk[0]), bflo(pk[1]), bfhi(pk[1])};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float sg = first ? -s4[e] : s4[e];
+            nq[i][4 * g4 + e] = gq[4 * g4 + e] * c4[e] + pqf[e] * sg;
+            nk[i][4 * g4 + e] = gk[4 * g4 + e] * c4[e] + pkf[e] * sg;
+          }
+        }
+        xq[i] = *reinterpret_cast<const u32x4*>(qkv_raw + tok * 3 * D + c * 8);
+        xk[i] = *reinterpret_cast<const u32x4*>(qkv_raw + tok * 3 * D + D + c * 8);
+        float a[8], bb[8];
+        unpack8(xq[i], a);
+        unpack8(xk[i], bb);
+        f32x4 pp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          pp[0] += a[e] * a[e];
+          pp[1] += nq[i][e] * a[e];
+          pp[2] += bb[e] * bb[e];
+          pp[3] += nk[i][e] * bb[e];
+        }
+        part[i] = pp;
+      }
+      // every lane's partner reads of wq are complete before any lane overwrites it (a wave's LDS accesses execute in
+      // program order; the fence and the barrier keep the compiler from reordering them)
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_s_waitcnt(0xc07f);
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int i = 0; i < NI; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nch) *reinterpret_cast<f32x4*>(wq + c * 16) = part[i];
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_s_waitcnt(0xc07f);
+      __builtin_amdgcn_wave_barrier();
+    }
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int c = lane + 64 * i;
@@ -786,25 +915,40 @@ __global__ __launch_bounds__(256) void qkv_rope_bwd_tok_kernel(const bf16_t* dq,
       const int hh = c / cph, j = c % cph;
       const long so = (((long)b * H + hh) * L + l) * hdp + 8 * j;
       float gq[8], gk[8], oq[8], ok_[8];
-      unpack8(rq[i], gq);
-      unpack8(rk[i], gk);
+      if constexpr (NORM) {
+        f32x4 acc = *reinterpret_cast<const f32x4*>(wq + (hh * cph) * 16);
+        for (int jj = 1; jj < cph; ++jj) acc += *reinterpret_cast<const f32x4*>(wq + (hh * cph + jj) * 16);
+        const float ihd = 1.0f / (float)hd;
+        const float r_q = rsqrtf(acc[0] * ihd + eps), r_k = rsqrtf(acc[2] * ihd + eps);
+        const float m_q = r_q * r_q * acc[1] * ihd, m_k = r_k * r_k * acc[3] * ihd;  // r * mean_d(g y): multiplies x
+        unpack8(xq[i], gq);
+        unpack8(xk[i], gk);
 #pragma unroll
-      for (int g4 = 0; g4 < 2; ++g4) {
-        const int d0 = 8 * j + 4 * g4;
-        const bool first = d0 < half;
-        const int pd = first ? d0 + half : d0 - half, ci = first ? d0 : d0 - half;
-        const u32x2 pq = *reinterpret_cast<const u32x2*>(wq + (hh * hd + pd) * 2);
-        const u32x2 pk = *reinterpret_cast<const u32x2*>(wk + (hh * hd + pd) * 2);
-        const f32x4 c4 = *reinterpret_cast<const f32x4*>(wc + ci);
-        const f32x4 s4 = *reinterpret_cast<const f32x4*>(wsn + ci);
-        const float pqf[4] = {bflo(pq[0]), bfhi(pq[0]), bflo(pq[1]), bfhi(pq[1])};
-        const float pkf[4] = {bflo(pk[0]), bfhi(pk[0]), bflo(pk[1]), bfhi(pk[1])};
+        for (int e = 0; e < 8; ++e) {
+          oq[e] = r_q * (nq[i][e] - gq[e] * m_q);
+          ok_[e] = r_k * (nk[i][e] - gk[e] * m_k);
+        }
+      } else {
+        unpack8(rq[i], gq);
+        unpack8(rk[i], gk);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          // transposed rotation: d1 = g1 c - g2 s ; d2 = g1 s + g2 c
-          const float sg = first ? -s4[e] : s4[e];
-          oq[4 * g4 + e] = gq[4 * g4 + e] * c4[e] + pqf[e] * sg;
-          ok_[4 * g4 + e] = gk[4 * g4 + e] * c4[e] + pkf[e] * sg;
+        for (int g4 = 0; g4 < 2; ++g4) {
+          const int d0 = 8 * j + 4 * g4;
+          const bool first = d0 < half;
+          const int pd = first ? d0 + half : d0 - half, ci = first ? d0 : d0 - half;
+          const u32x2 pq = *reinterpret_cast<const u32x2*>(wq + (hh * hd + pd) * 2);
+          const u32x2 pk = *reinterpret_cast<const u32x2*>(wk + (hh * hd + pd) * 2);
+          const f32x4 c4 = *reinterpret_cast<const f32x4*>(wc + ci);
+          const f32x4 s4 = *reinterpret_cast<const f32x4*>(wsn + ci);
+          const float pqf[4] = {bflo(pq[0]), bfhi(pq[0]), bflo(pq[1]), bfhi(pq[1])};
+          const float pkf[4] = {bflo(pk[0]), bfhi(pk[0]), bflo(pk[1]), bfhi(pk[1])};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            // transposed rotation: d1 = g1 c - g2 s ; d2 = g1 s + g2 c
+            const float sg = first ? -s4[e] : s4[e];
+            oq[4 * g4 + e] = gq[4 * g4 + e] * c4[e] + pqf[e] * sg;
+            ok_[4 * g4 + e] = gk[4 * g4 + e] * c4[e] + pkf[e] * sg;
+          }
         }
       }
       unsigned char* qdst = nullptr;
@@ -1547,9 +1691,11 @@ static bool rope_tok_form(int H, int hd, int hdp) {
   return on && (hdp & 7) == 0 && (hd & 7) == 0 && H * hd <= 2048;
 }
 
-extern "C" int vds_qkv_rope_fwd(const void* qkv, const float* cosb, const float* sinb, const void* v0,
-                                const void* lam, void* q, void* k, void* v, int32_t B, int32_t L, int32_t H,
-                                int32_t hd, int32_t hdp, vds_stream_t stream) {
+// NORM = false: vds_qkv_rope_fwd (launches the instances without the flag only); true: vds_qkv_rope_norm_fwd
+template <bool NORM>
+static int qkv_rope_fwd_impl(const void* qkv, const float* cosb, const float* sinb, const void* v0, const void* lam,
+                             void* q, void* k, void* v, int32_t B, int32_t L, int32_t H, int32_t hd, int32_t hdp,
+                             float eps, vds_stream_t stream) {
   if (!qkv || !cosb || !sinb || !q || !k || !v || (hd & 7) || hdp < hd || (hdp & 3)) return VDS_ERR_ARG;
   if (v0 && !lam) return VDS_ERR_ARG;
   if (((hdp - hd) >> 2) > (hd >> 3)) return VDS_ERR_UNSUPPORTED;
@@ -1562,16 +1708,16 @@ extern "C" int vds_qkv_rope_fwd(const void* qkv, const float* cosb, const float*
     const long ntok = (long)B * L;
 #define ROPE_TILE(HD, HDP, T)                                                                                      \
   do {                                                                                                             \
-    const int lds = ropestage::lds_bytes(T, H * HD);                                                               \
+    const int lds = ropestage::lds_bytes(T, H * HD) + (NORM ? T * 2 * H * 4 : 0); /* + the rows' rsqrt values */    \
     static bool attr = false;                                                                                      \
     if (!attr) {                                                                                                   \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qkv_rope_fwd_tile_kernel<HD, HDP, T>),              \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qkv_rope_fwd_tile_kernel<HD, HDP, T, NORM>),        \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                           \
       attr = true;                                                                                                 \
     }                                                                                                              \
-    hipLaunchKernelGGL((qkv_rope_fwd_tile_kernel<HD, HDP, T>), dim3((unsigned)((ntok + T - 1) / T)), dim3(256), lds, \
-                       (hipStream_t)stream, (const bf16_t*)qkv, cosb, sinb, (const bf16_t*)v0, (const bf16_t*)lam,  \
-                       (bf16_t*)q, (bf16_t*)k, (bf16_t*)v, ntok, L, H);                                             \
+    hipLaunchKernelGGL((qkv_rope_fwd_tile_kernel<HD, HDP, T, NORM>), dim3((unsigned)((ntok + T - 1) / T)),         \
+                       dim3(256), lds, (hipStream_t)stream, (const bf16_t*)qkv, cosb, sinb, (const bf16_t*)v0,     \
+                       (const bf16_t*)lam, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v, ntok, L, H, eps);                   \
     return ok();                                                                                                   \
   } while (0)
 #define ROPE_TILE_T(HD, HDP)                       \
@@ -1588,10 +1734,22 @@ extern "C" int vds_qkv_rope_fwd(const void* qkv, const float* cosb, const float*
 #undef ROPE_TILE_T
 #undef ROPE_TILE
   }
-  hipLaunchKernelGGL(qkv_rope_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(qkv_rope_fwd_kernel<NORM>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)qkv, cosb, sinb, (const bf16_t*)v0, (const bf16_t*)lam, (bf16_t*)q, (bf16_t*)k,
-                     (bf16_t*)v, B, L, H, hd, hdp);
+                     (bf16_t*)v, B, L, H, hd, hdp, eps);
   return ok();
+}
+extern "C" int vds_qkv_rope_fwd(const void* qkv, const float* cosb, const float* sinb, const void* v0,
+                                const void* lam, void* q, void* k, void* v, int32_t B, int32_t L, int32_t H,
+                                int32_t hd, int32_t hdp, vds_stream_t stream) {
+  return qkv_rope_fwd_impl<false>(qkv, cosb, sinb, v0, lam, q, k, v, B, L, H, hd, hdp, 0.f, stream);
+}
+// QK-norm: q and k head rows through a weightless RMSNorm (fp32, rounded to bf16) before the rotation
+extern "C" int vds_qkv_rope_norm_fwd(const void* qkv, const float* cosb, const float* sinb, const void* v0,
+                                     const void* lam, void* q, void* k, void* v, int32_t B, int32_t L, int32_t H,
+                                     int32_t hd, int32_t hdp, float eps, vds_stream_t stream) {
+  if (!(eps > 0.f)) return VDS_ERR_ARG;
+  return qkv_rope_fwd_impl<true>(qkv, cosb, sinb, v0, lam, q, k, v, B, L, H, hd, hdp, eps, stream);
 }
 
 // ---- residual-V: the gradient that reaches v_0 from the blocks that mixed it in (model.py:129-130), summed once -------
@@ -1655,10 +1813,11 @@ extern "C" int vds_dv0_reduce(const void* const* dv, const void* const* lam, int
   return ok();
 }
 
-extern "C" int vds_qkv_rope_bwd(const void* dq, const void* dk, const void* dv, const float* cosb,
-                                const float* sinb, const void* qkv_raw, const void* v0, const void* lam,
-                                float* dv0_acc, float* dlam, void* dqkv, int32_t mix, int32_t add_dv0, int32_t B,
-                                int32_t L, int32_t H, int32_t hd, int32_t hdp, vds_stream_t stream) {
+template <bool NORM>
+static int qkv_rope_bwd_impl(const void* dq, const void* dk, const void* dv, const float* cosb, const float* sinb,
+                             const void* qkv_raw, const void* v0, const void* lam, float* dv0_acc, float* dlam,
+                             void* dqkv, int32_t mix, int32_t add_dv0, int32_t B, int32_t L, int32_t H, int32_t hd,
+                             int32_t hdp, float eps, vds_stream_t stream) {
   if (!dq || !dk || !dv || !cosb || !sinb || !dqkv || (hd & 7)) return VDS_ERR_ARG;
   if (mix && (!qkv_raw || !v0 || !lam || !dlam || (mix == 1 && !dv0_acc) || mix < 0 || mix > 2)) return VDS_ERR_ARG;
   if (add_dv0 && !dv0_acc) return VDS_ERR_ARG;
@@ -1667,26 +1826,45 @@ extern "C" int vds_qkv_rope_bwd(const void* dq, const void* dk, const void* dv, 
   const bool tok = rope_tok_form(H, hd, hdp);
   const unsigned nblk = tok ? (unsigned)(((long)B * L + 3) / 4) : (unsigned)((n + 255) / 256);
   float* det = nullptr;  // deterministic mode: the lambda gradient as per-workgroup partials + one fixed-order sum
-  if (mix && vdsdet::on() && !(det = vdsdet::workspace(nblk, "vds_qkv_rope_bwd"))) return VDS_ERR_ARG;
+  if (mix && vdsdet::on() && !(det = vdsdet::workspace(nblk, NORM ? "vds_qkv_rope_norm_bwd" : "vds_qkv_rope_bwd")))
+    return VDS_ERR_ARG;
   if (tok) {
     const int D = H * hd, lds = 4 * (4 * D + 4 * hd);
     const dim3 grid(nblk);
 #define ROPE_BWD(NI)                                                                                                \
-  hipLaunchKernelGGL(qkv_rope_bwd_tok_kernel<NI>, grid, dim3(256), lds, (hipStream_t)stream, (const bf16_t*)dq,    \
-                     (const bf16_t*)dk, (const bf16_t*)dv, cosb, sinb, (const bf16_t*)qkv_raw, (const bf16_t*)v0,  \
-                     (const bf16_t*)lam, dv0_acc, dlam, (bf16_t*)dqkv, mix, add_dv0, B, L, H, hd, hdp, QOut{}, det)
+  hipLaunchKernelGGL((qkv_rope_bwd_tok_kernel<NI, -1, NORM>), grid, dim3(256), lds, (hipStream_t)stream,           \
+                     (const bf16_t*)dq, (const bf16_t*)dk, (const bf16_t*)dv, cosb, sinb, (const bf16_t*)qkv_raw,  \
+                     (const bf16_t*)v0, (const bf16_t*)lam, dv0_acc, dlam, (bf16_t*)dqkv, mix, add_dv0, B, L, H,   \
+                     hd, hdp, QOut{}, det, eps)
     if (D <= 512) ROPE_BWD(1);
     else if (D <= 1024) ROPE_BWD(2);
     else if (D <= 1536) ROPE_BWD(3);
     else ROPE_BWD(4);
 #undef ROPE_BWD
   } else {
-    hipLaunchKernelGGL(qkv_rope_bwd_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(qkv_rope_bwd_kernel<NORM>, dim3(nblk), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)dq, (const bf16_t*)dk, (const bf16_t*)dv, cosb, sinb, (const bf16_t*)qkv_raw,
-                       (const bf16_t*)v0, (const bf16_t*)lam, dv0_acc, dlam, (bf16_t*)dqkv, mix, add_dv0, B, L, H, hd, hdp, det);
+                       (const bf16_t*)v0, (const bf16_t*)lam, dv0_acc, dlam, (bf16_t*)dqkv, mix, add_dv0, B, L, H, hd, hdp, det,
+                       eps);
   }
   if (det) hipLaunchKernelGGL(det_finish_scalar_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)det, (int)nblk, dlam);
   return ok();
+}
+extern "C" int vds_qkv_rope_bwd(const void* dq, const void* dk, const void* dv, const float* cosb,
+                                const float* sinb, const void* qkv_raw, const void* v0, const void* lam,
+                                float* dv0_acc, float* dlam, void* dqkv, int32_t mix, int32_t add_dv0, int32_t B,
+                                int32_t L, int32_t H, int32_t hd, int32_t hdp, vds_stream_t stream) {
+  return qkv_rope_bwd_impl<false>(dq, dk, dv, cosb, sinb, qkv_raw, v0, lam, dv0_acc, dlam, dqkv, mix, add_dv0, B, L, H,
+                                  hd, hdp, 0.f, stream);
+}
+// backward of vds_qkv_rope_norm_fwd: qkv_raw (the forward's input) is read for the norm in every call
+extern "C" int vds_qkv_rope_norm_bwd(const void* dq, const void* dk, const void* dv, const float* cosb,
+                                     const float* sinb, const void* qkv_raw, const void* v0, const void* lam,
+                                     float* dv0_acc, float* dlam, void* dqkv, int32_t mix, int32_t add_dv0, int32_t B,
+                                     int32_t L, int32_t H, int32_t hd, int32_t hdp, float eps, vds_stream_t stream) {
+  if (!qkv_raw || !(eps > 0.f)) return VDS_ERR_ARG;
+  return qkv_rope_bwd_impl<true>(dq, dk, dv, cosb, sinb, qkv_raw, v0, lam, dv0_acc, dlam, dqkv, mix, add_dv0, B, L, H,
+                                 hd, hdp, eps, stream);
 }
 
 // as vds_qkv_rope_bwd, the [B*L, 3D] result written as fp8 (wave-per-token kernel only)
@@ -1709,7 +1887,7 @@ extern "C" int vds_qkv_rope_bwd_fp8(const void* dq, const void* dk, const void* 
 #define ROPE_BWD_Q(NI, F)                                                                                             \
   hipLaunchKernelGGL((qkv_rope_bwd_tok_kernel<NI, F>), grid, dim3(256), lds, (hipStream_t)stream, (const bf16_t*)dq, \
                      (const bf16_t*)dk, (const bf16_t*)dv, cosb, sinb, (const bf16_t*)qkv_raw, (const bf16_t*)v0,    \
-                     (const bf16_t*)lam, dv0_acc, dlam, (bf16_t*)nullptr, mix, add_dv0, B, L, H, hd, hdp, qo, det)
+                     (const bf16_t*)lam, dv0_acc, dlam, (bf16_t*)nullptr, mix, add_dv0, B, L, H, hd, hdp, qo, det, 0.f)
 #define ROPE_BWD_F(F)              \
   do {                             \
     if (D <= 512) ROPE_BWD_Q(1, F); \

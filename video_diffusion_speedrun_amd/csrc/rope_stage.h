@@ -36,11 +36,39 @@ __device__ __forceinline__ void issue_rows(const bf16_t* src, char* smem, int nt
   for (unsigned off = (unsigned)wave * 1024u; off < bytes; off += 4096u) lds_dma16(rs, base + off, off + (unsigned)lane * 16u);
 }
 
+// QK-norm, between phase A and phase B: rs[t * 2H + th] = rsqrt(mean_d(x^2) + eps) of every staged q / k head row.
+// Four lanes per row (lane s takes the 16-byte chunks s, s + 4, ..), partial sums joined by a fixed two-step butterfly:
+// the order of the additions does not depend on the launch.
+template <int HD>
+__device__ __forceinline__ void row_rstd(const char* smem, float* rs, int nt, int H, int row_b, float eps, int tid) {
+  constexpr int HQ = HD >> 3;
+  const Div by2h((unsigned)(2 * H));
+  const int nrows = nt * 2 * H, sub = tid & 3;
+  for (int r0 = 0; r0 < nrows; r0 += 64) {  // (uniform trip count: the shuffles below need all four lanes of a row)
+    const int r = r0 + (tid >> 2);
+    float ss = 0.f;
+    if (r < nrows) {
+      unsigned th;
+      const unsigned t = by2h.div((unsigned)r, th);
+      const char* p = smem + t * row_b + th * (HD * 2);
+      for (int c = sub; c < HQ; c += 4) {
+        const u32x4 w = *reinterpret_cast<const u32x4*>(p + c * 16);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ss += bflo(w[e]) * bflo(w[e]) + bfhi(w[e]) * bfhi(w[e]);
+      }
+    }
+    ss += __shfl_xor(ss, 1);
+    ss += __shfl_xor(ss, 2);
+    if (r < nrows && sub == 0) rs[r] = rsqrtf(ss / (float)HD + eps);
+  }
+}
+
 // phase B: RoPE of the q and k parts of the staged rows, in place (fp32 math, bf16 result -- model.py:266-275).
 // One unit = 4 columns d..d+3 of the first half of a head and their partners d + hd/2.
-template <int HD>
+// NORM (QK-norm): every element is first scaled by its row's rs and rounded to bf16 (the RMSNorm's output), then rotated.
+template <int HD, bool NORM = false>
 __device__ __forceinline__ void rotate_rows(char* smem, const float* cosb, const float* sinb, long tok0, int nt, int L,
-                                            int H, int row_b, int tid) {
+                                            int H, int row_b, int tid, const float* rs = nullptr) {
   constexpr int HQ = HD >> 3, HALF = HD >> 1;
   const Div by2h((unsigned)(2 * H));
   const int nunits = nt * 2 * H * HQ;
@@ -56,8 +84,16 @@ __device__ __forceinline__ void rotate_rows(char* smem, const float* cosb, const
     const f32x4 s4 = *reinterpret_cast<const f32x4*>(sinb + (long)l * HALF + 4 * i);
     const u32x2 lo = *reinterpret_cast<const u32x2*>(p);
     const u32x2 hi = *reinterpret_cast<const u32x2*>(p + HALF);
-    const float x1[4] = {bflo(lo[0]), bfhi(lo[0]), bflo(lo[1]), bfhi(lo[1])};
-    const float x2[4] = {bflo(hi[0]), bfhi(hi[0]), bflo(hi[1]), bfhi(hi[1])};
+    float x1[4] = {bflo(lo[0]), bfhi(lo[0]), bflo(lo[1]), bfhi(lo[1])};
+    float x2[4] = {bflo(hi[0]), bfhi(hi[0]), bflo(hi[1]), bfhi(hi[1])};
+    if constexpr (NORM) {
+      const float r = rs[u / HQ];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        x1[e] = bf2f(f2bf(x1[e] * r));
+        x2[e] = bf2f(f2bf(x2[e] * r));
+      }
+    }
     float y1[4], y2[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {

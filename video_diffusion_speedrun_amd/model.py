@@ -295,17 +295,24 @@ _FP8_CONTEXT_LENS = ("context_lens is not implemented for the fp8 cross-attentio
                      "enable_fp8(cross_attention=False) to keep the cross-attention products on the bf16 kernels")
 
 
+_FP8_QK_NORM = ("qk_norm is not implemented for the fp8 attention producers (vds_qkv_rope_fwd_fp8 has no normed form): "
+                "call enable_fp8(attention=False) to keep the attention products on the bf16 kernels")
+
+
 class DiTBlock(nn.Module):
     """model.py:44-167.  `forward(x, context, c, v_0=None, rope=None) -> (x, v)` has the reference's signature and
     runs the block's HIP kernel sequence (`_fwd`) under one autograd node whose backward is `_bwd`; DiT.forward
     drives the same two methods for all blocks inside its own whole-model node."""
 
     def __init__(self, hidden_size, cross_attn_input_size, num_heads, mlp_ratio=4.0, qkv_bias=True,
-                 residual_v=False):
+                 residual_v=False, qk_norm=False):
         super().__init__()
         self.hidden_size, self.num_heads = hidden_size, num_heads
         self.head_dim = hidden_size // num_heads
         self.residual_v = residual_v
+        # QK-norm (no reference counterpart): a weightless RMSNorm on every head row of the self-attention's q and k
+        # before the rotation, inside the qkv / RoPE kernels (ops.qkv_rope_norm_fwd / _bwd).  No parameter.
+        self.qk_norm = bool(qk_norm)
         self.norm1 = RMSNorm(hidden_size, trainable=qkv_bias)
         self.qkv = _Linear(hidden_size, hidden_size * 3, bias=qkv_bias)
         self.attn_proj = _Linear(hidden_size, hidden_size, bias=False)
@@ -381,6 +388,8 @@ class DiTBlock(nn.Module):
         use_fp8 = fp8 is not None
         if kv_lens is not None and use_fp8 and fp8[2] >= 2:
             raise NotImplementedError(_FP8_CONTEXT_LENS)
+        if self.qk_norm and use_fp8 and fp8[2]:
+            raise NotImplementedError(_FP8_QK_NORM)
         if use_fp8 and (keep is not None or replay is not None):
             raise ValueError("activation recomputation does not cover the fp8 path")
         fp8_hist, i, fp8_attn, fp8_lin, q_ctx = fp8 if use_fp8 else (None, 0, 0, False, None)
@@ -437,8 +446,8 @@ class DiTBlock(nn.Module):
                                       emit=(hist.prev(R0 + F8.ROW_ATTN), hist.cur(R0 + F8.ROW_ATTN))
                                       if (pemit and fp8_lin and not _NO_ATTN_EMIT) else None)
         else:
-            q, k, v = ops.qkv_rope_fwd(qkv, cos, sin, v0 if mix else None, W("lambda_param") if mix else None, B, L, H,
-                                       hd, hdp)
+            rope_fwd = ops.qkv_rope_norm_fwd if self.qk_norm else ops.qkv_rope_fwd
+            q, k, v = rope_fwd(qkv, cos, sin, v0 if mix else None, W("lambda_param") if mix else None, B, L, H, hd, hdp)
             if not kept_attn:
                 ops.attn_fwd(q[..., :hd], k[..., :hd], v[..., :hd], ops.heads_view(attn, B, L, H, hd), lse1,
                              kv_pad_ones=(hdp - hd) >= 8)
@@ -752,16 +761,18 @@ class DiTBlock(nn.Module):
                            accumulate=getattr(sv, "dv0_started", False))
             sv.dv0_started = True
             defer.clear()
-        rope_args = (dq, dk, dv, sv.cos, sv.sin, bs.qkv if bs.mix else None, sv.v0 if bs.mix else None,
+        # (QK-norm: the backward recomputes the rows' rsqrt from the qkv GEMM output, which every block keeps)
+        rope_args = (dq, dk, dv, sv.cos, sv.sin, bs.qkv if (bs.mix or self.qk_norm) else None, sv.v0 if bs.mix else None,
                      W("lambda_param") if bs.mix else None, dv0 if bs.mix else (dv0 if first else None),
                      Gr("lambda_param") if bs.mix else None, mix_mode, first and dv0 is not None, B, L, H, hd, hdp)
         # the qkv output gradient leaves the RoPE backward as e5m2 (a qkv bias gradient needs the bf16 tensor)
-        emit_dqkv = pemit and not G.has(pre + "qkv.bias") and hdp % 8 == 0 and D <= 2048
+        # (QK-norm: the normed backward has no fp8-emitting form -- the quantisation pass below takes its bf16 result)
+        emit_dqkv = pemit and not G.has(pre + "qkv.bias") and hdp % 8 == 0 and D <= 2048 and not self.qk_norm
         if emit_dqkv:
             fq, fs = ops.qkv_rope_bwd_fp8(*rope_args, F8.E5M2, hist.prev(F8.ROWS * i + 5), hist.part(F8.ROWS * i + 5, B * L))
             q_dqkv = F8.Q.from_rowmajor(fq, fs, True)
         else:
-            dqkv = ops.qkv_rope_bwd(*rope_args)
+            dqkv = (ops.qkv_rope_norm_bwd if self.qk_norm else ops.qkv_rope_bwd)(*rope_args)
         if G.has(pre + "qkv.bias"):
             ops.colsum(dqkv, Gr("qkv.bias"))
         if bs.f8:
@@ -799,7 +810,9 @@ def activation_bytes(dit, B: int, latent_shape, Lc: int, mode: str = "none") -> 
       kept        depth x per_block (+ nothing else: the root-level saves are the same in every mode)
       transient   one block's full set of intermediates -- what a replay holds between a block's second `_fwd` and
                   the end of its `_bwd` (0 in mode "none", whose `kept` already is depth x that)
-    bf16 fp8-free path; the lists mirror the `bs.*` assignments of DiTBlock._fwd."""
+    bf16 fp8-free path; the lists mirror the `bs.*` assignments of DiTBlock._fwd.  qk_norm changes nothing here: its
+    backward reads the qkv GEMM output (3 D bf16 elements per token row), which every block -- block 0, which mixes no
+    v_0, included -- already keeps and this sum already counts."""
     if mode not in RECOMPUTE_MODES:
         raise ValueError(f"activation_bytes: mode must be one of {RECOMPUTE_MODES}, got {mode!r}")
     D, H, hd = dit.hidden_size, dit.num_heads, dit.head_dim
@@ -847,8 +860,9 @@ def grad_arena(groups, device):
 class DiT(nn.Module):
     def __init__(self, in_channels=4, patch_size=2, time_patch_size=2, hidden_size=1152, depth=28, num_heads=16,
                  mlp_ratio=4.0, cross_attn_input_size=128, residual_v=False, train_bias_and_rms=True,
-                 use_rope=True):
+                 use_rope=True, qk_norm=False):
         super().__init__()
+        self.qk_norm = bool(qk_norm)  # see DiTBlock: parameter-free RMSNorm of q and k in the self-attention
         self.in_channels = self.out_channels = in_channels
         self.patch_size, self.time_patch_size = patch_size, time_patch_size
         self.hidden_size, self.num_heads, self.depth, self.mlp_ratio = hidden_size, num_heads, depth, mlp_ratio
@@ -876,7 +890,7 @@ class DiT(nn.Module):
         self.blocks = nn.ModuleList([
             DiTBlock(hidden_size=hidden_size, num_heads=num_heads, mlp_ratio=mlp_ratio,
                      cross_attn_input_size=cross_attn_input_size, residual_v=residual_v,
-                     qkv_bias=train_bias_and_rms) for _ in range(depth)])
+                     qkv_bias=train_bias_and_rms, qk_norm=qk_norm) for _ in range(depth)])
         self.final_modulation = nn.Sequential(_Act("silu"), _Linear(hidden_size, 2 * hidden_size, bias=True))
         self.final_norm = RMSNorm(hidden_size, trainable=train_bias_and_rms)
         self.final_proj = _Linear(hidden_size, patch_size * patch_size * time_patch_size * self.out_channels)
@@ -903,9 +917,13 @@ class DiT(nn.Module):
         e4m3 Q / K / V / P, e5m2 dO / dS; fp8.py states the recipe).  The reference has no such mode.
         `cross_attention=False` keeps the cross-attention products (L x 512 context keys) on the bf16 kernels: in fp8
         they are 1.1 % of the step faster at the C3b shape and leave the 200-step loss curve where it was, at a
-        cross-attention output 4.6 % instead of 0.3 % from the fp32 oracle."""
+        cross-attention output 4.6 % instead of 0.3 % from the fp32 oracle.
+        A model built with qk_norm=True has no fp8 attention producer: `attention=True` raises NotImplementedError there
+        (enable_fp8(attention=False) runs its linears in fp8 and the normed attention in bf16)."""
         if on and self.recompute != "none":
             raise ValueError(_FP8_RECOMPUTE)
+        if on and attention and self.qk_norm:
+            raise NotImplementedError(_FP8_QK_NORM)
         self.fp8 = bool(on)
         self.fp8_attn = (2 if cross_attention else 1) if (on and attention) else 0  # 0 none, 1 self, 2 self + cross
         self.fp8_lin = bool(on and all_linears)  # attn_proj, q_cross, context_kv, cross_proj too (qkv / MLP always)

@@ -546,6 +546,30 @@ def qkv_rope_bwd(dq, dk, dv, cos, sin, qkv_raw, v0, lam, dv0_acc, dlam, mix, add
     return dqkv
 
 
+QK_NORM_EPS = 1e-6  # RMSNorm's eps (model.py:34-41)
+
+
+def qkv_rope_norm_fwd(qkv, cos, sin, v0, lam, B, L, H, hd, hdp, eps: float = QK_NORM_EPS):
+    """qkv_rope_fwd with QK-norm: every head row of q and k goes through a weightless RMSNorm (fp32 math, rounded to
+    bf16) before the rotation; v, the pad and the ones columns are qkv_rope_fwd's (vds_qkv_rope_norm_fwd)"""
+    q = torch.empty(B, H, L, hdp, dtype=bf16, device=qkv.device)
+    k = torch.empty_like(q)
+    v = torch.empty_like(q)
+    check(_lib.load().vds_qkv_rope_norm_fwd(_p(qkv), _p(cos), _p(sin), _p(v0), _p(lam), _p(q), _p(k), _p(v), B, L, H,
+                                            hd, hdp, float(eps), _stream()), "vds_qkv_rope_norm_fwd")
+    return q, k, v
+
+
+def qkv_rope_norm_bwd(dq, dk, dv, cos, sin, qkv_raw, v0, lam, dv0_acc, dlam, mix, add_dv0, B, L, H, hd, hdp,
+                      eps: float = QK_NORM_EPS):
+    """backward of qkv_rope_norm_fwd; qkv_raw (the forward's qkv) is needed in every call (vds_qkv_rope_norm_bwd)"""
+    dqkv = torch.empty(B * L, 3 * H * hd, dtype=bf16, device=dq.device)
+    check(_lib.load().vds_qkv_rope_norm_bwd(_p(dq), _p(dk), _p(dv), _p(cos), _p(sin), _p(qkv_raw), _p(v0), _p(lam),
+                                            _p(dv0_acc), _p(dlam), _p(dqkv), int(mix), int(add_dv0), B, L, H, hd, hdp,
+                                            float(eps), _stream()), "vds_qkv_rope_norm_bwd")
+    return dqkv
+
+
 def dv0_reduce(dvs, lams, out, B, H, L, hd, hdp, accumulate: bool = False):
     """out[B,H,L,hdp] f32 (+)= sum_i (1 - lam_i) dvs[i][..., :hd]: the residual-V gradient of v_0 from all mixed blocks in one
     pass (vds_dv0_reduce; the blocks' RoPE backward then runs with mix = 2)"""
