@@ -249,6 +249,43 @@ int vds_gate_bwd(const void* dxn, int64_t lddxn, const void* y, int64_t ldy, con
                  int64_t ldmod, int32_t gate_col, void* dy, int64_t lddy, float* dmod, float* dbias,
                  int32_t B, int32_t L, int32_t D, vds_stream_t stream);
 
+/* ------------------------------------------- modulation groups (per-frame timesteps) ---
+ * The calls above read ONE modulation row per sample.  A group description splits the L rows of a sample into
+ * G = 1 + period modulation groups: group 0 is rows 0 .. lead-1 (the register tokens), and row l >= lead belongs to
+ * group 1 + (l - lead) % period (the token order is (h w t) with t fastest, so the rows of token-frame f are lead + f,
+ * lead + f + period, ...).  The modulation tables then have B*G rows, row b*G + g for group g of sample b.
+ * lead < 0, period < 1 or (L - lead) % period != 0: VDS_ERR_ARG; so is B*G > 65535 in the two backward calls (the modulation
+ * rows are a grid dimension).  groups == NULL forwards to the per-sample call. */
+typedef struct {
+  int32_t lead;    /* rows of group 0 at the head of every sample (may be 0: group 0 is empty, its dmod row untouched) */
+  int32_t period;  /* number of frame groups */
+} vds_mod_groups;
+/* vds_rmsnorm_mod_fwd with mod f32 [B*G, ldmod]: the same arithmetic per row, y / rstd bit-identical to the per-sample
+ * call run on the rows of one group with that group's mod row.  Every form of the dispatcher is covered. */
+int vds_rmsnorm_mod_fwd_grouped(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod,
+                                int32_t shift_col, int32_t scale_col, void* y, int64_t ldy, float* rstd,
+                                int32_t B, int32_t L, int32_t D, float eps, const vds_mod_groups* groups,
+                                vds_stream_t stream);
+/* vds_rmsnorm_mod_bwd with mod / dmod [B*G, ldmod]: a workgroup walks rows of ONE group of one sample (stride `period`
+ * for a frame group, the contiguous `lead` rows for group 0), the column sums stay in registers and go to dmod row
+ * b*G + g; dx as the per-sample call, dw summed over everything.  Deterministic mode: as vds_rmsnorm_mod_bwd. */
+int vds_rmsnorm_mod_bwd_grouped(const void* dy, int64_t lddy, const void* x, int64_t ldx, const void* w,
+                                const float* mod, int64_t ldmod, int32_t shift_col, int32_t scale_col,
+                                const float* rstd, const void* dres, int64_t lddres, void* dx, int64_t lddx,
+                                float* dmod, float* dw, int32_t B, int32_t L, int32_t D,
+                                const vds_mod_groups* groups, vds_stream_t stream);
+/* vds_gate_bwd with mod / dmod [B*G, ldmod]: dy = bf16(dx_new * gate[b*G + g]), dmod[b*G + g, gate_col + n] += the sum
+ * over the rows of that group; dbias over everything. */
+int vds_gate_bwd_grouped(const void* dxn, int64_t lddxn, const void* y, int64_t ldy, const float* mod,
+                         int64_t ldmod, int32_t gate_col, void* dy, int64_t lddy, float* dmod, float* dbias,
+                         int32_t B, int32_t L, int32_t D, const vds_mod_groups* groups, vds_stream_t stream);
+/* vds_gemm_bf16 for VDS_NT + VDS_EPI_GATE_RES with gate f32 [B*G, ldgate] and args->rows_per_batch = L (M % L == 0):
+ * output row r takes the gate row of its group.  Every tiling (vds_gemm_force_tile 0 / 128 / 256 / 2), both output
+ * forms (C may be NULL).  The gate row changes from row to row, so every sub-tile runs the per-row epilogue -- the
+ * path of a rows_per_batch = 1 launch with an expanded [M, N] gate table, to which the result is bit-identical.
+ * Any other layout / epilogue with groups != NULL: VDS_ERR_ARG. */
+int vds_gemm_bf16_grouped(const vds_gemm_args* args, const vds_mod_groups* groups, vds_stream_t stream);
+
 /* column sums: out[n] (f32, atomically +=) += sum_m x[m,n]  (bias gradients). */
 int vds_colsum_bf16(const void* x, int64_t ldx, float* out, int32_t M, int32_t N, vds_stream_t stream);
 /* the same over the token rows only of a [B * rows_per_sample] buffer: rows r with r % rows_per_sample < row_offset
@@ -380,6 +417,10 @@ int vds_registers_bwd(const void* dx, int64_t batch_stride, float* dreg, int32_t
  * z_t = x(1-t) + n t ; v = x - n  in bf16 (train.py:115-117); t f32 [B] already bf16-rounded. */
 int vds_noise_latents(const void* x, const void* noise, const float* t, void* z_t, void* v,
                       int32_t B, int64_t per_sample, vds_stream_t stream);
+/* the same with one noise level per token-frame: x [B,C,T,HW] bf16, t f32 [B, T / time_patch] (bf16-rounded values);
+ * latent frame j of sample b uses t[b, j / time_patch].  T % time_patch == 0. */
+int vds_noise_latents_frames(const void* x, const void* noise, const float* t, void* z_t, void* v, int32_t B,
+                             int32_t C, int32_t T, int64_t HW, int32_t time_patch, vds_stream_t stream);
 /* loss = mean_b mean_chw (v - out)^2 in f32 (train.py:121-125), as a FIXED-ORDER two-stage reduction (per-workgroup
  * partial sums -> one pass that sums a sample's partials, divides by per_sample_n, then sums the samples in index order
  * and divides by B): loss_out[0] and per_sample[b] are WRITTEN (no pre-zeroing), bit-identical run to run, and a batch of
@@ -393,6 +434,21 @@ int vds_flow_loss(const void* v, const void* out, float* loss_out, float* per_sa
  * scalar read from device memory (no host synchronisation; graph-capturable).  B*per_sample % 8 == 0. */
 int vds_flow_loss_bwd(const void* v, const void* out, const float* gloss_dev, void* dout, int32_t B,
                       int64_t per_sample_n, vds_stream_t stream);
+
+/* Frame-weighted loss over [B,C,T,HW] with w f32 [B, F], F = T / time_patch, w >= 0:
+ *   per_sample[b] = sum_f w[b,f] SSE[b,f] / (n_f * sum_f w[b,f]),  n_f = C * time_patch * HW elements per token-frame,
+ *   loss = mean_b per_sample[b];  sum_f w[b,f] == 0: per_sample[b] = 0 and dout = 0 for that sample (no NaN).
+ * The same fixed-order two-stage reduction (one partial per workgroup of a (sample, frame), then lanes / butterfly /
+ * frames / samples in index order): bit-identical run to run; w = 1 is vds_flow_loss up to fp32 summation order.
+ * workspace: vds_flow_loss_frames_workspace_floats(B, F, n_f) floats.  dout (may be NULL) =
+ * bf16( 2 (out - v) * gscale * w[b,f] / (B * n_f * sum_f w[b,f]) ), exact zeros where the factor is zero. */
+int64_t vds_flow_loss_frames_workspace_floats(int32_t B, int32_t F, int64_t n_f);
+int vds_flow_loss_frames(const void* v, const void* out, const float* w, float* loss_out, float* per_sample,
+                         void* dout, float gscale, int32_t B, int32_t C, int32_t T, int64_t HW, int32_t time_patch,
+                         float* workspace, vds_stream_t stream);
+/* its backward for an upstream gradient in device memory (as vds_flow_loss_bwd): dout with gscale = *gloss_dev */
+int vds_flow_loss_frames_bwd(const void* v, const void* out, const float* w, const float* gloss_dev, void* dout,
+                             int32_t B, int32_t C, int32_t T, int64_t HW, int32_t time_patch, vds_stream_t stream);
 
 /* ------------------------------------------------------------ sampler --
  * One Euler step of sampling/sample.py:139-146:  out = uncond + cfg_scale*(cond - uncond) in bf16

@@ -57,6 +57,10 @@ class Fp8Out(C.Structure):  # vds_fp8_out
                 ("colsum", C.c_void_p)]
 
 
+class ModGroups(C.Structure):  # vds_mod_groups
+    _fields_ = [("lead", c_i32), ("period", c_i32)]
+
+
 class ProfStat(C.Structure):
     _fields_ = [("launches", c_i64), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -100,6 +104,13 @@ SIGNATURES = {
                             c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp],
     "vds_gate_bwd": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32,
                      c_vp],
+    "vds_rmsnorm_mod_fwd_grouped": [c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp, c_i32, c_i32,
+                                    c_i32, c_f32, c_vp, c_vp],
+    "vds_rmsnorm_mod_bwd_grouped": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp,
+                                    c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp],
+    "vds_gate_bwd_grouped": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32,
+                             c_i32, c_vp, c_vp],
+    "vds_gemm_bf16_grouped": [C.POINTER(GemmArgs), c_vp, c_vp],
     "vds_colsum_bf16": [c_vp, c_i64, c_vp, c_i32, c_i32, c_vp],
     "vds_colsum_bf16_rows": [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp],
     "vds_qkv_rope_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
@@ -130,6 +141,10 @@ SIGNATURES = {
     "vds_flow_loss_workspace_floats": [c_i32, c_i64],
     "vds_flow_loss": [c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_i64, c_vp, c_vp],
     "vds_flow_loss_bwd": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp],
+    "vds_noise_latents_frames": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i64, c_i32, c_vp],
+    "vds_flow_loss_frames_workspace_floats": [c_i32, c_i32, c_i64],
+    "vds_flow_loss_frames": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i64, c_i32, c_vp, c_vp],
+    "vds_flow_loss_frames_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i64, c_i32, c_vp],
     "vds_cfg_euler_step": [c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_i64, c_vp],
     "vds_adamw_multi": [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_f32, c_i32, c_f32, c_f32, c_vp],
     "vds_adamw_multi_dev": [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp, c_f32, c_vp],

@@ -95,15 +95,35 @@ struct QState {
   }
 };
 
+// ---- modulation groups (vds_mod_groups: per-frame timesteps) -----------------------------------------------------------
+// The modulated row kernels below exist in two instances: GRP = false reads ONE modulation row per sample (the kernel as
+// it always was: every grouped step is behind `if constexpr (GRP)`), GRP = true one row per modulation group -- row l of
+// sample b reads modulation row b * (1 + period) + (l < lead ? 0 : 1 + (l - lead) % period).  MGrp is the last argument
+// of both instances (zeros in the per-sample launches).
+struct MGrp { int lead, period; };
+__device__ __forceinline__ long mod_row_grouped(long row, int b, int L, MGrp mg) {
+  const int l = (int)(row - (long)b * L);
+  return (long)b * (1 + mg.period) + (l < mg.lead ? 0 : 1 + (l - mg.lead) % mg.period);
+}
+// The grouped backward kernels: blockIdx.y is the modulation row b * G + g, and a workgroup walks rows of ONE group of one
+// sample -- the `lead` contiguous rows of group 0, or rows lead + (g - 1) + i * period of frame group g -- so that the
+// column sums of a group stay in the registers of its workgroups.
+struct RowWalk { long base; int stride, n; };
+__device__ __forceinline__ RowWalk row_walk(int mrow, int L, MGrp mg) {
+  const int G = 1 + mg.period, b = mrow / G, g = mrow - b * G;
+  if (g == 0) return RowWalk{(long)b * L, 1, mg.lead};
+  return RowWalk{(long)b * L + mg.lead + (g - 1), mg.period, (L - mg.lead) / mg.period};
+}
+
 // ------------------------------------------------------------------ RMSNorm + modulate ---
 // model.py:34-41 (RMSNorm, fp32 statistics, eps 1e-6) fused with model.py:123/144/164/389
 // (norm_x*(1+scale)+shift).  One wave per token row, the row stays in registers; each lane
 // owns 16-byte chunks lane, lane+64, ...  NC = chunks per lane (D <= 512*NC).
-template <int NC, int QF = -1>
+template <int NC, int QF = -1, bool GRP = false>
 __global__ __launch_bounds__(256) void rmsnorm_mod_fwd_kernel(const bf16_t* x, long ldx, const bf16_t* w,
                                                               const float* mod, long ldmod, int shift_col,
                                                               int scale_col, bf16_t* y, long ldy, float* rstd,
-                                                              int B, int L, int D, float eps, QOut qo) {
+                                                              int B, int L, int D, float eps, QOut qo, MGrp mg) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long row = (long)blockIdx.x * 4 + wave;
   if (row >= (long)B * L) return;
@@ -129,6 +149,7 @@ __global__ __launch_bounds__(256) void rmsnorm_mod_fwd_kernel(const bf16_t* x, l
   const float r = rsqrtf(ss / (float)D + eps);
   if (lane == 0) rstd[row] = r;
   const float* mrow = mod + (long)b * ldmod;
+  if constexpr (GRP) mrow = mod + mod_row_grouped(row, b, L, mg) * ldmod;
 #pragma unroll
   for (int i = 0; i < NC; ++i) {
     const int c = lane + 64 * i;
@@ -158,11 +179,11 @@ __global__ __launch_bounds__(256) void rmsnorm_mod_fwd_kernel(const bf16_t* x, l
 // (9 instead of 12 instructions per stream for four rows), the row statistics reduce over 16 lanes.  Same arithmetic
 // per element; the sum of squares is taken in a different order (16 partial sums of 9 x 8 terms instead of 64 of 3 x 8).
 // DiT-S / B / XL widths: D = 384, 768, 1152 (NCQ = 3, 6, 9).
-template <int NCQ, int QF = -1>
+template <int NCQ, int QF = -1, bool GRP = false>
 __global__ __launch_bounds__(256) void rmsnorm_mod_fwd_q4_kernel(const bf16_t* x, long ldx, const bf16_t* w,
                                                                  const float* mod, long ldmod, int shift_col,
                                                                  int scale_col, bf16_t* y, long ldy, float* rstd,
-                                                                 int B, int L, float eps, QOut qo) {
+                                                                 int B, int L, float eps, QOut qo, MGrp mg) {
   constexpr int D = NCQ * 128;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l16 = lane & 15;
@@ -190,6 +211,7 @@ __global__ __launch_bounds__(256) void rmsnorm_mod_fwd_q4_kernel(const bf16_t* x
   const float r = rsqrtf(ss / (float)D + eps);
   if (l16 == 0 && live) rstd[row] = r;
   const float* mrow = mod + (long)b * ldmod;
+  if constexpr (GRP) mrow = mod + mod_row_grouped(rowc, b, L, mg) * ldmod;  // (the four rows of a wave: four modulation rows)
 #pragma unroll
   for (int i = 0; i < NCQ; ++i) {
     const int c = l16 + 16 * i;
@@ -225,7 +247,8 @@ __global__ __launch_bounds__(256) void rmsnorm_mod_fwd_q4_kernel(const bf16_t* x
 // dy and x stay PACKED (bf16) between the two passes over a row and the norm-weight terms are
 // compiled out when there is no weight (the reference's default), which keeps the kernel at
 // >= 4 waves per SIMD -- it is HBM-bound and needs the loads in flight.
-template <int NC, bool HAS_W>
+// GRP (vds_rmsnorm_mod_bwd_grouped): grid = (row chunks of the largest group, B * G); the rows of one group of one sample.
+template <int NC, bool HAS_W, bool GRP = false>
 // (round 6: at D = 1152 (NC = 3) three waves per SIMD spilled 20 registers into the row loop; two waves, unspilled, run
 // 3-4 % faster: 185 -> 180 us with a residual gradient, 150 -> 144 us without, tools/bench_row_kernels.py.  Requesting
 // the next row's streams before working on the current one needs 72 more registers and spills again: measured, not kept.)
@@ -234,13 +257,21 @@ __global__ __launch_bounds__(256, ((NC <= 2 && !HAS_W) ? 3 : 2)) void rmsnorm_mo
                                                               int shift_col, int scale_col, const float* rstd,
                                                               const bf16_t* dres, long lddres, bf16_t* dx, long lddx,
                                                               float* dmod, float* dw, int B, int L, int D,
-                                                              int rows_per_block, float* det) {
+                                                              int rows_per_block, float* det, MGrp mg) {
   __shared__ float red[4][64 * NC * 8 + 8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.y;
   const int nch = D >> 3;
   const int l0 = blockIdx.x * rows_per_block;
-  const int l1 = min(L, l0 + rows_per_block);
+  int l1 = min(L, l0 + rows_per_block);
+  [[maybe_unused]] RowWalk rw;
+  if constexpr (GRP) {
+    rw = row_walk(b, L, mg);
+    l1 = min(rw.n, l0 + rows_per_block);
+    // the grid is sized by the largest group: a workgroup past the end of a smaller (or empty) one has nothing to add
+    // (deterministic mode: its partials are read by the finishing pass, so it goes on and leaves zeros)
+    if (l0 >= rw.n && !det) return;
+  }
   float sc1[NC][8], a_shift[NC][8], a_scale[NC][8];
   float wv[HAS_W ? NC : 1][8], a_w[HAS_W ? NC : 1][8];
   const float* mrow = mod + (long)b * ldmod;
@@ -261,7 +292,9 @@ __global__ __launch_bounds__(256, ((NC <= 2 && !HAS_W) ? 3 : 2)) void rmsnorm_mo
     }
   }
   for (int l = l0 + wave; l < l1; l += 4) {
-    const long row = (long)b * L + l;
+    long row;
+    if constexpr (GRP) row = rw.base + (long)l * rw.stride;
+    else row = (long)b * L + l;
     const float r = rstd[row];
     u32x4 pdy[NC], px[NC], pres[NC];
     float dot = 0.f;
@@ -350,17 +383,23 @@ __global__ __launch_bounds__(256, ((NC <= 2 && !HAS_W) ? 3 : 2)) void rmsnorm_mo
 // ------------------------------------------------------------------------ gate backward ---
 // x_new = x + y*gate (model.py:139,160,165): dy = dx_new*gate, dgate = sum_l dx_new*y,
 // dbias = sum_{b,l} dy.  Same sample-per-blockIdx.y structure as above.
-template <int NC, int QF = -1>
+template <int NC, int QF = -1, bool GRP = false>
 __global__ __launch_bounds__(256) void gate_bwd_kernel(const bf16_t* dxn, long lddxn, const bf16_t* y, long ldy,
                                                        const float* mod, long ldmod, int gate_col, bf16_t* dy,
                                                        long lddy, float* dmod, float* dbias, int B, int L, int D,
-                                                       int rows_per_block, QOut qo, float* det) {
+                                                       int rows_per_block, QOut qo, float* det, MGrp mg) {
   __shared__ float red[4][64 * NC * 8 + 8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.y;
   const int nch = D >> 3;
   const int l0 = blockIdx.x * rows_per_block;
-  const int l1 = min(L, l0 + rows_per_block);
+  int l1 = min(L, l0 + rows_per_block);
+  [[maybe_unused]] RowWalk rw;
+  if constexpr (GRP) {
+    rw = row_walk(b, L, mg);
+    l1 = min(rw.n, l0 + rows_per_block);
+    if (l0 >= rw.n && !det) return;  // (as rmsnorm_mod_bwd_kernel)
+  }
   float gt[NC][8], a_g[NC][8], a_b[NC][8];
   QState<(QF < 0 ? 0 : QF)> qs;
   if constexpr (QF >= 0)
@@ -373,7 +412,9 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const bf16_t* dxn, long l
     if (c < nch) load8f(mod + (long)b * ldmod + gate_col + c * 8, gt[i]);
   }
   for (int l = l0 + wave; l < l1; l += 4) {
-    const long row = (long)b * L + l;
+    long row;
+    if constexpr (GRP) row = rw.base + (long)l * rw.stride;
+    else row = (long)b * L + l;
 #pragma unroll
     for (int i = 0; i < NC; ++i) {
       const int c = lane + 64 * i;
@@ -1374,6 +1415,84 @@ __global__ __launch_bounds__(256) void flow_loss_final_kernel(const float* parti
   }
 }
 
+// ---- per-frame timesteps: noising and the frame-weighted loss over [B,C,T,HW] --------------------------------------------
+// latent frame j of sample b is noised with t[b, j / tps] (F = T / tps token-frames); the arithmetic of noise_kernel
+__global__ void noise_frames_kernel(const bf16_t* x, const bf16_t* n, const float* t, bf16_t* zt, bf16_t* v, int B, int T,
+                                    long HW, int tps, long per) {
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (long)B * per) return;
+  const int b = (int)(gid / per);
+  const int j = (int)((gid / HW) % T);
+  const float tb = t[(long)b * (T / tps) + j / tps];
+  const float omt = bf2f(f2bf(1.0f - tb));
+  const float xv = bf2f(x[gid]), nv = bf2f(n[gid]);
+  const float a = bf2f(f2bf(xv * omt)), c = bf2f(f2bf(nv * tb));
+  zt[gid] = f2bf(a + c);
+  v[gid] = f2bf(xv - nv);
+}
+
+// per_sample[b] = sum_f w[b,f] SSE[b,f] / (n_f sum_f w[b,f]) (0 when the weights of a sample sum to 0), loss = mean_b.
+// Stage 1, grid (blocks per frame, F, B): a workgroup sums squares over elements of ONE token-frame of one sample -- the
+// C runs of tps * HW contiguous elements [c][f * tps .. f * tps + tps - 1][HW] -- in an order that depends on the shape
+// only, and leaves one partial.  partials == null: gradient only (the backward call).  The gradient factor
+// 2 g w[b,f] / (B n_f sum_f w[b,f]) takes g from device memory when gloss is given (else gscale); the weights of the sample
+// are summed in index order by every thread, as stage 2 sums them.
+__global__ __launch_bounds__(256) void flow_loss_frames_partial_kernel(const bf16_t* v, const bf16_t* out, const float* w,
+                                                                       float* partials, bf16_t* dout, const float* gloss,
+                                                                       float gscale, int B, int C, int T, long HW, int tps,
+                                                                       int blocks_per_frame) {
+  __shared__ float red[4];
+  const int b = blockIdx.z, f = blockIdx.y, F = T / tps;
+  const long run = (long)tps * HW, n_f = (long)C * run, per = (long)C * T * HW;
+  float k = 0.f;
+  if (dout) {
+    float wsum = 0.f;
+    for (int ff = 0; ff < F; ++ff) wsum += w[(long)b * F + ff];
+    if (wsum > 0.f) k = 2.0f * (gloss ? gloss[0] : gscale) * w[(long)b * F + f] / ((float)B * (float)n_f * wsum);
+  }
+  const long base = (long)b * per + (long)f * run;
+  float s = 0.f;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_f; i += (long)blocks_per_frame * 256) {
+    const long c = i / run;
+    const long idx = base + c * (long)T * HW + (i - c * run);
+    const float d = bf2f(out[idx]) - bf2f(v[idx]);
+    s += d * d;
+    if (dout) dout[idx] = k == 0.f ? f2bf(0.f) : f2bf(d * k);  // (a frame or sample without weight: exact zeros)
+  }
+  if (!partials) return;
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    partials[((long)b * F + f) * blocks_per_frame + blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3]));
+}
+
+// Stage 2 (one workgroup): one wave per sample; its frames in index order, a frame's partials lane-strided + butterfly
+__global__ __launch_bounds__(256) void flow_loss_frames_final_kernel(const float* partials, const float* w, float* loss,
+                                                                     float* per_sample, int B, int F, long n_f,
+                                                                     int blocks_per_frame) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int b = wave; b < B; b += 4) {
+    float acc = 0.f, wsum = 0.f;
+    for (int f = 0; f < F; ++f) {
+      const float* p = partials + ((long)b * F + f) * blocks_per_frame;
+      float s = 0.f;
+      for (int j = lane; j < blocks_per_frame; j += 64) s += p[j];
+      s = wave_sum(s);
+      const float wf = w[(long)b * F + f];
+      acc += wf * s;
+      wsum += wf;
+    }
+    if (lane == 0) per_sample[b] = wsum > 0.f ? acc / ((float)n_f * wsum) : 0.f;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float tot = 0.f;
+    for (int b = 0; b < B; ++b) tot += per_sample[b];
+    loss[0] = tot / (float)B;
+  }
+}
+
 // d(loss)/d(out) for an upstream gradient held in device memory; 8 elements per thread, 16-byte accesses
 __global__ __launch_bounds__(256) void flow_loss_bwd_kernel(const bf16_t* v, const bf16_t* out, const float* gloss,
                                                             bf16_t* dout, float inv_n, long n8) {
@@ -1513,7 +1632,7 @@ extern "C" int vds_rmsnorm_mod_fwd(const void* x, int64_t ldx, const void* w, co
 #define CALLQ(NCQ)                                                                                             \
   hipLaunchKernelGGL((rmsnorm_mod_fwd_q4_kernel<NCQ>), dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s,     \
                      (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col,   \
-                     (bf16_t*)y, (long)ldy, rstd, B, L, eps, QOut{})
+                     (bf16_t*)y, (long)ldy, rstd, B, L, eps, QOut{}, MGrp{})
     if (D == 384) CALLQ(3);
     else if (D == 768) CALLQ(6);
     else CALLQ(9);
@@ -1523,7 +1642,44 @@ extern "C" int vds_rmsnorm_mod_fwd(const void* x, int64_t ldx, const void* w, co
 #define CALL(NC)                                                                                              \
   hipLaunchKernelGGL((rmsnorm_mod_fwd_kernel<NC>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,          \
                      (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col, \
-                     (bf16_t*)y, (long)ldy, rstd, B, L, D, eps, QOut{})
+                     (bf16_t*)y, (long)ldy, rstd, B, L, D, eps, QOut{}, MGrp{})
+  NC_DISPATCH(D, CALL);
+#undef CALL
+  return ok();
+}
+
+// a group description that fits L rows per sample (include/vds.h: vds_mod_groups)
+static bool groups_ok(const vds_mod_groups* g, int L) {
+  return g->lead >= 0 && g->period >= 1 && g->lead <= L && (L - g->lead) % g->period == 0;
+}
+
+extern "C" int vds_rmsnorm_mod_fwd_grouped(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod,
+                                           int32_t shift_col, int32_t scale_col, void* y, int64_t ldy, float* rstd,
+                                           int32_t B, int32_t L, int32_t D, float eps, const vds_mod_groups* groups,
+                                           vds_stream_t stream) {
+  if (!groups) return vds_rmsnorm_mod_fwd(x, ldx, w, mod, ldmod, shift_col, scale_col, y, ldy, rstd, B, L, D, eps, stream);
+  if (!x || !mod || !y || !rstd || (D & 7) || (ldx & 7) || (ldy & 7) || (shift_col & 3) || (scale_col & 3) || (ldmod & 3) ||
+      B < 1 || L < 1 || !groups_ok(groups, L))
+    return VDS_ERR_ARG;
+  const long rows = (long)B * L;
+  const MGrp mg{groups->lead, groups->period};
+  hipStream_t s = (hipStream_t)stream;
+  vdsprof::Scope ps(VDS_PROF_RMSNORM_FWD, s, 0.0, 4.0 * rows * D + 4.0 * rows);
+  if (rmsnorm_q4(D)) {
+#define CALLQ(NCQ)                                                                                                      \
+  hipLaunchKernelGGL((rmsnorm_mod_fwd_q4_kernel<NCQ, -1, true>), dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s,      \
+                     (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col, (bf16_t*)y, \
+                     (long)ldy, rstd, B, L, eps, QOut{}, mg)
+    if (D == 384) CALLQ(3);
+    else if (D == 768) CALLQ(6);
+    else CALLQ(9);
+#undef CALLQ
+    return ok();
+  }
+#define CALL(NC)                                                                                                        \
+  hipLaunchKernelGGL((rmsnorm_mod_fwd_kernel<NC, -1, true>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,            \
+                     (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col, (bf16_t*)y, \
+                     (long)ldy, rstd, B, L, D, eps, QOut{}, mg)
   NC_DISPATCH(D, CALL);
 #undef CALL
   return ok();
@@ -1550,11 +1706,11 @@ extern "C" int vds_rmsnorm_mod_fwd_fp8(const void* x, int64_t ldx, const void* w
     if (fmt == 0)                                                                                                \
       hipLaunchKernelGGL((rmsnorm_mod_fwd_q4_kernel<NCQ, 0>), dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s, \
                          (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col,   \
-                         (bf16_t*)nullptr, 0L, rstd, B, L, eps, qo);                                             \
+                         (bf16_t*)nullptr, 0L, rstd, B, L, eps, qo, MGrp{});                                             \
     else                                                                                                         \
       hipLaunchKernelGGL((rmsnorm_mod_fwd_q4_kernel<NCQ, 1>), dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s, \
                          (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col,   \
-                         (bf16_t*)nullptr, 0L, rstd, B, L, eps, qo);                                             \
+                         (bf16_t*)nullptr, 0L, rstd, B, L, eps, qo, MGrp{});                                             \
   } while (0)
     if (D == 384) CALLQ(3);
     else if (D == 768) CALLQ(6);
@@ -1567,11 +1723,11 @@ extern "C" int vds_rmsnorm_mod_fwd_fp8(const void* x, int64_t ldx, const void* w
     if (fmt == 0)                                                                                              \
       hipLaunchKernelGGL((rmsnorm_mod_fwd_kernel<NC, 0>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,    \
                          (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col, \
-                         (bf16_t*)nullptr, 0L, rstd, B, L, D, eps, qo);                                        \
+                         (bf16_t*)nullptr, 0L, rstd, B, L, D, eps, qo, MGrp{});                                        \
     else                                                                                                       \
       hipLaunchKernelGGL((rmsnorm_mod_fwd_kernel<NC, 1>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,    \
                          (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col, \
-                         (bf16_t*)nullptr, 0L, rstd, B, L, D, eps, qo);                                        \
+                         (bf16_t*)nullptr, 0L, rstd, B, L, D, eps, qo, MGrp{});                                        \
   } while (0)
   NC_DISPATCH(D, CALL);
 #undef CALL
@@ -1595,12 +1751,12 @@ extern "C" int vds_rmsnorm_mod_bwd(const void* dy, int64_t lddy, const void* x, 
     if (w)                                                                                                        \
       hipLaunchKernelGGL((rmsnorm_mod_bwd_kernel<NC, true>), grid, dim3(256), 0, s, (const bf16_t*)dy, (long)lddy, \
                          (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col,   \
-                         rstd, (const bf16_t*)dres, (long)lddres, (bf16_t*)dx, (long)lddx, dmod, dw, B, L, D, rpb, det); \
+                         rstd, (const bf16_t*)dres, (long)lddres, (bf16_t*)dx, (long)lddx, dmod, dw, B, L, D, rpb, det, MGrp{}); \
     else                                                                                                          \
       hipLaunchKernelGGL((rmsnorm_mod_bwd_kernel<NC, false>), grid, dim3(256), 0, s, (const bf16_t*)dy, (long)lddy, \
                          (const bf16_t*)x, (long)ldx, (const bf16_t*)nullptr, mod, (long)ldmod, shift_col,        \
                          scale_col, rstd, (const bf16_t*)dres, (long)lddres, (bf16_t*)dx, (long)lddx, dmod,       \
-                         (float*)nullptr, B, L, D, rpb, det);                                                     \
+                         (float*)nullptr, B, L, D, rpb, det, MGrp{});                                                     \
   } while (0)
   NC_DISPATCH(D, CALL);
 #undef CALL
@@ -1626,12 +1782,87 @@ extern "C" int vds_gate_bwd(const void* dxn, int64_t lddxn, const void* y, int64
 #define CALL(NC)                                                                                             \
   hipLaunchKernelGGL((gate_bwd_kernel<NC>), grid, dim3(256), 0, s, (const bf16_t*)dxn, (long)lddxn,           \
                      (const bf16_t*)y, (long)ldy, mod, (long)ldmod, gate_col, (bf16_t*)dy, (long)lddy, dmod, \
-                     dbias, B, L, D, rpb, QOut{}, det)
+                     dbias, B, L, D, rpb, QOut{}, det, MGrp{})
   NC_DISPATCH(D, CALL);
 #undef CALL
   if (det) {
     det_finish(det, (int)grid.x, D, dmod + gate_col, ldmod, B, s);
     if (dbias) det_finish(det + (long)B * grid.x * D, (int)(B * grid.x), D, dbias, 0, 1, s);
+  }
+  return ok();
+}
+
+// the grouped backward calls: blockIdx.y = modulation row b * G + g, blockIdx.x = row chunks of the LARGEST group (the
+// workgroups past a smaller group's end leave at once); the deterministic partials are sized by this grid
+extern "C" int vds_rmsnorm_mod_bwd_grouped(const void* dy, int64_t lddy, const void* x, int64_t ldx, const void* w,
+                                           const float* mod, int64_t ldmod, int32_t shift_col, int32_t scale_col,
+                                           const float* rstd, const void* dres, int64_t lddres, void* dx, int64_t lddx,
+                                           float* dmod, float* dw, int32_t B, int32_t L, int32_t D,
+                                           const vds_mod_groups* groups, vds_stream_t stream) {
+  if (!groups)
+    return vds_rmsnorm_mod_bwd(dy, lddy, x, ldx, w, mod, ldmod, shift_col, scale_col, rstd, dres, lddres, dx, lddx, dmod, dw,
+                               B, L, D, stream);
+  if (!dy || !x || !mod || !rstd || !dx || !dmod || (D & 7) || (lddy & 7) || (ldx & 7) || (lddx & 7)) return VDS_ERR_ARG;
+  if ((w && !dw) || B < 1 || L < 1 || !groups_ok(groups, L)) return VDS_ERR_ARG;
+  const long BG = (long)B * (1 + groups->period);
+  if (BG > 65535) return VDS_ERR_ARG;  // (the modulation rows are the grid's y dimension)
+  const MGrp mg{groups->lead, groups->period};
+  const int nmax = max(groups->lead, (L - groups->lead) / groups->period);
+  const int rpb = rows_per_block_for(nmax, (int)BG);
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((nmax + rpb - 1) / rpb, (unsigned)BG);
+  float* det = nullptr;
+  if (vdsdet::on() && !(det = vdsdet::workspace((size_t)(w ? 3 : 2) * BG * grid.x * D, "vds_rmsnorm_mod_bwd_grouped")))
+    return VDS_ERR_ARG;
+  vdsprof::Scope ps(VDS_PROF_RMSNORM_BWD, s, 0.0, (dres ? 8.0 : 6.0) * B * L * D + 4.0 * B * L);
+#define CALL(NC)                                                                                                       \
+  do {                                                                                                                 \
+    if (w)                                                                                                             \
+      hipLaunchKernelGGL((rmsnorm_mod_bwd_kernel<NC, true, true>), grid, dim3(256), 0, s, (const bf16_t*)dy,          \
+                         (long)lddy, (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col,       \
+                         scale_col, rstd, (const bf16_t*)dres, (long)lddres, (bf16_t*)dx, (long)lddx, dmod, dw, B, L,  \
+                         D, rpb, det, mg);                                                   \
+    else                                                                                                               \
+      hipLaunchKernelGGL((rmsnorm_mod_bwd_kernel<NC, false, true>), grid, dim3(256), 0, s, (const bf16_t*)dy,         \
+                         (long)lddy, (const bf16_t*)x, (long)ldx, (const bf16_t*)nullptr, mod, (long)ldmod, shift_col, \
+                         scale_col, rstd, (const bf16_t*)dres, (long)lddres, (bf16_t*)dx, (long)lddx, dmod,            \
+                         (float*)nullptr, B, L, D, rpb, det, mg);                            \
+  } while (0)
+  NC_DISPATCH(D, CALL);
+#undef CALL
+  if (det) {
+    const long plane = BG * grid.x * D;
+    det_finish(det, (int)grid.x, D, dmod + shift_col, ldmod, (int)BG, s);
+    det_finish(det + plane, (int)grid.x, D, dmod + scale_col, ldmod, (int)BG, s);
+    if (w) det_finish(det + 2 * plane, (int)(BG * grid.x), D, dw, 0, 1, s);
+  }
+  return ok();
+}
+
+extern "C" int vds_gate_bwd_grouped(const void* dxn, int64_t lddxn, const void* y, int64_t ldy, const float* mod,
+                                    int64_t ldmod, int32_t gate_col, void* dy, int64_t lddy, float* dmod, float* dbias,
+                                    int32_t B, int32_t L, int32_t D, const vds_mod_groups* groups, vds_stream_t stream) {
+  if (!groups) return vds_gate_bwd(dxn, lddxn, y, ldy, mod, ldmod, gate_col, dy, lddy, dmod, dbias, B, L, D, stream);
+  if (!dxn || !y || !mod || !dy || !dmod || (D & 7) || B < 1 || L < 1 || !groups_ok(groups, L)) return VDS_ERR_ARG;
+  const long BG = (long)B * (1 + groups->period);
+  if (BG > 65535) return VDS_ERR_ARG;  // (the modulation rows are the grid's y dimension)
+  const MGrp mg{groups->lead, groups->period};
+  const int nmax = max(groups->lead, (L - groups->lead) / groups->period);
+  const int rpb = rows_per_block_for(nmax, (int)BG);
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((nmax + rpb - 1) / rpb, (unsigned)BG);
+  float* det = nullptr;
+  if (vdsdet::on() && !(det = vdsdet::workspace((size_t)2 * BG * grid.x * D, "vds_gate_bwd_grouped"))) return VDS_ERR_ARG;
+  vdsprof::Scope ps(VDS_PROF_GATE_BWD, s, 0.0, 6.0 * B * L * D);
+#define CALL(NC)                                                                                                     \
+  hipLaunchKernelGGL((gate_bwd_kernel<NC, -1, true>), grid, dim3(256), 0, s, (const bf16_t*)dxn, (long)lddxn,           \
+                     (const bf16_t*)y, (long)ldy, mod, (long)ldmod, gate_col, (bf16_t*)dy, (long)lddy, dmod, dbias, B, \
+                     L, D, rpb, QOut{}, det, mg)
+  NC_DISPATCH(D, CALL);
+#undef CALL
+  if (det) {
+    det_finish(det, (int)grid.x, D, dmod + gate_col, ldmod, (int)BG, s);
+    if (dbias) det_finish(det + BG * grid.x * D, (int)(BG * grid.x), D, dbias, 0, 1, s);
   }
   return ok();
 }
@@ -1653,11 +1884,11 @@ extern "C" int vds_gate_bwd_fp8(const void* dxn, int64_t lddxn, const void* y, i
     if (fmt == 0)                                                                                                  \
       hipLaunchKernelGGL((gate_bwd_kernel<NC, 0>), grid, dim3(256), 0, s, (const bf16_t*)dxn, (long)lddxn,          \
                          (const bf16_t*)y, (long)ldy, mod, (long)ldmod, gate_col, (bf16_t*)nullptr, 0L, dmod, dbias, \
-                         B, L, D, rpb, qo, det);                                                                   \
+                         B, L, D, rpb, qo, det, MGrp{});                                                                   \
     else                                                                                                           \
       hipLaunchKernelGGL((gate_bwd_kernel<NC, 1>), grid, dim3(256), 0, s, (const bf16_t*)dxn, (long)lddxn,          \
                          (const bf16_t*)y, (long)ldy, mod, (long)ldmod, gate_col, (bf16_t*)nullptr, 0L, dmod, dbias, \
-                         B, L, D, rpb, qo, det);                                                                   \
+                         B, L, D, rpb, qo, det, MGrp{});                                                                   \
   } while (0)
   NC_DISPATCH(D, CALL);
 #undef CALL
@@ -2201,6 +2432,51 @@ extern "C" int vds_flow_loss(const void* v, const void* out, float* loss_out, fl
                      (const bf16_t*)out, workspace, (bf16_t*)dout, gscale, B, (long)per_sample_n, bps);
   hipLaunchKernelGGL(flow_loss_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)workspace,
                      loss_out, per_sample, B, (long)per_sample_n, bps);
+  return ok();
+}
+
+extern "C" int vds_noise_latents_frames(const void* x, const void* noise, const float* t, void* z_t, void* v, int32_t B,
+                                        int32_t C, int32_t T, int64_t HW, int32_t time_patch, vds_stream_t stream) {
+  if (!x || !noise || !t || !z_t || !v || B < 1 || C < 1 || T < 1 || HW < 1 || time_patch < 1 || T % time_patch) return VDS_ERR_ARG;
+  const long per = (long)C * T * HW, n = (long)B * per;
+  hipLaunchKernelGGL(noise_frames_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)x, (const bf16_t*)noise, t, (bf16_t*)z_t, (bf16_t*)v, B, T, (long)HW, time_patch, per);
+  return ok();
+}
+
+static bool loss_frames_ok(int32_t B, int32_t C, int32_t T, int64_t HW, int32_t tps) {
+  return B >= 1 && B <= 65535 && C >= 1 && T >= 1 && HW >= 1 && tps >= 1 && T % tps == 0 && T / tps <= 65535;
+}
+
+extern "C" int64_t vds_flow_loss_frames_workspace_floats(int32_t B, int32_t F, int64_t n_f) {
+  if (B <= 0 || F <= 0 || n_f <= 0) return 0;
+  return (int64_t)B * F * flow_loss_bps(n_f);
+}
+
+extern "C" int vds_flow_loss_frames(const void* v, const void* out, const float* w, float* loss_out, float* per_sample,
+                                    void* dout, float gscale, int32_t B, int32_t C, int32_t T, int64_t HW,
+                                    int32_t time_patch, float* workspace, vds_stream_t stream) {
+  if (!v || !out || !w || !loss_out || !per_sample || !workspace || !loss_frames_ok(B, C, T, HW, time_patch)) return VDS_ERR_ARG;
+  const int F = T / time_patch;
+  const long n_f = (long)C * time_patch * HW;
+  const int bps = flow_loss_bps(n_f);
+  hipLaunchKernelGGL(flow_loss_frames_partial_kernel, dim3(bps, F, B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)v,
+                     (const bf16_t*)out, w, workspace, (bf16_t*)dout, (const float*)nullptr, gscale, B, C, T, (long)HW,
+                     time_patch, bps);
+  hipLaunchKernelGGL(flow_loss_frames_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, w,
+                     loss_out, per_sample, B, F, n_f, bps);
+  return ok();
+}
+
+extern "C" int vds_flow_loss_frames_bwd(const void* v, const void* out, const float* w, const float* gloss_dev, void* dout,
+                                        int32_t B, int32_t C, int32_t T, int64_t HW, int32_t time_patch,
+                                        vds_stream_t stream) {
+  if (!v || !out || !w || !gloss_dev || !dout || !loss_frames_ok(B, C, T, HW, time_patch)) return VDS_ERR_ARG;
+  const int F = T / time_patch;
+  const int bps = flow_loss_bps((long)C * time_patch * HW);
+  hipLaunchKernelGGL(flow_loss_frames_partial_kernel, dim3(bps, F, B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)v,
+                     (const bf16_t*)out, w, (float*)nullptr, (bf16_t*)dout, gloss_dev, 1.0f, B, C, T, (long)HW, time_patch,
+                     bps);
   return ok();
 }
 

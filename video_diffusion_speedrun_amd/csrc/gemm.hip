@@ -57,12 +57,30 @@ struct GemmP {
   int group_m;
   int joint_xcd;   // split-K launches: XCD-aware order over the joint (split, tile) list
   int narrow;      // 256^2 kernel: the last tile column holds <= 128 columns and runs the 256 x 128 body (round 5)
+  int g_lead;      // grouped GATE_RES (vds_gemm_bf16_grouped): rows of modulation group 0 at the head of every sample
+                   // (this word and g_period sit in what was padding: every other member keeps its offset)
   const float* sa; const float* sb;  // fp8 path: per-tensor dequantisation factors (device), else unused
   double prof_k;                      // contraction length in elements (profiler flop count)
   // fp8 path, optional: the epilogue also emits its result (gelu output / gelu' product) as fp8 (vds_fp8_out)
   unsigned char* e_q; long e_ldq; unsigned char* e_qt; long e_ldqt;
-  const float* e_amax_in; float* e_amax_out; float* e_dq_out; int e_fmt; float* e_colsum;
+  const float* e_amax_in; float* e_amax_out; float* e_dq_out; int e_fmt;
+  int g_period;    // grouped GATE_RES: groups 1 .. g_period repeat with this period over a sample's remaining rows
+  float* e_colsum;
 };
+
+// GATE_RES with one gate row per MODULATION GROUP instead of one per sample (per-frame timesteps): an epilogue id of its
+// own, internal to this file, so that the instances of VDS_EPI_GATE_RES are compiled from exactly the code they had.
+// Row r of the matrix is row l = r % L of sample b = r / L (L = rows_per_batch) and reads gate row
+// b * (1 + period) + (l < lead ? 0 : 1 + (l - lead) % period).  A 64-row sub-tile spans many groups, so these
+// instances never take the lean epilogue (one gate row per sub-tile): every sub-tile goes through epilogue_64x64, the
+// path a rows_per_batch = 1 launch with an expanded [M, N] gate table takes -- same arithmetic, same bits.
+constexpr int EPI_GATE_RES_G = 64;
+__host__ __device__ constexpr bool is_gate_res(int epi) { return epi == VDS_EPI_GATE_RES || epi == EPI_GATE_RES_G; }
+__device__ __forceinline__ long gate_group_row(const GemmP& p, long r) {
+  const long b = r / p.rows_per_batch;
+  const int l = (int)(r - b * p.rows_per_batch);
+  return b * (1 + p.g_period) + (l < p.g_lead ? 0 : 1 + (l - p.g_lead) % p.g_period);
+}
 
 // ---- swizzles -------------------------------------------------------------------------
 // k-contiguous tile: [128 rows][64 k] bf16, 128-B rows, 8 chunks of 16 B.
@@ -220,7 +238,7 @@ __device__ __forceinline__ unsigned cvt4_fp8(int fmt, float a, float b, float c,
 // NIT: row groups of 8 rows per staged sub-tile (8: 64 rows; 4: the 32-row steps of the compact staging, see gemm_tile)
 template <int EPI, int WC = 64, int NIT = 8>
 __device__ __forceinline__ void epilogue_prefetch(const GemmP& p, int row0, int col0, int lane, u32x4 (&auxr)[NIT]) {
-  if constexpr (EPI == VDS_EPI_GATE_RES || EPI == VDS_EPI_DGELU) {
+  if constexpr (is_gate_res(EPI) || EPI == VDS_EPI_DGELU) {
     const int c8 = lane & 7, rin = lane >> 3;
     const int gcol = col0 + c8 * 8;
     const bool cok = gcol < p.N && (WC == 64 || c8 * 8 < WC);
@@ -310,9 +328,11 @@ __device__ __forceinline__ void epilogue_64x64(const GemmP& p, float* stg, int r
       if (p.C) *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(p.C) + grow * p.ldc + gcol) = o;  // (NULL: act only)
       if (p.C2) *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(p.C2) + grow * p.ldc2 + gcol) = o2;
       if constexpr (EMIT) ev = o2;
-    } else if constexpr (EPI == VDS_EPI_GATE_RES) {
-      const int b = (int)((grow + p.row_base) / p.rows_per_batch);
-      const float* gp = p.gate + (long)b * p.ldgate + gcol;
+    } else if constexpr (is_gate_res(EPI)) {
+      long b;
+      if constexpr (EPI == EPI_GATE_RES_G) b = gate_group_row(p, grow + p.row_base);
+      else b = (int)((grow + p.row_base) / p.rows_per_batch);
+      const float* gp = p.gate + b * p.ldgate + gcol;
       const f32x4 g0 = *reinterpret_cast<const f32x4*>(gp);
       const f32x4 g1 = *reinterpret_cast<const f32x4*>(gp + 4);
       const float g[8] = {g0[0], g0[1], g0[2], g0[3], g1[0], g1[1], g1[2], g1[3]};
@@ -976,7 +996,7 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, char* smem, const int 
   if (wr == 0) __builtin_amdgcn_s_barrier();  // re-align the two wave groups
   // the zero-fill tail DMAs target LDS the epilogue reuses
   // (a wave whose sub-tile sticks out of the matrix may have issued fewer than 16: it drains everything)
-  const bool aux_all = (EPI == VDS_EPI_GATE_RES || EPI == VDS_EPI_DGELU) && m0 + wr * 128 + 128 <= p.M &&
+  const bool aux_all = (is_gate_res(EPI) || EPI == VDS_EPI_DGELU) && m0 + wr * 128 + 128 <= p.M &&
                        n0 + (wc + 1) * G::WCOLS <= p.N;
   if (aux_all) VDS_WAIT_VM(16);
   else VDS_WAIT_VM(0);
@@ -1018,7 +1038,7 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, char* smem, const int 
     // sub-tiles completely inside the matrix (all but the last row / column of tiles) take the lean path
     bool full = row0 + RSTEP <= p.M && col0 + WCOLS <= p.N;
     if constexpr (EPI == VDS_EPI_GATE_RES) full = full && ((row0 + p.row_base) % p.rows_per_batch) + RSTEP <= p.rows_per_batch;
-    if constexpr (EPI == VDS_EPI_F32) full = false;
+    if constexpr (EPI == VDS_EPI_F32 || EPI == EPI_GATE_RES_G) full = false;
     bool done = false;
     if (full) done = epilogue_full_dispatch<EPI, EMIT, WCOLS, NIT>(p, stg, lut, row0, col0, lane, cs, ew[qa], auxr, e_scale, e_max);
     if (!done) epilogue_64x64<EPI, EMIT, USE_LUT, WCOLS, NIT>(p, stg, row0, col0, lane, cs, ew[qa], auxr, lut);
@@ -1447,7 +1467,7 @@ extern "C" int vds_gemm_force_tile(int32_t tile) {
   return prev;
 }
 
-extern "C" int vds_gemm_bf16(const vds_gemm_args* a, vds_stream_t stream) {
+static int gemm_bf16_impl(const vds_gemm_args* a, const vds_mod_groups* grp, vds_stream_t stream) {
   if (!a || !a->A || !a->B || a->M <= 0 || a->N <= 0 || a->K <= 0) return VDS_ERR_ARG;
   if ((a->N & 7) || (a->lda & 7) || (a->ldb & 7)) return VDS_ERR_ARG;
   GemmP p;
@@ -1460,6 +1480,14 @@ extern "C" int vds_gemm_bf16(const vds_gemm_args* a, vds_stream_t stream) {
   p.gate = a->gate; p.ldgate = a->ldgate;
   p.rows_per_batch = a->rows_per_batch > 0 ? a->rows_per_batch : a->M;
   p.row_base = 0;
+  p.g_lead = p.g_period = 0;
+  if (grp) {  // one gate row per modulation group: rows_per_batch is L, the rows of one sample
+    if (a->epilogue != VDS_EPI_GATE_RES || a->layout != VDS_NT || a->rows_per_batch <= 0 || a->M % a->rows_per_batch != 0 ||
+        grp->lead < 0 || grp->period < 1 || grp->lead > a->rows_per_batch || (a->rows_per_batch - grp->lead) % grp->period != 0)
+      return VDS_ERR_ARG;
+    p.g_lead = grp->lead;
+    p.g_period = grp->period;
+  }
   p.slab_stride = 0;
   // split_k: > 1 that many K splits (atomic accumulation into a pre-zeroed C); 1 none; <= -2: |split_k| splits and
   // atomic accumulation; 0 / -1 (TN + F32 only): the library picks tiling and split count itself (-1: and always
@@ -1596,6 +1624,7 @@ extern "C" int vds_gemm_bf16(const vds_gemm_args* a, vds_stream_t stream) {
 #define GOM(L, E) if (a->layout == L && a->epilogue == E) return mid::launch<L, E>(p, s);
       GOM(VDS_NT, VDS_EPI_STORE)
       GOM(VDS_NT, VDS_EPI_BIAS_GELU)
+      if (grp) return mid::launch<VDS_NT, EPI_GATE_RES_G>(p, s);
       GOM(VDS_NT, VDS_EPI_GATE_RES)
       GOM(VDS_NN, VDS_EPI_STORE)
       GOM(VDS_NN, VDS_EPI_DGELU)
@@ -1613,7 +1642,8 @@ extern "C" int vds_gemm_bf16(const vds_gemm_args* a, vds_stream_t stream) {
 #define GOB(L, E) if (a->layout == L && a->epilogue == E) rc = big::launch<L, E>(p, s);
     GOB(VDS_NT, VDS_EPI_STORE)
     GOB(VDS_NT, VDS_EPI_BIAS_GELU)
-    GOB(VDS_NT, VDS_EPI_GATE_RES)
+    if (grp) rc = big::launch<VDS_NT, EPI_GATE_RES_G>(p, s);
+    else GOB(VDS_NT, VDS_EPI_GATE_RES)
     GOB(VDS_NN, VDS_EPI_STORE)
     GOB(VDS_NN, VDS_EPI_DGELU)
 #undef GOB
@@ -1629,6 +1659,7 @@ extern "C" int vds_gemm_bf16(const vds_gemm_args* a, vds_stream_t stream) {
 #define GO(L, E) if (a->layout == L && a->epilogue == E) return launch<L, E>(p, s);
   GO(VDS_NT, VDS_EPI_STORE)
   GO(VDS_NT, VDS_EPI_BIAS_GELU)
+  if (grp) return launch<VDS_NT, EPI_GATE_RES_G>(p, s);
   GO(VDS_NT, VDS_EPI_GATE_RES)
   GO(VDS_NN, VDS_EPI_STORE)
   GO(VDS_NN, VDS_EPI_DGELU)
@@ -1636,6 +1667,12 @@ extern "C" int vds_gemm_bf16(const vds_gemm_args* a, vds_stream_t stream) {
   if (a->layout == VDS_TN && a->epilogue == VDS_EPI_F32)
     return launch_tn(BK, [&](GemmP& q) { return launch<VDS_TN, VDS_EPI_F32>(q, s); });
   return VDS_ERR_UNSUPPORTED;
+}
+
+extern "C" int vds_gemm_bf16(const vds_gemm_args* a, vds_stream_t stream) { return gemm_bf16_impl(a, nullptr, stream); }
+// GATE_RES (NT) with the gate row looked up per output row through a group description; NULL: vds_gemm_bf16
+extern "C" int vds_gemm_bf16_grouped(const vds_gemm_args* a, const vds_mod_groups* groups, vds_stream_t stream) {
+  return gemm_bf16_impl(a, groups, stream);
 }
 
 // OCP fp8 GEMM, NT only: C[M,N] = (sum_k A[m,k] B[n,k]) * scale_a * scale_b with A, B one byte per element
@@ -1657,6 +1694,7 @@ extern "C" int vds_gemm_fp8(const vds_gemm_args* a, const float* scale_a, const 
   p.gate = a->gate; p.ldgate = a->ldgate;
   p.rows_per_batch = a->rows_per_batch > 0 ? a->rows_per_batch : a->M;
   p.row_base = 0;
+  p.g_lead = p.g_period = 0;
   p.slab_stride = 0;
   p.split_k = a->split_k > 1 ? a->split_k : (a->split_k < -1 ? -a->split_k : 1);
   p.atomic = (a->split_k > 1 || a->split_k < 0) ? 1 : 0;

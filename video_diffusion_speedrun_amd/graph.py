@@ -14,7 +14,8 @@ in device memory rather than in kernel arguments:
   * the AdamW bias corrections, LR multiplier and EMA decay -> device float[4] read by `vds_adamw_multi_dev` /
                             `vds_adamw_guarded_multi_dev`; the guarded step's norm, clip coefficient and skip flag never
                             leave the device (optim.py): a replay fed a non-finite batch skips itself;
-  * z / noise / caption-dropout draws -> torch's default device generator (graph-safe Philox: the
+  * z / noise / caption-dropout / frame-conditioning draws (`frame_mode=`: per-frame timesteps, train.forward)
+                         -> torch's default device generator (graph-safe Philox: the
                             captured kernels take seed/offset from device memory).
 
 The first `eager_steps` calls run the ordinary path (they are real train steps: they build the
@@ -53,7 +54,13 @@ bf16 = torch.bfloat16
 class GraphedTrainStep:
     """`step(batch) -> loss` with the semantics of `train.train_step` (train.py:412-434)."""
 
-    def __init__(self, dit_model, optimizer, lr_scheduler, device, eager_steps: int = 2):
+    def __init__(self, dit_model, optimizer, lr_scheduler, device, eager_steps: int = 2, frame_mode=None,
+                 cond_prob: float = 0.5):
+        """frame_mode / cond_prob: train.forward's per-frame timestep modes; the levels, weights and the conditioning
+        draw live on the device, so the captured step replays with new draws"""
+        if frame_mode not in _train.FRAME_MODES:
+            raise ValueError(f"frame_mode must be one of {_train.FRAME_MODES}, got {frame_mode!r}")
+        self.frame_kw = {} if frame_mode is None else {"frame_mode": frame_mode, "cond_prob": cond_prob}
         if eager_steps < 1:
             raise ValueError("at least one eager step is needed before the capture (descriptor tables, shadows)")
         self.model, self.opt, self.sched = dit_model, optimizer, lr_scheduler
@@ -98,7 +105,8 @@ class GraphedTrainStep:
         return st
 
     def _body(self, rope_start):
-        loss, _ = _train.forward(self.model, self.static, None, None, self.device, 0, False, rope_start=rope_start)
+        loss, _ = _train.forward(self.model, self.static, None, None, self.device, 0, False, rope_start=rope_start,
+                                 **self.frame_kw)
         self.opt.zero_grad()
         loss.backward()
         self.opt.step()

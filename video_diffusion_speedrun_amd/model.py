@@ -291,8 +291,50 @@ def check_context_lens(context_lens, B: int, Lc: int) -> torch.Tensor:
     return torch.tensor(vals, dtype=torch.int32)
 
 
+def check_timesteps(timesteps, B: int, t: int) -> bool:
+    """DiT.forward's timesteps: a tensor [B] (one noise level per sample; returns False) or [B, t] (one per token-frame, t = T //
+    time_patch_size; returns True).  Any other shape: ValueError naming the expected t."""
+    if not (isinstance(timesteps, torch.Tensor) and timesteps.dim() in (1, 2) and timesteps.shape[0] == B
+            and (timesteps.dim() == 1 or timesteps.shape[1] == t)):
+        got = tuple(timesteps.shape) if isinstance(timesteps, torch.Tensor) else type(timesteps).__name__
+        raise ValueError(f"DiT: timesteps must have shape [{B}] (one per sample) or [{B}, {t}] (one per token-frame: "
+                         f"t = T // time_patch_size = {t}), got {got}")
+    return timesteps.dim() == 2
+
+
 _FP8_CONTEXT_LENS = ("context_lens is not implemented for the fp8 cross-attention kernels: call "
                      "enable_fp8(cross_attention=False) to keep the cross-attention products on the bf16 kernels")
+
+
+_FP8_FRAME_TIMESTEPS = ("per-frame timesteps (timesteps [B, t]) are not implemented for the fp8 kernels -- the fp8 forms of "
+                        "RMSNorm+modulate, the gate backward and the GATE_RES GEMM read one modulation row per sample: "
+                        "call enable_fp8(False), or pass timesteps [B]")
+
+
+# the modulated kernels of a block / the final layer: per-sample (groups None: one modulation row per sample, the calls
+# this model always made) or grouped (groups = (lead, period): mod / dmod are [B*G, .] tables, ops.*_grouped)
+def _norm_fwd(groups, X, w, mod, shift_col, scale_col, B, L):
+    if groups is None:
+        return ops.rmsnorm_mod_fwd(X, w, mod, shift_col, scale_col, B, L)
+    return ops.rmsnorm_mod_fwd_grouped(X, w, mod, shift_col, scale_col, B, L, groups)
+
+
+def _gate_res(groups, x, W, bias, mod, gate_col, res, L, want_y=True):
+    if groups is None:
+        return ops.linear_fwd_gate_res(x, W, bias, mod, gate_col, res, L, want_y=want_y)
+    return ops.linear_fwd_gate_res_grouped(x, W, bias, mod, gate_col, res, L, groups, want_y=want_y)
+
+
+def _gate_bwd(groups, dxn, y, mod, gate_col, dmod, dbias, B, L):
+    if groups is None:
+        return ops.gate_bwd(dxn, y, mod, gate_col, dmod, dbias, B, L)
+    return ops.gate_bwd_grouped(dxn, y, mod, gate_col, dmod, dbias, B, L, groups)
+
+
+def _norm_bwd(groups, dy, x, w, mod, shift_col, scale_col, rstd, dres, dmod, dw, B, L):
+    if groups is None:
+        return ops.rmsnorm_mod_bwd(dy, x, w, mod, shift_col, scale_col, rstd, dres, dmod, dw, B, L)
+    return ops.rmsnorm_mod_bwd_grouped(dy, x, w, mod, shift_col, scale_col, rstd, dres, dmod, dw, B, L, groups)
 
 
 _FP8_QK_NORM = ("qk_norm is not implemented for the fp8 attention producers (vds_qkv_rope_fwd_fp8 has no normed form): "
@@ -374,7 +416,7 @@ class DiTBlock(nn.Module):
 
     # ---- the kernel sequence of one block (used by DiT's whole-model autograd node and by `forward`) ----
     def _fwd(self, G, pre, X, ctx2d, cvec, v0, cos, sin, B, L, Lc, save, fp8=None, mod=None, keep=None, replay=None,
-             kv_lens=None):
+             kv_lens=None, groups=None):
         """X [B*L, D] bf16 token buffer -> (X_out, v [B,H,L,hdp], saved).  G: the FlatGroup holding this block's
         parameters under the name prefix `pre`; cvec f32 [B, D]; v0: block 0's v in the padded head-major layout
         or None; cos / sin f32 [L, hd/2]; fp8 = (AmaxHistory | None, block index) when the fp8 linears are on.
@@ -382,7 +424,9 @@ class DiTBlock(nn.Module):
         only what the replay needs (X, mod; selective: attn, lse1 too).  replay = that object, with save=True: the run
         before the block's `_bwd` -- the self-attention forward is not launched when attn / lse1 were kept, and the
         new residual stream after the MLP is not stored (X_out is None: the next block's kept X already holds it).
-        kv_lens: int32 device tensor [B] or None -- per-sample key counts of the cross-attention (bf16 kernels only)."""
+        kv_lens: int32 device tensor [B] or None -- per-sample key counts of the cross-attention (bf16 kernels only).
+        groups: None, or (lead, period) -- per-frame timesteps: cvec is f32 [B*G, D] and the modulation table [B*G, 9D],
+        G = 1 + period, row b*G + g for modulation group g of sample b (bf16 kernels only)."""
         D, H, hd = self.hidden_size, self.num_heads, self.head_dim
         hdp = HDP_OF[hd]
         use_fp8 = fp8 is not None
@@ -390,6 +434,8 @@ class DiTBlock(nn.Module):
             raise NotImplementedError(_FP8_CONTEXT_LENS)
         if self.qk_norm and use_fp8 and fp8[2]:
             raise NotImplementedError(_FP8_QK_NORM)
+        if groups is not None and use_fp8:
+            raise NotImplementedError(_FP8_FRAME_TIMESTEPS)
         if use_fp8 and (keep is not None or replay is not None):
             raise ValueError("activation recomputation does not cover the fp8 path")
         fp8_hist, i, fp8_attn, fp8_lin, q_ctx = fp8 if use_fp8 else (None, 0, 0, False, None)
@@ -413,7 +459,7 @@ class DiTBlock(nn.Module):
                                                   hist.prev(F8.ROWS * i + 2), hist.part(F8.ROWS * i + 2, B * L))
             q_xn1 = F8.Q.from_rowmajor(fq, fs, save)
         else:
-            xn1, rstd1 = ops.rmsnorm_mod_fwd(X, Wo("norm1.weight"), mod, 0, D, B, L)
+            xn1, rstd1 = _norm_fwd(groups, X, Wo("norm1.weight"), mod, 0, D, B, L)
         if f8:
             if not pemit:
                 q_xn1 = F8.Q(xn1, F8.E4M3, True, save, hist, F8.ROWS * i + 2)
@@ -462,7 +508,7 @@ class DiTBlock(nn.Module):
             q_wap = F8.Q(W("attn_proj.weight"), F8.E4M3, True, save, hist, R0 + F8.ROW_W + 1, weight=True, remeasure=moved)
             y_sa, X1 = F8.fwd_gate_res(q_attn, q_wap, None, mod, 2 * D, X, L)
         else:
-            y_sa, X1 = ops.linear_fwd_gate_res(attn, W("attn_proj.weight"), None, mod, 2 * D, X, L, want_y=save)
+            y_sa, X1 = _gate_res(groups, attn, W("attn_proj.weight"), None, mod, 2 * D, X, L, want_y=save)
         # --- cross attention (model.py:142-160)
         has_cross = G.has(pre + "q_cross.weight")
         if has_cross:
@@ -473,7 +519,7 @@ class DiTBlock(nn.Module):
                                                       hist.prev(R0 + F8.ROW_XN2), hist.part(R0 + F8.ROW_XN2, B * L))
                 q_xn2 = F8.Q.from_rowmajor(fq, fs, save)
             else:
-                xn2, rstd2 = ops.rmsnorm_mod_fwd(X1, Wo("norm2.weight"), mod, 3 * D, 4 * D, B, L)
+                xn2, rstd2 = _norm_fwd(groups, X1, Wo("norm2.weight"), mod, 3 * D, 4 * D, B, L)
             if f8c:
                 if q_xn2 is None:
                     q_xn2 = F8.Q(xn2, F8.E4M3, True, save, hist, R0 + F8.ROW_XN2)
@@ -524,7 +570,7 @@ class DiTBlock(nn.Module):
                 q_wcp = F8.Q(W("cross_proj.weight"), F8.E4M3, True, save, hist, R0 + F8.ROW_W + 4, weight=True, remeasure=moved)
                 y_ca, X2 = F8.fwd_gate_res(q_catt, q_wcp, None, mod, 5 * D, X1, L)
             else:
-                y_ca, X2 = ops.linear_fwd_gate_res(catt, W("cross_proj.weight"), None, mod, 5 * D, X1, L, want_y=save)
+                y_ca, X2 = _gate_res(groups, catt, W("cross_proj.weight"), None, mod, 5 * D, X1, L, want_y=save)
         else:
             X2 = X1
             f8c = False
@@ -534,7 +580,7 @@ class DiTBlock(nn.Module):
                                                   hist.prev(F8.ROWS * i + 3), hist.part(F8.ROWS * i + 3, B * L))
             q_xn3 = F8.Q.from_rowmajor(fq, fs, save)
         else:
-            xn3, rstd3 = ops.rmsnorm_mod_fwd(X2, Wo("norm3.weight"), mod, 6 * D, 7 * D, B, L)
+            xn3, rstd3 = _norm_fwd(groups, X2, Wo("norm3.weight"), mod, 6 * D, 7 * D, B, L)
         if f8:
             if not pemit:
                 q_xn3 = F8.Q(xn3, F8.E4M3, True, save, hist, F8.ROWS * i + 3)
@@ -554,7 +600,7 @@ class DiTBlock(nn.Module):
             if replay is not None:  # the backward reads y_mlp only: the store epilogue writes the same bits
                 y_mlp, X3 = ops.linear_fwd(hact, W("mlp.2.weight"), W("mlp.2.bias")), None
             else:
-                y_mlp, X3 = ops.linear_fwd_gate_res(hact, W("mlp.2.weight"), W("mlp.2.bias"), mod, 8 * D, X2, L,
+                y_mlp, X3 = _gate_res(groups, hact, W("mlp.2.weight"), W("mlp.2.bias"), mod, 8 * D, X2, L,
                                                     want_y=save)
         bs = None
         if keep is not None and not save:
@@ -591,10 +637,11 @@ class DiTBlock(nn.Module):
         return X3, v, bs
 
 
-    def _bwd(self, G, pre, bs, dX, sv, dc, dv0, B, L, Lc, first, fp8=None, dmod=None):
+    def _bwd(self, G, pre, bs, dX, sv, dc, dv0, B, L, Lc, first, fp8=None, dmod=None, groups=None):
         """backward of `_fwd`: dX [B*L, D] bf16 -> d(input tokens); parameter gradients go to G's fp32 gradient
         buffer; dc (f32 [B, D]) and dv0 (f32 [B,H,L,hdp]) accumulate the conditioning / residual-V gradients.
-        sv carries cos, sin, v0, ctx2d, cvec.  first: this is the block whose v was handed out as v_0."""
+        sv carries cos, sin, v0, ctx2d, cvec.  first: this is the block whose v was handed out as v_0.
+        groups: as in `_fwd` (dc is then f32 [B*G, D])."""
         D, H, hd = self.hidden_size, self.num_heads, self.head_dim
         hdp = HDP_OF[hd]
         fp8_hist, i, _, _, q_ctx = fp8 if fp8 is not None else (None, 0, False, False, None)
@@ -610,7 +657,7 @@ class DiTBlock(nn.Module):
         # footprints fragment the CUs; removed in round 6, profiles/r05/wgrad_side_stream_ab.log)
         wgrad, wgrad8 = ops.linear_wgrad, F8.wgrad
         if dmod is None:
-            dmod = torch.zeros(B, 9 * D, dtype=f32, device=dev)
+            dmod = torch.zeros(mod.shape[0], 9 * D, dtype=f32, device=dev)
         # --- MLP
         hist = fp8_hist if bs.f8 else None
         # (deterministic mode: the fc2 input gradient keeps its separate, fixed-order bias-gradient pass -- the GEMM epilogue's
@@ -623,7 +670,7 @@ class DiTBlock(nn.Module):
             q_dy = F8.Q.from_rowmajor(fq, fs, True)
             dy = None
         else:
-            dy = ops.gate_bwd(dX, bs.y_mlp, mod, 8 * D, dmod, Gr("mlp.2.bias"), B, L)
+            dy = _gate_bwd(groups, dX, bs.y_mlp, mod, 8 * D, dmod, Gr("mlp.2.bias"), B, L)
         if bs.f8:
             if not pemit:
                 q_dy = F8.Q(dy, F8.E5M2, True, True, hist, F8.ROWS * i + 4)
@@ -645,7 +692,7 @@ class DiTBlock(nn.Module):
             wgrad(dh, bs.xn3, Gr("mlp.0.weight"))
             dxn = ops.linear_dgrad(dh, W("mlp.0.weight"))
         del dh
-        dX2 = ops.rmsnorm_mod_bwd(dxn, bs.X2, Wo("norm3.weight"), mod, 6 * D, 7 * D, bs.rstd3, dX, dmod,
+        dX2 = _norm_bwd(groups, dxn, bs.X2, Wo("norm3.weight"), mod, 6 * D, 7 * D, bs.rstd3, dX, dmod,
                                   Go("norm3.weight"), B, L)
         # --- cross attention
         def gate_bwd_q(dXo, y, col, row):
@@ -653,7 +700,7 @@ class DiTBlock(nn.Module):
             if pemit:
                 fq, fs = ops.gate_bwd_fp8(dXo, y, mod, col, dmod, None, B, L, F8.E5M2, hist.prev(row), hist.part(row, B * L))
                 return F8.Q.from_rowmajor(fq, fs, True)
-            return F8.Q(ops.gate_bwd(dXo, y, mod, col, dmod, None, B, L), F8.E5M2, True, True, hist, row)
+            return F8.Q(_gate_bwd(groups, dXo, y, mod, col, dmod, None, B, L), F8.E5M2, True, True, hist, row)
 
         if bs.has_cross:
             if bs.f8c:
@@ -662,7 +709,7 @@ class DiTBlock(nn.Module):
                 dcatt = F8.dgrad(q_dy, bs.q_wcp)
                 del q_dy
             else:
-                dy = ops.gate_bwd(dX2, bs.y_ca, mod, 5 * D, dmod, None, B, L)
+                dy = _gate_bwd(groups, dX2, bs.y_ca, mod, 5 * D, dmod, None, B, L)
                 wgrad(dy, bs.catt, Gr("cross_proj.weight"))
                 dcatt = ops.linear_dgrad(dy, W("cross_proj.weight"))
             # fp8 cross-attention + fp8 q_cross: dQ leaves the attention kernel as e5m2 (and as bf16 only for a bias gradient)
@@ -711,7 +758,7 @@ class DiTBlock(nn.Module):
                 wgrad(dckv, sv.ctx2d, Gr("context_kv.weight"))
                 wgrad(dqc, bs.xn2, Gr("q_cross.weight"))
                 dxn = ops.linear_dgrad(dqc, W("q_cross.weight"))
-            dX1 = ops.rmsnorm_mod_bwd(dxn, bs.X1, Wo("norm2.weight"), mod, 3 * D, 4 * D, bs.rstd2, dX2, dmod,
+            dX1 = _norm_bwd(groups, dxn, bs.X1, Wo("norm2.weight"), mod, 3 * D, 4 * D, bs.rstd2, dX2, dmod,
                                       Go("norm2.weight"), B, L)
         else:
             dX1 = dX2
@@ -722,7 +769,7 @@ class DiTBlock(nn.Module):
             dattn = F8.dgrad(q_dy, bs.q_wap)
             del q_dy
         else:
-            dy = ops.gate_bwd(dX1, bs.y_sa, mod, 2 * D, dmod, None, B, L)
+            dy = _gate_bwd(groups, dX1, bs.y_sa, mod, 2 * D, dmod, None, B, L)
             wgrad(dy, bs.attn, Gr("attn_proj.weight"))
             dattn = ops.linear_dgrad(dy, W("attn_proj.weight"))
         dq = torch.empty(B, H, L, hdp, dtype=bf16, device=dev)
@@ -784,7 +831,7 @@ class DiTBlock(nn.Module):
         else:
             wgrad(dqkv, bs.xn1, Gr("qkv.weight"))
             dxn = ops.linear_dgrad(dqkv, W("qkv.weight"))
-        dX0 = ops.rmsnorm_mod_bwd(dxn, bs.X, Wo("norm1.weight"), mod, 0, D, bs.rstd1, dX1, dmod, Go("norm1.weight"),
+        dX0 = _norm_bwd(groups, dxn, bs.X, Wo("norm1.weight"), mod, 0, D, bs.rstd1, dX1, dmod, Go("norm1.weight"),
                                   B, L)
         # --- adaLN modulation (model.py:89-94,107)
         if not batched_adaln:
@@ -1017,6 +1064,9 @@ class DiT(nn.Module):
     # ------------------------------------------------------------------------ forward ----
     def forward(self, x, context, timesteps, rope_start: Optional[Tuple[int, int, int]] = None, context_lens=None):
         """x [B,C,T,H,W], context [B,Lc,Cc], timesteps [B] -> [B,C,T,H,W] bf16 (model.py:358-402).
+        timesteps [B, t], t = T // time_patch_size: one noise level per token-frame (image-to-video, video extension,
+        diffusion forcing).  The tokens of frame f of sample b are modulated from timesteps[b, f], the register tokens
+        from max_f timesteps[b, f]; constant rows reproduce the [B] call.  bf16 kernels only.
         context_lens: per-sample context lengths -- sample b cross-attends its first context_lens[b] context rows only, 0
         = no context at all (the cross-attention adds nothing for that sample).  A sequence of ints or a CPU integer tensor
         [B] is validated on the host and uploaded once; a CUDA integer tensor [B] is used as it is, without a host sync.
@@ -1036,6 +1086,9 @@ class DiT(nn.Module):
                                  "way; the model only exists to hold / convert such a checkpoint")
         b, c, t, h, w = x.shape
         thw = (t // self.time_patch_size, h // self.patch_size, w // self.patch_size)
+        if check_timesteps(timesteps, b, thw[0]):
+            if self.fp8:
+                raise NotImplementedError(_FP8_FRAME_TIMESTEPS)
         if rope_start is None:
             rope_start = self.rope.draw_start(thw)
         if not isinstance(rope_start, torch.Tensor):  # a device int32[3] tensor is read by the kernel (graph.py)
@@ -1099,6 +1152,14 @@ class DiT(nn.Module):
         cos, sin = self.rope.rows((t, h, w), rope_start, N_REG)
 
         # timestep conditioning (model.py:374-377), kept in fp32
+        # per-frame timesteps [B, t]: the conditioning path runs on B*G rows, G = 1 + t modulation groups per sample --
+        # group 0 (the register rows) on the sample's noisiest frame, group 1 + f (the rows of token-frame f: the token
+        # order is (h w t), t fastest) on timesteps[b, f] -- and every modulated kernel looks its row up per group
+        groups = None
+        if timesteps.dim() == 2:
+            groups = (N_REG, t)
+            tf = timesteps.to(f32)
+            timesteps = torch.cat([tf.max(dim=1, keepdim=True).values, tf], dim=1).reshape(B * (1 + t))
         temb = ops.timestep_embedding(timesteps.to(f32).contiguous(), D)
         h1 = ops.small_linear_fwd(temb, R.w("time_embed.0.weight"), R.w("time_embed.0.bias"), 0)
         cvec = ops.small_linear_fwd(h1, R.w("time_embed.2.weight"), R.w("time_embed.2.bias"), 1)
@@ -1107,12 +1168,15 @@ class DiT(nn.Module):
             sv.dims = (B, C, T, Hh, Ww, t, h, w, N, L, Lc, Cc)
             sv.ctx2d = ctx2d
             sv.kv_lens = kv_lens
+            sv.groups = groups
             sv.blocks = []
 
         # adaLN modulation of every block in ONE launch (K4 of SURVEY 2.3): all blocks read the same conditioning vector.
         # Not under sharding -- it would need every group's gathered weights before block 0 -- nor beyond 16 samples.
         mods = None
-        if fs is None and B <= 16 and self.depth > 1 and os.environ.get("VDS_ADALN_BATCH", "1") != "0":
+        # Nor with per-frame timesteps: B*G modulation rows exceed the launch's 16 at every real shape, so such a call
+        # always takes the per-block linears (any number of rows; what sharded models run) -- one path to test.
+        if fs is None and groups is None and B <= 16 and self.depth > 1 and os.environ.get("VDS_ADALN_BATCH", "1") != "0":
             wt, bt, _, _ = self._adaln_tables()
             mods = ops.small_linear_fwd_batched(cvec, wt, bt, self.depth, 9 * D, 1)
         v0 = None
@@ -1123,7 +1187,8 @@ class DiT(nn.Module):
             X, v, bs = self.blocks[i]._fwd(self.block_group(i), f"blocks.{i}.", X, ctx2d, cvec, v0, cos, sin, B, L, Lc,
                                            save and keep is None,
                                            (self._fp8_hist, i, self.fp8_attn, self.fp8_lin, q_ctx) if self.fp8 else None,
-                                           mods[i] if mods is not None else None, keep=keep, kv_lens=kv_lens)
+                                           mods[i] if mods is not None else None, keep=keep, kv_lens=kv_lens,
+                                           groups=groups)
             if v0 is None:
                 v0 = v
             if save:
@@ -1141,7 +1206,7 @@ class DiT(nn.Module):
         wfn = R.w("final_norm.weight") if R.has("final_norm.weight") else None
         # norm, modulation and projection run over all B*L rows (the 16 register rows of a sample are 0.2 % of them and
         # are simply not read back: the reference slices them off first, model.py:386); unpatchify picks the token rows
-        xnf, rstdf = ops.rmsnorm_mod_fwd(X, wfn, fmod, 0, D, B, L)
+        xnf, rstdf = _norm_fwd(groups, X, wfn, fmod, 0, D, B, L)
         yf = ops.linear_fwd(xnf, R.w("final_proj.weight"), R.w("final_proj.bias"))
         out = ops.unpatchify(yf, B, C, T, Hh, Ww, pt, p, lead_rows=N_REG)
         if save:
@@ -1158,6 +1223,8 @@ class DiT(nn.Module):
         dev = dout.device
         fs = self._fsdp
         R = self.root_group
+        groups = sv.groups
+        Bc = sv.cvec.shape[0]  # rows of the conditioning path: B, or B*G with per-frame timesteps
         # gradients already held in p.grad (a second backward before zero_grad: micro-batch accumulation, like
         # autograd's accumulate-into-.grad in the reference loop) are set aside and added back at the end
         held = [g.hold_grads() for g in self._groups]  # per parameter: only slices whose .grad is live are kept
@@ -1173,14 +1240,15 @@ class DiT(nn.Module):
         dxnf = ops.linear_dgrad(dyf, R.w("final_proj.weight"))
         # the small zero-initialised accumulators of this pass come out of ONE fill: d(final modulation) [B, 2D],
         # d(conditioning vector) [B, D], d(time-embed hidden) [B, 4D] and the adaLN modulation gradients of all blocks
-        nmods = self.depth * B * 9 * D if sv.batched_adaln else 0
-        zs = torch.zeros(B * 7 * D + nmods, dtype=f32, device=dev)
-        dfmod, dc, dh1 = zs[:B * 2 * D].view(B, 2 * D), zs[B * 2 * D:B * 3 * D].view(B, D), zs[B * 3 * D:B * 7 * D].view(B, 4 * D)
-        dmods = zs[B * 7 * D:].view(self.depth, B, 9 * D) if sv.batched_adaln else None
+        nmods = self.depth * Bc * 9 * D if sv.batched_adaln else 0
+        zs = torch.zeros(Bc * 7 * D + nmods, dtype=f32, device=dev)
+        dfmod, dc, dh1 = (zs[:Bc * 2 * D].view(Bc, 2 * D), zs[Bc * 2 * D:Bc * 3 * D].view(Bc, D),
+                          zs[Bc * 3 * D:Bc * 7 * D].view(Bc, 4 * D))
+        dmods = zs[Bc * 7 * D:].view(self.depth, Bc, 9 * D) if sv.batched_adaln else None
         wfn = R.w("final_norm.weight") if R.has("final_norm.weight") else None
         dwfn = R.g("final_norm.weight") if wfn is not None else None
         # register rows: dxnf = 0 there, so they get a zero gradient from the final layer (they were sliced off)
-        dX = ops.rmsnorm_mod_bwd(dxnf, sv.x_last, wfn, sv.fmod, 0, D, sv.rstdf, None, dfmod, dwfn, B, L)
+        dX = _norm_bwd(groups, dxnf, sv.x_last, wfn, sv.fmod, 0, D, sv.rstdf, None, dfmod, dwfn, B, L)
         ops.small_linear_bwd(dfmod, sv.cvec, R.w("final_modulation.1.weight"), R.g("final_modulation.1.weight"),
                              R.g("final_modulation.1.bias"), dc, 1)
         hdp = HDP_OF[hd]
@@ -1199,10 +1267,10 @@ class DiT(nn.Module):
                 # block-0 v (sv.v0 stays the v handed out in the first forward; block 0 makes its own copy again)
                 _, _, bs = self.blocks[i]._fwd(self.block_group(i), f"blocks.{i}.", bs.X, sv.ctx2d, sv.cvec,
                                                sv.v0 if i > 0 else None, sv.cos, sv.sin, B, L, Lc, True, None, bs.mod,
-                                               replay=bs, kv_lens=sv.kv_lens)
+                                               replay=bs, kv_lens=sv.kv_lens, groups=groups)
             dX = self.blocks[i]._bwd(self.block_group(i), f"blocks.{i}.", bs, dX, sv, dc, dv0, B, L, Lc,
                                      i == 0, (self._fp8_hist, i, self.fp8_attn, self.fp8_lin, sv.q_ctx) if self.fp8 else None,
-                                     dmods[i] if dmods is not None else None)
+                                     dmods[i] if dmods is not None else None, groups=groups)
             sv.blocks[i] = bs = None
             if fs is not None:
                 fs.post_backward_block(i)

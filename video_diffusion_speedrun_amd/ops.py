@@ -137,6 +137,21 @@ def linear_fwd_gate_res(x, W, bias, mod, gate_col: int, res, rows_per_batch: int
     return y, xn
 
 
+def linear_fwd_gate_res_grouped(x, W, bias, mod, gate_col: int, res, L: int, groups, want_y: bool = True):
+    """linear_fwd_gate_res with one gate row per modulation group: mod f32 [B*G, 9D], `groups` = (lead, period), L rows
+    per sample; output row r takes the gate row of its group (vds_gemm_bf16_grouped)"""
+    M, K = x.shape
+    N = W.shape[0]
+    y = torch.empty(M, N, dtype=bf16, device=x.device) if want_y else None
+    xn = torch.empty(M, N, dtype=bf16, device=x.device)
+    gate = mod[:, gate_col:]
+    a = GemmArgs(VDS_NT, EPI_GATE_RES, M, N, K, _p(x), x.stride(0), _p(W), W.stride(0), _p(y), N, _p(xn), N, _p(bias),
+                 _p(res), res.stride(0), _p(gate), mod.stride(0), L, 1, None)
+    check(_lib.load().vds_gemm_bf16_grouped(C.byref(a), _groups(groups, L, mod, M // L), _stream()),
+          f"vds_gemm_bf16_grouped(M={M},N={N},K={K},L={L},groups={tuple(groups)})")
+    return y, xn
+
+
 def linear_dgrad(dy, W, pre: Optional[torch.Tensor] = None, colsum: Optional[torch.Tensor] = None):
     """dx = dy W  (dy [M,N], W [N,K] -> [M,K]); with `pre`: dx *= gelu'(pre) (fused), and then optionally
     colsum[k] += sum_m dx[m,k] (f32; the bias gradient of the layer whose pre-activation `pre` is)."""
@@ -441,6 +456,61 @@ def heads_view(t: torch.Tensor, B: int, L: int, H: int, hd: int, offset: int = 0
 
 
 # ---------------------------------------------------------- norm / modulation / gates ----
+def mod_group_of(l: int, lead: int, period: int) -> int:
+    """modulation group of row l of a sample (include/vds.h: vds_mod_groups): 0 for the `lead` rows at its head, then
+    1 + (l - lead) % period"""
+    return 0 if l < lead else 1 + (l - lead) % period
+
+
+def check_mod_groups(groups, L: int):
+    """(lead, period) that splits L rows per sample into 1 + period groups, or ValueError"""
+    lead, period = (int(v) for v in groups)
+    if lead < 0 or period < 1 or lead > L or (L - lead) % period != 0:
+        raise ValueError(f"modulation groups (lead={lead}, period={period}) do not fit {L} rows per sample: lead >= 0, "
+                         f"period >= 1 and (L - lead) % period == 0 are required")
+    return lead, period
+
+
+def _groups(groups, L: int, mod: torch.Tensor, B: int):
+    lead, period = check_mod_groups(groups, L)
+    assert mod.shape[0] == B * (1 + period), f"grouped modulation table: {B * (1 + period)} rows expected, got {mod.shape[0]}"
+    return C.byref(_lib.ModGroups(lead, period))
+
+
+def rmsnorm_mod_fwd_grouped(x, w, mod, shift_col, scale_col, B, L, groups, eps=1e-6):
+    """rmsnorm_mod_fwd with mod f32 [B*G, ld]: row l of sample b reads modulation row b*G + mod_group_of(l)"""
+    D = x.shape[1]
+    y = torch.empty(B * L, D, dtype=bf16, device=x.device)
+    rstd = torch.empty(B * L, dtype=f32, device=x.device)
+    check(_lib.load().vds_rmsnorm_mod_fwd_grouped(_p(x), x.stride(0), _p(w), _p(mod), mod.stride(0), shift_col, scale_col,
+                                                  _p(y), D, _p(rstd), B, L, D, eps, _groups(groups, L, mod, B),
+                                                  _stream()), "vds_rmsnorm_mod_fwd_grouped")
+    return y, rstd
+
+
+def rmsnorm_mod_bwd_grouped(dy, x, w, mod, shift_col, scale_col, rstd, dres, dmod, dw, B, L, groups):
+    """rmsnorm_mod_bwd with mod / dmod [B*G, ld]: dmod row b*G + g accumulates the sums over the rows of that group"""
+    D = x.shape[1]
+    dx = torch.empty(B * L, D, dtype=bf16, device=x.device)
+    assert dmod.shape[0] == mod.shape[0] and dmod.stride(0) == mod.stride(0)
+    check(_lib.load().vds_rmsnorm_mod_bwd_grouped(_p(dy), dy.stride(0), _p(x), x.stride(0), _p(w), _p(mod), mod.stride(0),
+                                                  shift_col, scale_col, _p(rstd), _p(dres),
+                                                  dres.stride(0) if dres is not None else 0, _p(dx), D, _p(dmod), _p(dw),
+                                                  B, L, D, _groups(groups, L, mod, B), _stream()),
+          "vds_rmsnorm_mod_bwd_grouped")
+    return dx
+
+
+def gate_bwd_grouped(dxn, y, mod, gate_col, dmod, dbias, B, L, groups):
+    D = y.shape[1]
+    dy = torch.empty(B * L, D, dtype=bf16, device=y.device)
+    assert dmod.shape[0] == mod.shape[0] and dmod.stride(0) == mod.stride(0)
+    check(_lib.load().vds_gate_bwd_grouped(_p(dxn), dxn.stride(0), _p(y), y.stride(0), _p(mod), mod.stride(0), gate_col,
+                                           _p(dy), D, _p(dmod), _p(dbias), B, L, D, _groups(groups, L, mod, B), _stream()),
+          "vds_gate_bwd_grouped")
+    return dy
+
+
 def rmsnorm_mod_fwd(x, w, mod, shift_col, scale_col, B, L, eps=1e-6):
     D = x.shape[1]
     y = torch.empty(B * L, D, dtype=bf16, device=x.device)
@@ -722,6 +792,51 @@ def flow_loss(v, out, want_grad: bool, gscale: float = 1.0):
     check(lib.vds_flow_loss(_p(v), _p(out), _p(acc), _p(acc[1:]), _p(dout), gscale, B, per, _p(acc[1 + B:]), _stream()),
           "vds_flow_loss")
     return acc[0], acc[1:1 + B], dout
+
+
+def _frames_tab(t, B: int, T: int, tps: int, what: str) -> torch.Tensor:
+    assert T % tps == 0
+    assert t.is_cuda and t.dtype == f32 and tuple(t.shape) == (B, T // tps) and t.is_contiguous(), \
+        f"{what}: a contiguous f32 CUDA tensor [{B}, {T // tps}] expected"
+    return t
+
+
+def noise_latents_frames(x, noise, t, time_patch: int):
+    """noise_latents with t f32 [B, T / time_patch]: latent frame j of sample b is noised with t[b, j // time_patch]"""
+    B, Cc, T, H, W = x.shape
+    assert x.is_contiguous() and noise.is_contiguous()
+    zt = torch.empty_like(x)
+    v = torch.empty_like(x)
+    check(_lib.load().vds_noise_latents_frames(_p(x), _p(noise), _p(_frames_tab(t, B, T, time_patch, "t")), _p(zt), _p(v),
+                                               B, Cc, T, H * W, time_patch, _stream()), "vds_noise_latents_frames")
+    return zt, v
+
+
+def flow_loss_frames(v, out, w, time_patch: int, want_grad: bool, gscale: float = 1.0):
+    """frame-weighted flow loss (include/vds.h: vds_flow_loss_frames): v / out [B,C,T,H,W] bf16, w f32 [B, T / time_patch]
+    -> (loss, per_sample [B], dout | None)"""
+    B, Cc, T, H, W = v.shape
+    assert v.is_contiguous() and out.is_contiguous()
+    lib = _lib.load()
+    F = T // time_patch
+    acc = torch.empty(1 + B + lib.vds_flow_loss_frames_workspace_floats(B, F, Cc * time_patch * H * W), dtype=f32,
+                      device=v.device)
+    dout = torch.empty_like(out) if want_grad else None
+    check(lib.vds_flow_loss_frames(_p(v), _p(out), _p(_frames_tab(w, B, T, time_patch, "w")), _p(acc), _p(acc[1:]),
+                                   _p(dout), gscale, B, Cc, T, H * W, time_patch, _p(acc[1 + B:]), _stream()),
+          "vds_flow_loss_frames")
+    return acc[0], acc[1:1 + B], dout
+
+
+def flow_loss_frames_bwd(v, out, w, time_patch: int, gloss):
+    """d loss / d out of flow_loss_frames; gloss: f32 device scalar (the upstream gradient)"""
+    B, Cc, T, H, W = v.shape
+    assert gloss.is_cuda and gloss.dtype == f32 and gloss.numel() == 1 and out.is_contiguous() and v.is_contiguous()
+    dout = torch.empty_like(out)
+    check(_lib.load().vds_flow_loss_frames_bwd(_p(v), _p(out), _p(_frames_tab(w, B, T, time_patch, "w")), _p(gloss),
+                                               _p(dout), B, Cc, T, H * W, time_patch, _stream()),
+          "vds_flow_loss_frames_bwd")
+    return dout
 
 
 def flow_loss_bwd(v, out, gloss):

@@ -36,8 +36,13 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
                      inference_steps: int = 50, cfg_scale: float = 6.0, height: int = 512, width: int = 512,
                      seed: int = 42, latents: Optional[torch.Tensor] = None,
                      rope_starts: Optional[Sequence[Tuple[int, int, int]]] = None, device="cuda",
-                     prompt_lens=None, negative_lens=None) -> torch.Tensor:
-    """prompt_lens / negative_lens ([B] ints, DiT.forward's context_lens): the number of real tokens of the prompt / the
+                     prompt_lens=None, negative_lens=None, cond_latents: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cond_latents ([1,16,Tc,h,w], Tc a multiple of the model's time_patch_size; image-to-video, video extension): the
+    first Tc latent frames are held at these values -- their token-frames are given t = 0 in every model call (per-frame
+    timesteps, DiT.forward), the other frames the step's t, and the frames are written back into the latents and the
+    accumulator after every Euler step.  None: the loop below is the reference's.
+
+    prompt_lens / negative_lens ([B] ints, DiT.forward's context_lens): the number of real tokens of the prompt / the
     negative prompt; if either is given every model call passes lengths, a side without them attends all its rows, and
     `negative_embeds=None` with prompt_lens means an EMPTY negative prompt (length 0: no context), not 512 zero rows.
 
@@ -74,6 +79,31 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
     lat = latents.to(dev, bf16).contiguous().clone()
     acc = lat.to(f32)
     call = 0
+    n_cond = 0
+    if cond_latents is not None:
+        pt = model.time_patch_size
+        Tc = cond_latents.shape[2] if cond_latents.dim() == 5 else -1
+        want = (lat.shape[0], lat.shape[1], Tc, lat.shape[3], lat.shape[4])
+        if Tc < 1 or Tc % pt != 0 or Tc > lat.shape[2] or tuple(cond_latents.shape) != want:
+            raise ValueError(f"cond_latents must have shape [{lat.shape[0]}, {lat.shape[1]}, Tc, {lat.shape[3]}, {lat.shape[4]}] "
+                             f"with Tc a multiple of time_patch_size ({pt}) and at most {lat.shape[2]}, got "
+                             f"{tuple(cond_latents.shape)}")
+        n_cond, n_frames = Tc // pt, lat.shape[2] // pt
+        cond_acc = cond_latents.to(dev, f32)
+        cond_lat = cond_acc.to(bf16)
+        is_cond = torch.arange(n_frames, device=dev) < n_cond
+
+        def impose():
+            acc[:, :, :Tc] = cond_acc
+            lat[:, :, :Tc] = cond_lat
+        impose()
+
+    def times(t, nb):
+        """the timesteps of a model call on nb samples: [nb], or [nb, t] with the conditioning frames at 0"""
+        tt = torch.tensor([t] * nb, device=dev).to(bf16)
+        if not n_cond:
+            return tt
+        return torch.where(is_cond[None, :], torch.zeros((), dtype=bf16, device=dev), tt[:, None]).contiguous()
     for i in range(inference_steps, 0, -1):
         t, t_next = shifted_times(i, inference_steps)
         dt = t - t_next
@@ -82,20 +112,22 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
             s_u = tuple(rope_starts[call + 1]) if rope_starts is not None else None
             call += 2
             if s_c == s_u:  # one batched forward: [cond, uncond]
-                tt = torch.tensor([t, t], device=dev).to(bf16)
+                tt = times(t, 2)
                 out = model(torch.cat([lat, lat]), torch.cat([prompt_embeds, negative_embeds.to(dev, bf16)]), tt,
                             **({"rope_start": s_c} if s_c is not None else {}),
                             **({} if lens_c is None else {"context_lens": lens_cu}))
                 cond, uncond = out[0:1].contiguous(), out[1:2].contiguous()
             else:
-                tt = torch.tensor([t], device=dev).to(bf16)
+                tt = times(t, 1)
                 cond = model(lat, prompt_embeds, tt, rope_start=s_c, **kw_c)
                 uncond = model(lat, negative_embeds.to(dev, bf16), tt, rope_start=s_u, **kw_u)
         else:
-            tt = torch.tensor([t], device=dev).to(bf16)
+            tt = times(t, 1)
             s_c = tuple(rope_starts[call]) if rope_starts is not None else None
             call += 1
             cond = model(lat, prompt_embeds, tt, **({"rope_start": s_c} if s_c is not None else {}), **kw_c)
             uncond = None
         ops.cfg_euler_step(cond, uncond, acc, lat, cfg_scale, dt)
+        if n_cond:
+            impose()
     return acc

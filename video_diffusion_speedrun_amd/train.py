@@ -9,6 +9,9 @@ the loop body of train.py:431-434, on the HIP path.
 (frozen, third-party; out of scope) -- for synthetic runs pass `batch["context"]` (a pre-encoded
 [B,Lc,Cc] tensor) and text_encoder=None.  Optional `batch["context_lens"]` ([B] ints: the number of real caption tokens
 of each sample, `lens_from_mask(attention_mask)`) restricts the cross-attention to those rows (DiT.forward).
+
+`forward(..., frame_mode="first_frame" | "independent")` trains with one noise level per token-frame (image-to-video
+conditioning, diffusion forcing): DiT.forward takes `timesteps [B, t]`, the noising and the loss work per frame.
 """
 from __future__ import annotations
 
@@ -78,6 +81,69 @@ def flow_loss(out, v):
     return _FlowLoss.apply(out, v)
 
 
+class _FrameFlowLoss(torch.autograd.Function):
+    """frame-weighted flow loss: mean_b sum_f w[b,f] SSE[b,f] / (n_f sum_f w[b,f]) (ops.flow_loss_frames); the upstream
+    gradient is read from device memory, as in _FlowLoss.  w gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, out, v, w, time_patch):
+        loss, per, _ = ops.flow_loss_frames(v, out, w, time_patch, want_grad=False)
+        ctx.save_for_backward(out, v, w)
+        ctx.time_patch = time_patch
+        ctx.mark_non_differentiable(per)
+        return loss.reshape(()), per
+
+    @staticmethod
+    def backward(ctx, gloss, _gper):
+        out, v, w = ctx.saved_tensors
+        return ops.flow_loss_frames_bwd(v, out, w, ctx.time_patch, gloss.to(f32).reshape(1).contiguous()), None, None, None
+
+
+def frame_flow_loss(out, v, weights, time_patch: int):
+    """out / v [B,C,T,H,W] bf16, weights f32 [B, T // time_patch] >= 0 -> (loss, per_sample [B]); a sample whose weights
+    are all zero contributes 0 and gets a zero gradient"""
+    return _FrameFlowLoss.apply(out.contiguous(), v.contiguous(), weights.to(f32).contiguous(), int(time_patch))
+
+
+FRAME_MODES = (None, "first_frame", "independent")
+
+
+def frame_group_of(l: int, n_frames: int, lead: int = 16) -> int:
+    """modulation group of token row l of a sample under per-frame timesteps: 0 for the `lead` register rows, then
+    1 + the token-frame of the row (token order (h w t), t fastest)"""
+    return ops.mod_group_of(l, lead, n_frames)
+
+
+def draw_frame_levels(frame_mode: str, B: int, n_frames: int, device, generator=None) -> torch.Tensor:
+    """the first random draw of a per-frame step, in bf16: "first_frame" -> t [B], the very draw of the per-sample path
+    (randn(B), time shift); "independent" -> t [B, n_frames], one level per token-frame"""
+    if frame_mode not in ("first_frame", "independent"):
+        raise ValueError(f"frame_mode must be one of {FRAME_MODES}, got {frame_mode!r}")
+    shape = (B,) if frame_mode == "first_frame" else (B, n_frames)
+    return time_shift_from_normal(torch.randn(shape, device=device, dtype=bf16, generator=generator))
+
+
+def frame_schedule(frame_mode: str, t: torch.Tensor, n_frames: int, cond_prob: float = 0.5, generator=None):
+    """levels from draw_frame_levels -> (timesteps [B, n_frames] in t.dtype, weights f32 [B, n_frames]).
+    "first_frame": every frame of sample b at t[b]; with probability cond_prob token-frame 0 is a clean conditioning
+    frame -- t = 0 and weight 0 (out of the loss).  "independent": t as drawn, weights 1.
+    Only device-side elementwise work: no host sync, no boolean indexing (capturable)."""
+    if frame_mode == "independent":
+        if t.dim() != 2 or t.shape[1] != n_frames:
+            raise ValueError(f"frame_schedule('independent'): t [B, {n_frames}] expected, got {tuple(t.shape)}")
+        return t, torch.ones(t.shape, dtype=f32, device=t.device)
+    if frame_mode != "first_frame":
+        raise ValueError(f"frame_mode must be one of {FRAME_MODES}, got {frame_mode!r}")
+    if t.dim() != 1:
+        raise ValueError(f"frame_schedule('first_frame'): t [B] expected, got {tuple(t.shape)}")
+    B = t.shape[0]
+    cond = torch.rand(B, device=t.device, generator=generator) < cond_prob
+    clean = cond[:, None] & (torch.arange(n_frames, device=t.device) == 0)[None, :]
+    tf = torch.where(clean, torch.zeros((), dtype=t.dtype, device=t.device), t[:, None].expand(B, n_frames))
+    w = torch.where(clean, torch.zeros((), dtype=f32, device=t.device), torch.ones((), dtype=f32, device=t.device))
+    return tf.contiguous(), w.contiguous()
+
+
 def time_shift_from_normal(z: torch.Tensor) -> torch.Tensor:
     """t = sigmoid(z); t = a t / (1 + (a-1) t), in z.dtype (bf16) like train.py:93-96.
     B scalars: left to torch (host-side plumbing, not a hot-path kernel)."""
@@ -86,7 +152,12 @@ def time_shift_from_normal(z: torch.Tensor) -> torch.Tensor:
 
 
 def forward(dit_model, batch, text_encoder, tokenizer, device, global_step, master_process, generator=None,
-            binnings=None, batch_size=None, return_index=-1, rope_start=None):
+            binnings=None, batch_size=None, return_index=-1, rope_start=None, frame_mode=None, cond_prob=0.5,
+            frame_timesteps=None, frame_weights=None):
+    """frame_mode=None (default): one noise level per sample, the reference's step.
+    frame_mode="first_frame": one level per sample, and with probability cond_prob token-frame 0 stays clean (t = 0) and
+    leaves the loss (image-to-video); "independent": one level per token-frame (diffusion forcing).  frame_timesteps
+    [B, t] / frame_weights [B, t] override the drawn levels / weights (t = T // time_patch_size)."""
     logger = logging.getLogger(__name__)
     vae_latent = batch["latent"].to(device).to(bf16)
     with torch.no_grad():
@@ -108,11 +179,38 @@ def forward(dit_model, batch, text_encoder, tokenizer, device, global_step, mast
             context_lens = check_context_lens(context_lens, caption_encoded.shape[0], caption_encoded.shape[1]).to(device)
             context_lens = torch.where(do_zero_out, torch.zeros((), dtype=torch.int32, device=device), context_lens)
     B = vae_latent.size(0)
+    kw = {} if context_lens is None else {"context_lens": context_lens}
+    if frame_mode is not None or frame_timesteps is not None or frame_weights is not None:
+        # per-frame path.  Draw order: levels, noise, conditioning -- "first_frame" consumes the generator exactly as the
+        # per-sample path does for its first two draws
+        pt = dit_model.time_patch_size
+        n_frames = vae_latent.shape[2] // pt
+        if frame_timesteps is None:
+            if frame_mode is None:
+                raise ValueError("frame_weights without frame_mode or frame_timesteps: nothing defines the per-frame levels")
+            levels = draw_frame_levels(frame_mode, B, n_frames, device, generator)
+        noise = torch.randn(vae_latent.shape, device=device, dtype=bf16, generator=generator)
+        if frame_timesteps is None:
+            t, weights = frame_schedule(frame_mode, levels, n_frames, cond_prob, generator)
+        else:
+            t = torch.as_tensor(frame_timesteps).to(device=device, dtype=bf16)
+            weights = torch.ones(t.shape, dtype=f32, device=device)
+        if frame_weights is not None:
+            weights = torch.as_tensor(frame_weights).to(device=device, dtype=f32)
+        if tuple(t.shape) != (B, n_frames) or tuple(weights.shape) != (B, n_frames):
+            raise ValueError(f"per-frame timesteps / weights must have shape [{B}, {n_frames}] (t = T // time_patch_size), "
+                             f"got {tuple(t.shape)} / {tuple(weights.shape)}")
+        z_t, v_objective = ops.noise_latents_frames(vae_latent.contiguous(), noise, t.to(f32).contiguous(), pt)
+        output = dit_model(z_t, caption_encoded, t, rope_start=rope_start, **kw) if rope_start is not None \
+            else dit_model(z_t, caption_encoded, t, **kw)
+        diffusion_loss, _per = frame_flow_loss(output, v_objective, weights, pt)
+        if master_process:
+            logger.debug("forward done (step %s)", global_step)
+        return diffusion_loss, diffusion_loss
     z = torch.randn(B, device=device, dtype=bf16, generator=generator)
     t = time_shift_from_normal(z)
     noise = torch.randn(vae_latent.shape, device=device, dtype=bf16, generator=generator)
     z_t, v_objective = ops.noise_latents(vae_latent.contiguous(), noise, t.to(f32))
-    kw = {} if context_lens is None else {"context_lens": context_lens}
     output = dit_model(z_t, caption_encoded, t, rope_start=rope_start, **kw) if rope_start is not None \
         else dit_model(z_t, caption_encoded, t, **kw)
     diffusion_loss, _per = flow_loss(output, v_objective)
@@ -145,10 +243,13 @@ def get_schedule(optimizer, lr_scheduler_type: str = "cosine", num_warmup_steps:
         optimizer, lambda s: lr_lambda(s, lr_scheduler_type, num_warmup_steps, num_training_steps))
 
 
-def train_step(dit_model, optimizer, lr_scheduler, batch, device, generator=None, rope_start=None):
-    """train.py:412-434 for one batch with a pre-encoded context; returns the loss tensor."""
+def train_step(dit_model, optimizer, lr_scheduler, batch, device, generator=None, rope_start=None, frame_mode=None,
+               cond_prob=0.5):
+    """train.py:412-434 for one batch with a pre-encoded context; returns the loss tensor.  frame_mode / cond_prob: the
+    per-frame timestep modes of `forward`."""
+    fkw = {} if frame_mode is None else {"frame_mode": frame_mode, "cond_prob": cond_prob}
     total_loss, _ = forward(dit_model, batch, None, None, device, 0, False, generator=generator,
-                            rope_start=rope_start)
+                            rope_start=rope_start, **fkw)
     optimizer.zero_grad()
     total_loss.backward()
     optimizer.step()
