@@ -260,6 +260,19 @@ typedef struct {
   int32_t lead;    /* rows of group 0 at the head of every sample (may be 0: group 0 is empty, its dmod row untouched) */
   int32_t period;  /* number of frame groups */
 } vds_mod_groups;
+/* Frame-causal self-attention: vds_attn_fwd / vds_attn_bwd restricted by the row groups above (frames = {lead, period},
+ * the same validation against L = Lq).  Query row q attends key row k iff group(k) <= group(q): the lead rows attend
+ * each other, a row of token-frame f attends the lead rows and every row of frames 0 .. f (its own included); every
+ * query has a key, there is no empty row.  o, lse and dq are those of the restricted softmax, a dk / dv row sums over
+ * the queries that attend it, and an excluded pair contributes P = 0 exactly (its score never enters a running maximum).
+ * The rows of a frame are interleaved with the period, so the mask is applied per element and no key tile is skipped.
+ * lead and period travel by value in the kernel arguments (a captured graph replays them).  Self-attention only:
+ * Lq != Lk or kv_pad_ones == 2 is VDS_ERR_ARG; kv_pad_ones 0 and 1, every head dim of the dispatcher and every
+ * vds_attn_set_variant / knob setting have a masked instance; L > 2^21 rows is VDS_ERR_UNSUPPORTED.  frames == NULL
+ * forwards to vds_attn_fwd / vds_attn_bwd, which launch what they always launched; vds_attn_bwd_workspace_bytes is
+ * unchanged. */
+int vds_attn_fwd_causal(const vds_attn_args* args, const vds_mod_groups* frames, vds_stream_t stream);
+int vds_attn_bwd_causal(const vds_attn_args* args, const vds_mod_groups* frames, vds_stream_t stream);
 /* vds_rmsnorm_mod_fwd with mod f32 [B*G, ldmod]: the same arithmetic per row, y / rstd bit-identical to the per-sample
  * call run on the rows of one group with that group's mod row.  Every form of the dispatcher is covered. */
 int vds_rmsnorm_mod_fwd_grouped(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod,

@@ -59,6 +59,8 @@ struct AttnP {
   int wide_o, wide_dq, wide_dkv;
   // per-sample key counts (vds_attn_*_kvlen): B int32 on the device, read by the KVLEN instances of the kernels only
   const int* kv_lens;
+  // frame-causal map (vds_attn_*_causal): by value, read by the CAUSAL instances of the kernels only
+  int fc_lead, fc_period;
 };
 
 // Keys of sample b.  KVLEN: kv_lens[b] clamped to [0, Lk] -- b is the same for the whole workgroup, so this is one
@@ -67,6 +69,52 @@ template <bool KVLEN>
 __device__ __forceinline__ int kv_len_of(const AttnP& p, int b) {
   if constexpr (KVLEN) return min(max(p.kv_lens[b], 0), p.Lk);
   else return p.Lk;
+}
+
+// Frame-causal mask (CAUSAL instances, vds_attn_*_causal).  Row l of a sample belongs to group 0 (l < lead: the register
+// tokens) or 1 + (l - lead) % period (token-frame (l - lead) % period: the token order is (h w t), t fastest), and query q
+// attends key k iff group(k) <= group(q).  The rows of a frame are interleaved with that period, so every MFMA block holds
+// every frame: the mask is applied per element and no tile is skipped.
+// x(l) = (l - lead) % period for l >= lead and a value in [-period, -1] for the lead rows, without an integer division:
+// the quotient is trunc((l - lead + 0.5) / period) in fp32 -- the half keeps the exact value 0.5 / period away from every
+// integer, further than the two fp32 roundings (2^-23 relative) move it while |l - lead| < 2^21 (the entry points refuse
+// longer sequences).  Four full-rate VALU instructions per row; a row's x serves every block that shares the row.
+struct FcMap {
+  int lead, negp;
+  float inv, hinv;
+  __device__ __forceinline__ explicit FcMap(const AttnP& p) : lead(p.fc_lead), negp(-p.fc_period) {
+    inv = 1.0f / (float)p.fc_period;
+    hinv = 0.5f * inv;
+  }
+  __device__ __forceinline__ int x(int l) const {
+    const int kk = l - lead;
+    return kk + __mul24((int)__builtin_fmaf((float)kk, inv, hinv), negp);
+  }
+  // a query attends the keys with x(key) <= fq(query): the lead keys always, no token key from a lead query
+  __device__ __forceinline__ int fq(int q) const { return max(x(q), -1); }
+  // the same test seen from a key (the dK/dV kernels): its gradient comes from the queries with x(query) >= fk(key)
+  __device__ __forceinline__ int fk(int k) const { return k < lead ? -0x7fffffff : x(k); }
+};
+// 32x32 accumulator with the key on the registers (rows row0 + acc_row(r, 0); row0 includes the lane half's 4 h):
+// `fill` where the lane's query (f = fq) may not attend the key
+__device__ __forceinline__ void fc_fill(const FcMap& fm, int row0, int f, f32x16& s, float fill) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    if (fm.x(row0 + (r & 3) + 8 * (r >> 2)) > f) s[r] = fill;
+}
+__device__ __forceinline__ void fc_fill2(const FcMap& fm, int row0, int f0, int f1, f32x16& s0, f32x16& s1, float fill) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int xk = fm.x(row0 + (r & 3) + 8 * (r >> 2));
+    if (xk > f0) s0[r] = fill;
+    if (xk > f1) s1[r] = fill;
+  }
+}
+// 32x32 accumulators with the QUERY on the registers and the lane's key f = fk: P and dS of the pairs that are not attended
+__device__ __forceinline__ void fc_zero_q(const FcMap& fm, int row0, int f, f32x16& pm, f32x16& ds) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    if (fm.x(row0 + (r & 3) + 8 * (r >> 2)) < f) { pm[r] = 0.f; ds[r] = 0.f; }
 }
 
 // ---- LDS image (a): rows x HDP bf16, 8x32 sub-tiles of 512 B -------------------------------
@@ -351,7 +399,9 @@ struct DmaStage {
 // ---- forward kernel: lazy softmax + LDS-DMA staging (PIPE: explicit fragment prefetch) ---------
 // KVLEN (all forward kernels): sample b attends its first kv_lens[b] keys; the K / V bounds, the tile count and the
 // ragged-tile mask follow that count, and a sample without keys gets O = 0, lse = 0 before anything is staged.
-template <int HDP, int HDQ, int WPS, bool PIPE, bool KVLEN = false>
+// CAUSAL (all forward kernels): the frame-causal mask; masked scores become -inf BEFORE the sub-block maximum, so they
+// neither raise the running maximum nor get a nonzero P (their V rows are live, ones columns included).
+template <int HDP, int HDQ, int WPS, bool PIPE, bool KVLEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, TILE = 64 * HDP * 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -398,6 +448,9 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   float m = -1e30f, l = 0.f;
   const float c = p.scale * LOG2E;
   const int nkt = (Lk + 63) / 64;
+  const FcMap fm(p);
+  int fcq = 0;
+  if constexpr (CAUSAL) fcq = fm.fq(qrow);
 #pragma unroll
   for (int ks = 0; ks < KSQ; ++ks) retire(qf[ks]);
   VDS_WAIT_VM(0);
@@ -431,6 +484,10 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
           if (j * 64 + 32 + acc_row(r, h) >= Lk) s1[r] = -INFINITY;
         }
       }
+      if constexpr (CAUSAL) {
+        fc_fill(fm, j * 64 + 4 * h, fcq, s0, -INFINITY);
+        fc_fill(fm, j * 64 + 32 + 4 * h, fcq, s1, -INFINITY);
+      }
       bf16x8 pf[2];
       lazy_softmax<NDB>(s0, c, m, l, o, pf);
       bf16x8 v1[2][NDB];
@@ -456,6 +513,7 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
           for (int r = 0; r < 16; ++r)
             if (j * 64 + kb * 32 + acc_row(r, h) >= Lk) s[r] = -INFINITY;
         }
+        if constexpr (CAUSAL) fc_fill(fm, j * 64 + kb * 32 + 4 * h, fcq, s, -INFINITY);
         bf16x8 pf[2];
         lazy_softmax<NDB>(s, c, m, l, o, pf);
 #pragma unroll
@@ -527,7 +585,7 @@ __device__ __forceinline__ void ones_softmax(f32x16& s, float& m, bf16x8& q_ones
   pf[1] = acc_frag(s, 1);
 }
 
-template <int HDP, int HDQ, bool ONES, bool KVLEN = false>
+template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_wide_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, TILE = 64 * HDP * 2;
   static_assert(!ONES || (HDP == 96 && HDQ == 80), "ones columns: head_dim 72 layout");
@@ -596,6 +654,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_wide_kernel(AttnP p) {
   float m[2], l[2] = {0.f, 0.f};
   m[0] = m[1] = ONES ? 0.f : -1e30f;
   const int nkt = (Lk + 63) / 64;
+  const FcMap fm(p);
+  int fcq[2] = {0, 0};
+  if constexpr (CAUSAL) { fcq[0] = fm.fq(qrow0); fcq[1] = fm.fq(qrow0 + 32); }
   VDS_WAIT_VM(0);
   __syncthreads();
 
@@ -630,6 +691,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_wide_kernel(AttnP p) {
             if (j * 64 + kb * 32 + acc_row(r, h) >= Lk) { s0[r] = -INFINITY; s1[r] = -INFINITY; }
         }
       }
+      // (the frame mask cannot lean on zero V rows: with ONES too the scores themselves go to -inf, before the maxima --
+      // key 0 is attended by every query, so the first sub-block's maximum is finite)
+      if constexpr (CAUSAL) fc_fill2(fm, j * 64 + kb * 32 + 4 * h, fcq[0], fcq[1], s0, s1, -INFINITY);
       bf16x8 vfr[2][NDB];
       load_vfrags<HDP, NDB>(vfr, vt, kb * 32, lane);
       bf16x8 p0[2], p1[2];
@@ -765,7 +829,8 @@ __global__ __launch_bounds__(256) void attn_delta_tokmajor_kernel(AttnP p) {
 // 1.0 there): S' = log2 P and dP - delta come straight out of the two MFMA chains, leaving
 // exp2, one multiply and the bf16 pack per element.  Keys past Lk need no mask in either mode.
 // KVLEN (all dQ kernels): the sweep covers the first kv_lens[b] keys of sample b; without keys dQ = 0.
-template <int HDP, int HDQ, bool ONES, bool KVLEN = false>
+// CAUSAL (all dQ kernels): dS of the pairs the frame-causal mask excludes is set to zero (P = 0 exactly).
+template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, TILE = 64 * HDP * 2;
   static_assert(!ONES || (HDP == 96 && HDQ == 80), "ones columns: head_dim 72 layout");
@@ -835,6 +900,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
 #pragma unroll
   for (int i = 0; i < NDB; ++i) dq[i] = zero16();
   const int nkt = (Lk + 63) / 64;
+  const FcMap fm(p);
+  int fcq = 0;
+  if constexpr (CAUSAL) fcq = fm.fq(qrow);
   VDS_WAIT_VM(0);
   __syncthreads();  // tile 0 landed
 
@@ -870,6 +938,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r] * c - lse2) * dp[r];
       }
+      if constexpr (CAUSAL) fc_fill(fm, j * 64 + kb * 32 + 4 * h, fcq, s, 0.f);
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
         const bf16x8 df = acc_frag(s, s2);
@@ -901,7 +970,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
 // KVLEN: rows at or past kv_lens[b] of dK / dV are zeros.  A workgroup whose 128 keys all lie there stores them and
 // leaves (query split: it leaves at once -- dkv_reduce_kernel<true> writes the zeros without reading its partial); the
 // workgroup that holds the boundary runs as usual and clears the accumulators of the rows past it before the store.
-template <int HDP, int HDQ, bool ONES, bool KVLEN = false>
+// CAUSAL (both dK/dV kernels): P and dS of the pairs the frame-causal mask excludes are set to zero, so a key row sums
+// over the queries that attend it and nothing is cleared afterwards.
+template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void attn_bwd_dkv_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, Q_TILE = 64 * HDP * 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1039,6 +1110,12 @@ __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void att
           }
         }
       }
+      // (built here and not in the prologue as in the forward / dQ kernels: a prologue copy, though dead without CAUSAL,
+      // changed the register allocation of this kernel's unmasked instances)
+      if constexpr (CAUSAL) {  // (the map and the lane's key are loop-invariant: hoisted by the compiler)
+        const FcMap fm(p);
+        fc_zero_q(fm, j * 64 + qb * 32 + 4 * h, fm.fk(krow), pm, s);
+      }
       PRIO_HI();
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
@@ -1123,7 +1200,9 @@ __device__ __forceinline__ bf16x8 pack2(const f32x4& a, const f32x4& b) {
 // views of a linear layer's output), so only head_dim columns of a q row are staged and the S accumulators START from
 // -lse2 of their queries, read from the statistics this kernel stages beside -delta anyway.
 // KVLEN: as in attn_bwd_dkv_kernel; 16-key blocks past kv_lens[b] are not computed at all (NKB).
-template <int HDP, bool QPAD = true, bool KVLEN = false>
+// CAUSAL: a lane holds one key per 16-key block (fk fixed) and its registers walk the queries 16 rb + 4 g + r of the
+// sub-block: x(query) is formed once per register and serves both key blocks; P and dS of excluded pairs become zero.
+template <int HDP, bool QPAD = true, bool KVLEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv16_kernel(AttnP p) {
   static_assert(HDP == 96, "head_dim 72 layout (ones columns at 72, 73)");
   constexpr int KS = HDP / 32, NDB = 5, Q_TILE = 64 * HDP * 2;
@@ -1258,6 +1337,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv16_kernel(AttnP p) {
         for (int cb = 0; cb < NKB; ++cb)
 #pragma unroll
           for (int r = 0; r < 4; ++r) dp[rb][cb][r] *= s[rb][cb][r];  // dS (unscaled)
+      if constexpr (CAUSAL) {  // (the map and the lane's keys are loop-invariant: hoisted by the compiler)
+        const FcMap fm(p);
+        const int fck[2] = {fm.fk(key0 + (lane & 15)), fm.fk(key0 + 16 + (lane & 15))};
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int xq = fm.x(j * 64 + qb * 32 + rb * 16 + 4 * g + r);
+#pragma unroll
+            for (int cb = 0; cb < NKB; ++cb)
+              if (xq < fck[cb]) { s[rb][cb][r] = 0.f; dp[rb][cb][r] = 0.f; }
+          }
+      }
       bf16x8 pf[2], df[2];
 #pragma unroll
       for (int cb = 0; cb < NKB; ++cb) {
@@ -1327,7 +1419,9 @@ __device__ __forceinline__ float max_over_lane_groups(float x) {  // max over th
   return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
 }
 
-template <int HDP, bool KVLEN = false>
+// CAUSAL: a lane holds one query per 16-query block (fq fixed) and its registers walk the keys 16 rb + 4 g + r of the
+// sub-block: x(key) is formed once per register and serves all four query blocks.
+template <int HDP, bool KVLEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
   static_assert(HDP == 96, "head_dim 72 layout (ones columns at 72, 73 / 72, 76)");
   constexpr int KS = HDP / 32, NDB = 5, TILE = 64 * HDP * 2;
@@ -1385,6 +1479,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
     for (int cb = 0; cb < 4; ++cb) o[db][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m[4] = {0.f, 0.f, 0.f, 0.f};
   const int nkt = (Lk + 63) / 64;
+  const FcMap fm(p);
+  int fcq[4] = {0, 0, 0, 0};
+  if constexpr (CAUSAL) {
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) fcq[cb] = fm.fq(qrow0 + 16 * cb);
+  }
   VDS_WAIT_VM(0);
   __syncthreads();
 
@@ -1422,6 +1522,19 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
       PRIO_LO();
       // keys past Lk need no mask: their zero-filled V rows (ones columns included) add nothing to the numerators or
       // to the denominator, whatever exp2 makes of their scores
+      // (the frame mask cannot lean on zero V rows: the scores themselves go to -inf, before the maxima -- key 0 is
+      // attended by every query, so the first sub-block's maximum is finite)
+      if constexpr (CAUSAL) {
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int xk = fm.x(j * 64 + kb * 32 + rb * 16 + 4 * g + r);
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb)
+              if (xk > fcq[cb]) s[rb][cb][r] = -INFINITY;
+          }
+      }
       const bool first = (j == 0) && (kb == 0);
       float mx[4];
 #pragma unroll
@@ -1515,7 +1628,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
 // two cross-lane adds), writes -delta and lse * log2(e) to the workspace and the (hi, lo) pair of -lse2 into the pad of its
 // Q row -- what attn_delta_*_kernel did in a pass of its own over O and dO (6.5 ms per C3b step).  The host then runs this
 // kernel BEFORE the dK/dV kernel, which reads those statistics.
-template <int HDP, bool FOLD = false, bool KVLEN = false>
+template <int HDP, bool FOLD = false, bool KVLEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
   static_assert(HDP == 96, "head_dim 72 layout");
   constexpr int KS = HDP / 32, NDB = 5, TILE = 64 * HDP * 2, NQ = 2;
@@ -1612,6 +1725,12 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
 #pragma unroll
     for (int cb = 0; cb < NQ; ++cb) dq[db][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int nkt = (Lk + 63) / 64;
+  const FcMap fm(p);
+  int fcq[NQ] = {0, 0};
+  if constexpr (CAUSAL) {
+#pragma unroll
+    for (int cb = 0; cb < NQ; ++cb) fcq[cb] = fm.fq(qrow0 + 16 * cb);
+  }
   VDS_WAIT_VM(0);
   __syncthreads();  // tile 0 landed
 
@@ -1659,6 +1778,17 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
         for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
           for (int r = 0; r < 4; ++r) s[rb][cb][r] *= dp[rb][cb][r];  // dS^T (unscaled)
+      if constexpr (CAUSAL) {
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int xk = fm.x(j * 64 + kb * 32 + rb * 16 + 4 * g + r);
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb)
+              if (xk > fcq[cb]) s[rb][cb][r] = 0.f;
+          }
+      }
       bf16x8 df[NQ];
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) df[cb] = pack2(s[0][cb], s[1][cb]);
@@ -1719,6 +1849,8 @@ AttnP to_p(const vds_attn_args* a) {
   p.q_split = 1;
   p.dkv_part = nullptr;
   p.kv_lens = nullptr;
+  p.fc_lead = 0;
+  p.fc_period = 1;
   const bool wide_on = vdscfg::geti(vdscfg::ATTN_WIDE_STORES) != 0;  // A/B knob
   p.wide_o = wide_on && p.hd > 64 && rows16(p.o, p.o_sb, p.o_sh, p.o_sl);
   p.wide_dq = wide_on && p.hd > 64 && rows16(p.dq, p.dq_sb, p.dq_sh, p.dq_sl);
@@ -1764,15 +1896,18 @@ static int tail_last_for(int L, int tile) {
 
 // KVLEN (vds_attn_*_kvlen): the same choices and launch geometry -- functions of Lk, never of the device-side lengths --
 // on the kernel instances that read p.kv_lens
-template <int HDP, int HDQ, bool KVLEN = false>
+// CAUSAL (vds_attn_*_causal): likewise -- the same choices and geometry on the instances that read p.fc_lead / p.fc_period.
+// (The profiler credits a frame-causal call with the unmasked FLOPs: in the (h w t) row order no tile is skipped, so
+// that is the work executed.)
+template <int HDP, int HDQ, bool KVLEN = false, bool CAUSAL = false>
 int run_fwd(AttnP p, hipStream_t s) {
   constexpr int LDS = 4 * 64 * HDP * 2;
   static bool once = false;
   if (!once) {
-    set_lds(attn_fwd_kernel<HDP, HDQ, 2, true, KVLEN>, LDS);
-    if constexpr (HDP <= 96) set_lds(attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN>, LDS);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd_wide_kernel<HDP, HDQ, true, KVLEN>, LDS);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd16_kernel<HDP, KVLEN>, LDS);
+    set_lds(attn_fwd_kernel<HDP, HDQ, 2, true, KVLEN, CAUSAL>, LDS);
+    if constexpr (HDP <= 96) set_lds(attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN, CAUSAL>, LDS);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd_wide_kernel<HDP, HDQ, true, KVLEN, CAUSAL>, LDS);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd16_kernel<HDP, KVLEN, CAUSAL>, LDS);
     once = true;
   }
   const int wide = vdscfg::geti(vdscfg::ATTN_FWD_WIDE);  // 0 / 1 forces (experiments); 2 (default): head_dim 64 / 72, long query sequences
@@ -1791,7 +1926,7 @@ int run_fwd(AttnP p, hipStream_t s) {
                     2.0 * p.B * p.H * p.hd * (2.0 * p.Lq + 2.0 * p.Lk));
   if constexpr (HDP == 64) {
     if (use_wide) {
-      hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN>), dim3(grid), dim3(256), LDS, s, p);
+      hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS, s, p);
       return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
     }
   }
@@ -1802,16 +1937,16 @@ int run_fwd(AttnP p, hipStream_t s) {
         if (p.kv_pad_ones && p.hd == 72) {
           // (round 5 measured a form of this kernel software-pipelined inside the wave: +9.5 % slower, removed in round 6;
           // profiles/r05/attn_fwd_software_pipelined.log)
-          if (attn_variant() & 4) hipLaunchKernelGGL((attn_fwd16_kernel<HDP, KVLEN>), dim3(grid), dim3(256), LDS, s, p);
-          else hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, true, KVLEN>), dim3(grid), dim3(256), LDS, s, p);
+          if (attn_variant() & 4) hipLaunchKernelGGL((attn_fwd16_kernel<HDP, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS, s, p);
+          else hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, true, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS, s, p);
           done = true;
         }
       }
-      if (!done) hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN>), dim3(grid), dim3(256), LDS, s, p);
+      if (!done) hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS, s, p);
       return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
     }
   }
-  hipLaunchKernelGGL((attn_fwd_kernel<HDP, HDQ, 2, true, KVLEN>), dim3(grid), dim3(256), LDS, s, p);
+  hipLaunchKernelGGL((attn_fwd_kernel<HDP, HDQ, 2, true, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS, s, p);
   return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
 }
 
@@ -1826,20 +1961,20 @@ int dkv_qsplit(int B, int H, int Lq, int Lk) {
   return (int)(sp < 1 ? 1 : sp > 16 ? 16 : sp);
 }
 
-template <int HDP, int HDQ, bool KVLEN = false>
+template <int HDP, int HDQ, bool KVLEN = false, bool CAUSAL = false>
 int run_bwd(AttnP p, hipStream_t s, size_t ws_floats) {
   constexpr int LDS_DQ = 4 * 64 * HDP * 2;
   constexpr int LDS_DKV = 4 * 64 * HDP * 2 + 2 * 128 * 4;
   static bool once = false;
   if (!once) {
-    set_lds(attn_bwd_dq_kernel<HDP, HDQ, false, KVLEN>, LDS_DQ);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dq_kernel<HDP, HDQ, true, KVLEN>, LDS_DQ);
-    set_lds(attn_bwd_dkv_kernel<HDP, HDQ, false, KVLEN>, LDS_DKV);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dkv_kernel<HDP, HDQ, true>, LDS_DKV);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dkv16_kernel<HDP>, LDS_DKV);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dkv16_kernel<HDP, false, KVLEN>, LDS_DKV);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dq16_kernel<HDP, false, KVLEN>, LDS_DQ);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dq16_kernel<HDP, true, KVLEN>, LDS_DQ);
+    set_lds(attn_bwd_dq_kernel<HDP, HDQ, false, KVLEN, CAUSAL>, LDS_DQ);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dq_kernel<HDP, HDQ, true, KVLEN, CAUSAL>, LDS_DQ);
+    set_lds(attn_bwd_dkv_kernel<HDP, HDQ, false, KVLEN, CAUSAL>, LDS_DKV);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dkv_kernel<HDP, HDQ, true, false, CAUSAL>, LDS_DKV);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dkv16_kernel<HDP, true, false, CAUSAL>, LDS_DKV);
+    if constexpr (HDP == 96 && HDQ == 80 && !CAUSAL) set_lds(attn_bwd_dkv16_kernel<HDP, false, KVLEN>, LDS_DKV);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dq16_kernel<HDP, false, KVLEN, CAUSAL>, LDS_DQ);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dq16_kernel<HDP, true, KVLEN, CAUSAL>, LDS_DQ);
     once = true;
   }
   const long rows = (long)p.B * p.H * p.Lq;
@@ -1863,13 +1998,13 @@ int run_bwd(AttnP p, hipStream_t s, size_t ws_floats) {
       // (48 queries per wave -- every fragment read feeds 3 MFMAs, two waves per SIMD instead of three -- measured 2-6 %
       // slower in round 5, removed in round 6; profiles/r05/attn_dq_three_blocks_per_wave.log)
       if (fold)
-        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, true, KVLEN>), dim3(grid), dim3(256), LDS_DQ, s, p);
+        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, true, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS_DQ, s, p);
       else if (ones && (attn_variant() & 2))
-        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, false, KVLEN>), dim3(grid), dim3(256), LDS_DQ, s, p);
+        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, false, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS_DQ, s, p);
       else if (ones)
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, HDQ, true, KVLEN>), dim3(grid), dim3(256), LDS_DQ, s, p);
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, HDQ, true, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS_DQ, s, p);
     }
-    if (!ones) hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, HDQ, false, KVLEN>), dim3(grid), dim3(256), LDS_DQ, s, p);
+    if (!ones) hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, HDQ, false, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS_DQ, s, p);
   };
   if (fold) launch_dq();
   else {
@@ -1897,12 +2032,12 @@ int run_bwd(AttnP p, hipStream_t s, size_t ws_floats) {
       // groups in alternating MFMA and VALU / LDS segments under s_barrier: bit-identical, +5 % slower; the kernel executes 77 %
       // of what a bare MFMA loop reaches at the board's power limit.  profiles/r06/negative_attn_dkv_pingpong.log)
       if (ones_kv && (attn_variant() & 1))
-        hipLaunchKernelGGL((attn_bwd_dkv16_kernel<HDP>), dim3(grid), dim3(256), LDS_DKV, s, p);
+        hipLaunchKernelGGL((attn_bwd_dkv16_kernel<HDP, true, false, CAUSAL>), dim3(grid), dim3(256), LDS_DKV, s, p);
       else if (ones_kv)
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, true>), dim3(grid), dim3(256), LDS_DKV, s, p);
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, true, false, CAUSAL>), dim3(grid), dim3(256), LDS_DKV, s, p);
     }
     bool done16 = false;
-    if constexpr (HDP == 96 && HDQ == 80) {
+    if constexpr (HDP == 96 && HDQ == 80 && !CAUSAL) {
       // cross-attention with padded K / V (kv_pad_ones = 2) and enough workgroups to fill the chip once (B*H*n_rt >= 512;
       // the query-range split below exists in the plain kernel only): the 16x16x32 kernel with S started from -lse2
       const int x16 = vdscfg::geti(vdscfg::CROSS_DKV16);  // 0 = plain kernel, 1 = rule, 2 = also for small grids (tests)
@@ -1925,13 +2060,13 @@ int run_bwd(AttnP p, hipStream_t s, size_t ws_floats) {
         p.dkv_part = p.delta + 2 * rows;
         p.tail_last = 0;
         const int g2 = cdiv(p.B * p.H, 8) * 8 * p.n_rt * split;
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, false, KVLEN>), dim3(g2), dim3(256), LDS_DKV, s, p);
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, false, KVLEN, CAUSAL>), dim3(g2), dim3(256), LDS_DKV, s, p);
         const long n = (long)p.B * p.H * p.Lk * 2 * (p.hd >> 2);
         hipLaunchKernelGGL(dkv_reduce_kernel<KVLEN>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
         p.q_split = 1;
         p.dkv_part = nullptr;
       } else {
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, false, KVLEN>), dim3(grid), dim3(256), LDS_DKV, s, p);
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, false, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS_DKV, s, p);
       }
     }
   }
@@ -2063,6 +2198,57 @@ extern "C" int vds_attn_bwd_kvlen(const vds_attn_args* a, const int32_t* kv_lens
     case 80: return run_bwd<96, 80, true>(p, s, ws);
     case 96: return run_bwd<96, 96, true>(p, s, ws);
     case 128: return run_bwd<128, 128, true>(p, s, ws);
+    default: return VDS_ERR_UNSUPPORTED;
+  }
+}
+
+// frame-causal self-attention: the same checks, then the CAUSAL instances (frames == NULL: the plain calls, unchanged)
+static int fc_check(const vds_attn_args* a, const vds_mod_groups* f) {
+  if (a->Lq != a->Lk || a->kv_pad_ones == 2) return VDS_ERR_ARG;
+  if (f->lead < 0 || f->period < 1 || a->Lq < f->lead || (a->Lq - f->lead) % f->period != 0) return VDS_ERR_ARG;
+  if (a->Lq > (1 << 21)) return VDS_ERR_UNSUPPORTED;  // FcMap: the fp32 quotient is exact below 2^21 rows
+  return VDS_OK;
+}
+
+extern "C" int vds_attn_fwd_causal(const vds_attn_args* a, const vds_mod_groups* frames, vds_stream_t stream) {
+  if (!a) return VDS_ERR_ARG;
+  if (!frames) return vds_attn_fwd(a, stream);
+  if (!a->q || !a->k || !a->v || !a->o || !a->lse || a->Lq <= 0 || a->Lk <= 0) return VDS_ERR_ARG;
+  if (!strides_ok(a, false)) return VDS_ERR_ARG;
+  if (const int e = fc_check(a, frames)) return e;
+  AttnP p = to_p(a);
+  p.fc_lead = frames->lead;
+  p.fc_period = frames->period;
+  hipStream_t s = (hipStream_t)stream;
+  switch (kernel_instance(a->head_dim)) {
+    case 32: return run_fwd<32, 32, false, true>(p, s);
+    case 64: return run_fwd<64, 64, false, true>(p, s);
+    case 80: return run_fwd<96, 80, false, true>(p, s);
+    case 96: return run_fwd<96, 96, false, true>(p, s);
+    case 128: return run_fwd<128, 128, false, true>(p, s);
+    default: return VDS_ERR_UNSUPPORTED;
+  }
+}
+
+extern "C" int vds_attn_bwd_causal(const vds_attn_args* a, const vds_mod_groups* frames, vds_stream_t stream) {
+  if (!a) return VDS_ERR_ARG;
+  if (!frames) return vds_attn_bwd(a, stream);
+  if (!a->q || !a->k || !a->v || !a->o || !a->lse || !a->d_o || !a->dq || !a->dk || !a->dv || !a->delta || a->Lq <= 0 ||
+      a->Lk <= 0)
+    return VDS_ERR_ARG;
+  if (!strides_ok(a, true)) return VDS_ERR_ARG;
+  if (const int e = fc_check(a, frames)) return e;
+  AttnP p = to_p(a);
+  p.fc_lead = frames->lead;
+  p.fc_period = frames->period;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t ws = a->ws_floats > 0 ? (size_t)a->ws_floats : (size_t)2 * a->B * a->H * a->Lq;
+  switch (kernel_instance(a->head_dim)) {
+    case 32: return run_bwd<32, 32, false, true>(p, s, ws);
+    case 64: return run_bwd<64, 64, false, true>(p, s, ws);
+    case 80: return run_bwd<96, 80, false, true>(p, s, ws);
+    case 96: return run_bwd<96, 96, false, true>(p, s, ws);
+    case 128: return run_bwd<128, 128, false, true>(p, s, ws);
     default: return VDS_ERR_UNSUPPORTED;
   }
 }

@@ -341,13 +341,17 @@ _FP8_QK_NORM = ("qk_norm is not implemented for the fp8 attention producers (vds
                 "call enable_fp8(attention=False) to keep the attention products on the bf16 kernels")
 
 
+_FP8_FRAME_CAUSAL = ("frame_causal is not implemented for the fp8 attention kernels (they have no masked instance): "
+                     "call enable_fp8(attention=False) to keep the attention products on the bf16 kernels")
+
+
 class DiTBlock(nn.Module):
     """model.py:44-167.  `forward(x, context, c, v_0=None, rope=None) -> (x, v)` has the reference's signature and
     runs the block's HIP kernel sequence (`_fwd`) under one autograd node whose backward is `_bwd`; DiT.forward
     drives the same two methods for all blocks inside its own whole-model node."""
 
     def __init__(self, hidden_size, cross_attn_input_size, num_heads, mlp_ratio=4.0, qkv_bias=True,
-                 residual_v=False, qk_norm=False):
+                 residual_v=False, *, frame_causal=False, qk_norm=False):
         super().__init__()
         self.hidden_size, self.num_heads = hidden_size, num_heads
         self.head_dim = hidden_size // num_heads
@@ -355,6 +359,11 @@ class DiTBlock(nn.Module):
         # QK-norm (no reference counterpart): a weightless RMSNorm on every head row of the self-attention's q and k
         # before the rotation, inside the qkv / RoPE kernels (ops.qkv_rope_norm_fwd / _bwd).  No parameter.
         self.qk_norm = bool(qk_norm)
+        # frame-causal self-attention (no reference counterpart): row q attends row k iff ops.mod_group_of(k) <=
+        # ops.mod_group_of(q) for the frames = (lead, period) of the call -- the masked attention kernels
+        # (ops.attn_fwd / attn_bwd, frames=).  Every other kernel of the block works per row and the cross-attention only
+        # reads the text, so the block (and the model) is then causal over token-frames.  No parameter.
+        self.frame_causal = bool(frame_causal)
         self.norm1 = RMSNorm(hidden_size, trainable=qkv_bias)
         self.qkv = _Linear(hidden_size, hidden_size * 3, bias=qkv_bias)
         self.attn_proj = _Linear(hidden_size, hidden_size, bias=False)
@@ -395,12 +404,23 @@ class DiTBlock(nn.Module):
         self._own_group = g
         return g, ""
 
-    def forward(self, x, context, c, v_0=None, rope=None, context_lens=None):
+    def _check_frames(self, frames, L):
+        if not self.frame_causal:
+            if frames is not None:
+                raise ValueError("DiTBlock: frames given to a block built without frame_causal=True")
+            return None
+        if frames is None:
+            raise ValueError("DiTBlock: a frame_causal block needs frames=(lead, period), the row groups of its sequence")
+        return ops.check_mod_groups(frames, L)
+
+    def forward(self, x, context, c, v_0=None, rope=None, context_lens=None, frames=None):
         """x [B,L,D], context [B,Lc,Cc] (None without cross-attention), c [B,D] conditioning, v_0 [B,H,L,hd] (block
         0's v; None in block 0), rope = (cos, sin) each [1,1,L,hd/2] or None -> (x [B,L,D], v [B,H,L,hd]) in bf16.
         Gradients flow to x, c, v_0 and the block's parameters (fp32 .grad); `context` is data (the frozen text
         encoder's output, train.py:70-87) and gets none.  context_lens (see DiT.forward): sample b attends its first
-        context_lens[b] context rows only."""
+        context_lens[b] context rows only.  frames = (lead, period): required by (and only by) a frame_causal block --
+        the first `lead` rows are register rows, row l >= lead belongs to token-frame (l - lead) % period."""
+        frames = self._check_frames(frames, x.shape[1])
         kv_lens = None
         if context_lens is not None:
             if context is None:
@@ -412,11 +432,11 @@ class DiTBlock(nn.Module):
         params = [p for p in self.parameters()]
         save = torch.is_grad_enabled()  # (always off inside an autograd.Function's forward: decided here)
         return _BlockFunction.apply(self, save, x, context, c, v_0, rope[0] if rope is not None else None,
-                                    rope[1] if rope is not None else None, kv_lens, *params)
+                                    rope[1] if rope is not None else None, kv_lens, frames, *params)
 
     # ---- the kernel sequence of one block (used by DiT's whole-model autograd node and by `forward`) ----
     def _fwd(self, G, pre, X, ctx2d, cvec, v0, cos, sin, B, L, Lc, save, fp8=None, mod=None, keep=None, replay=None,
-             kv_lens=None, groups=None):
+             kv_lens=None, groups=None, frames=None):
         """X [B*L, D] bf16 token buffer -> (X_out, v [B,H,L,hdp], saved).  G: the FlatGroup holding this block's
         parameters under the name prefix `pre`; cvec f32 [B, D]; v0: block 0's v in the padded head-major layout
         or None; cos / sin f32 [L, hd/2]; fp8 = (AmaxHistory | None, block index) when the fp8 linears are on.
@@ -426,14 +446,18 @@ class DiTBlock(nn.Module):
         new residual stream after the MLP is not stored (X_out is None: the next block's kept X already holds it).
         kv_lens: int32 device tensor [B] or None -- per-sample key counts of the cross-attention (bf16 kernels only).
         groups: None, or (lead, period) -- per-frame timesteps: cvec is f32 [B*G, D] and the modulation table [B*G, 9D],
-        G = 1 + period, row b*G + g for modulation group g of sample b (bf16 kernels only)."""
+        G = 1 + period, row b*G + g for modulation group g of sample b (bf16 kernels only).
+        frames: (lead, period) of a frame_causal block's masked self-attention (bf16 attention kernels only), else None."""
         D, H, hd = self.hidden_size, self.num_heads, self.head_dim
+        frames = self._check_frames(frames, L)
         hdp = HDP_OF[hd]
         use_fp8 = fp8 is not None
         if kv_lens is not None and use_fp8 and fp8[2] >= 2:
             raise NotImplementedError(_FP8_CONTEXT_LENS)
         if self.qk_norm and use_fp8 and fp8[2]:
             raise NotImplementedError(_FP8_QK_NORM)
+        if frames is not None and use_fp8 and fp8[2]:
+            raise NotImplementedError(_FP8_FRAME_CAUSAL)
         if groups is not None and use_fp8:
             raise NotImplementedError(_FP8_FRAME_TIMESTEPS)
         if use_fp8 and (keep is not None or replay is not None):
@@ -496,7 +520,7 @@ class DiTBlock(nn.Module):
             q, k, v = rope_fwd(qkv, cos, sin, v0 if mix else None, W("lambda_param") if mix else None, B, L, H, hd, hdp)
             if not kept_attn:
                 ops.attn_fwd(q[..., :hd], k[..., :hd], v[..., :hd], ops.heads_view(attn, B, L, H, hd), lse1,
-                             kv_pad_ones=(hdp - hd) >= 8)
+                             kv_pad_ones=(hdp - hd) >= 8, frames=frames)
             if a8_on and save:  # first steps: record the amax the next step quantises with
                 for j, t in enumerate((q, k, v)):
                     ops.absmax(t.view(B * H * L, hdp)[:, :hd], fp8_hist.cur(F8.ROWS * i + F8.ROW_Q + j))
@@ -615,6 +639,7 @@ class DiTBlock(nn.Module):
             if a8:
                 bs.v = None  # (block 0's bf16 v lives on as v_0; the backward contracts the fp8 copies)
             bs.mix, bs.has_cross = mix, has_cross
+            bs.frames = frames
             if has_cross:
                 bs.xn2, bs.rstd2, bs.qc, bs.ckv, bs.catt, bs.lse2, bs.y_ca = xn2, rstd2, qc, ckv, catt, lse2, y_ca
                 bs.c8, bs.c8_on, bs.qc8, bs.kc8, bs.vc8, bs.deqc = c8, c8_on, qc8, kc8, vc8, deqc
@@ -786,7 +811,7 @@ class DiTBlock(nn.Module):
             delta = torch.empty(2, B, H, L, dtype=f32, device=dev)
             ops.attn_bwd(bs.q[..., :hd], bs.k[..., :hd], bs.v[..., :hd], ops.heads_view(bs.attn, B, L, H, hd), bs.lse1,
                          ops.heads_view(dattn, B, L, H, hd), dq[..., :hd], dk[..., :hd], dv[..., :hd], delta,
-                         kv_pad_ones=(hdp - hd) >= 8)
+                         kv_pad_ones=(hdp - hd) >= 8, frames=bs.frames)
             if bs.a8_on:
                 ops.absmax(dattn, fp8_hist.cur(F8.ROWS * i + F8.ROW_DO))
         defer = getattr(sv, "dv_terms", None)  # DiT.backward: [(dv, lambda)] of the mixed blocks, summed at block 0
@@ -907,9 +932,14 @@ def grad_arena(groups, device):
 class DiT(nn.Module):
     def __init__(self, in_channels=4, patch_size=2, time_patch_size=2, hidden_size=1152, depth=28, num_heads=16,
                  mlp_ratio=4.0, cross_attn_input_size=128, residual_v=False, train_bias_and_rms=True,
-                 use_rope=True, qk_norm=False):
+                 use_rope=True, *, frame_causal=False, qk_norm=False):
         super().__init__()
         self.qk_norm = bool(qk_norm)  # see DiTBlock: parameter-free RMSNorm of q and k in the self-attention
+        # see DiTBlock: every self-attention runs with frames = (N_REG, t) -- the registers attend each other, a token of
+        # frame f the registers and frames 0 .. f.  The model is then causal over token-frames in the LATENTS; with
+        # per-frame timesteps the registers are still modulated from the row maximum of the timesteps, so it is not causal
+        # in the noise levels of later frames.
+        self.frame_causal = bool(frame_causal)
         self.in_channels = self.out_channels = in_channels
         self.patch_size, self.time_patch_size = patch_size, time_patch_size
         self.hidden_size, self.num_heads, self.depth, self.mlp_ratio = hidden_size, num_heads, depth, mlp_ratio
@@ -937,7 +967,7 @@ class DiT(nn.Module):
         self.blocks = nn.ModuleList([
             DiTBlock(hidden_size=hidden_size, num_heads=num_heads, mlp_ratio=mlp_ratio,
                      cross_attn_input_size=cross_attn_input_size, residual_v=residual_v,
-                     qkv_bias=train_bias_and_rms, qk_norm=qk_norm) for _ in range(depth)])
+                     qkv_bias=train_bias_and_rms, qk_norm=qk_norm, frame_causal=frame_causal) for _ in range(depth)])
         self.final_modulation = nn.Sequential(_Act("silu"), _Linear(hidden_size, 2 * hidden_size, bias=True))
         self.final_norm = RMSNorm(hidden_size, trainable=train_bias_and_rms)
         self.final_proj = _Linear(hidden_size, patch_size * patch_size * time_patch_size * self.out_channels)
@@ -966,11 +996,14 @@ class DiT(nn.Module):
         they are 1.1 % of the step faster at the C3b shape and leave the 200-step loss curve where it was, at a
         cross-attention output 4.6 % instead of 0.3 % from the fp32 oracle.
         A model built with qk_norm=True has no fp8 attention producer: `attention=True` raises NotImplementedError there
-        (enable_fp8(attention=False) runs its linears in fp8 and the normed attention in bf16)."""
+        (enable_fp8(attention=False) runs its linears in fp8 and the normed attention in bf16).  The same
+        holds for a model built with frame_causal=True: the fp8 attention kernels have no masked instance."""
         if on and self.recompute != "none":
             raise ValueError(_FP8_RECOMPUTE)
         if on and attention and self.qk_norm:
             raise NotImplementedError(_FP8_QK_NORM)
+        if on and attention and self.frame_causal:
+            raise NotImplementedError(_FP8_FRAME_CAUSAL)
         self.fp8 = bool(on)
         self.fp8_attn = (2 if cross_attention else 1) if (on and attention) else 0  # 0 none, 1 self, 2 self + cross
         self.fp8_lin = bool(on and all_linears)  # attn_proj, q_cross, context_kv, cross_proj too (qkv / MLP always)
@@ -1155,6 +1188,7 @@ class DiT(nn.Module):
         # per-frame timesteps [B, t]: the conditioning path runs on B*G rows, G = 1 + t modulation groups per sample --
         # group 0 (the register rows) on the sample's noisiest frame, group 1 + f (the rows of token-frame f: the token
         # order is (h w t), t fastest) on timesteps[b, f] -- and every modulated kernel looks its row up per group
+        frames = (N_REG, t) if self.frame_causal else None  # [B] and [B, t] timesteps alike
         groups = None
         if timesteps.dim() == 2:
             groups = (N_REG, t)
@@ -1169,6 +1203,7 @@ class DiT(nn.Module):
             sv.ctx2d = ctx2d
             sv.kv_lens = kv_lens
             sv.groups = groups
+            sv.frames = frames
             sv.blocks = []
 
         # adaLN modulation of every block in ONE launch (K4 of SURVEY 2.3): all blocks read the same conditioning vector.
@@ -1188,7 +1223,7 @@ class DiT(nn.Module):
                                            save and keep is None,
                                            (self._fp8_hist, i, self.fp8_attn, self.fp8_lin, q_ctx) if self.fp8 else None,
                                            mods[i] if mods is not None else None, keep=keep, kv_lens=kv_lens,
-                                           groups=groups)
+                                           groups=groups, frames=frames)
             if v0 is None:
                 v0 = v
             if save:
@@ -1267,7 +1302,7 @@ class DiT(nn.Module):
                 # block-0 v (sv.v0 stays the v handed out in the first forward; block 0 makes its own copy again)
                 _, _, bs = self.blocks[i]._fwd(self.block_group(i), f"blocks.{i}.", bs.X, sv.ctx2d, sv.cvec,
                                                sv.v0 if i > 0 else None, sv.cos, sv.sin, B, L, Lc, True, None, bs.mod,
-                                               replay=bs, kv_lens=sv.kv_lens, groups=groups)
+                                               replay=bs, kv_lens=sv.kv_lens, groups=groups, frames=sv.frames)
             dX = self.blocks[i]._bwd(self.block_group(i), f"blocks.{i}.", bs, dX, sv, dc, dv0, B, L, Lc,
                                      i == 0, (self._fp8_hist, i, self.fp8_attn, self.fp8_lin, sv.q_ctx) if self.fp8 else None,
                                      dmods[i] if dmods is not None else None, groups=groups)
@@ -1403,7 +1438,7 @@ class _BlockFunction(torch.autograd.Function):
     """DiTBlock.forward as one autograd node (see DiTBlock.forward for the contract)."""
 
     @staticmethod
-    def forward(ctx, block, need, x, context, c, v_0, cos, sin, kv_lens, *params):
+    def forward(ctx, block, need, x, context, c, v_0, cos, sin, kv_lens, frames, *params):
         B, L, D = x.shape
         H, hd = block.num_heads, block.head_dim
         hdp = HDP_OF[hd]
@@ -1434,7 +1469,7 @@ class _BlockFunction(torch.autograd.Function):
             else:
                 v0p = torch.zeros(B, H, L, hdp, dtype=bf16, device=dev)
                 v0p[..., :hd].copy_(v_0)
-        Xo, v, bs = block._fwd(G, pre, X, ctx2d, cvec, v0p, cos2, sin2, B, L, Lc, need, kv_lens=kv_lens)
+        Xo, v, bs = block._fwd(G, pre, X, ctx2d, cvec, v0p, cos2, sin2, B, L, Lc, need, kv_lens=kv_lens, frames=frames)
         if need:
             sv = _Saved()
             sv.cos, sv.sin, sv.v0, sv.ctx2d, sv.cvec, sv.kv_lens = cos2, sin2, v0p, ctx2d, cvec, kv_lens
@@ -1467,7 +1502,7 @@ class _BlockFunction(torch.autograd.Function):
         G.add_held(held)
         gv0 = dv0[..., :hd].to(v0dt) if (bs.mix and v0dt is not None) else None
         n_params = len(list(block.parameters()))
-        return (None, None, dX0.view(B, L, D).to(xdt), None, dc.to(cdt), gv0, None, None, None) + (None,) * n_params
+        return (None, None, dX0.view(B, L, D).to(xdt), None, dc.to(cdt), gv0, None, None, None, None) + (None,) * n_params
 
 
 class _DiTFunction(torch.autograd.Function):

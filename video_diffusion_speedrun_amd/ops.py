@@ -265,12 +265,25 @@ def _kv_lens_ptr(kv_lens, B: int) -> int:
     return kv_lens.data_ptr()
 
 
-def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None):
+def _frames(frames, kv_lens, Lq: int, Lk: int):
+    """vds_mod_groups of a frame-causal self-attention call: (lead, period) checked against the sequence, or ValueError"""
+    if kv_lens is not None:
+        raise ValueError("attention: frames (frame-causal self-attention) and kv_lens (cross-attention) exclude each other")
+    if Lq != Lk:
+        raise ValueError(f"frame-causal attention is self-attention: Lq = {Lq} != Lk = {Lk}")
+    lead, period = check_mod_groups(frames, Lq)
+    return C.byref(_lib.ModGroups(lead, period))
+
+
+def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=None):
     """q [B,H,Lq,hd], k/v [B,H,Lk,hd], o [B,H,Lq,hd] strided views (last dim contiguous); lse f32 [B,H,Lq].
     kv_pad_ones: k / v are views into qkv_rope_fwd outputs whose pad carries the ones columns.
-    kv_lens: int32 CUDA tensor [B]; sample b attends its first kv_lens[b] keys only (vds_attn_fwd_kvlen)."""
+    kv_lens: int32 CUDA tensor [B]; sample b attends its first kv_lens[b] keys only (vds_attn_fwd_kvlen).
+    frames: (lead, period) -- frame-causal self-attention: row q attends row k iff mod_group_of(k) <= mod_group_of(q)
+    (vds_attn_fwd_causal); not together with kv_lens."""
     B, H, Lq, hd = q.shape
     Lk = k.shape[2]
+    fr = _frames(frames, kv_lens, Lq, Lk) if frames is not None else None
     a = AttnArgs()
     a.B, a.H, a.Lq, a.Lk, a.head_dim = B, H, Lq, Lk, hd
     a.q, (a.q_sb, a.q_sh, a.q_sl) = _p(q), _st(q)
@@ -279,7 +292,10 @@ def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None):
     a.o, (a.o_sb, a.o_sh, a.o_sl) = _p(o), _st(o)
     a.lse = _p(lse)
     a.kv_pad_ones = int(kv_pad_ones)  # (True = 1: self-attention layout; 2: ones in k / v only, cross-attention)
-    if kv_lens is None:
+    if fr is not None:
+        check(_lib.load().vds_attn_fwd_causal(C.byref(a), fr, _stream()),
+              f"vds_attn_fwd_causal(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)})")
+    elif kv_lens is None:
         check(_lib.load().vds_attn_fwd(C.byref(a), _stream()), f"vds_attn_fwd(B={B},H={H},Lq={Lq},Lk={Lk},hd={hd})")
     else:
         check(_lib.load().vds_attn_fwd_kvlen(C.byref(a), _kv_lens_ptr(kv_lens, B), _stream()),
@@ -304,13 +320,15 @@ def attn_bwd_workspace_floats(B, H, Lq, Lk, hd, kv_pad_ones: bool = False) -> in
     return _lib.load().vds_attn_bwd_workspace_bytes(C.byref(a)) // 4
 
 
-def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = False, kv_lens=None):
+def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = False, kv_lens=None, frames=None):
     """delta: f32 workspace of 2*B*H*Lq elements (rowsum(dO*O), then lse*log2 e); allocated here when None
     (size from vds_attn_bwd_workspace_bytes).
-    kv_lens: as in attn_fwd; rows kv_lens[b].. of dk[b] / dv[b] are written as zeros (vds_attn_bwd_kvlen)."""
+    kv_lens: as in attn_fwd; rows kv_lens[b].. of dk[b] / dv[b] are written as zeros (vds_attn_bwd_kvlen).
+    frames: as in attn_fwd; a dk / dv row sums over the queries that attend it (vds_attn_bwd_causal)."""
     B, H, Lq, hd = q.shape
     assert lse.is_contiguous()
     Lk = k.shape[2]
+    fr = _frames(frames, kv_lens, Lq, Lk) if frames is not None else None
     a = AttnArgs()
     a.B, a.H, a.Lq, a.Lk, a.head_dim = B, H, Lq, Lk, hd
     a.kv_pad_ones = int(kv_pad_ones)
@@ -329,7 +347,10 @@ def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = Fa
     a.dv, (a.dv_sb, a.dv_sh, a.dv_sl) = _p(dv), _st(dv)
     a.delta = _p(delta)
     a.kv_pad_ones = int(kv_pad_ones)
-    if kv_lens is None:
+    if fr is not None:
+        check(_lib.load().vds_attn_bwd_causal(C.byref(a), fr, _stream()),
+              f"vds_attn_bwd_causal(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)})")
+    elif kv_lens is None:
         check(_lib.load().vds_attn_bwd(C.byref(a), _stream()), f"vds_attn_bwd(B={B},H={H},Lq={Lq},Lk={Lk},hd={hd})")
     else:
         check(_lib.load().vds_attn_bwd_kvlen(C.byref(a), _kv_lens_ptr(kv_lens, B), _stream()),

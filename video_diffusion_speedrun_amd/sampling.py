@@ -36,8 +36,18 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
                      inference_steps: int = 50, cfg_scale: float = 6.0, height: int = 512, width: int = 512,
                      seed: int = 42, latents: Optional[torch.Tensor] = None,
                      rope_starts: Optional[Sequence[Tuple[int, int, int]]] = None, device="cuda",
-                     prompt_lens=None, negative_lens=None, cond_latents: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """cond_latents ([1,16,Tc,h,w], Tc a multiple of the model's time_patch_size; image-to-video, video extension): the
+                     prompt_lens=None, negative_lens=None, cond_latents: Optional[torch.Tensor] = None,
+                     rollout_frames: Optional[int] = None) -> torch.Tensor:
+    """rollout_frames = k >= 1 (frame rollout): after any cond_latents frames the remaining token-frames are generated k
+    at a time, in order.  Every chunk runs the whole `inference_steps` Euler loop with per-frame timesteps -- 0 for the
+    frames before the chunk, the step's t for the chunk's frames, 1.0 for the frames after it (still the initial noise)
+    -- and after every Euler step the frames outside the chunk are put back, in the latents and in the accumulator, to
+    the values they had when the chunk started.  Cost: (number of chunks) x inference_steps model calls (x the guided
+    pair); there is no KV cache.  `rope_starts` then lists the offsets of all those calls, chunk after chunk.  Runs on
+    any model; on a DiT built with frame_causal=True a finished chunk does not depend on the noise of later frames.
+    None: the loop below, call for call.
+
+    cond_latents ([1,16,Tc,h,w], Tc a multiple of the model's time_patch_size; image-to-video, video extension): the
     first Tc latent frames are held at these values -- their token-frames are given t = 0 in every model call (per-frame
     timesteps, DiT.forward), the other frames the step's t, and the frames are written back into the latents and the
     accumulator after every Euler step.  None: the loop below is the reference's.
@@ -80,6 +90,14 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
     acc = lat.to(f32)
     call = 0
     n_cond = 0
+    k_roll = 0
+    if rollout_frames is not None:
+        if isinstance(rollout_frames, bool) or int(rollout_frames) != rollout_frames or int(rollout_frames) < 1:
+            raise ValueError(f"rollout_frames must be an integer >= 1 (token-frames per chunk) or None, got {rollout_frames!r}")
+        k_roll = int(rollout_frames)
+        if lat.shape[2] % model.time_patch_size != 0:
+            raise ValueError(f"frame rollout: {lat.shape[2]} latent frames are no multiple of time_patch_size "
+                             f"({model.time_patch_size})")
     if cond_latents is not None:
         pt = model.time_patch_size
         Tc = cond_latents.shape[2] if cond_latents.dim() == 5 else -1
@@ -104,30 +122,57 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
         if not n_cond:
             return tt
         return torch.where(is_cond[None, :], torch.zeros((), dtype=bf16, device=dev), tt[:, None]).contiguous()
-    for i in range(inference_steps, 0, -1):
-        t, t_next = shifted_times(i, inference_steps)
-        dt = t - t_next
-        if guided:
-            s_c = tuple(rope_starts[call]) if rope_starts is not None else None
-            s_u = tuple(rope_starts[call + 1]) if rope_starts is not None else None
-            call += 2
-            if s_c == s_u:  # one batched forward: [cond, uncond]
-                tt = times(t, 2)
-                out = model(torch.cat([lat, lat]), torch.cat([prompt_embeds, negative_embeds.to(dev, bf16)]), tt,
-                            **({"rope_start": s_c} if s_c is not None else {}),
-                            **({} if lens_c is None else {"context_lens": lens_cu}))
-                cond, uncond = out[0:1].contiguous(), out[1:2].contiguous()
+
+    def euler_loop(times, restore):
+        """one pass of `inference_steps` Euler steps; times(t, nb) makes the timesteps of a model call, restore() (or
+        None) runs after every step"""
+        nonlocal call
+        for i in range(inference_steps, 0, -1):
+            t, t_next = shifted_times(i, inference_steps)
+            dt = t - t_next
+            if guided:
+                s_c = tuple(rope_starts[call]) if rope_starts is not None else None
+                s_u = tuple(rope_starts[call + 1]) if rope_starts is not None else None
+                call += 2
+                if s_c == s_u:  # one batched forward: [cond, uncond]
+                    tt = times(t, 2)
+                    out = model(torch.cat([lat, lat]), torch.cat([prompt_embeds, negative_embeds.to(dev, bf16)]), tt,
+                                **({"rope_start": s_c} if s_c is not None else {}),
+                                **({} if lens_c is None else {"context_lens": lens_cu}))
+                    cond, uncond = out[0:1].contiguous(), out[1:2].contiguous()
+                else:
+                    tt = times(t, 1)
+                    cond = model(lat, prompt_embeds, tt, rope_start=s_c, **kw_c)
+                    uncond = model(lat, negative_embeds.to(dev, bf16), tt, rope_start=s_u, **kw_u)
             else:
                 tt = times(t, 1)
-                cond = model(lat, prompt_embeds, tt, rope_start=s_c, **kw_c)
-                uncond = model(lat, negative_embeds.to(dev, bf16), tt, rope_start=s_u, **kw_u)
-        else:
-            tt = times(t, 1)
-            s_c = tuple(rope_starts[call]) if rope_starts is not None else None
-            call += 1
-            cond = model(lat, prompt_embeds, tt, **({"rope_start": s_c} if s_c is not None else {}), **kw_c)
-            uncond = None
-        ops.cfg_euler_step(cond, uncond, acc, lat, cfg_scale, dt)
-        if n_cond:
-            impose()
+                s_c = tuple(rope_starts[call]) if rope_starts is not None else None
+                call += 1
+                cond = model(lat, prompt_embeds, tt, **({"rope_start": s_c} if s_c is not None else {}), **kw_c)
+                uncond = None
+            ops.cfg_euler_step(cond, uncond, acc, lat, cfg_scale, dt)
+            if restore is not None:
+                restore()
+
+    if rollout_frames is None:
+        euler_loop(times, impose if n_cond else None)
+        return acc
+
+    # frame rollout: chunk after chunk of k token-frames, each with its own full Euler pass
+    pt = model.time_patch_size
+    n_frames = lat.shape[2] // pt
+    frame = torch.arange(n_frames, device=dev)
+    for f0 in range(n_cond, n_frames, k_roll):
+        f1 = min(f0 + k_roll, n_frames)
+        acc0, lat0 = acc.clone(), lat.clone()  # the finished frames before the chunk, the initial noise after it
+
+        def chunk_times(t, nb, f0=f0, f1=f1):
+            row = torch.where(frame < f0, 0.0, torch.where(frame < f1, float(t), 1.0)).to(bf16)
+            return row[None, :].expand(nb, n_frames).contiguous()
+
+        def restore(f0=f0, f1=f1, acc0=acc0, lat0=lat0):
+            for cur, old in ((acc, acc0), (lat, lat0)):
+                cur[:, :, :f0 * pt] = old[:, :, :f0 * pt]
+                cur[:, :, f1 * pt:] = old[:, :, f1 * pt:]
+        euler_loop(chunk_times, restore)
     return acc
