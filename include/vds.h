@@ -273,6 +273,17 @@ typedef struct {
  * unchanged. */
 int vds_attn_fwd_causal(const vds_attn_args* args, const vds_mod_groups* frames, vds_stream_t stream);
 int vds_attn_bwd_causal(const vds_attn_args* args, const vds_mod_groups* frames, vds_stream_t stream);
+/* Frame-causal forward with a past (inference with a frame KV cache).  The queries are the Lq = lead + n * period rows of
+ * one model call (the lead rows, then the call's token rows: the (lead, period) map above, validated against Lq).  The
+ * keys and values are Lk = Lq + past rows: j < lead the call's lead rows, lead <= j < lead + past the past (token rows of
+ * finished frames, in any order), j >= lead + past the call's own token rows (key j belongs to query row j - past).  A
+ * lead query attends the lead keys only; a token query attends the lead keys, every past key and own key j iff
+ * group(j - past) <= group(query).  Key 0 is attended by every query: no empty row.  A 32-key sub-block that lies wholly
+ * in the past is attended without any mask code by every wave that holds no lead query.  `past` travels by value in the
+ * kernel arguments.  past == 0 forwards to vds_attn_fwd_causal (the same bits); past < 0, frames == NULL with past != 0,
+ * Lk != Lq + past or kv_pad_ones == 2: VDS_ERR_ARG; Lk > 2^21: VDS_ERR_UNSUPPORTED.  kv_pad_ones 0 and 1, every head dim
+ * of the dispatcher and every vds_attn_set_variant setting have an instance.  Forward only. */
+int vds_attn_fwd_causal_past(const vds_attn_args* args, const vds_mod_groups* frames, int32_t past, vds_stream_t stream);
 /* vds_rmsnorm_mod_fwd with mod f32 [B*G, ldmod]: the same arithmetic per row, y / rstd bit-identical to the per-sample
  * call run on the rows of one group with that group's mod row.  Every form of the dispatcher is covered. */
 int vds_rmsnorm_mod_fwd_grouped(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod,
@@ -339,6 +350,18 @@ int vds_qkv_rope_bwd(const void* dq, const void* dk, const void* dv, const float
 int vds_qkv_rope_norm_fwd(const void* qkv, const float* cosb, const float* sinb, const void* v0,
                           const void* lam, void* q, void* k, void* v, int32_t B, int32_t L, int32_t H,
                           int32_t hd, int32_t hdp, float eps, vds_stream_t stream);
+/* Cache forms of the two forwards (inference with a frame KV cache): q as above; the k and v rows of token l go to
+ * k / v + b * kv_sb + h * kv_sh + (l < lead ? l : l + past) * kv_sl (strides in elements, multiples of 4, kv_sl >= hdp):
+ * their place in a [lead rows | past rows | this call's rows] cache buffer.  v0 (block 0's v, residual-V) is read through
+ * the same strides and row map.  Same arithmetic, rounding, pad and ones columns as the plain forms (element-wise
+ * kernel).  lead < 0, lead > L or past < 0: VDS_ERR_ARG. */
+int vds_qkv_rope_fwd_cache(const void* qkv, const float* cosb, const float* sinb, const void* v0, const void* lam,
+                           void* q, void* k, void* v, int64_t kv_sb, int64_t kv_sh, int64_t kv_sl, int32_t lead,
+                           int32_t past, int32_t B, int32_t L, int32_t H, int32_t hd, int32_t hdp, vds_stream_t stream);
+int vds_qkv_rope_norm_fwd_cache(const void* qkv, const float* cosb, const float* sinb, const void* v0, const void* lam,
+                                void* q, void* k, void* v, int64_t kv_sb, int64_t kv_sh, int64_t kv_sl, int32_t lead,
+                                int32_t past, int32_t B, int32_t L, int32_t H, int32_t hd, int32_t hdp, float eps,
+                                vds_stream_t stream);
 int vds_qkv_rope_norm_bwd(const void* dq, const void* dk, const void* dv, const float* cosb,
                           const float* sinb, const void* qkv_raw, const void* v0, const void* lam,
                           float* dv0_acc, float* dlam, void* dqkv, int32_t mix, int32_t add_dv0, int32_t B,

@@ -9,7 +9,7 @@ __all__ = ["DiT", "DiTBlock", "apply_fsdp", "forward", "MuAdamW", "generate_late
 
 
 def __getattr__(name):  # lazy: `import video_diffusion_speedrun_amd` itself stays light
-    if name in ("DiT", "DiTBlock", "PatchEmbed", "RMSNorm", "ThreeDimRotary", "timestep_embedding"):
+    if name in ("DiT", "DiTBlock", "PatchEmbed", "RMSNorm", "ThreeDimRotary", "timestep_embedding", "FrameKVCache"):
         from . import model
         return getattr(model, name)
     if name in ("apply_fsdp", "get_device_mesh"):

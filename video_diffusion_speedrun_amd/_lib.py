@@ -96,6 +96,7 @@ SIGNATURES = {
     "vds_attn_bwd_kvlen": [C.POINTER(AttnArgs), c_vp, c_vp],
     "vds_attn_fwd_causal": [C.POINTER(AttnArgs), c_vp, c_vp],
     "vds_attn_bwd_causal": [C.POINTER(AttnArgs), c_vp, c_vp],
+    "vds_attn_fwd_causal_past": [C.POINTER(AttnArgs), c_vp, c_i32, c_vp],
     "vds_attn_set_variant": [c_i32],
     "vds_kv_pad_ones": [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
     "vds_dv0_reduce": [c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
@@ -122,6 +123,10 @@ SIGNATURES = {
                               c_vp],
     "vds_qkv_rope_norm_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
                               c_i32, c_i32, c_i32, c_i32, c_f32, c_vp],
+    "vds_qkv_rope_fwd_cache": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32,
+                               c_i32, c_i32, c_i32, c_i32, c_vp],
+    "vds_qkv_rope_norm_fwd_cache": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32,
+                                    c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp],
     "vds_rope_apply": [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32,
                        c_i32, c_vp],
     "vds_rope_rows": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp,

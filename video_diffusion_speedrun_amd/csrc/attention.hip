@@ -61,6 +61,8 @@ struct AttnP {
   const int* kv_lens;
   // frame-causal map (vds_attn_*_causal): by value, read by the CAUSAL instances of the kernels only
   int fc_lead, fc_period;
+  // cached key rows behind the lead rows (vds_attn_fwd_causal_past): by value, read by the PAST forward instances only
+  int fc_past;
 };
 
 // Keys of sample b.  KVLEN: kv_lens[b] clamped to [0, Lk] -- b is the same for the whole workgroup, so this is one
@@ -109,6 +111,29 @@ __device__ __forceinline__ void fc_fill2(const FcMap& fm, int row0, int f0, int 
     if (xk > f0) s0[r] = fill;
     if (xk > f1) s1[r] = fill;
   }
+}
+// PAST instances (vds_attn_fwd_causal_past): the Lk = Lq + past key rows are [lead rows | past rows | own token rows] and
+// key j is compared as row max(j - past, min(j, lead)) of the query map -- itself for a lead key, `lead` (x = 0, which
+// every token query attends and no lead query does) for a past key, the key's own query row behind the past.
+__device__ __forceinline__ int fc_past_row(const FcMap& fm, int past, int j) { return max(j - past, min(j, fm.lead)); }
+__device__ __forceinline__ void fc_fill_past(const FcMap& fm, int past, int row0, int f, f32x16& s, float fill) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    if (fm.x(fc_past_row(fm, past, row0 + (r & 3) + 8 * (r >> 2))) > f) s[r] = fill;
+}
+__device__ __forceinline__ void fc_fill2_past(const FcMap& fm, int past, int row0, int f0, int f1, f32x16& s0, f32x16& s1,
+                                              float fill) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int xk = fm.x(fc_past_row(fm, past, row0 + (r & 3) + 8 * (r >> 2)));
+    if (xk > f0) s0[r] = fill;
+    if (xk > f1) s1[r] = fill;
+  }
+}
+// the 32 keys from k0 are all past rows and the wave holds no lead query (q0: its first query row): every pair is attended,
+// the mask code is branched around (wave-uniform: k0, q0 and the map are scalars)
+__device__ __forceinline__ bool fc_past_open(const FcMap& fm, int past, int k0, int q0) {
+  return k0 >= fm.lead && k0 + 32 <= fm.lead + past && q0 >= fm.lead;
 }
 // 32x32 accumulators with the QUERY on the registers and the lane's key f = fk: P and dS of the pairs that are not attended
 __device__ __forceinline__ void fc_zero_q(const FcMap& fm, int row0, int f, f32x16& pm, f32x16& ds) {
@@ -401,7 +426,9 @@ struct DmaStage {
 // ragged-tile mask follow that count, and a sample without keys gets O = 0, lse = 0 before anything is staged.
 // CAUSAL (all forward kernels): the frame-causal mask; masked scores become -inf BEFORE the sub-block maximum, so they
 // neither raise the running maximum nor get a nonzero P (their V rows are live, ones columns included).
-template <int HDP, int HDQ, int WPS, bool PIPE, bool KVLEN = false, bool CAUSAL = false>
+// PAST (with CAUSAL, all forward kernels): the keys are [lead | past | own] (fc_past_row); a 32-key sub-block that lies
+// wholly in the past skips the mask in every wave without a lead query.
+template <int HDP, int HDQ, int WPS, bool PIPE, bool KVLEN = false, bool CAUSAL = false, bool PAST = false>
 __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, TILE = 64 * HDP * 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -451,6 +478,7 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   const FcMap fm(p);
   int fcq = 0;
   if constexpr (CAUSAL) fcq = fm.fq(qrow);
+  [[maybe_unused]] const int wq0 = qt * 128 + wave * 32;  // PAST: the wave's first query row
 #pragma unroll
   for (int ks = 0; ks < KSQ; ++ks) retire(qf[ks]);
   VDS_WAIT_VM(0);
@@ -484,7 +512,10 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
           if (j * 64 + 32 + acc_row(r, h) >= Lk) s1[r] = -INFINITY;
         }
       }
-      if constexpr (CAUSAL) {
+      if constexpr (PAST) {
+        if (!fc_past_open(fm, p.fc_past, j * 64, wq0)) fc_fill_past(fm, p.fc_past, j * 64 + 4 * h, fcq, s0, -INFINITY);
+        if (!fc_past_open(fm, p.fc_past, j * 64 + 32, wq0)) fc_fill_past(fm, p.fc_past, j * 64 + 32 + 4 * h, fcq, s1, -INFINITY);
+      } else if constexpr (CAUSAL) {
         fc_fill(fm, j * 64 + 4 * h, fcq, s0, -INFINITY);
         fc_fill(fm, j * 64 + 32 + 4 * h, fcq, s1, -INFINITY);
       }
@@ -513,7 +544,10 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
           for (int r = 0; r < 16; ++r)
             if (j * 64 + kb * 32 + acc_row(r, h) >= Lk) s[r] = -INFINITY;
         }
-        if constexpr (CAUSAL) fc_fill(fm, j * 64 + kb * 32 + 4 * h, fcq, s, -INFINITY);
+        if constexpr (PAST) {
+          if (!fc_past_open(fm, p.fc_past, j * 64 + kb * 32, wq0))
+            fc_fill_past(fm, p.fc_past, j * 64 + kb * 32 + 4 * h, fcq, s, -INFINITY);
+        } else if constexpr (CAUSAL) fc_fill(fm, j * 64 + kb * 32 + 4 * h, fcq, s, -INFINITY);
         bf16x8 pf[2];
         lazy_softmax<NDB>(s, c, m, l, o, pf);
 #pragma unroll
@@ -585,7 +619,7 @@ __device__ __forceinline__ void ones_softmax(f32x16& s, float& m, bf16x8& q_ones
   pf[1] = acc_frag(s, 1);
 }
 
-template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false>
+template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false, bool PAST = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_wide_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, TILE = 64 * HDP * 2;
   static_assert(!ONES || (HDP == 96 && HDQ == 80), "ones columns: head_dim 72 layout");
@@ -657,6 +691,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_wide_kernel(AttnP p) {
   const FcMap fm(p);
   int fcq[2] = {0, 0};
   if constexpr (CAUSAL) { fcq[0] = fm.fq(qrow0); fcq[1] = fm.fq(qrow0 + 32); }
+  [[maybe_unused]] const int wq0 = qt * 256 + wave * 64;  // PAST: the wave's first query row
   VDS_WAIT_VM(0);
   __syncthreads();
 
@@ -693,7 +728,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_wide_kernel(AttnP p) {
       }
       // (the frame mask cannot lean on zero V rows: with ONES too the scores themselves go to -inf, before the maxima --
       // key 0 is attended by every query, so the first sub-block's maximum is finite)
-      if constexpr (CAUSAL) fc_fill2(fm, j * 64 + kb * 32 + 4 * h, fcq[0], fcq[1], s0, s1, -INFINITY);
+      if constexpr (PAST) {
+        if (!fc_past_open(fm, p.fc_past, j * 64 + kb * 32, wq0))
+          fc_fill2_past(fm, p.fc_past, j * 64 + kb * 32 + 4 * h, fcq[0], fcq[1], s0, s1, -INFINITY);
+      } else if constexpr (CAUSAL) fc_fill2(fm, j * 64 + kb * 32 + 4 * h, fcq[0], fcq[1], s0, s1, -INFINITY);
       bf16x8 vfr[2][NDB];
       load_vfrags<HDP, NDB>(vfr, vt, kb * 32, lane);
       bf16x8 p0[2], p1[2];
@@ -1421,7 +1459,7 @@ __device__ __forceinline__ float max_over_lane_groups(float x) {  // max over th
 
 // CAUSAL: a lane holds one query per 16-query block (fq fixed) and its registers walk the keys 16 rb + 4 g + r of the
 // sub-block: x(key) is formed once per register and serves all four query blocks.
-template <int HDP, bool KVLEN = false, bool CAUSAL = false>
+template <int HDP, bool KVLEN = false, bool CAUSAL = false, bool PAST = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
   static_assert(HDP == 96, "head_dim 72 layout (ones columns at 72, 73 / 72, 76)");
   constexpr int KS = HDP / 32, NDB = 5, TILE = 64 * HDP * 2;
@@ -1485,6 +1523,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) fcq[cb] = fm.fq(qrow0 + 16 * cb);
   }
+  [[maybe_unused]] const int wq0 = qt * 256 + wave * 64;  // PAST: the wave's first query row
   VDS_WAIT_VM(0);
   __syncthreads();
 
@@ -1524,7 +1563,19 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
       // to the denominator, whatever exp2 makes of their scores
       // (the frame mask cannot lean on zero V rows: the scores themselves go to -inf, before the maxima -- key 0 is
       // attended by every query, so the first sub-block's maximum is finite)
-      if constexpr (CAUSAL) {
+      if constexpr (PAST) {
+        if (!fc_past_open(fm, p.fc_past, j * 64 + kb * 32, wq0)) {
+#pragma unroll
+          for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int xk = fm.x(fc_past_row(fm, p.fc_past, j * 64 + kb * 32 + rb * 16 + 4 * g + r));
+#pragma unroll
+              for (int cb = 0; cb < NCB; ++cb)
+                if (xk > fcq[cb]) s[rb][cb][r] = -INFINITY;
+            }
+        }
+      } else if constexpr (CAUSAL) {
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -1851,6 +1902,7 @@ AttnP to_p(const vds_attn_args* a) {
   p.kv_lens = nullptr;
   p.fc_lead = 0;
   p.fc_period = 1;
+  p.fc_past = 0;
   const bool wide_on = vdscfg::geti(vdscfg::ATTN_WIDE_STORES) != 0;  // A/B knob
   p.wide_o = wide_on && p.hd > 64 && rows16(p.o, p.o_sb, p.o_sh, p.o_sl);
   p.wide_dq = wide_on && p.hd > 64 && rows16(p.dq, p.dq_sb, p.dq_sh, p.dq_sl);
@@ -1899,15 +1951,17 @@ static int tail_last_for(int L, int tile) {
 // CAUSAL (vds_attn_*_causal): likewise -- the same choices and geometry on the instances that read p.fc_lead / p.fc_period.
 // (The profiler credits a frame-causal call with the unmasked FLOPs: in the (h w t) row order no tile is skipped, so
 // that is the work executed.)
-template <int HDP, int HDQ, bool KVLEN = false, bool CAUSAL = false>
+// PAST (vds_attn_fwd_causal_past): likewise, on the instances that also read p.fc_past; the FLOPs credited are those of
+// all Lq x Lk pairs.
+template <int HDP, int HDQ, bool KVLEN = false, bool CAUSAL = false, bool PAST = false>
 int run_fwd(AttnP p, hipStream_t s) {
   constexpr int LDS = 4 * 64 * HDP * 2;
   static bool once = false;
   if (!once) {
-    set_lds(attn_fwd_kernel<HDP, HDQ, 2, true, KVLEN, CAUSAL>, LDS);
-    if constexpr (HDP <= 96) set_lds(attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN, CAUSAL>, LDS);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd_wide_kernel<HDP, HDQ, true, KVLEN, CAUSAL>, LDS);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd16_kernel<HDP, KVLEN, CAUSAL>, LDS);
+    set_lds(attn_fwd_kernel<HDP, HDQ, 2, true, KVLEN, CAUSAL, PAST>, LDS);
+    if constexpr (HDP <= 96) set_lds(attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN, CAUSAL, PAST>, LDS);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd_wide_kernel<HDP, HDQ, true, KVLEN, CAUSAL, PAST>, LDS);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd16_kernel<HDP, KVLEN, CAUSAL, PAST>, LDS);
     once = true;
   }
   const int wide = vdscfg::geti(vdscfg::ATTN_FWD_WIDE);  // 0 / 1 forces (experiments); 2 (default): head_dim 64 / 72, long query sequences
@@ -1926,7 +1980,7 @@ int run_fwd(AttnP p, hipStream_t s) {
                     2.0 * p.B * p.H * p.hd * (2.0 * p.Lq + 2.0 * p.Lk));
   if constexpr (HDP == 64) {
     if (use_wide) {
-      hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS, s, p);
+      hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN, CAUSAL, PAST>), dim3(grid), dim3(256), LDS, s, p);
       return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
     }
   }
@@ -1937,16 +1991,16 @@ int run_fwd(AttnP p, hipStream_t s) {
         if (p.kv_pad_ones && p.hd == 72) {
           // (round 5 measured a form of this kernel software-pipelined inside the wave: +9.5 % slower, removed in round 6;
           // profiles/r05/attn_fwd_software_pipelined.log)
-          if (attn_variant() & 4) hipLaunchKernelGGL((attn_fwd16_kernel<HDP, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS, s, p);
-          else hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, true, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS, s, p);
+          if (attn_variant() & 4) hipLaunchKernelGGL((attn_fwd16_kernel<HDP, KVLEN, CAUSAL, PAST>), dim3(grid), dim3(256), LDS, s, p);
+          else hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, true, KVLEN, CAUSAL, PAST>), dim3(grid), dim3(256), LDS, s, p);
           done = true;
         }
       }
-      if (!done) hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS, s, p);
+      if (!done) hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN, CAUSAL, PAST>), dim3(grid), dim3(256), LDS, s, p);
       return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
     }
   }
-  hipLaunchKernelGGL((attn_fwd_kernel<HDP, HDQ, 2, true, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS, s, p);
+  hipLaunchKernelGGL((attn_fwd_kernel<HDP, HDQ, 2, true, KVLEN, CAUSAL, PAST>), dim3(grid), dim3(256), LDS, s, p);
   return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
 }
 
@@ -2249,6 +2303,34 @@ extern "C" int vds_attn_bwd_causal(const vds_attn_args* a, const vds_mod_groups*
     case 80: return run_bwd<96, 80, false, true>(p, s, ws);
     case 96: return run_bwd<96, 96, false, true>(p, s, ws);
     case 128: return run_bwd<128, 128, false, true>(p, s, ws);
+    default: return VDS_ERR_UNSUPPORTED;
+  }
+}
+
+// frame-causal forward with a past (the cached rollout): the queries are the Lq rows of one call, the keys
+// [lead rows | past cached rows | the call's own token rows]; see fc_past_row for the mask.  past == 0: the call above.
+extern "C" int vds_attn_fwd_causal_past(const vds_attn_args* a, const vds_mod_groups* frames, int32_t past,
+                                        vds_stream_t stream) {
+  if (!a || past < 0) return VDS_ERR_ARG;
+  if (past == 0) return vds_attn_fwd_causal(a, frames, stream);
+  if (!frames) return VDS_ERR_ARG;
+  if (!a->q || !a->k || !a->v || !a->o || !a->lse || a->Lq <= 0 || a->Lk <= 0) return VDS_ERR_ARG;
+  if (!strides_ok(a, false)) return VDS_ERR_ARG;
+  if ((int64_t)a->Lk != (int64_t)a->Lq + past || a->kv_pad_ones == 2) return VDS_ERR_ARG;
+  if (frames->lead < 0 || frames->period < 1 || a->Lq < frames->lead || (a->Lq - frames->lead) % frames->period != 0)
+    return VDS_ERR_ARG;
+  if (a->Lk > (1 << 21)) return VDS_ERR_UNSUPPORTED;  // FcMap: the fp32 quotient is exact below 2^21 rows
+  AttnP p = to_p(a);
+  p.fc_lead = frames->lead;
+  p.fc_period = frames->period;
+  p.fc_past = past;
+  hipStream_t s = (hipStream_t)stream;
+  switch (kernel_instance(a->head_dim)) {
+    case 32: return run_fwd<32, 32, false, true, true>(p, s);
+    case 64: return run_fwd<64, 64, false, true, true>(p, s);
+    case 80: return run_fwd<96, 80, false, true, true>(p, s);
+    case 96: return run_fwd<96, 96, false, true, true>(p, s);
+    case 128: return run_fwd<128, 128, false, true, true>(p, s);
     default: return VDS_ERR_UNSUPPORTED;
   }
 }

@@ -612,6 +612,96 @@ __global__ __launch_bounds__(256) void qkv_rope_fwd_kernel(const bf16_t* qkv, co
   }
 }
 
+// Cache form of the kernel above (vds_qkv_rope_fwd_cache / vds_qkv_rope_norm_fwd_cache, inference with a frame KV cache):
+// q goes to the contiguous [B,H,L,hdp] as above; the k and v rows of token l go to row (l < lead ? l : l + past) of
+// caller-given buffers with batch / head / row strides (elements) -- their place in the block's cache, so no copy pass runs
+// per model call.  v0 (residual-V: block 0's cache V buffer) is read through the same strides and row map.  Same
+// arithmetic and rounding points.
+template <bool NORM = false>
+__global__ __launch_bounds__(256) void qkv_rope_fwd_cache_kernel(const bf16_t* qkv, const float* cosb, const float* sinb,
+                                                           const bf16_t* v0, const bf16_t* lamp, bf16_t* q,
+                                                           bf16_t* k, bf16_t* v, long kv_sb, long kv_sh, long kv_sl, int lead, int past, int B,
+                                                                 int L, int H, int hd,
+                                                           int hdp, float eps) {
+  const int upt = H * (hd >> 3);
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (long)B * L * upt) return;
+  const long tok = gid / upt;
+  const int u = (int)(gid % upt);
+  const int hq = hd >> 3, hh = u / hq, i = u % hq, half = hd >> 1;
+  const int b = (int)(tok / L), l = (int)(tok % L);
+  const int D = H * hd;
+  const bf16_t* src = qkv + tok * 3 * D + hh * hd + 4 * i;
+  const long dst = (((long)b * H + hh) * L + l) * hdp + 4 * i;
+  const long kvd = b * kv_sb + hh * kv_sh + (long)(l < lead ? l : l + past) * kv_sl + 4 * i;
+  const f32x4 c4 = *reinterpret_cast<const f32x4*>(cosb + (long)l * half + 4 * i);
+  const f32x4 s4 = *reinterpret_cast<const f32x4*>(sinb + (long)l * half + 4 * i);
+#pragma unroll
+  for (int which = 0; which < 2; ++which) {
+    const u32x2 lo = *reinterpret_cast<const u32x2*>(src + which * D);
+    const u32x2 hi = *reinterpret_cast<const u32x2*>(src + which * D + half);
+    float x1[4] = {bflo(lo[0]), bfhi(lo[0]), bflo(lo[1]), bfhi(lo[1])};
+    float x2[4] = {bflo(hi[0]), bfhi(hi[0]), bflo(hi[1]), bfhi(hi[1])};
+    if constexpr (NORM) {
+      const bf16_t* row = qkv + tok * 3 * D + which * D + hh * hd;
+      float ss = 0.f;
+      for (int d = 0; d < hd; d += 4) {
+        const u32x2 w = *reinterpret_cast<const u32x2*>(row + d);
+        ss += bflo(w[0]) * bflo(w[0]) + bfhi(w[0]) * bfhi(w[0]) + bflo(w[1]) * bflo(w[1]) + bfhi(w[1]) * bfhi(w[1]);
+      }
+      const float r = rsqrtf(ss / (float)hd + eps);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        x1[e] = bf2f(f2bf(x1[e] * r));
+        x2[e] = bf2f(f2bf(x2[e] * r));
+      }
+    }
+    float y1[4], y2[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      y1[e] = x1[e] * c4[e] + x2[e] * s4[e];
+      y2[e] = x2[e] * c4[e] - x1[e] * s4[e];
+    }
+    bf16_t* o = which == 0 ? q + dst : k + kvd;
+    u32x2 w1 = {pack_bf2(y1[0], y1[1]), pack_bf2(y1[2], y1[3])};
+    u32x2 w2 = {pack_bf2(y2[0], y2[1]), pack_bf2(y2[2], y2[3])};
+    *reinterpret_cast<u32x2*>(o) = w1;
+    *reinterpret_cast<u32x2*>(o + half) = w2;
+  }
+  {
+    const u32x2 lo = *reinterpret_cast<const u32x2*>(src + 2 * D);
+    const u32x2 hi = *reinterpret_cast<const u32x2*>(src + 2 * D + half);
+    u32x2 w1 = lo, w2 = hi;
+    if (v0) {
+      const float lam = bf2f(*lamp);
+      const u32x2 a = *reinterpret_cast<const u32x2*>(v0 + kvd);
+      const u32x2 c = *reinterpret_cast<const u32x2*>(v0 + kvd + half);
+      // reference (bf16 tensors): lam*v rounds, (1-lam) rounds, (1-lam)*v0 rounds, sum rounds
+      const float oml = bf2f(f2bf(1.0f - lam));
+      auto mix = [&](unsigned vr, unsigned v0r) {
+        const float a0 = bf2f(f2bf(lam * bflo(vr))) + bf2f(f2bf(oml * bflo(v0r)));
+        const float a1 = bf2f(f2bf(lam * bfhi(vr))) + bf2f(f2bf(oml * bfhi(v0r)));
+        return pack_bf2(a0, a1);
+      };
+      w1[0] = mix(lo[0], a[0]); w1[1] = mix(lo[1], a[1]);
+      w2[0] = mix(hi[0], c[0]); w2[1] = mix(hi[1], c[1]);
+    }
+    *reinterpret_cast<u32x2*>(v + kvd) = w1;
+    *reinterpret_cast<u32x2*>(v + kvd + half) = w2;
+  }
+  // pad columns hd..hdp: as in the kernel above (ones columns in the K / V pad)
+  const int npad = (hdp - hd) >> 2;
+  if (i < npad) {
+    const long pd = dst + hd, kpd = kvd + hd;  // (dst, kvd include 4 i)
+    const u32x2 z = {0u, 0u};
+    const u32x2 one = {0x3f80u, 0u}, one2 = {0x3f803f80u, 0u};
+    const bool ones = (hdp - hd) >= 8;
+    *reinterpret_cast<u32x2*>(q + pd) = z;
+    *reinterpret_cast<u32x2*>(k + kpd) = (ones && i == 0) ? one2 : z;
+    *reinterpret_cast<u32x2*>(v + kpd) = (ones && i < 2) ? one : z;
+  }
+}
+
 // Token-tile form of the kernel above (rope_stage.h): T consecutive tokens per workgroup, qkv rows copied to LDS by
 // LDS-DMA, q / k rotated in place there, every global access 16 bytes wide and every (tensor, head) written as a run of T
 // complete head rows.  Same arithmetic and rounding points.
@@ -1981,6 +2071,41 @@ extern "C" int vds_qkv_rope_norm_fwd(const void* qkv, const float* cosb, const f
                                      int32_t hd, int32_t hdp, float eps, vds_stream_t stream) {
   if (!(eps > 0.f)) return VDS_ERR_ARG;
   return qkv_rope_fwd_impl<true>(qkv, cosb, sinb, v0, lam, q, k, v, B, L, H, hd, hdp, eps, stream);
+}
+
+// cache forms: k / v rows (and the v0 rows read) at b * kv_sb + h * kv_sh + (l < lead ? l : l + past) * kv_sl
+template <bool NORM>
+static int qkv_rope_fwd_cache_impl(const void* qkv, const float* cosb, const float* sinb, const void* v0, const void* lam,
+                                   void* q, void* k, void* v, int64_t kv_sb, int64_t kv_sh, int64_t kv_sl, int32_t lead,
+                                   int32_t past, int32_t B, int32_t L, int32_t H, int32_t hd, int32_t hdp, float eps,
+                                   vds_stream_t stream) {
+  if (!qkv || !cosb || !sinb || !q || !k || !v || (hd & 7) || hdp < hd || (hdp & 3)) return VDS_ERR_ARG;
+  if (v0 && !lam) return VDS_ERR_ARG;
+  if (B <= 0 || L <= 0 || H <= 0 || lead < 0 || lead > L || past < 0) return VDS_ERR_ARG;
+  if ((kv_sb & 3) || (kv_sh & 3) || (kv_sl & 3) || kv_sl < hdp) return VDS_ERR_ARG;
+  if (((hdp - hd) >> 2) > (hd >> 3)) return VDS_ERR_UNSUPPORTED;
+  const long n = (long)B * L * H * (hd >> 3);
+  vdsprof::Scope ps(VDS_PROF_QKV_ROPE_FWD, (hipStream_t)stream, 0.0, (v0 ? 14.0 : 12.0) * B * L * H * hd);
+  hipLaunchKernelGGL(qkv_rope_fwd_cache_kernel<NORM>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, (const bf16_t*)qkv, cosb, sinb, (const bf16_t*)v0, (const bf16_t*)lam,
+                     (bf16_t*)q, (bf16_t*)k, (bf16_t*)v, (long)kv_sb, (long)kv_sh, (long)kv_sl, lead, past, B, L, H, hd,
+                     hdp, eps);
+  return ok();
+}
+extern "C" int vds_qkv_rope_fwd_cache(const void* qkv, const float* cosb, const float* sinb, const void* v0,
+                                      const void* lam, void* q, void* k, void* v, int64_t kv_sb, int64_t kv_sh,
+                                      int64_t kv_sl, int32_t lead, int32_t past, int32_t B, int32_t L, int32_t H,
+                                      int32_t hd, int32_t hdp, vds_stream_t stream) {
+  return qkv_rope_fwd_cache_impl<false>(qkv, cosb, sinb, v0, lam, q, k, v, kv_sb, kv_sh, kv_sl, lead, past, B, L, H, hd,
+                                        hdp, 0.f, stream);
+}
+extern "C" int vds_qkv_rope_norm_fwd_cache(const void* qkv, const float* cosb, const float* sinb, const void* v0,
+                                           const void* lam, void* q, void* k, void* v, int64_t kv_sb, int64_t kv_sh,
+                                           int64_t kv_sl, int32_t lead, int32_t past, int32_t B, int32_t L, int32_t H,
+                                           int32_t hd, int32_t hdp, float eps, vds_stream_t stream) {
+  if (!(eps > 0.f)) return VDS_ERR_ARG;
+  return qkv_rope_fwd_cache_impl<true>(qkv, cosb, sinb, v0, lam, q, k, v, kv_sb, kv_sh, kv_sl, lead, past, B, L, H, hd,
+                                       hdp, eps, stream);
 }
 
 // ---- residual-V: the gradient that reaches v_0 from the blocks that mixed it in (model.py:129-130), summed once -------

@@ -436,7 +436,7 @@ class DiTBlock(nn.Module):
 
     # ---- the kernel sequence of one block (used by DiT's whole-model autograd node and by `forward`) ----
     def _fwd(self, G, pre, X, ctx2d, cvec, v0, cos, sin, B, L, Lc, save, fp8=None, mod=None, keep=None, replay=None,
-             kv_lens=None, groups=None, frames=None):
+             kv_lens=None, groups=None, frames=None, cache=None):
         """X [B*L, D] bf16 token buffer -> (X_out, v [B,H,L,hdp], saved).  G: the FlatGroup holding this block's
         parameters under the name prefix `pre`; cvec f32 [B, D]; v0: block 0's v in the padded head-major layout
         or None; cos / sin f32 [L, hd/2]; fp8 = (AmaxHistory | None, block index) when the fp8 linears are on.
@@ -447,9 +447,14 @@ class DiTBlock(nn.Module):
         kv_lens: int32 device tensor [B] or None -- per-sample key counts of the cross-attention (bf16 kernels only).
         groups: None, or (lead, period) -- per-frame timesteps: cvec is f32 [B*G, D] and the modulation table [B*G, 9D],
         G = 1 + period, row b*G + g for modulation group g of sample b (bf16 kernels only).
-        frames: (lead, period) of a frame_causal block's masked self-attention (bf16 attention kernels only), else None."""
+        frames: (lead, period) of a frame_causal block's masked self-attention (bf16 attention kernels only), else None.
+        cache: (k_buf, v_buf, past) of a cached chunk call (DiT.forward(frame_cache=)), inference only -- the block's k / v
+        rows go straight to their place in its cache buffers [B,H,rows,hdp], the self-attention reads the first L + past
+        rows of them, and the returned v IS v_buf (block 0's: the v0 later blocks read through the same row map)."""
         D, H, hd = self.hidden_size, self.num_heads, self.head_dim
         frames = self._check_frames(frames, L)
+        if cache is not None and (save or keep is not None or replay is not None or fp8 is not None or frames is None):
+            raise RuntimeError("DiTBlock: a frame cache runs the bf16 inference forward of a frame_causal block only")
         hdp = HDP_OF[hd]
         use_fp8 = fp8 is not None
         if kv_lens is not None and use_fp8 and fp8[2] >= 2:
@@ -516,9 +521,18 @@ class DiTBlock(nn.Module):
                                       emit=(hist.prev(R0 + F8.ROW_ATTN), hist.cur(R0 + F8.ROW_ATTN))
                                       if (pemit and fp8_lin and not _NO_ATTN_EMIT) else None)
         else:
-            rope_fwd = ops.qkv_rope_norm_fwd if self.qk_norm else ops.qkv_rope_fwd
-            q, k, v = rope_fwd(qkv, cos, sin, v0 if mix else None, W("lambda_param") if mix else None, B, L, H, hd, hdp)
-            if not kept_attn:
+            if cache is not None:
+                kb, vb, past = cache
+                rope_fwd = ops.qkv_rope_norm_fwd_cache if self.qk_norm else ops.qkv_rope_fwd_cache
+                q = rope_fwd(qkv, cos, sin, v0 if mix else None, W("lambda_param") if mix else None, kb, vb, frames[0], past,
+                             B, L, H, hd, hdp)
+                ops.attn_fwd(q[..., :hd], kb[:, :, :L + past, :hd], vb[:, :, :L + past, :hd],
+                             ops.heads_view(attn, B, L, H, hd), lse1, kv_pad_ones=(hdp - hd) >= 8, frames=frames, past=past)
+                k, v = kb, vb
+            else:
+                rope_fwd = ops.qkv_rope_norm_fwd if self.qk_norm else ops.qkv_rope_fwd
+                q, k, v = rope_fwd(qkv, cos, sin, v0 if mix else None, W("lambda_param") if mix else None, B, L, H, hd, hdp)
+            if cache is None and not kept_attn:
                 ops.attn_fwd(q[..., :hd], k[..., :hd], v[..., :hd], ops.heads_view(attn, B, L, H, hd), lse1,
                              kv_pad_ones=(hdp - hd) >= 8, frames=frames)
             if a8_on and save:  # first steps: record the amax the next step quantises with
@@ -865,6 +879,50 @@ class DiTBlock(nn.Module):
         return dX0
 
 
+class FrameKVCache:
+    """K / V rows of the finished token-frames of a cached frame rollout (DiT.new_frame_cache, DiT.forward(frame_cache=)).
+    Per block one K and one V buffer [batch, H, N_REG + frames*h*w, hdp] bf16 in the padded head-major layout the qkv / RoPE
+    kernel writes (ones columns included): rows [0, N_REG) the register rows of the last call, then the committed frames'
+    token rows, then the rows of the last call's chunk.  past_frames counts the committed token-frames."""
+
+    def __init__(self, depth, batch, heads, frames, h_tokens, w_tokens, hdp, device):
+        self.batch, self.frames, self.h_tokens, self.w_tokens = batch, frames, h_tokens, w_tokens
+        rows = N_REG + frames * h_tokens * w_tokens
+        self.k = [torch.zeros(batch, heads, rows, hdp, dtype=bf16, device=device) for _ in range(depth)]
+        self.v = [torch.zeros(batch, heads, rows, hdp, dtype=bf16, device=device) for _ in range(depth)]
+        self.past_frames = 0
+        self.pending_frames = 0  # token-frames of the last forward, not yet committed
+        self._rope = None  # (base, cos, sin) of the whole video's RoPE table
+
+    def rope_rows(self, rope, start, k):
+        """cos / sin rows [N_REG + k*h*w, hd/2] of a chunk of k token-frames whose first frame sits at t = start[0]: the rows
+        the chunk's tokens have in the table of the WHOLE video (`frames` x h x w from the base start[0] - past_frames).  The
+        reference's table is flattened (t h w) while the tokens are ordered (h w t), so a token's rotation depends on the
+        video's frame count, not on its own position alone: only these rows make a chunk call equal to the full-sequence
+        call restricted to the chunk's frames."""
+        base = (int(start[0]) - self.past_frames, int(start[1]), int(start[2]))
+        if self._rope is None or self._rope[0] != base:
+            self._rope = (base,) + tuple(rope.rows((self.frames, self.h_tokens, self.w_tokens), base, N_REG))
+        _, cos, sin = self._rope
+        dev = cos.device
+        tok = torch.arange(self.h_tokens * self.w_tokens, device=dev)[:, None] * self.frames
+        rows = N_REG + tok + self.past_frames + torch.arange(k, device=dev)[None, :]
+        idx = torch.cat([torch.arange(N_REG, device=dev), rows.reshape(-1)])
+        return cos.index_select(0, idx), sin.index_select(0, idx)
+
+    def commit(self):
+        """the token rows of the last forward become part of the past: a counter increment, the rows already sit behind
+        the earlier ones"""
+        if not self.pending_frames:
+            raise RuntimeError("FrameKVCache.commit: no forward(frame_cache=) has run since the last commit() / reset()")
+        self.past_frames += self.pending_frames
+        self.pending_frames = 0
+
+    def reset(self):
+        """forget every frame (the buffers are kept and overwritten)"""
+        self.past_frames = self.pending_frames = 0
+
+
 class _Saved:
     """activations kept for the backward pass"""
     pass
@@ -1095,7 +1153,8 @@ class DiT(nn.Module):
                 g.gfull.zero_()
 
     # ------------------------------------------------------------------------ forward ----
-    def forward(self, x, context, timesteps, rope_start: Optional[Tuple[int, int, int]] = None, context_lens=None):
+    def forward(self, x, context, timesteps, rope_start: Optional[Tuple[int, int, int]] = None, context_lens=None,
+                register_timesteps=None, frame_cache=None):
         """x [B,C,T,H,W], context [B,Lc,Cc], timesteps [B] -> [B,C,T,H,W] bf16 (model.py:358-402).
         timesteps [B, t], t = T // time_patch_size: one noise level per token-frame (image-to-video, video extension,
         diffusion forcing).  The tokens of frame f of sample b are modulated from timesteps[b, f], the register tokens
@@ -1103,7 +1162,36 @@ class DiT(nn.Module):
         context_lens: per-sample context lengths -- sample b cross-attends its first context_lens[b] context rows only, 0
         = no context at all (the cross-attention adds nothing for that sample).  A sequence of ints or a CPU integer tensor
         [B] is validated on the host and uploaded once; a CUDA integer tensor [B] is used as it is, without a host sync.
-        None (the default, the reference's behaviour): all Lc rows of every sample are attended."""
+        None (the default, the reference's behaviour): all Lc rows of every sample are attended.
+        register_timesteps ([B] tensor or sequence, with timesteps [B, t] only): the noise level the register tokens are
+        modulated from, in place of the row maximum.  Pinned, a frame_causal model is causal in the noise levels too: what
+        it computes for frame f depends on timesteps[:, :f + 1] and this value alone.  Works with and without grad.  None:
+        the row maximum, call for call.
+        frame_cache (a FrameKVCache of new_frame_cache; inference on a frame_causal model): x holds only a chunk of k
+        token-frames, the ones after the cache's past_frames committed frames; N_REG + k*h*w rows run through the model,
+        every block's self-attention reads the committed frames' K / V from the cache and writes the chunk's into it (a
+        later frame_cache.commit() makes them part of the past).  timesteps must be [B, k] and rope_start's t component the
+        chunk's absolute position (the rollout's base t + past_frames); the chunk's tokens get the RoPE rows they have in the
+        table of the whole video of frame_cache.frames frames (FrameKVCache.rope_rows), so the cache must be made for the
+        video's full frame count.  Returns [B, C, k*pt, H, W].  The cached K / V are only valid if every call pins the
+        same register_timesteps.  With those two, the call computes what the full-sequence call (earlier frames at t = 0,
+        later ones at any level) computes for the chunk's frames."""
+        reg_t = None
+        if register_timesteps is not None or frame_cache is not None:  # validated before the device is touched
+            b = x.shape[0]
+            thw = (x.shape[2] // self.time_patch_size, x.shape[3] // self.patch_size, x.shape[4] // self.patch_size)
+            per_frame = check_timesteps(timesteps, b, thw[0])
+            if frame_cache is not None:
+                self._check_frame_cache(frame_cache, b, thw, per_frame, rope_start)
+            if register_timesteps is not None:
+                if not per_frame:
+                    raise ValueError("DiT: register_timesteps pins the register tokens' noise level of a per-frame call -- "
+                                     f"pass timesteps of shape [{b}, {thw[0]}] (one per token-frame), or drop "
+                                     "register_timesteps")
+                reg_t = torch.as_tensor(register_timesteps).to(device=x.device, dtype=f32)
+                if tuple(reg_t.shape) != (b,):
+                    raise ValueError(f"DiT: register_timesteps must have shape [{b}] (one per sample), got "
+                                     f"{tuple(reg_t.shape)}")
         kv_lens = None
         if context_lens is not None:
             if self.cross_attn_input_size is None:
@@ -1132,9 +1220,68 @@ class DiT(nn.Module):
         if kv_lens is not None:
             kv_lens = kv_lens.to(x.device)
         if need_grad:
-            return _DiTFunction.apply(self, x, context, timesteps, rope_start, kv_lens, *params)
-        out, _ = self._forward_impl(x, context, timesteps, rope_start, save=False, kv_lens=kv_lens)
+            return _DiTFunction.apply(self, x, context, timesteps, rope_start, kv_lens, reg_t, *params)
+        out, _ = self._forward_impl(x, context, timesteps, rope_start, save=False, kv_lens=kv_lens, reg_t=reg_t,
+                                    cache=frame_cache)
+        if frame_cache is not None:
+            frame_cache.pending_frames = thw[0]
         return out
+
+    def new_frame_cache(self, batch: int, frames: int, h_tokens: int, w_tokens: int, device=None) -> "FrameKVCache":
+        """The K / V store of a cached frame rollout (forward(frame_cache=)): per block, K and V buffers
+        [batch, heads, N_REG + frames*h_tokens*w_tokens, padded head dim] bf16 -- the register rows, then the token rows of
+        up to `frames` token-frames of h_tokens x w_tokens tokens, in the order the chunks are run."""
+        if not self.frame_causal:
+            raise ValueError("DiT.new_frame_cache: a frame KV cache needs a model built with frame_causal=True (on any other "
+                             "model the K / V rows of finished frames change with the frames after them)")
+        if min(int(batch), int(frames), int(h_tokens), int(w_tokens)) < 1:
+            raise ValueError(f"DiT.new_frame_cache: batch, frames, h_tokens, w_tokens must be >= 1, got "
+                             f"{(batch, frames, h_tokens, w_tokens)}")
+        if device is None:
+            device = next(self.parameters()).device
+        return FrameKVCache(self.depth, int(batch), self.num_heads, int(frames), int(h_tokens), int(w_tokens),
+                            HDP_OF[self.head_dim], device)
+
+    def _check_frame_cache(self, cache, b, thw, per_frame, rope_start):
+        """the conditions of a cached chunk call, each with its remedy (all before the device is touched)"""
+        k, h, w = thw
+        if not isinstance(cache, FrameKVCache):
+            raise ValueError("DiT: frame_cache must be a FrameKVCache -- make one with DiT.new_frame_cache(batch, frames, "
+                             "h_tokens, w_tokens)")
+        if not self.frame_causal:
+            raise ValueError("DiT: frame_cache needs a model built with frame_causal=True; run this model without "
+                             "frame_cache (generate_latents(kv_cache=False))")
+        if torch.is_grad_enabled():
+            raise RuntimeError("DiT: frame_cache is inference only (the past layout has no backward kernel) -- call the "
+                               "model under torch.no_grad()")
+        if self.fp8 and self.fp8_attn:
+            raise NotImplementedError("frame_cache is not implemented for the fp8 attention kernels (they have no masked "
+                                      "instance): call enable_fp8(attention=False), or enable_fp8(False)")
+        if self.fp8:
+            raise NotImplementedError(_FP8_FRAME_TIMESTEPS)
+        if self._fsdp is not None:
+            raise NotImplementedError("frame_cache is not implemented for a model sharded with apply_fsdp: sample from an "
+                                      "unsharded copy of the weights (full_state_dict())")
+        if not per_frame:
+            raise ValueError(f"DiT: a frame_cache call takes per-frame timesteps of shape [{b}, {k}] (one per token-frame of "
+                             "the chunk), not [B]")
+        if (cache.batch, cache.h_tokens, cache.w_tokens) != (b, h, w) or len(cache.k) != self.depth:
+            raise ValueError(f"DiT: frame_cache was made for batch {cache.batch} and {cache.h_tokens} x {cache.w_tokens} "
+                             f"tokens per frame, this call has batch {b} and {h} x {w}: make a cache with "
+                             f"new_frame_cache({b}, frames, {h}, {w})")
+        if cache.past_frames + k > cache.frames:
+            raise ValueError(f"DiT: frame_cache holds {cache.frames} token-frames, {cache.past_frames} are committed and this "
+                             f"chunk brings {k}: make a larger cache (new_frame_cache(frames=...)) or reset() it")
+        if rope_start is None or isinstance(rope_start, torch.Tensor):
+            raise ValueError("DiT: a frame_cache call needs rope_start=(t, h, w) as host ints, t being the chunk's absolute "
+                             "position: the rollout's base t + frame_cache.past_frames")
+        base_t = int(tuple(rope_start)[0]) - cache.past_frames
+        if base_t < 0 or base_t + cache.frames > self.rope.t:
+            raise ValueError(f"DiT: rope_start t = {tuple(rope_start)[0]} is the chunk's absolute position (the rollout's "
+                             f"base t + past_frames = {cache.past_frames}): it puts the base at {base_t}, and the cache's "
+                             f"{cache.frames} frames must lie inside the RoPE table's {self.rope.t} positions -- pass "
+                             f"rope_start=(base_t + frame_cache.past_frames, h, w) with 0 <= base_t <= "
+                             f"{self.rope.t - cache.frames}")
 
     def _gather_all(self):
         """bf16 compute copies of every group.  world == 1: one cast kernel per group."""
@@ -1143,7 +1290,7 @@ class DiT(nn.Module):
         for g in self._groups:
             g.gather(ops.cast_f32_bf16, None)
 
-    def _forward_impl(self, x, context, timesteps, rope_start, save: bool, kv_lens=None):
+    def _forward_impl(self, x, context, timesteps, rope_start, save: bool, kv_lens=None, reg_t=None, cache=None):
         D, H, hd = self.hidden_size, self.num_heads, self.head_dim
         pt, p = self.time_patch_size, self.patch_size
         B, C, T, Hh, Ww = x.shape
@@ -1182,7 +1329,10 @@ class DiT(nn.Module):
         Wpe = R.w("patch_embed.patch_proj.weight").view(D, P)
         X = ops.linear_fwd(patches, Wpe, R.w("patch_embed.patch_proj.bias"))
         ops.fill_registers(R.w("register_tokens").view(N_REG, D), X, L * D, B, N_REG, D)
-        cos, sin = self.rope.rows((t, h, w), rope_start, N_REG)
+        if cache is not None:
+            cos, sin = cache.rope_rows(self.rope, rope_start, t)
+        else:
+            cos, sin = self.rope.rows((t, h, w), rope_start, N_REG)
 
         # timestep conditioning (model.py:374-377), kept in fp32
         # per-frame timesteps [B, t]: the conditioning path runs on B*G rows, G = 1 + t modulation groups per sample --
@@ -1193,7 +1343,8 @@ class DiT(nn.Module):
         if timesteps.dim() == 2:
             groups = (N_REG, t)
             tf = timesteps.to(f32)
-            timesteps = torch.cat([tf.max(dim=1, keepdim=True).values, tf], dim=1).reshape(B * (1 + t))
+            lead_t = tf.max(dim=1, keepdim=True).values if reg_t is None else reg_t.view(B, 1)
+            timesteps = torch.cat([lead_t, tf], dim=1).reshape(B * (1 + t))
         temb = ops.timestep_embedding(timesteps.to(f32).contiguous(), D)
         h1 = ops.small_linear_fwd(temb, R.w("time_embed.0.weight"), R.w("time_embed.0.bias"), 0)
         cvec = ops.small_linear_fwd(h1, R.w("time_embed.2.weight"), R.w("time_embed.2.bias"), 1)
@@ -1215,6 +1366,7 @@ class DiT(nn.Module):
             wt, bt, _, _ = self._adaln_tables()
             mods = ops.small_linear_fwd_batched(cvec, wt, bt, self.depth, 9 * D, 1)
         v0 = None
+        past = cache.past_frames * h * w if cache is not None else 0
         keep = self.recompute if (save and self.recompute != "none") else None  # blocks keep their inputs, not their work
         for i in range(self.depth):
             if fs is not None:
@@ -1223,7 +1375,8 @@ class DiT(nn.Module):
                                            save and keep is None,
                                            (self._fp8_hist, i, self.fp8_attn, self.fp8_lin, q_ctx) if self.fp8 else None,
                                            mods[i] if mods is not None else None, keep=keep, kv_lens=kv_lens,
-                                           groups=groups, frames=frames)
+                                           groups=groups, frames=frames,
+                                           **({} if cache is None else {"cache": (cache.k[i], cache.v[i], past)}))
             if v0 is None:
                 v0 = v
             if save:
@@ -1510,8 +1663,8 @@ class _DiTFunction(torch.autograd.Function):
     parameter gradients are written into the flat fp32 gradient buffers that p.grad aliases."""
 
     @staticmethod
-    def forward(ctx, model, x, context, timesteps, rope_start, kv_lens, *params):
-        out, sv = model._forward_impl(x, context, timesteps, rope_start, save=True, kv_lens=kv_lens)
+    def forward(ctx, model, x, context, timesteps, rope_start, kv_lens, reg_t, *params):
+        out, sv = model._forward_impl(x, context, timesteps, rope_start, save=True, kv_lens=kv_lens, reg_t=reg_t)
         ctx.model, ctx.sv = model, sv
         return out
 
@@ -1520,4 +1673,4 @@ class _DiTFunction(torch.autograd.Function):
         model, sv = ctx.model, ctx.sv
         ctx.sv = None
         model._backward_impl(sv, dout)
-        return (None,) * (6 + len([p for p in model.parameters() if p.requires_grad]))
+        return (None,) * (7 + len([p for p in model.parameters() if p.requires_grad]))

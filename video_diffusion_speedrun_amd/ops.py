@@ -265,25 +265,31 @@ def _kv_lens_ptr(kv_lens, B: int) -> int:
     return kv_lens.data_ptr()
 
 
-def _frames(frames, kv_lens, Lq: int, Lk: int):
+def _frames(frames, kv_lens, Lq: int, Lk: int, past: int = 0):
     """vds_mod_groups of a frame-causal self-attention call: (lead, period) checked against the sequence, or ValueError"""
     if kv_lens is not None:
         raise ValueError("attention: frames (frame-causal self-attention) and kv_lens (cross-attention) exclude each other")
-    if Lq != Lk:
-        raise ValueError(f"frame-causal attention is self-attention: Lq = {Lq} != Lk = {Lk}")
+    if Lq + past != Lk:
+        raise ValueError(f"frame-causal attention is self-attention: Lq = {Lq}" + (f" + past = {past}" if past else "") +
+                         f" != Lk = {Lk}")
     lead, period = check_mod_groups(frames, Lq)
     return C.byref(_lib.ModGroups(lead, period))
 
 
-def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=None):
+def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=None, past: int = 0):
     """q [B,H,Lq,hd], k/v [B,H,Lk,hd], o [B,H,Lq,hd] strided views (last dim contiguous); lse f32 [B,H,Lq].
     kv_pad_ones: k / v are views into qkv_rope_fwd outputs whose pad carries the ones columns.
     kv_lens: int32 CUDA tensor [B]; sample b attends its first kv_lens[b] keys only (vds_attn_fwd_kvlen).
     frames: (lead, period) -- frame-causal self-attention: row q attends row k iff mod_group_of(k) <= mod_group_of(q)
-    (vds_attn_fwd_causal); not together with kv_lens."""
+    (vds_attn_fwd_causal); not together with kv_lens.
+    past (with frames): k / v hold Lk = Lq + past rows [lead rows | past cached token rows | this call's token rows]; a
+    token query also attends every past key, a lead query none of them (vds_attn_fwd_causal_past).  Forward only."""
     B, H, Lq, hd = q.shape
     Lk = k.shape[2]
-    fr = _frames(frames, kv_lens, Lq, Lk) if frames is not None else None
+    past = int(past)
+    if past < 0 or (past and frames is None):
+        raise ValueError(f"attention: past = {past} must be >= 0 and needs frames=(lead, period)")
+    fr = _frames(frames, kv_lens, Lq, Lk, past) if frames is not None else None
     a = AttnArgs()
     a.B, a.H, a.Lq, a.Lk, a.head_dim = B, H, Lq, Lk, hd
     a.q, (a.q_sb, a.q_sh, a.q_sl) = _p(q), _st(q)
@@ -292,7 +298,10 @@ def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=No
     a.o, (a.o_sb, a.o_sh, a.o_sl) = _p(o), _st(o)
     a.lse = _p(lse)
     a.kv_pad_ones = int(kv_pad_ones)  # (True = 1: self-attention layout; 2: ones in k / v only, cross-attention)
-    if fr is not None:
+    if fr is not None and past:
+        check(_lib.load().vds_attn_fwd_causal_past(C.byref(a), fr, past, _stream()),
+              f"vds_attn_fwd_causal_past(B={B},H={H},Lq={Lq},Lk={Lk},hd={hd},frames={tuple(frames)},past={past})")
+    elif fr is not None:
         check(_lib.load().vds_attn_fwd_causal(C.byref(a), fr, _stream()),
               f"vds_attn_fwd_causal(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)})")
     elif kv_lens is None:
@@ -629,6 +638,27 @@ def qkv_rope_fwd(qkv, cos, sin, v0, lam, B, L, H, hd, hdp):
     return q, k, v
 
 
+def _kv_cache_args(k, v, v0, B, H, hdp, lead, past, L):
+    """(kv_sb, kv_sh, kv_sl) shared by the cache buffers k, v (and v0) [B,H,rows,hdp] of the cache forms below"""
+    for t in (k, v) + ((v0,) if v0 is not None else ()):
+        if not (t.dtype == bf16 and t.dim() == 4 and t.shape[0] == B and t.shape[1] == H and t.shape[3] == hdp
+                and t.stride(3) == 1 and t.stride() == k.stride() and t.shape[2] >= L + past):
+            raise ValueError(f"kv cache buffers must be bf16 [B={B},H={H},rows>={L + past},hdp={hdp}] with equal strides")
+    if not 0 <= lead <= L or past < 0:
+        raise ValueError(f"kv cache: lead = {lead} not in [0, {L}] or past = {past} < 0")
+    return k.stride(0), k.stride(1), k.stride(2)
+
+
+def qkv_rope_fwd_cache(qkv, cos, sin, v0, lam, k, v, lead, past, B, L, H, hd, hdp):
+    """qkv_rope_fwd whose k / v rows go to row (l < lead ? l : l + past) of the cache buffers k, v [B,H,rows,hdp]; v0 is
+    block 0's cache v buffer, read through the same map (vds_qkv_rope_fwd_cache).  Returns q [B,H,L,hdp]."""
+    st = _kv_cache_args(k, v, v0, B, H, hdp, lead, past, L)
+    q = torch.empty(B, H, L, hdp, dtype=bf16, device=qkv.device)
+    check(_lib.load().vds_qkv_rope_fwd_cache(_p(qkv), _p(cos), _p(sin), _p(v0), _p(lam), _p(q), _p(k), _p(v), *st, lead,
+                                             past, B, L, H, hd, hdp, _stream()), "vds_qkv_rope_fwd_cache")
+    return q
+
+
 def qkv_rope_bwd(dq, dk, dv, cos, sin, qkv_raw, v0, lam, dv0_acc, dlam, mix, add_dv0, B, L, H, hd, hdp):
     dqkv = torch.empty(B * L, 3 * H * hd, dtype=bf16, device=dq.device)
     check(_lib.load().vds_qkv_rope_bwd(_p(dq), _p(dk), _p(dv), _p(cos), _p(sin), _p(qkv_raw), _p(v0), _p(lam),
@@ -649,6 +679,16 @@ def qkv_rope_norm_fwd(qkv, cos, sin, v0, lam, B, L, H, hd, hdp, eps: float = QK_
     check(_lib.load().vds_qkv_rope_norm_fwd(_p(qkv), _p(cos), _p(sin), _p(v0), _p(lam), _p(q), _p(k), _p(v), B, L, H,
                                             hd, hdp, float(eps), _stream()), "vds_qkv_rope_norm_fwd")
     return q, k, v
+
+
+def qkv_rope_norm_fwd_cache(qkv, cos, sin, v0, lam, k, v, lead, past, B, L, H, hd, hdp, eps: float = QK_NORM_EPS):
+    """qkv_rope_fwd_cache with QK-norm (vds_qkv_rope_norm_fwd_cache)"""
+    st = _kv_cache_args(k, v, v0, B, H, hdp, lead, past, L)
+    q = torch.empty(B, H, L, hdp, dtype=bf16, device=qkv.device)
+    check(_lib.load().vds_qkv_rope_norm_fwd_cache(_p(qkv), _p(cos), _p(sin), _p(v0), _p(lam), _p(q), _p(k), _p(v), *st,
+                                                  lead, past, B, L, H, hd, hdp, float(eps), _stream()),
+          "vds_qkv_rope_norm_fwd_cache")
+    return q
 
 
 def qkv_rope_norm_bwd(dq, dk, dv, cos, sin, qkv_raw, v0, lam, dv0_acc, dlam, mix, add_dv0, B, L, H, hd, hdp,

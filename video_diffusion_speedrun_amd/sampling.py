@@ -37,7 +37,7 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
                      seed: int = 42, latents: Optional[torch.Tensor] = None,
                      rope_starts: Optional[Sequence[Tuple[int, int, int]]] = None, device="cuda",
                      prompt_lens=None, negative_lens=None, cond_latents: Optional[torch.Tensor] = None,
-                     rollout_frames: Optional[int] = None) -> torch.Tensor:
+                     rollout_frames: Optional[int] = None, kv_cache: bool = False) -> torch.Tensor:
     """rollout_frames = k >= 1 (frame rollout): after any cond_latents frames the remaining token-frames are generated k
     at a time, in order.  Every chunk runs the whole `inference_steps` Euler loop with per-frame timesteps -- 0 for the
     frames before the chunk, the step's t for the chunk's frames, 1.0 for the frames after it (still the initial noise)
@@ -46,6 +46,20 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
     pair); there is no KV cache.  `rope_starts` then lists the offsets of all those calls, chunk after chunk.  Runs on
     any model; on a DiT built with frame_causal=True a finished chunk does not depend on the noise of later frames.
     None: the loop below, call for call.
+
+    kv_cache=True (with rollout_frames, on a DiT built with frame_causal=True): the cached rollout.  Every model call
+    runs on the chunk's token-frames alone (DiT.forward(frame_cache=)): the K / V rows of the finished frames come from a
+    FrameKVCache and the frames after the chunk, which nothing in the chunk reads, are not computed.  One RoPE base serves
+    the whole rollout (`rope_starts[0]` if given -- a list of any other length is an error -- else one draw for the full
+    video), the guided pair always runs as one batched call, and the register tokens are at noise level 1.0 in every call
+    (register_timesteps): a cached K / V row is only valid later if the registers were at the same level both times.
+    Calls: one on any cond_latents frames at t = 0, then per chunk `inference_steps` calls on the chunk and -- after every
+    chunk but the last -- one on the finished chunk at t = 0, which writes its clean K / V.  For every chunk that has
+    frames after it the uncached rollout has its registers at 1.0 too (the row maximum: the frames after the chunk sit at
+    1.0), so the two rollouts compute the same thing there.  On the last chunk the uncached registers follow the step's
+    t, the K / V of the earlier frames then change with every step and no cache can reproduce that: the cached rollout's
+    last chunk is its own defined computation -- registers at 1.0 -- pinned by tests/helpers/frame_cache_ref.py.
+    False (the default): the loop described above, call for call.
 
     cond_latents ([1,16,Tc,h,w], Tc a multiple of the model's time_patch_size; image-to-video, video extension): the
     first Tc latent frames are held at these values -- their token-frames are given t = 0 in every model call (per-frame
@@ -98,6 +112,15 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
         if lat.shape[2] % model.time_patch_size != 0:
             raise ValueError(f"frame rollout: {lat.shape[2]} latent frames are no multiple of time_patch_size "
                              f"({model.time_patch_size})")
+    if kv_cache:
+        if rollout_frames is None:
+            raise ValueError("kv_cache=True caches the finished frames of a frame rollout: pass rollout_frames=k too")
+        if not getattr(model, "frame_causal", False):
+            raise ValueError("kv_cache=True needs a DiT built with frame_causal=True (without the mask the finished frames' "
+                             "K / V change with the frames after them); use kv_cache=False on this model")
+        if rope_starts is not None and len(rope_starts) != 1:
+            raise ValueError(f"kv_cache=True: the cached rollout has ONE RoPE base, rope_starts must list exactly one "
+                             f"(t, h, w), got {len(rope_starts)}")
     if cond_latents is not None:
         pt = model.time_patch_size
         Tc = cond_latents.shape[2] if cond_latents.dim() == 5 else -1
@@ -161,6 +184,41 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
     # frame rollout: chunk after chunk of k token-frames, each with its own full Euler pass
     pt = model.time_patch_size
     n_frames = lat.shape[2] // pt
+    if kv_cache:
+        p = model.patch_size
+        nb = 2 if guided else 1
+        base = tuple(rope_starts[0]) if rope_starts is not None else model.rope.draw_start(
+            (n_frames, lat.shape[3] // p, lat.shape[4] // p))
+        cache = model.new_frame_cache(nb, n_frames, lat.shape[3] // p, lat.shape[4] // p, device=dev)
+        ctx = torch.cat([prompt_embeds, negative_embeds.to(dev, bf16)]) if guided else prompt_embeds
+        kw = {} if lens_c is None else {"context_lens": lens_cu if guided else lens_c}
+        reg = torch.ones(nb, dtype=f32, device=dev)
+
+        def chunk_call(f0, f1, t):
+            """the model on token-frames f0 .. f1 at noise level t, the frames before them read from the cache"""
+            x = lat[:, :, f0 * pt:f1 * pt]
+            tt = torch.full((nb, f1 - f0), float(t), device=dev).to(bf16)
+            return model(torch.cat([x, x]) if guided else x.contiguous(), ctx, tt,
+                         rope_start=(base[0] + f0, base[1], base[2]), register_timesteps=reg, frame_cache=cache, **kw)
+
+        if n_cond:
+            chunk_call(0, n_cond, 0.0)
+            cache.commit()
+        for f0 in range(n_cond, n_frames, k_roll):
+            f1 = min(f0 + k_roll, n_frames)
+            lat_c = lat[:, :, f0 * pt:f1 * pt].contiguous()
+            acc_c = acc[:, :, f0 * pt:f1 * pt].contiguous()
+            for i in range(inference_steps, 0, -1):
+                t, t_next = shifted_times(i, inference_steps)
+                out = chunk_call(f0, f1, t)
+                cond, uncond = (out[0:1].contiguous(), out[1:2].contiguous()) if guided else (out, None)
+                ops.cfg_euler_step(cond, uncond, acc_c, lat_c, cfg_scale, t - t_next)
+                lat[:, :, f0 * pt:f1 * pt] = lat_c
+                acc[:, :, f0 * pt:f1 * pt] = acc_c
+            if f1 < n_frames:
+                chunk_call(f0, f1, 0.0)  # the finished chunk's clean K / V
+                cache.commit()
+        return acc
     frame = torch.arange(n_frames, device=dev)
     for f0 in range(n_cond, n_frames, k_roll):
         f1 = min(f0 + k_roll, n_frames)
