@@ -284,6 +284,37 @@ int vds_attn_bwd_causal(const vds_attn_args* args, const vds_mod_groups* frames,
  * Lk != Lq + past or kv_pad_ones == 2: VDS_ERR_ARG; Lk > 2^21: VDS_ERR_UNSUPPORTED.  kv_pad_ones 0 and 1, every head dim
  * of the dispatcher and every vds_attn_set_variant setting have an instance.  Forward only. */
 int vds_attn_fwd_causal_past(const vds_attn_args* args, const vds_mod_groups* frames, int32_t past, vds_stream_t stream);
+/* Frame-major self-attention: vds_attn_fwd_causal / vds_attn_bwd_causal with a frame's rows contiguous, so that the key
+ * tiles the mask excludes are skipped, not computed.  Layout contract, with S = (L - lead) / period and fm / tok as under
+ * vds_qkv_rope_fwd_fm:
+ *   - q, k, v, dq, dk, dv, lse and the delta workspace are indexed by the FRAME-MAJOR row r: group(r) = 0 for r < lead,
+ *     1 + (r - lead) / S otherwise, and query r attends key j iff group(j) <= group(r) -- the mask above with the rows
+ *     permuted; the results are those of the interleaved calls on the permuted rows up to fp32 summation order.
+ *   - o and d_o are addressed by TOKEN row: row r of the computation is stored to / loaded from row tok(r) of o / d_o, in
+ *     the attention kernels and in the delta preprocess alike.  No extra pass over them is added; the map costs one fp32
+ *     quotient per row where the row pointer is formed (exact below 2^21 rows).
+ * What is skipped: a forward / dQ workgroup with query rows [q0, q1) runs its key loop to kend = lead if q1 <= lead, else
+ * lead + ((q1 - 1 - lead) / S + 1) * S; a dK/dV workgroup with key rows from k0 starts its query loop at the 64-row tile
+ * that holds qstart = 0 if k0 < lead, else lead + ((k0 - lead) / S) * S.  Inside the visited range an element is compared
+ * against its row's own bound (masked scores are -inf before the sub-block maxima, P = 0 exactly); a 32 x 32 sub-block in
+ * which every pair is attended -- all its keys below the kend of the wave's first query and no lead query in the wave,
+ * resp. its first query at or past the qstart of the wave's last key -- is branched around.  Key 0 is attended by every
+ * query: no empty row.  The profiler credits the FLOPs of the visited range.
+ * Every head dim of the dispatcher and kv_pad_ones 0 and 1 run.  Frame-major instances exist of the plain 32x32x16 kernels
+ * (attn_fwd_kernel, attn_bwd_dq_kernel, attn_bwd_dkv_kernel: every head dim) and, for the ones layout at head dim 72
+ * (kv_pad_ones = 1), of the 16x16x32 family -- attn_fwd16_kernel, attn_bwd_dq16_kernel with and without the folded
+ * preprocess, attn_bwd_dkv16_kernel -- selected by the same vds_attn_set_variant bits (attn_mfma16), attn_delta_fold knob
+ * and attn_fwd_wide rule (64 queries per wave from 2048 queries, or forced) as in vds_attn_*_causal.  The
+ * 64-queries-per-wave 32x32 forwards and the ones-column 32x32 kernels have no frame-major instance: where those settings
+ * would select one of them (variant bit off in the ones layout, attn_fwd_wide at head dims 64 / 96), the plain 32x32x16
+ * frame-major kernel runs instead, on the same rows.  The query range of the dK/dV kernel is never split.  The late query
+ * tiles of a head are issued first (knob attn_fm_heavy_first = 0: the plain order).
+ * frames == NULL, Lq != Lk or kv_pad_ones == 2: VDS_ERR_ARG; L > 2^21 rows, or a (batch, head) slice of o (backward: of d_o
+ * too) of 4 GiB or more -- L * o_sl * 2 >= 2^32 bytes, the token rows are reached through 32-bit byte offsets --:
+ * VDS_ERR_UNSUPPORTED.  lead and period travel by value (a captured graph replays them).  The workspace is that of
+ * vds_attn_bwd_workspace_bytes (2 B H L floats are used). */
+int vds_attn_fwd_causal_fm(const vds_attn_args* args, const vds_mod_groups* frames, vds_stream_t stream);
+int vds_attn_bwd_causal_fm(const vds_attn_args* args, const vds_mod_groups* frames, vds_stream_t stream);
 /* vds_rmsnorm_mod_fwd with mod f32 [B*G, ldmod]: the same arithmetic per row, y / rstd bit-identical to the per-sample
  * call run on the rows of one group with that group's mod row.  Every form of the dispatcher is covered. */
 int vds_rmsnorm_mod_fwd_grouped(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod,
@@ -366,6 +397,38 @@ int vds_qkv_rope_norm_bwd(const void* dq, const void* dk, const void* dv, const 
                           const float* sinb, const void* qkv_raw, const void* v0, const void* lam,
                           float* dv0_acc, float* dlam, void* dqkv, int32_t mix, int32_t add_dv0, int32_t B,
                           int32_t L, int32_t H, int32_t hd, int32_t hdp, float eps, vds_stream_t stream);
+/* Frame-major forms of the four calls above (frame-major self-attention).  Every token-major tensor -- qkv, qkv_raw, dqkv
+ * and the cos / sin table rows -- keeps the model's (h w t) row order; the head-major tensors q, k, v, dq, dk, dv, v0 and
+ * dv0_acc [B,H,L,hdp] are addressed with a frame's rows contiguous.  With frames = {lead, period} (validated against L as
+ * vds_mod_groups) and S = (L - lead) / period rows per frame, token row l lives at head row
+ *   fm(l) = l                                                        for l < lead,
+ *           lead + ((l - lead) % period) * S + (l - lead) / period   otherwise
+ * (the inverse: tok(r) = r for r < lead, lead + ((r - lead) % S) * period + (r - lead) / S otherwise).
+ *   forward:  token l reads table row l; its q / k / v head rows (pad and ones columns included) are written at row
+ *             fm(l), and v0 is read at row fm(l).
+ *   backward: dq / dk / dv, v0 and dv0_acc are read (dv0_acc updated, mix == 1) at row fm(l); dqkv row l is written.
+ * Arithmetic and rounding points are those of the plain calls: the outputs are the plain calls' outputs with the head rows
+ * permuted, bit for bit (dlam under vds_set_deterministic).  The token-tile forward writes one complete head row per
+ * (token, tensor, head) instead of a run of T rows, still 16 bytes per lane; the wave-per-token backward maps the row
+ * once per token; the element-wise kernels are the fallback under the same conditions and knobs as the plain calls.
+ * frames == NULL, a frames that does not fit L, or B, L, H <= 0: VDS_ERR_ARG.  No fp8-emitting form.  The plain calls
+ * launch none of the frame-major kernel instances. */
+int vds_qkv_rope_fwd_fm(const void* qkv, const float* cosb, const float* sinb, const void* v0,
+                        const void* lam, void* q, void* k, void* v, int32_t B, int32_t L, int32_t H,
+                        int32_t hd, int32_t hdp, const vds_mod_groups* frames, vds_stream_t stream);
+int vds_qkv_rope_norm_fwd_fm(const void* qkv, const float* cosb, const float* sinb, const void* v0,
+                             const void* lam, void* q, void* k, void* v, int32_t B, int32_t L, int32_t H,
+                             int32_t hd, int32_t hdp, float eps, const vds_mod_groups* frames, vds_stream_t stream);
+int vds_qkv_rope_bwd_fm(const void* dq, const void* dk, const void* dv, const float* cosb,
+                        const float* sinb, const void* qkv_raw, const void* v0, const void* lam,
+                        float* dv0_acc, float* dlam, void* dqkv, int32_t mix, int32_t add_dv0, int32_t B,
+                        int32_t L, int32_t H, int32_t hd, int32_t hdp, const vds_mod_groups* frames,
+                        vds_stream_t stream);
+int vds_qkv_rope_norm_bwd_fm(const void* dq, const void* dk, const void* dv, const float* cosb,
+                             const float* sinb, const void* qkv_raw, const void* v0, const void* lam,
+                             float* dv0_acc, float* dlam, void* dqkv, int32_t mix, int32_t add_dv0, int32_t B,
+                             int32_t L, int32_t H, int32_t hd, int32_t hdp, float eps, const vds_mod_groups* frames,
+                             vds_stream_t stream);
 /* residual-V (/root/reference/model.py:129-130, backward): out[b,h,l,:hd] (f32 [B,H,L,hdp]; + its old value when
  * accumulate != 0) = sum_i (1 - lam_i) dv_i[b,h,l,:hd] over n blocks.  dv / lam: HOST arrays of n DEVICE pointers (dv_i bf16
  * [B,H,L,hdp] contiguous, 16-byte aligned; lam_i one bf16).  Columns >= hd of out are not touched. */

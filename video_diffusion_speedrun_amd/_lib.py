@@ -96,6 +96,8 @@ SIGNATURES = {
     "vds_attn_bwd_kvlen": [C.POINTER(AttnArgs), c_vp, c_vp],
     "vds_attn_fwd_causal": [C.POINTER(AttnArgs), c_vp, c_vp],
     "vds_attn_bwd_causal": [C.POINTER(AttnArgs), c_vp, c_vp],
+    "vds_attn_fwd_causal_fm": [C.POINTER(AttnArgs), c_vp, c_vp],
+    "vds_attn_bwd_causal_fm": [C.POINTER(AttnArgs), c_vp, c_vp],
     "vds_attn_fwd_causal_past": [C.POINTER(AttnArgs), c_vp, c_i32, c_vp],
     "vds_attn_set_variant": [c_i32],
     "vds_kv_pad_ones": [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
@@ -123,6 +125,13 @@ SIGNATURES = {
                               c_vp],
     "vds_qkv_rope_norm_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
                               c_i32, c_i32, c_i32, c_i32, c_f32, c_vp],
+    "vds_qkv_rope_fwd_fm": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp],
+    "vds_qkv_rope_norm_fwd_fm": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32,
+                                 c_vp, c_vp],
+    "vds_qkv_rope_bwd_fm": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
+                            c_i32, c_i32, c_i32, c_i32, c_vp, c_vp],
+    "vds_qkv_rope_norm_bwd_fm": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
+                                 c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp],
     "vds_qkv_rope_fwd_cache": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32,
                                c_i32, c_i32, c_i32, c_i32, c_vp],
     "vds_qkv_rope_norm_fwd_cache": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32,

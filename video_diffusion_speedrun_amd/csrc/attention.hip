@@ -63,6 +63,9 @@ struct AttnP {
   int fc_lead, fc_period;
   // cached key rows behind the lead rows (vds_attn_fwd_causal_past): by value, read by the PAST forward instances only
   int fc_past;
+  // frame-major rows (vds_attn_*_causal_fm): rows per frame S = (L - lead) / period (>= 1) next to fc_lead / fc_period, and
+  // the heaviest-tiles-first order; by value, read by the FM instances of the kernels only
+  int fm_S, fm_rev;
 };
 
 // Keys of sample b.  KVLEN: kv_lens[b] clamped to [0, Lk] -- b is the same for the whole workgroup, so this is one
@@ -141,6 +144,69 @@ __device__ __forceinline__ void fc_zero_q(const FcMap& fm, int row0, int f, f32x
   for (int r = 0; r < 16; ++r)
     if (fm.x(row0 + (r & 3) + 8 * (r >> 2)) < f) { pm[r] = 0.f; ds[r] = 0.f; }
 }
+
+// Frame-major rows (FM instances, vds_attn_*_causal_fm).  q, k, v, dq, dk, dv, lse and delta rows are stored with a
+// frame's rows contiguous: row r belongs to group 0 (r < lead) or 1 + (r - lead) / S, and query r attends key j iff
+// group(j) <= group(r) -- the CAUSAL mask with the rows permuted.  The attended keys of a query are then a PREFIX of the
+// rows, [0, kend(r)), and the queries that attend a key a SUFFIX, [qstart(j), L): the element-wise compare is one integer
+// compare against a per-lane bound (one quotient per row, at the top of the kernel), a workgroup's loop runs over the
+// tiles below the largest bound of its rows only, and a sub-block below the smallest bound of a wave is attended without
+// any mask code.  o and d_o stay token-major: row r of the computation is row tok(r) of those tensors.
+// The quotient is FcMap's: trunc((r - lead + 0.5) / S) in fp32, exact while |r - lead| < 2^21.
+struct FmMap {
+  int lead, S, period;
+  float inv, hinv;
+  __device__ __forceinline__ explicit FmMap(const AttnP& p) : lead(p.fc_lead), S(p.fm_S), period(p.fc_period) {
+    inv = 1.0f / (float)p.fm_S;
+    hinv = 0.5f * inv;
+  }
+  __device__ __forceinline__ int frame(int r) const { return (int)__builtin_fmaf((float)(r - lead), inv, hinv); }  // r >= lead
+  // the first key row that query row r does not attend
+  __device__ __forceinline__ int kend(int r) const { return r < lead ? lead : lead + __mul24(frame(r) + 1, S); }
+  // the first query row that attends key row j
+  __device__ __forceinline__ int qstart(int j) const { return j < lead ? 0 : lead + __mul24(frame(j), S); }
+  // the token row of frame-major row r (o / d_o)
+  __device__ __forceinline__ int tok(int r) const {
+    if (r < lead) return r;
+    const int f = frame(r);
+    return lead + __mul24(r - lead - __mul24(f, S), period) + f;
+  }
+};
+__device__ __forceinline__ int fm_kend(const AttnP& p, int r) { return FmMap(p).kend(r); }
+__device__ __forceinline__ int fm_qstart(const AttnP& p, int j) { return FmMap(p).qstart(j); }
+// row of o / d_o that holds row r of the computation: tok(r) in the FM instances, r itself otherwise
+template <bool FM>
+__device__ __forceinline__ int out_row(const AttnP& p, int r) {
+  if constexpr (FM) return FmMap(p).tok(r);
+  else return r;
+}
+// keys of the workgroup whose query rows are [q0, q0 + rows): FM -- the largest kend of its rows (<= L); else Lk
+template <bool FM>
+__device__ __forceinline__ int fm_keys(const AttnP& p, int q0, int rows, int Lk) {
+  if constexpr (FM) return fm_kend(p, min(q0 + rows, p.Lq) - 1);
+  else return Lk;
+}
+// first 64-row query tile of the workgroup whose first key row is k0: FM -- the tile that holds qstart(k0); else dflt
+template <bool FM>
+__device__ __forceinline__ int fm_first_qtile(const AttnP& p, int k0, int dflt) {
+  if constexpr (FM) return fm_qstart(p, k0) >> 6;
+  else return dflt;
+}
+// 32x32 accumulator with the key on the registers (rows row0 + acc_row(r, 0)): `fill` at the keys from the lane's kend
+__device__ __forceinline__ void fm_fill(int row0, int kend, f32x16& s, float fill) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    if (row0 + (r & 3) + 8 * (r >> 2) >= kend) s[r] = fill;
+}
+// 32x32 accumulators with the QUERY on the registers: P and dS of the queries before the lane's qstart
+__device__ __forceinline__ void fm_zero_q(int row0, int qstart, f32x16& pm, f32x16& ds) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    if (row0 + (r & 3) + 8 * (r >> 2) < qstart) { pm[r] = 0.f; ds[r] = 0.f; }
+}
+// FM instances of the forward and dQ kernels: the row-tile order of a head is reversed, so that its longest workgroups
+// (the late query tiles) are issued first; the dK/dV kernel's natural order already starts with its longest (early keys)
+__device__ __forceinline__ int fm_tile(const AttnP& p, int rt) { return p.fm_rev ? p.n_rt - 1 - rt : rt; }
 
 // ---- LDS image (a): rows x HDP bf16, 8x32 sub-tiles of 512 B -------------------------------
 template <int HDP>
@@ -345,7 +411,10 @@ __device__ __forceinline__ void load_vfrags(bf16x8 (&vf)[2][NDB], const char* ti
 }
 
 // one 32-key sub-block of the lazy online softmax: s (scores, fp32) -> P fragments (bf16)
-template <int NDB>
+// OWN (the FM forward): inside the wave-uniform branch a lane raises its maximum only if its OWN row is over the threshold,
+// so a row's m, l and O never depend on what the other queries of its wave hold -- rows of later frames share waves with
+// rows of earlier ones there, and o / lse of a row must not move by a bit when a later frame's Q changes.
+template <int NDB, bool OWN = false>
 __device__ __forceinline__ void lazy_softmax(f32x16& s, float c, float& m, float& l, f32x16 (&o)[NDB],
                                              bf16x8 (&pf)[2]) {
   float mx = fmaxf(s[0], s[1]);
@@ -354,7 +423,7 @@ __device__ __forceinline__ void lazy_softmax(f32x16& s, float c, float& m, float
   mx = max_with_other_half(mx) * c;
   if (__builtin_amdgcn_ballot_w64(mx > m + LAZY_THR) != 0) {  // wave-uniform, rare
     asm volatile("; rescale" ::: "memory");  // keeps this a real branch (no if-conversion)
-    const float m_new = fmaxf(m, mx);
+    const float m_new = (!OWN || mx > m + LAZY_THR) ? fmaxf(m, mx) : m;
     const float alpha = __builtin_amdgcn_exp2f(m - m_new);
     m = m_new;
     l *= alpha;
@@ -421,6 +490,40 @@ struct DmaStage {
   }
 };
 
+// FM instances of the dK/dV kernels: the dO tile of the frame-major query rows row0 .. row0 + ROWS - 1 is gathered from
+// the token-major tensor, row r from row tok(r) (one quotient per 16-byte piece and tile); rows at or past Lq are sent
+// out of range (zeros) -- tok() of such a row may name a real one.
+template <int ROWS, int HDP, int IMG = 0>
+struct DmaStageFm {
+  static constexpr int PIECES = ROWS * HDP * 2 / 1024;
+  static constexpr int PER_WAVE = PIECES / 4;
+  int row[PER_WAVE];
+  unsigned chb[PER_WAVE];  // byte offset of this lane's 16-B chunk inside its row
+  bool valid[PER_WAVE];
+  __device__ __forceinline__ void init(int hd, int wave, int lane) {
+#pragma unroll
+    for (int i = 0; i < PER_WAVE; ++i) {
+      const int q = wave * PER_WAVE + i;
+      const int st = 2 * q + (lane >> 5);
+      const int w = lane & 31, r7 = w >> 2, cs = w & 3;
+      row[i] = (st / (HDP / 32)) * 8 + r7;
+      const int ch = (st % (HDP / 32)) * 4 + (cs ^ (IMG == 0 ? ((row[i] >> 2) & 3) : swz_t(row[i])));
+      chb[i] = (unsigned)(ch * 16);
+      valid[i] = ch * 8 < hd;
+    }
+  }
+  __device__ __forceinline__ void issue(srd_t rs, char* tile, int row0, long sl, const AttnP& p, int wave) const {
+    const unsigned base = lds_addr_of(tile) + wave * PER_WAVE * 1024;
+    const FmMap fm(p);
+#pragma unroll
+    for (int i = 0; i < PER_WAVE; ++i) {
+      const int r = row0 + row[i];
+      const unsigned off = (valid[i] && r < p.Lq) ? (unsigned)((long)fm.tok(r) * sl * 2) + chb[i] : 0xfffffff0u;
+      lds_dma16(rs, base + i * 1024, off);
+    }
+  }
+};
+
 // ---- forward kernel: lazy softmax + LDS-DMA staging (PIPE: explicit fragment prefetch) ---------
 // KVLEN (all forward kernels): sample b attends its first kv_lens[b] keys; the K / V bounds, the tile count and the
 // ragged-tile mask follow that count, and a sample without keys gets O = 0, lse = 0 before anything is staged.
@@ -428,17 +531,22 @@ struct DmaStage {
 // neither raise the running maximum nor get a nonzero P (their V rows are live, ones columns included).
 // PAST (with CAUSAL, all forward kernels): the keys are [lead | past | own] (fc_past_row); a 32-key sub-block that lies
 // wholly in the past skips the mask in every wave without a lead query.
-template <int HDP, int HDQ, int WPS, bool PIPE, bool KVLEN = false, bool CAUSAL = false, bool PAST = false>
+// FM (vds_attn_fwd_causal_fm; without KVLEN / CAUSAL / PAST): frame-major rows.  The key loop ends at the largest kend of
+// the workgroup's queries (the K / V bounds and the tile count follow it, the way KVLEN's count does), a sub-block is
+// compared against the lane's kend unless it lies below the kend of the wave's first query, and the o row goes to tok(row).
+template <int HDP, int HDQ, int WPS, bool PIPE, bool KVLEN = false, bool CAUSAL = false, bool PAST = false, bool FM = false>
 __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, TILE = 64 * HDP * 2;
+  static_assert(!FM || !(KVLEN || CAUSAL || PAST), "frame-major: its own mask");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int bh, qt;
   if (!decode_block(p.n_rt, p.tail_last, p.B * p.H, bh, qt)) return;
+  if constexpr (FM) qt = fm_tile(p, qt);
   const int b = bh / p.H, hh = bh % p.H;
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qrow = qt * 128 + wave * 32 + (lane & 31);
-  const int Lk = kv_len_of<KVLEN>(p, b);
+  const int Lk = fm_keys<FM>(p, qt * 128, 128, kv_len_of<KVLEN>(p, b));
   if constexpr (KVLEN) {
     if (Lk == 0) {  // no context: O = 0, lse = 0
       if (qrow < p.Lq) {
@@ -479,6 +587,12 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   int fcq = 0;
   if constexpr (CAUSAL) fcq = fm.fq(qrow);
   [[maybe_unused]] const int wq0 = qt * 128 + wave * 32;  // PAST: the wave's first query row
+  // FM: the lane's kend, and the wave's smallest (its first query's; 0 with a lead query in the wave: nothing is open)
+  [[maybe_unused]] int klim = 0, wklim = 0;
+  if constexpr (FM) {
+    klim = fm_kend(p, qrow);
+    wklim = wq0 >= p.fc_lead ? __builtin_amdgcn_readfirstlane(fm_kend(p, wq0)) : 0;
+  }
 #pragma unroll
   for (int ks = 0; ks < KSQ; ++ks) retire(qf[ks]);
   VDS_WAIT_VM(0);
@@ -505,6 +619,10 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
       load_vfrags<HDP, NDB>(v0, vt, 0, lane);
 #pragma unroll
       for (int ks = 0; ks < KSQ; ++ks) s1 = mfma32(k1[ks], qf[ks], s1);
+      if constexpr (FM) {  // (kend <= Lk: the compare covers the ragged tile too)
+        if (j * 64 + 32 > wklim) fm_fill(j * 64 + 4 * h, klim, s0, -INFINITY);
+        if (j * 64 + 64 > wklim) fm_fill(j * 64 + 32 + 4 * h, klim, s1, -INFINITY);
+      } else {
       if (ragged) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -519,8 +637,9 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
         fc_fill(fm, j * 64 + 4 * h, fcq, s0, -INFINITY);
         fc_fill(fm, j * 64 + 32 + 4 * h, fcq, s1, -INFINITY);
       }
+      }
       bf16x8 pf[2];
-      lazy_softmax<NDB>(s0, c, m, l, o, pf);
+      lazy_softmax<NDB, FM>(s0, c, m, l, o, pf);
       bf16x8 v1[2][NDB];
       load_vfrags<HDP, NDB>(v1, vt, 32, lane);
 #pragma unroll
@@ -528,7 +647,7 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
 #pragma unroll
         for (int db = 0; db < NDB; ++db) o[db] = mfma32(v0[s2][db], pf[s2], o[db]);
       bf16x8 pg[2];
-      lazy_softmax<NDB>(s1, c, m, l, o, pg);
+      lazy_softmax<NDB, FM>(s1, c, m, l, o, pg);
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
@@ -539,6 +658,9 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
         f32x16 s = zero16();
 #pragma unroll
         for (int ks = 0; ks < KSQ; ++ks) s = mfma32(frag_row<HDP>(kt, kb * 32, ks, lane), qf[ks], s);
+        if constexpr (FM) {
+          if (j * 64 + kb * 32 + 32 > wklim) fm_fill(j * 64 + kb * 32 + 4 * h, klim, s, -INFINITY);
+        } else {
         if (ragged) {
 #pragma unroll
           for (int r = 0; r < 16; ++r)
@@ -548,8 +670,9 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
           if (!fc_past_open(fm, p.fc_past, j * 64 + kb * 32, wq0))
             fc_fill_past(fm, p.fc_past, j * 64 + kb * 32 + 4 * h, fcq, s, -INFINITY);
         } else if constexpr (CAUSAL) fc_fill(fm, j * 64 + kb * 32 + 4 * h, fcq, s, -INFINITY);
+        }
         bf16x8 pf[2];
-        lazy_softmax<NDB>(s, c, m, l, o, pf);
+        lazy_softmax<NDB, FM>(s, c, m, l, o, pf);
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
@@ -567,7 +690,7 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
 
   const float lt = add_with_other_half(l);
   if (qrow < p.Lq) {
-    store_rows<NDB>(p.o + b * p.o_sb + hh * p.o_sh + (long)qrow * p.o_sl, o, 1.0f / lt, p.hd, h);
+    store_rows<NDB>(p.o + b * p.o_sb + hh * p.o_sh + (long)out_row<FM>(p, qrow) * p.o_sl, o, 1.0f / lt, p.hd, h);
     if (h == 0) p.lse[((long)b * p.H + hh) * p.Lq + qrow] = (m + __builtin_amdgcn_logf(lt)) * LN2;
   }
 }
@@ -791,6 +914,8 @@ __device__ __forceinline__ void annotate_q(const AttnP& p, int b, int hh, int q,
 // ndelta[b,h,q] = -sum_d dO[q,d] * O[q,d] and lse2 = lse * log2(e) (one wave per row; HBM-bound
 // preprocess).  Workspace layout: ndelta[0 .. rows) | lse2[rows .. 2 rows).  The NEGATED delta is
 // what the backward kernels load straight into the dP accumulators (dP - delta for free).
+// FM: the statistics (and lse) are indexed by the frame-major row, whose O / dO rows are those of token row tok(row).
+template <bool FM = false>
 __global__ void attn_delta_kernel(AttnP p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long rows = (long)p.B * p.H * p.Lq;
@@ -799,8 +924,8 @@ __global__ void attn_delta_kernel(AttnP p) {
   const int q = row % p.Lq;
   const int bh = row / p.Lq;
   const int b = bh / p.H, hh = bh % p.H;
-  const bf16_t* o = p.o + b * p.o_sb + hh * p.o_sh + (long)q * p.o_sl;
-  const bf16_t* d = p.d_o + b * p.do_sb + hh * p.do_sh + (long)q * p.do_sl;
+  const bf16_t* o = p.o + b * p.o_sb + hh * p.o_sh + (long)out_row<FM>(p, q) * p.o_sl;
+  const bf16_t* d = p.d_o + b * p.do_sb + hh * p.do_sh + (long)out_row<FM>(p, q) * p.do_sl;
   float acc = 0.f;
   for (int e = lane * 2; e < p.hd; e += 128) {
     const unsigned a = *reinterpret_cast<const unsigned*>(o + e);
@@ -819,12 +944,21 @@ __global__ void attn_delta_kernel(AttnP p) {
 // token-major fast path of the same preprocess: O and dO are [B*Lq, H*hd] row-major (what the model
 // passes), one wave per token reads both rows with 16-byte accesses; each 8-element chunk belongs
 // to one head (hd % 8 == 0), the per-chunk partial dots are folded per head through LDS.
+// FM: a wave still reads one TOKEN row of O and dO; its statistics go to the frame-major row fm(token row).
+template <bool FM = false>
 __global__ __launch_bounds__(256) void attn_delta_tokmajor_kernel(AttnP p) {
   __shared__ float part[4][192];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long tok = (long)blockIdx.x * 4 + wave;  // over B*Lq
   if (tok >= (long)p.B * p.Lq) return;
   const int b = (int)(tok / p.Lq), q = (int)(tok % p.Lq);
+  int sq = q;  // the row of lse / delta / q
+  if constexpr (FM) {
+    if (q >= p.fc_lead) {
+      const int x = q - p.fc_lead, f = x / p.fc_period;
+      sq = p.fc_lead + (x - f * p.fc_period) * p.fm_S + f;
+    }
+  }
   const int nch = p.H * p.hd / 8, cph = p.hd / 8;
   const bf16_t* o = p.o + b * p.o_sb + (long)q * p.o_sl;
   const bf16_t* d = p.d_o + b * p.do_sb + (long)q * p.do_sl;
@@ -851,11 +985,11 @@ __global__ __launch_bounds__(256) void attn_delta_tokmajor_kernel(AttnP p) {
     float acc = 0.f;
     for (int i = 0; i < cph; ++i) acc += part[wave][lane * cph + i];
     const long rows = (long)p.B * p.H * p.Lq;
-    const long row = ((long)b * p.H + lane) * p.Lq + q;
+    const long row = ((long)b * p.H + lane) * p.Lq + sq;
     const float l2 = p.lse[row] * LOG2E;
     p.delta[row] = -acc;
     p.delta[rows + row] = l2;
-    if (p.kv_pad_ones == 1) annotate_q(p, b, lane, q, l2);
+    if (p.kv_pad_ones == 1) annotate_q(p, b, lane, sq, l2);
   }
 }
 
@@ -868,19 +1002,24 @@ __global__ __launch_bounds__(256) void attn_delta_tokmajor_kernel(AttnP p) {
 // exp2, one multiply and the bf16 pack per element.  Keys past Lk need no mask in either mode.
 // KVLEN (all dQ kernels): the sweep covers the first kv_lens[b] keys of sample b; without keys dQ = 0.
 // CAUSAL (all dQ kernels): dS of the pairs the frame-causal mask excludes is set to zero (P = 0 exactly).
-template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false>
+// FM (vds_attn_bwd_causal_fm; the plain layout only): frame-major rows -- the key sweep ends at the largest kend of the
+// workgroup's queries, dS is zeroed from the lane's kend unless the sub-block lies below the kend of the wave's first query,
+// and the dO row is that of token row tok(row); q, dq and the statistics are indexed by the frame-major row.
+template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false, bool FM = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, TILE = 64 * HDP * 2;
   static_assert(!ONES || (HDP == 96 && HDQ == 80), "ones columns: head_dim 72 layout");
+  static_assert(!FM || !(ONES || KVLEN || CAUSAL), "frame-major: the plain layout, its own mask");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int bh, qt;
   if (!decode_block(p.n_rt, p.tail_last, p.B * p.H, bh, qt)) return;
+  if constexpr (FM) qt = fm_tile(p, qt);
   const int b = bh / p.H, hh = bh % p.H;
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qrow = qt * 128 + wave * 32 + (lane & 31);
   const int hd_kv = ONES ? p.hd + 8 : p.hd;
-  const int Lk = kv_len_of<KVLEN>(p, b);
+  const int Lk = fm_keys<FM>(p, qt * 128, 128, kv_len_of<KVLEN>(p, b));
   if constexpr (KVLEN) {
     if (Lk == 0) {  // no context: dQ = 0
       if (qrow < p.Lq) store_zero_rows<NDB>(p.dq + b * p.dq_sb + hh * p.dq_sh + (long)qrow * p.dq_sl, p.hd, h);
@@ -905,7 +1044,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   for (int ks = 0; ks < KSQ; ++ks) {
     const int e = ks * 16 + 8 * h;
     unsigned off = (unsigned)(((long)qrow * p.q_sl + e) * 2);
-    unsigned off2 = (unsigned)(((long)qrow * p.do_sl + e) * 2);
+    unsigned off2 = (unsigned)(((long)out_row<FM>(p, qrow) * p.do_sl + e) * 2);
     if (e >= p.hd) { off = 0xfffffff0u; off2 = 0xfffffff0u; }
     qf[ks] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rq, off, 0, 0));
     dof[ks] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rdo, off2, 0, 0));
@@ -941,6 +1080,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   const FcMap fm(p);
   int fcq = 0;
   if constexpr (CAUSAL) fcq = fm.fq(qrow);
+  [[maybe_unused]] int klim = 0, wklim = 0;  // FM: as in the forward kernel
+  if constexpr (FM) {
+    const int wq0 = qt * 128 + wave * 32;
+    klim = fm_kend(p, qrow);
+    wklim = wq0 >= p.fc_lead ? __builtin_amdgcn_readfirstlane(fm_kend(p, wq0)) : 0;
+  }
   VDS_WAIT_VM(0);
   __syncthreads();  // tile 0 landed
 
@@ -977,6 +1122,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
         for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r] * c - lse2) * dp[r];
       }
       if constexpr (CAUSAL) fc_fill(fm, j * 64 + kb * 32 + 4 * h, fcq, s, 0.f);
+      if constexpr (FM) {
+        if (j * 64 + kb * 32 + 32 > wklim) fm_fill(j * 64 + kb * 32 + 4 * h, klim, s, 0.f);
+      }
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
         const bf16x8 df = acc_frag(s, s2);
@@ -1010,9 +1158,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
 // workgroup that holds the boundary runs as usual and clears the accumulators of the rows past it before the store.
 // CAUSAL (both dK/dV kernels): P and dS of the pairs the frame-causal mask excludes are set to zero, so a key row sums
 // over the queries that attend it and nothing is cleared afterwards.
-template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false>
+// FM (vds_attn_bwd_causal_fm; the plain layout, no query split): frame-major rows -- the query sweep starts at the tile
+// that holds qstart of the workgroup's first key, P and dS are zeroed before the lane's qstart unless the sub-block starts
+// at or past the qstart of the wave's last key, and the dO tile is gathered from the token rows tok(row) (DmaStageFm).
+template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false, bool FM = false>
 __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void attn_bwd_dkv_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, Q_TILE = 64 * HDP * 2;
+  static_assert(!FM || !(ONES || KVLEN || CAUSAL), "frame-major: the plain layout, its own mask");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // LDS: [buf0: Q | dO][buf1: Q | dO][stats: 2 bufs x (lse2[64], delta[64])]
   char* qbuf = smem;
@@ -1055,14 +1207,17 @@ __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void att
   const srd_t rl2 = make_srd(p.delta + nrows + srow0, (unsigned)(p.Lq * 4));
   const float c = p.scale * LOG2E;
 
-  DmaStage<64, HDP> dq_, dd_;
+  DmaStage<64, HDP> dq_;
+  std::conditional_t<FM, DmaStageFm<64, HDP>, DmaStage<64, HDP>> dd_;
   dq_.init(p.q_sl, hd_q, wave, lane);
-  dd_.init(p.do_sl, p.hd, wave, lane);
+  if constexpr (FM) dd_.init(p.hd, wave, lane);
+  else dd_.init(p.do_sl, p.hd, wave, lane);
   const unsigned q_step = (unsigned)(64 * p.q_sl * 2), do_step = (unsigned)(64 * p.do_sl * 2);
   auto issue_tile = [&](int j, int par) {
     char* nb = qbuf + par * 2 * Q_TILE;
     dq_.issue(rq, nb, (unsigned)j * q_step, wave);
-    dd_.issue(rdo, nb + Q_TILE, (unsigned)j * do_step, wave);
+    if constexpr (FM) dd_.issue(rdo, nb + Q_TILE, j * 64, p.do_sl, p, wave);
+    else dd_.issue(rdo, nb + Q_TILE, (unsigned)j * do_step, wave);
     if (wave == 0) {  // 64 rows x 4 B each: lse2 then delta
       char* st = stats + par * 512;
       const unsigned sa = lds_addr_of(st);
@@ -1072,8 +1227,14 @@ __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void att
   };
   // this workgroup's query tiles [j0, j1) (all of them unless the query range is split)
   const int nqt_all = (p.Lq + 63) / 64, jper = (nqt_all + p.q_split - 1) / (p.q_split > 0 ? p.q_split : 1);
-  const int j0 = sp * jper, j1 = min(nqt_all, j0 + jper);
+  const int j0 = fm_first_qtile<FM>(p, key0, sp * jper), j1 = min(nqt_all, j0 + jper);
   issue_tile(j0, 0);
+  // FM: the lane's qstart, and the wave's largest (its last key's, the sequence's last row at most)
+  [[maybe_unused]] int qlim = 0, wqlim = 0;
+  if constexpr (FM) {
+    qlim = fm_qstart(p, krow);
+    wqlim = __builtin_amdgcn_readfirstlane(fm_qstart(p, min(key0 + wave * 32 + 31, p.Lk - 1)));
+  }
 
   // this lane's key row as B-operand fragments (rows past Lk / columns past hd read as zero)
   bf16x8 kf[KSQ], vf[KSQ];
@@ -1153,6 +1314,9 @@ __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void att
       if constexpr (CAUSAL) {  // (the map and the lane's key are loop-invariant: hoisted by the compiler)
         const FcMap fm(p);
         fc_zero_q(fm, j * 64 + qb * 32 + 4 * h, fm.fk(krow), pm, s);
+      }
+      if constexpr (FM) {
+        if (j * 64 + qb * 32 < wqlim) fm_zero_q(j * 64 + qb * 32 + 4 * h, qlim, pm, s);
       }
       PRIO_HI();
 #pragma unroll
@@ -1240,9 +1404,13 @@ __device__ __forceinline__ bf16x8 pack2(const f32x4& a, const f32x4& b) {
 // KVLEN: as in attn_bwd_dkv_kernel; 16-key blocks past kv_lens[b] are not computed at all (NKB).
 // CAUSAL: a lane holds one key per 16-key block (fk fixed) and its registers walk the queries 16 rb + 4 g + r of the
 // sub-block: x(query) is formed once per register and serves both key blocks; P and dS of excluded pairs become zero.
-template <int HDP, bool QPAD = true, bool KVLEN = false, bool CAUSAL = false>
+// FM (vds_attn_bwd_causal_fm, ones layout): as attn_bwd_dkv_kernel's -- the query sweep starts at the tile that holds qstart
+// of the workgroup's first key, a lane compares the query row of each register against the qstart of its two keys unless
+// the sub-block starts at or past the qstart of the wave's last key, and the dO tile is gathered from the token rows.
+template <int HDP, bool QPAD = true, bool KVLEN = false, bool CAUSAL = false, bool FM = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv16_kernel(AttnP p) {
   static_assert(HDP == 96, "head_dim 72 layout (ones columns at 72, 73)");
+  static_assert(!FM || (QPAD && !KVLEN && !CAUSAL), "frame-major: the ones layout, its own mask");
   constexpr int KS = HDP / 32, NDB = 5, Q_TILE = 64 * HDP * 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* qbuf = smem;
@@ -1277,14 +1445,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv16_kernel(AttnP p) {
   const srd_t rl2 = make_srd(p.delta + nrows + srow0, (unsigned)(p.Lq * 4));
   const float c = p.scale * LOG2E;
 
-  DmaStage<64, HDP, 1> dq_, dd_;
+  DmaStage<64, HDP, 1> dq_;
+  std::conditional_t<FM, DmaStageFm<64, HDP, 1>, DmaStage<64, HDP, 1>> dd_;
   dq_.init(p.q_sl, hd_q, wave, lane);
-  dd_.init(p.do_sl, p.hd, wave, lane);
+  if constexpr (FM) dd_.init(p.hd, wave, lane);
+  else dd_.init(p.do_sl, p.hd, wave, lane);
   const unsigned q_step = (unsigned)(64 * p.q_sl * 2), do_step = (unsigned)(64 * p.do_sl * 2);
   auto issue_tile = [&](int j, int par) {
     char* nb = qbuf + par * 2 * Q_TILE;
     dq_.issue(rq, nb, (unsigned)j * q_step, wave);
-    dd_.issue(rdo, nb + Q_TILE, (unsigned)j * do_step, wave);
+    if constexpr (FM) dd_.issue(rdo, nb + Q_TILE, j * 64, p.do_sl, p, wave);
+    else dd_.issue(rdo, nb + Q_TILE, (unsigned)j * do_step, wave);
     if (wave == 0) {
       char* st = stats + par * 512;
       const unsigned sa = lds_addr_of(st);
@@ -1292,7 +1463,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv16_kernel(AttnP p) {
       lds_dma4(rdl, sa + 256, (unsigned)((j * 64 + lane) * 4));
     }
   };
-  issue_tile(0, 0);
+  const int j0 = fm_first_qtile<FM>(p, kt_idx * 128, 0);  // first query tile of the sweep (0 unless FM)
+  issue_tile(j0, 0);
+  // FM: qstart of the lane's two keys, and the wave's largest (its last key's, the sequence's last row at most)
+  [[maybe_unused]] int qlim[2] = {0, 0}, wqlim = 0;
+  if constexpr (FM) {
+    qlim[0] = fm_qstart(p, key0 + (lane & 15));
+    qlim[1] = fm_qstart(p, key0 + 16 + (lane & 15));
+    wqlim = __builtin_amdgcn_readfirstlane(fm_qstart(p, min(key0 + 31, p.Lk - 1)));
+  }
 
   // the two 16-key blocks of this wave as B operands: lane (c = l & 15, g) holds columns 32 ks + 8 g .. + 7 of key c
   bf16x8 kf[2][KS], vf[2][KS];
@@ -1388,6 +1567,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv16_kernel(AttnP p) {
               if (xq < fck[cb]) { s[rb][cb][r] = 0.f; dp[rb][cb][r] = 0.f; }
           }
       }
+      if constexpr (FM) {
+        if (j * 64 + qb * 32 < wqlim) {
+#pragma unroll
+          for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int qr = j * 64 + qb * 32 + rb * 16 + 4 * g + r;
+#pragma unroll
+              for (int cb = 0; cb < NKB; ++cb)
+                if (qr < qlim[cb]) { s[rb][cb][r] = 0.f; dp[rb][cb][r] = 0.f; }
+            }
+        }
+      }
       bf16x8 pf[2], df[2];
 #pragma unroll
       for (int cb = 0; cb < NKB; ++cb) {
@@ -1411,7 +1603,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv16_kernel(AttnP p) {
     __syncthreads();
   };
   auto run = [&](auto NKBT) {
-    for (int j = 0; j < nqt; j += 2) {
+    for (int j = j0; j < nqt; j += 2) {
       q_tile(j, std::integral_constant<int, 0>{}, NKBT);
       if (j + 1 < nqt) q_tile(j + 1, std::integral_constant<int, 1>{}, NKBT);
     }
@@ -1459,19 +1651,25 @@ __device__ __forceinline__ float max_over_lane_groups(float x) {  // max over th
 
 // CAUSAL: a lane holds one query per 16-query block (fq fixed) and its registers walk the keys 16 rb + 4 g + r of the
 // sub-block: x(key) is formed once per register and serves all four query blocks.
-template <int HDP, bool KVLEN = false, bool CAUSAL = false, bool PAST = false>
+// FM (vds_attn_fwd_causal_fm, ones layout): as attn_fwd_kernel's -- the key loop ends at the largest kend of the
+// workgroup's 256 queries, a lane compares the key row of each register against the kend of its four queries unless the
+// sub-block lies below the kend of the wave's first query, the o row goes to tok(row), and a query's running maximum is
+// raised only when its OWN scores cross the threshold (rows of several frames share a wave).
+template <int HDP, bool KVLEN = false, bool CAUSAL = false, bool PAST = false, bool FM = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
   static_assert(HDP == 96, "head_dim 72 layout (ones columns at 72, 73 / 72, 76)");
+  static_assert(!FM || !(KVLEN || CAUSAL || PAST), "frame-major: its own mask");
   constexpr int KS = HDP / 32, NDB = 5, TILE = 64 * HDP * 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int bh, qt;
   if (!decode_block(p.n_rt, p.tail_last, p.B * p.H, bh, qt)) return;
+  if constexpr (FM) qt = fm_tile(p, qt);
   const int b = bh / p.H, hh = bh % p.H;
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qrow0 = qt * 256 + wave * 64 + (lane & 15);  // query of block 0; block cb = + 16 cb
   const int hd_kv = p.hd + 8;
-  const int Lk = kv_len_of<KVLEN>(p, b);
+  const int Lk = fm_keys<FM>(p, qt * 256, 256, kv_len_of<KVLEN>(p, b));
   if constexpr (KVLEN) {
     if (Lk == 0) {  // no context: O = 0, lse = 0 (all 64 lanes call the store: it exchanges lanes)
 #pragma unroll
@@ -1524,6 +1722,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
     for (int cb = 0; cb < 4; ++cb) fcq[cb] = fm.fq(qrow0 + 16 * cb);
   }
   [[maybe_unused]] const int wq0 = qt * 256 + wave * 64;  // PAST: the wave's first query row
+  [[maybe_unused]] int klim[4] = {0, 0, 0, 0}, wklim = 0;  // FM: kend of the lane's queries; the wave's smallest (0: none open)
+  if constexpr (FM) {
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) klim[cb] = fm_kend(p, qrow0 + 16 * cb);
+    wklim = wq0 >= p.fc_lead ? __builtin_amdgcn_readfirstlane(fm_kend(p, wq0)) : 0;
+  }
   VDS_WAIT_VM(0);
   __syncthreads();
 
@@ -1586,6 +1790,19 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
               if (xk > fcq[cb]) s[rb][cb][r] = -INFINITY;
           }
       }
+      if constexpr (FM) {
+        if (j * 64 + kb * 32 + 32 > wklim) {
+#pragma unroll
+          for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int key = j * 64 + kb * 32 + rb * 16 + 4 * g + r;
+#pragma unroll
+              for (int cb = 0; cb < NCB; ++cb)
+                if (key >= klim[cb]) s[rb][cb][r] = -INFINITY;
+            }
+        }
+      }
       const bool first = (j == 0) && (kb == 0);
       float mx[4];
 #pragma unroll
@@ -1605,7 +1822,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
           const float mxf = max_over_lane_groups(mx[cb]);  // all four lanes of a query agree
-          const float m_new = bf2f(f2bf(m[cb] + (first ? mxf : fmaxf(mxf, 0.f))));
+          float m_new = bf2f(f2bf(m[cb] + (first ? mxf : fmaxf(mxf, 0.f))));
+          if constexpr (FM) {
+            if (!first && !(mxf > LAZY_THR)) m_new = m[cb];  // only the query's own scores move its maximum
+          }
           const float delta = m_new - m[cb];
           const float alpha = first ? 1.0f : __builtin_amdgcn_exp2f(-delta);
           m[cb] = m_new;
@@ -1661,7 +1881,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
     for (int db = 0; db < NDB; ++db)
 #pragma unroll
       for (int e = 0; e < 4; ++e) vo[db][e] = o[db][cb][e];
-    store_block_bf16_t(vo, 1.0f / lt, p.o + b * p.o_sb + hh * p.o_sh + (long)qrow * p.o_sl, p.hd, g, qrow < p.Lq, p.wide_o);
+    store_block_bf16_t(vo, 1.0f / lt, p.o + b * p.o_sb + hh * p.o_sh + (long)out_row<FM>(p, qrow) * p.o_sl, p.hd, g, qrow < p.Lq,
+                       p.wide_o);
     if (qrow < p.Lq && g == 0) p.lse[((long)b * p.H + hh) * p.Lq + qrow] = (m[cb] + __builtin_amdgcn_logf(lt)) * LN2;
   }
 }
@@ -1679,19 +1900,25 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
 // two cross-lane adds), writes -delta and lse * log2(e) to the workspace and the (hi, lo) pair of -lse2 into the pad of its
 // Q row -- what attn_delta_*_kernel did in a pass of its own over O and dO (6.5 ms per C3b step).  The host then runs this
 // kernel BEFORE the dK/dV kernel, which reads those statistics.
-template <int HDP, bool FOLD = false, bool KVLEN = false, bool CAUSAL = false>
+// FM (vds_attn_bwd_causal_fm, ones layout): as attn_bwd_dq_kernel's -- the key sweep ends at the largest kend of the
+// workgroup's queries, dS is zeroed from the kend of the lane's queries unless the sub-block lies below the kend of the wave's
+// first query, and the dO row -- with FOLD the O row too -- is that of token row tok(row); q, dq, the statistics written by
+// FOLD and the annotated q pad are indexed by the frame-major row.
+template <int HDP, bool FOLD = false, bool KVLEN = false, bool CAUSAL = false, bool FM = false>
 __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
   static_assert(HDP == 96, "head_dim 72 layout");
+  static_assert(!FM || !(KVLEN || CAUSAL), "frame-major: its own mask");
   constexpr int KS = HDP / 32, NDB = 5, TILE = 64 * HDP * 2, NQ = 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int bh, qt;
   if (!decode_block(p.n_rt, p.tail_last, p.B * p.H, bh, qt)) return;
+  if constexpr (FM) qt = fm_tile(p, qt);
   const int b = bh / p.H, hh = bh % p.H;
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qrow0 = qt * (64 * NQ) + wave * (16 * NQ) + (lane & 15);  // query of column block 0; block cb = + 16 cb
   const int hd_kv = p.hd + 8;
-  const int Lk = kv_len_of<KVLEN>(p, b);
+  const int Lk = fm_keys<FM>(p, qt * (64 * NQ), 64 * NQ, kv_len_of<KVLEN>(p, b));
   if constexpr (KVLEN) {
     // no context: dQ = 0.  (FOLD: the statistics of this sample stay unwritten -- every dK/dV workgroup of a sample
     // without keys leaves before it reads them)
@@ -1726,7 +1953,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
     for (int ks = 0; ks < KS; ++ks) {
       const int e = ks * 32 + 8 * g;
       unsigned off = (unsigned)(((long)qrow * p.q_sl + e) * 2);
-      unsigned off2 = (unsigned)(((long)qrow * p.do_sl + e) * 2);
+      unsigned off2 = (unsigned)(((long)out_row<FM>(p, qrow) * p.do_sl + e) * 2);
       if (e >= p.hd) { off = 0xfffffff0u; off2 = 0xfffffff0u; }
       qf[cb][ks] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rq, off, 0, 0));
       dof[cb][ks] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rdo, off2, 0, 0));
@@ -1739,7 +1966,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         const int e = ks * 32 + 8 * g;
-        const unsigned off3 = e >= p.hd ? 0xfffffff0u : (unsigned)(((long)qrow * p.o_sl + e) * 2);
+        const unsigned off3 = e >= p.hd ? 0xfffffff0u : (unsigned)(((long)out_row<FM>(p, qrow) * p.o_sl + e) * 2);
         const bf16x8 of = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(ro, off3, 0, 0));
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc = __builtin_fmaf((float)of[j], (float)dof[cb][ks][j], acc);
@@ -1781,6 +2008,13 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
   if constexpr (CAUSAL) {
 #pragma unroll
     for (int cb = 0; cb < NQ; ++cb) fcq[cb] = fm.fq(qrow0 + 16 * cb);
+  }
+  [[maybe_unused]] int klim[NQ] = {0, 0}, wklim = 0;  // FM: as in attn_fwd16_kernel
+  if constexpr (FM) {
+    const int wq0 = qt * (64 * NQ) + wave * (16 * NQ);
+#pragma unroll
+    for (int cb = 0; cb < NQ; ++cb) klim[cb] = fm_kend(p, qrow0 + 16 * cb);
+    wklim = wq0 >= p.fc_lead ? __builtin_amdgcn_readfirstlane(fm_kend(p, wq0)) : 0;
   }
   VDS_WAIT_VM(0);
   __syncthreads();  // tile 0 landed
@@ -1839,6 +2073,19 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
             for (int cb = 0; cb < NCB; ++cb)
               if (xk > fcq[cb]) s[rb][cb][r] = 0.f;
           }
+      }
+      if constexpr (FM) {
+        if (j * 64 + kb * 32 + 32 > wklim) {
+#pragma unroll
+          for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int key = j * 64 + kb * 32 + rb * 16 + 4 * g + r;
+#pragma unroll
+              for (int cb = 0; cb < NCB; ++cb)
+                if (key >= klim[cb]) s[rb][cb][r] = 0.f;
+            }
+        }
       }
       bf16x8 df[NQ];
 #pragma unroll
@@ -1903,6 +2150,8 @@ AttnP to_p(const vds_attn_args* a) {
   p.fc_lead = 0;
   p.fc_period = 1;
   p.fc_past = 0;
+  p.fm_S = 1;
+  p.fm_rev = 0;
   const bool wide_on = vdscfg::geti(vdscfg::ATTN_WIDE_STORES) != 0;  // A/B knob
   p.wide_o = wide_on && p.hd > 64 && rows16(p.o, p.o_sb, p.o_sh, p.o_sl);
   p.wide_dq = wide_on && p.hd > 64 && rows16(p.dq, p.dq_sb, p.dq_sh, p.dq_sl);
@@ -2066,9 +2315,9 @@ int run_bwd(AttnP p, hipStream_t s, size_t ws_floats) {
     const bool tokmajor = p.o_sh == p.hd && p.do_sh == p.hd && p.o_sl == (long)p.H * p.hd && p.do_sl == p.o_sl &&
                           (p.o_sl & 7) == 0 && (p.o_sb & 7) == 0 && (p.do_sb & 7) == 0 && p.H * p.hd <= 1536 && p.H <= 64;
     if (tokmajor)
-      hipLaunchKernelGGL(attn_delta_tokmajor_kernel, dim3((unsigned)(((long)p.B * p.Lq + 3) / 4)), dim3(256), 0, s, p);
+      hipLaunchKernelGGL(attn_delta_tokmajor_kernel<false>, dim3((unsigned)(((long)p.B * p.Lq + 3) / 4)), dim3(256), 0, s, p);
     else
-      hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, p);
+      hipLaunchKernelGGL(attn_delta_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, p);
   }
   // (a 64-keys-per-wave, one-wave-per-SIMD variant of this kernel -- half the LDS reads per MFMA -- was
   // measured at 0.55-0.8x: hipcc's single-wave schedule does not overlap the VALU softmax with the MFMAs)
@@ -2331,6 +2580,194 @@ extern "C" int vds_attn_fwd_causal_past(const vds_attn_args* a, const vds_mod_gr
     case 80: return run_fwd<96, 80, false, true, true>(p, s);
     case 96: return run_fwd<96, 96, false, true, true>(p, s);
     case 128: return run_fwd<128, 128, false, true, true>(p, s);
+    default: return VDS_ERR_UNSUPPORTED;
+  }
+}
+
+// ---- frame-major self-attention (include/vds.h) -----------------------------------------------------------------------
+// FM instances exist of the plain 32x32x16 kernels (every head dim; kv_pad_ones 0, and 1 where a 16x16x32 kernel is
+// switched off: the pad columns are not read) and, for the ones layout at head dim 72, of the 16x16x32 family --
+// attn_fwd16_kernel, attn_bwd_dq16_kernel with and without FOLD, attn_bwd_dkv16_kernel -- under the same attn_mfma16 bits
+// (vds_attn_set_variant), attn_delta_fold knob and attn_fwd_wide rule as their CAUSAL siblings.  There is no frame-major
+// instance of the 64-queries-per-wave 32x32 forwards nor of the ones-column 32x32 kernels: where the interleaved dispatcher
+// would take one of those, this one takes the plain 32x32x16 FM kernel.  The query range of the dK/dV kernel is never split.
+namespace {
+int fm_kend_host(int r, int lead, int S) { return r < lead ? lead : lead + ((r - lead) / S + 1) * S; }
+int fm_qstart_host(int j, int lead, int S) { return j < lead ? 0 : lead + ((j - lead) / S) * S; }
+// (query, key) pairs the forward / dQ kernels visit: `tile` queries per workgroup, keys [0, kend of its last query)
+double fm_pairs_q(int L, int lead, int S, int tile) {
+  double n = 0;
+  for (int q0 = 0; q0 < L; q0 += tile) {
+    const int q1 = q0 + tile < L ? q0 + tile : L;
+    n += (double)(q1 - q0) * fm_kend_host(q1 - 1, lead, S);
+  }
+  return n;
+}
+// ... and the dK/dV kernel: `tile` keys per workgroup, queries from the 64-row tile that holds qstart of its first key
+double fm_pairs_k(int L, int lead, int S, int tile) {
+  double n = 0;
+  for (int k0 = 0; k0 < L; k0 += tile) {
+    const int k1 = k0 + tile < L ? k0 + tile : L;
+    n += (double)(k1 - k0) * (L - (fm_qstart_host(k0, lead, S) & ~63));
+  }
+  return n;
+}
+
+// the profiler credits the pairs of the key range actually visited, not the unmasked L x L
+template <int HDP, int HDQ>
+int run_fwd_fm(AttnP p, hipStream_t s) {
+  constexpr int LDS = 4 * 64 * HDP * 2;
+  static bool once = false;
+  if (!once) {
+    set_lds(attn_fwd_kernel<HDP, HDQ, 2, true, false, false, false, true>, LDS);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd16_kernel<HDP, false, false, false, true>, LDS);
+    once = true;
+  }
+  if constexpr (HDP == 96 && HDQ == 80) {
+    // the ones layout on the 16x16x32 forward, where the interleaved dispatcher takes it: 64 queries per wave by the
+    // attn_fwd_wide rule (0 / 1 forces, 2: from 2048 queries) and bit 2 of the variant mask
+    const int wide = vdscfg::geti(vdscfg::ATTN_FWD_WIDE);
+    if (p.kv_pad_ones == 1 && p.hd == 72 && (attn_variant() & 4) && (wide == 1 || (wide == 2 && p.Lq >= 2048))) {
+      p.n_rt = cdiv(p.Lq, 256);
+      p.tail_last = tail_last_for(p.Lq, 256);
+      const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
+      const double fl = 4.0 * p.B * p.H * p.hd * fm_pairs_q(p.Lq, p.fc_lead, p.fm_S, 256);
+      vdsprof::Scope ps(VDS_PROF_ATTN_FWD, s, fl, 2.0 * p.B * p.H * p.hd * (2.0 * p.Lq + 2.0 * p.Lk));
+      hipLaunchKernelGGL((attn_fwd16_kernel<HDP, false, false, false, true>), dim3(grid), dim3(256), LDS, s, p);
+      return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
+    }
+  }
+  p.n_rt = cdiv(p.Lq, 128);
+  p.tail_last = tail_last_for(p.Lq, 128);
+  const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
+  const double fl = 4.0 * p.B * p.H * p.hd * fm_pairs_q(p.Lq, p.fc_lead, p.fm_S, 128);
+  vdsprof::Scope ps(VDS_PROF_ATTN_FWD_PLAIN, s, fl, 2.0 * p.B * p.H * p.hd * (2.0 * p.Lq + 2.0 * p.Lk));
+  hipLaunchKernelGGL((attn_fwd_kernel<HDP, HDQ, 2, true, false, false, false, true>), dim3(grid), dim3(256), LDS, s, p);
+  return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
+}
+
+template <int HDP, int HDQ>
+int run_bwd_fm(AttnP p, hipStream_t s) {
+  constexpr int LDS_DQ = 4 * 64 * HDP * 2;
+  constexpr int LDS_DKV = 4 * 64 * HDP * 2 + 2 * 128 * 4;
+  static bool once = false;
+  if (!once) {
+    set_lds(attn_bwd_dq_kernel<HDP, HDQ, false, false, false, true>, LDS_DQ);
+    set_lds(attn_bwd_dkv_kernel<HDP, HDQ, false, false, false, true>, LDS_DKV);
+    if constexpr (HDP == 96 && HDQ == 80) {
+      set_lds(attn_bwd_dkv16_kernel<HDP, true, false, false, true>, LDS_DKV);
+      set_lds(attn_bwd_dq16_kernel<HDP, false, false, false, true>, LDS_DQ);
+      set_lds(attn_bwd_dq16_kernel<HDP, true, false, false, true>, LDS_DQ);
+    }
+    once = true;
+  }
+  const long rows = (long)p.B * p.H * p.Lq;
+  const double per = 2.0 * p.B * p.H * p.hd;  // FLOPs of one product per (query, key) pair
+  const double qb = 2.0 * p.B * p.H * p.hd * (double)p.Lq, kb = qb;
+  // the ones layout at head dim 72: the 16x16x32 kernels under the variant bits of their CAUSAL siblings (bit 0 dK/dV, bit 1
+  // dQ; with attn_delta_fold the dQ kernel is its own preprocess and runs first)
+  bool ones = false;
+  if constexpr (HDP == 96 && HDQ == 80) ones = p.kv_pad_ones == 1 && p.hd == 72;
+  const bool dq16 = ones && (attn_variant() & 2), dkv16 = ones && (attn_variant() & 1);
+  const bool fold = dq16 && vdscfg::geti(vdscfg::ATTN_DELTA_FOLD);
+  auto launch_dq = [&]() {
+    p.n_rt = cdiv(p.Lq, 128);
+    p.tail_last = tail_last_for(p.Lq, 128);
+    const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
+    vdsprof::Scope ps(ones ? VDS_PROF_ATTN_BWD_DQ : VDS_PROF_ATTN_BWD_DQ_PLAIN, s,
+                      2.0 * per * fm_pairs_q(p.Lq, p.fc_lead, p.fm_S, 128), (fold ? 4.0 : 3.0) * qb + 2.0 * kb);
+    if constexpr (HDP == 96 && HDQ == 80) {
+      if (fold) {
+        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, true, false, false, true>), dim3(grid), dim3(256), LDS_DQ, s, p);
+        return;
+      }
+      if (dq16) {
+        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, false, false, false, true>), dim3(grid), dim3(256), LDS_DQ, s, p);
+        return;
+      }
+    }
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, HDQ, false, false, false, true>), dim3(grid), dim3(256), LDS_DQ, s, p);
+  };
+  if (fold) launch_dq();
+  else {
+    vdsprof::Scope ps(VDS_PROF_ATTN_BWD_DELTA, s, 2.0 * rows * p.hd, 2.0 * qb);
+    const bool tokmajor = p.o_sh == p.hd && p.do_sh == p.hd && p.o_sl == (long)p.H * p.hd && p.do_sl == p.o_sl &&
+                          (p.o_sl & 7) == 0 && (p.o_sb & 7) == 0 && (p.do_sb & 7) == 0 && p.H * p.hd <= 1536 && p.H <= 64;
+    if (tokmajor)
+      hipLaunchKernelGGL(attn_delta_tokmajor_kernel<true>, dim3((unsigned)(((long)p.B * p.Lq + 3) / 4)), dim3(256), 0, s, p);
+    else
+      hipLaunchKernelGGL(attn_delta_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, p);
+  }
+  p.n_rt = cdiv(p.Lk, 128);
+  p.tail_last = tail_last_for(p.Lk, 128);
+  {
+    const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
+    vdsprof::Scope ps(ones ? VDS_PROF_ATTN_BWD_DKV : VDS_PROF_ATTN_BWD_DKV_PLAIN, s,
+                      2.0 * per * fm_pairs_k(p.Lq, p.fc_lead, p.fm_S, 128), 2.0 * qb + 4.0 * kb);
+    bool done = false;
+    if constexpr (HDP == 96 && HDQ == 80) {
+      if (dkv16) {
+        hipLaunchKernelGGL((attn_bwd_dkv16_kernel<HDP, true, false, false, true>), dim3(grid), dim3(256), LDS_DKV, s, p);
+        done = true;
+      }
+    }
+    if (!done) hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, false, false, false, true>), dim3(grid), dim3(256), LDS_DKV, s, p);
+  }
+  if (!fold) launch_dq();
+  return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
+}
+
+int fm_check(const vds_attn_args* a, const vds_mod_groups* f, bool bwd) {
+  if (!f || a->Lq != a->Lk || a->kv_pad_ones == 2) return VDS_ERR_ARG;
+  if (f->lead < 0 || f->period < 1 || a->Lq < f->lead || (a->Lq - f->lead) % f->period != 0) return VDS_ERR_ARG;
+  if (a->Lq > (1 << 21)) return VDS_ERR_UNSUPPORTED;  // FmMap: the fp32 quotient is exact below 2^21 rows
+  // the token rows of o / d_o are reached through 32-bit byte offsets (tok(r) * row stride * 2): a (b, h) slice of them
+  // has to stay below 4 GiB
+  const int64_t lim = (int64_t)1 << 32;
+  if ((int64_t)a->Lq * a->o_sl * 2 >= lim || (bwd && (int64_t)a->Lq * a->do_sl * 2 >= lim)) return VDS_ERR_UNSUPPORTED;
+  return VDS_OK;
+}
+void fm_set(AttnP& p, const vds_mod_groups* f) {
+  p.fc_lead = f->lead;
+  p.fc_period = f->period;
+  const int S = (p.Lq - f->lead) / f->period;
+  p.fm_S = S > 0 ? S : 1;  // (no token rows: every row is a lead row and the quotient is never taken)
+  p.fm_rev = vdscfg::geti(vdscfg::ATTN_FM_HEAVY_FIRST) ? 1 : 0;
+}
+}  // namespace
+
+extern "C" int vds_attn_fwd_causal_fm(const vds_attn_args* a, const vds_mod_groups* frames, vds_stream_t stream) {
+  if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse || a->Lq <= 0 || a->Lk <= 0) return VDS_ERR_ARG;
+  if (!strides_ok(a, false)) return VDS_ERR_ARG;
+  if (const int e = fm_check(a, frames, false)) return e;
+  AttnP p = to_p(a);
+  fm_set(p, frames);
+  hipStream_t s = (hipStream_t)stream;
+  switch (kernel_instance(a->head_dim)) {
+    case 32: return run_fwd_fm<32, 32>(p, s);
+    case 64: return run_fwd_fm<64, 64>(p, s);
+    case 80: return run_fwd_fm<96, 80>(p, s);
+    case 96: return run_fwd_fm<96, 96>(p, s);
+    case 128: return run_fwd_fm<128, 128>(p, s);
+    default: return VDS_ERR_UNSUPPORTED;
+  }
+}
+
+extern "C" int vds_attn_bwd_causal_fm(const vds_attn_args* a, const vds_mod_groups* frames, vds_stream_t stream) {
+  if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse || !a->d_o || !a->dq || !a->dk || !a->dv || !a->delta || a->Lq <= 0 ||
+      a->Lk <= 0)
+    return VDS_ERR_ARG;
+  if (!strides_ok(a, true)) return VDS_ERR_ARG;
+  if (const int e = fm_check(a, frames, true)) return e;
+  AttnP p = to_p(a);
+  fm_set(p, frames);
+  hipStream_t s = (hipStream_t)stream;
+  switch (kernel_instance(a->head_dim)) {
+    case 32: return run_bwd_fm<32, 32>(p, s);
+    case 64: return run_bwd_fm<64, 64>(p, s);
+    case 80: return run_bwd_fm<96, 80>(p, s);
+    case 96: return run_bwd_fm<96, 96>(p, s);
+    case 128: return run_bwd_fm<128, 128>(p, s);
     default: return VDS_ERR_UNSUPPORTED;
   }
 }

@@ -24,6 +24,7 @@ enum Knob {
   ATTN_QSPLIT,       // VDS_ATTN_QSPLIT: 0 = rule (default) | 1 = off | N = force N query splits of the plain dK/dV kernel
   CROSS_DKV16,       // VDS_CROSS_DKV16: cross-attention dK/dV on the 16x16x32 kernel: 0 never | 1 when the grid fills the chip
                      // (default) | 2 always
+  ATTN_FM_HEAVY_FIRST,  // VDS_ATTN_FM_HEAVY_FIRST: frame-major forward / dQ: a head's late (longest) query tiles are issued first (default 1)
   ATTN8_DQ_WAVES,    // VDS_ATTN8_DQ_WAVES: waves per workgroup of the fp8 dQ kernel: 4 (default) | 6
   // ---- row kernels (csrc/elementwise.hip)
   EW_MIN_ROWS,       // VDS_EW_MIN_ROWS: floor of the rows per workgroup of the row kernels (default 8: 8, and 32 from 8192 rows)

@@ -25,6 +25,7 @@ const Def kDefs[N_KNOBS] = {
     {"attn_wide_stores", "VDS_ATTN_WIDE_STORES", 1},
     {"attn_qsplit", "VDS_ATTN_QSPLIT", 0},
     {"cross_dkv16", "VDS_CROSS_DKV16", 1},
+    {"attn_fm_heavy_first", "VDS_ATTN_FM_HEAVY_FIRST", 1},
     {"attn8_dq_waves", "VDS_ATTN8_DQ_WAVES", 4},
     {"ew_min_rows", "VDS_EW_MIN_ROWS", 8},
     {"ew_wgs", "VDS_EW_WGS", 768},

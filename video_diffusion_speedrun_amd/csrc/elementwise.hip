@@ -519,17 +519,31 @@ __global__ __launch_bounds__(256) void det_finish_scalar_kernel(const float* par
   if (threadIdx.x == 0) target[0] += (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// ---- frame-major head rows (vds_qkv_rope_*_fm) --------------------------------------------------------------------------
+// The FM instances of the qkv / RoPE kernels below keep every token-major tensor (qkv, dqkv, the RoPE table rows) in the
+// model's (h w t) order and address the head-major ones -- q, k, v, dq, dk, dv, v0, dv0_acc -- with a frame's rows
+// contiguous: token row l of a sample lives at head row fm(l) = l for the `lead` rows, else
+// lead + ((l - lead) % period) * S + (l - lead) / period with S = (L - lead) / period rows per frame.  FM = false is the
+// kernel as it always was: every use of the map is behind `if constexpr (FM)`; FmRows is the last argument of both
+// instances (zeros in the plain launches).
+struct FmRows { int lead, period, S; };
+__device__ __forceinline__ int fm_row(int l, FmRows f) {
+  if (l < f.lead) return l;
+  const int x = l - f.lead, s = x / f.period;
+  return f.lead + (x - s * f.period) * f.S + s;
+}
+
 // ------------------------------------------------- qkv split + RoPE + residual-V (fwd) ---
 // model.py:126-134,266-275.  One thread = 4 elements d..d+3 of the first half of one head of
 // one token and their rotation partners d+hd/2.. (hd/2 is a multiple of 4 for 64/72/128).
 // NORM (QK-norm, vds_qkv_rope_norm_fwd): q and k head rows go through a weightless RMSNorm first -- x * rsqrt(mean_d x^2
 // + eps) in fp32, rounded to bf16 -- and the rotation takes that.  Every thread of a head sums the head row's squares
 // itself, in column order (this is the fallback form: the token-tile kernel below shares the sums through LDS).
-template <bool NORM = false>
+template <bool NORM = false, bool FM = false>
 __global__ __launch_bounds__(256) void qkv_rope_fwd_kernel(const bf16_t* qkv, const float* cosb, const float* sinb,
                                                            const bf16_t* v0, const bf16_t* lamp, bf16_t* q,
                                                            bf16_t* k, bf16_t* v, int B, int L, int H, int hd,
-                                                           int hdp, float eps) {
+                                                           int hdp, float eps, FmRows fr) {
   const int upt = H * (hd >> 3);
   const long gid = (long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long)B * L * upt) return;
@@ -539,7 +553,9 @@ __global__ __launch_bounds__(256) void qkv_rope_fwd_kernel(const bf16_t* qkv, co
   const int b = (int)(tok / L), l = (int)(tok % L);
   const int D = H * hd;
   const bf16_t* src = qkv + tok * 3 * D + hh * hd + 4 * i;
-  const long dst = (((long)b * H + hh) * L + l) * hdp + 4 * i;
+  int lr = l;  // the head row of token l
+  if constexpr (FM) lr = fm_row(l, fr);
+  const long dst = (((long)b * H + hh) * L + lr) * hdp + 4 * i;
   const f32x4 c4 = *reinterpret_cast<const f32x4*>(cosb + (long)l * half + 4 * i);
   const f32x4 s4 = *reinterpret_cast<const f32x4*>(sinb + (long)l * half + 4 * i);
 #pragma unroll
@@ -602,7 +618,7 @@ __global__ __launch_bounds__(256) void qkv_rope_fwd_kernel(const bf16_t* qkv, co
   // subtract delta inside the dO V^T MFMA (backward).  Consumers without the flag ignore the pad.
   const int npad = (hdp - hd) >> 2;
   if (i < npad) {
-    const long pd = (((long)b * H + hh) * L + l) * hdp + hd + 4 * i;
+    const long pd = (((long)b * H + hh) * L + lr) * hdp + hd + 4 * i;
     const u32x2 z = {0u, 0u};
     const u32x2 one = {0x3f80u, 0u}, one2 = {0x3f803f80u, 0u};
     const bool ones = (hdp - hd) >= 8;
@@ -708,11 +724,14 @@ __global__ __launch_bounds__(256) void qkv_rope_fwd_cache_kernel(const bf16_t* q
 // NORM (QK-norm): the nt * 2H values rsqrt(mean_d x^2 + eps) of the staged q / k head rows are computed from LDS into a
 // small array behind the rows (ropestage::row_rstd), and the rotation pass scales and rounds each element before it
 // rotates: no byte more of global traffic than the plain instance.
-template <int HD, int HDP, int T, bool NORM = false>
+// FM (vds_qkv_rope_*_fm): the head rows of consecutive tokens are S rows apart, so every (tensor, head) run of T rows
+// becomes T single-row stores of one complete head row each (HDP * 2 contiguous bytes, 16 per lane); the staging, the
+// rotation and the table rows are the plain instance's.
+template <int HD, int HDP, int T, bool NORM = false, bool FM = false>
 __global__ __launch_bounds__(256) void qkv_rope_fwd_tile_kernel(const bf16_t* qkv, const float* cosb, const float* sinb,
                                                                 const bf16_t* v0, const bf16_t* lamp, bf16_t* q,
                                                                 bf16_t* k, bf16_t* v, long ntok, int L, int H,
-                                                                float eps) {
+                                                                float eps, FmRows fr) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -739,6 +758,7 @@ __global__ __launch_bounds__(256) void qkv_rope_fwd_tile_kernel(const bf16_t* qk
   constexpr int CPR = HDP >> 3, DCH = HD >> 3;
   constexpr bool ONES = (HDP - HD) >= 8;
   const ropestage::Div by_nt((unsigned)nt), by_h((unsigned)H);
+  [[maybe_unused]] const ropestage::Div by_p(FM ? (unsigned)fr.period : 1u);
   const int b0 = (int)(tok0 / L), l0 = (int)(tok0 % L);
   const int nch = nt * 3 * H * CPR;
   for (int u = tid; u < nch; u += 256) {
@@ -748,6 +768,13 @@ __global__ __launch_bounds__(256) void qkv_rope_fwd_tile_kernel(const bf16_t* qk
     const unsigned tensor = by_h.div(r, hh);
     int l = l0 + (int)t, b = b0;
     if (l >= L) { l -= L; ++b; }
+    if constexpr (FM) {
+      if (l >= fr.lead) {  // fm_row with the reciprocal quotient (the host keeps L below 2^22 for this form)
+        unsigned x;
+        const unsigned s = by_p.div((unsigned)(l - fr.lead), x);
+        l = fr.lead + (int)x * fr.S + (int)s;
+      }
+    }
     const long dst = (((long)b * H + hh) * L + l) * HDP + 8 * c;
     u32x4 w = {0u, 0u, 0u, 0u};
     if (c < DCH) {
@@ -799,13 +826,13 @@ __global__ __launch_bounds__(256) void rope_apply_kernel(const bf16_t* x, long x
 // NORM (QK-norm, vds_qkv_rope_norm_bwd): with g = the inverse rotation of dq (fp32), x = the raw q row of qkv_raw,
 // r = rsqrt(mean_d x^2 + eps) and y = x r, the kernel writes bf16(r (g - y mean_d(g y))) -- one rounding; the same for k.
 // Every thread of a head walks the whole head row for the two sums, in column order (fallback form).
-template <bool NORM = false>
+template <bool NORM = false, bool FM = false>
 __global__ __launch_bounds__(256) void qkv_rope_bwd_kernel(const bf16_t* dq, const bf16_t* dk, const bf16_t* dv,
                                                            const float* cosb, const float* sinb,
                                                            const bf16_t* qkv_raw, const bf16_t* v0,
                                                            const bf16_t* lamp, float* dv0_acc, float* dlam,
                                                            bf16_t* dqkv, int mix, int add_dv0, int B, int L, int H,
-                                                           int hd, int hdp, float* det, float eps) {
+                                                           int hd, int hdp, float* det, float eps, FmRows fr) {
   __shared__ float red[4];
   const int upt = H * (hd >> 3);
   const long gid = (long)blockIdx.x * 256 + threadIdx.x;
@@ -817,7 +844,9 @@ __global__ __launch_bounds__(256) void qkv_rope_bwd_kernel(const bf16_t* dq, con
     const int b = (int)(tok / L), l = (int)(tok % L);
     const int D = H * hd;
     bf16_t* dstp = dqkv + tok * 3 * D + hh * hd + 4 * i;
-    const long src = (((long)b * H + hh) * L + l) * hdp + 4 * i;
+    int lr = l;  // the head row of token l
+    if constexpr (FM) lr = fm_row(l, fr);
+    const long src = (((long)b * H + hh) * L + lr) * hdp + 4 * i;
     const f32x4 c4 = *reinterpret_cast<const f32x4*>(cosb + (long)l * half + 4 * i);
     const f32x4 s4 = *reinterpret_cast<const f32x4*>(sinb + (long)l * half + 4 * i);
 #pragma unroll
@@ -835,7 +864,7 @@ __global__ __launch_bounds__(256) void qkv_rope_bwd_kernel(const bf16_t* dq, con
       }
       if constexpr (NORM) {
         const bf16_t* xrow = qkv_raw + tok * 3 * D + which * D + hh * hd;
-        const bf16_t* grow = (which == 0 ? dq : dk) + (((long)b * H + hh) * L + l) * hdp;
+        const bf16_t* grow = (which == 0 ? dq : dk) + (((long)b * H + hh) * L + lr) * hdp;
         float ss = 0.f, gx = 0.f;
         for (int d = 0; d < half; d += 4) {
           const f32x4 cc = *reinterpret_cast<const f32x4*>(cosb + (long)l * half + d);
@@ -934,15 +963,18 @@ __global__ __launch_bounds__(256) void qkv_rope_bwd_kernel(const bf16_t* dq, con
 // hd/8 chunks -- 9 at head_dim 72, not a power-of-two lane group -- so the partials meet in LDS, not in a butterfly: they
 // overwrite the wave's dq copy (16 bytes per chunk: the same D * 2 bytes; every partner read is done by then), and each
 // lane adds the hd/8 partials of its head in chunk order.  The result r (g - x r^2 mean_d(g x)) is rounded once.
-template <int NI, int QF = -1, bool NORM = false>
+// FM (vds_qkv_rope_*_bwd_fm; bf16 output only): the token's dq / dk / dv, v0 and dv0_acc head rows are those of row fm(l)
+// -- one wave-uniform map per token -- and the [3D] output row stays the token's.
+template <int NI, int QF = -1, bool NORM = false, bool FM = false>
 __global__ __launch_bounds__(256) void qkv_rope_bwd_tok_kernel(const bf16_t* dq, const bf16_t* dk, const bf16_t* dv,
                                                                const float* cosb, const float* sinb,
                                                                const bf16_t* qkv_raw, const bf16_t* v0,
                                                                const bf16_t* lamp, float* dv0_acc, float* dlam,
                                                                bf16_t* dqkv, int mix, int add_dv0, int B, int L,
                                                                int H, int hd, int hdp, QOut qo, float* det,
-                                                               float eps) {
+                                                               float eps, FmRows fr) {
   static_assert(!NORM || QF < 0, "the normed backward writes bf16");
+  static_assert(!FM || QF < 0, "the frame-major backward writes bf16");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ float red[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -953,6 +985,8 @@ __global__ __launch_bounds__(256) void qkv_rope_bwd_tok_kernel(const bf16_t* dq,
   if constexpr (QF >= 0) qs.init(qo, blockIdx.x == 0 && threadIdx.x == 0, tok);
   if (live) {
     const int b = (int)(tok / L), l = (int)(tok % L);
+    int lr = l;  // the head row of token l
+    if constexpr (FM) lr = fm_row(l, fr);
     const int D = H * hd, nch = D >> 3, cph = hd >> 3, half = hd >> 1;
     const int wstride = 2 * D * 2 + 2 * half * 4;
     char* wq = smem + wave * wstride;
@@ -966,7 +1000,7 @@ __global__ __launch_bounds__(256) void qkv_rope_bwd_tok_kernel(const bf16_t* dq,
       const int c = lane + 64 * i;
       if (c < nch) {
         const int hh = c / cph, j = c % cph;
-        const long so = (((long)b * H + hh) * L + l) * hdp + 8 * j;
+        const long so = (((long)b * H + hh) * L + lr) * hdp + 8 * j;
         rq[i] = ld_stream<16>(dq + so);
         rk[i] = ld_stream<16>(dk + so);
         *reinterpret_cast<u32x4*>(wq + c * 16) = rq[i];
@@ -1044,7 +1078,7 @@ __global__ __launch_bounds__(256) void qkv_rope_bwd_tok_kernel(const bf16_t* dq,
       const int c = lane + 64 * i;
       if (c >= nch) continue;
       const int hh = c / cph, j = c % cph;
-      const long so = (((long)b * H + hh) * L + l) * hdp + 8 * j;
+      const long so = (((long)b * H + hh) * L + lr) * hdp + 8 * j;
       float gq[8], gk[8], oq[8], ok_[8];
       if constexpr (NORM) {
         f32x4 acc = *reinterpret_cast<const f32x4*>(wq + (hh * cph) * 16);
@@ -2012,33 +2046,43 @@ static bool rope_tok_form(int H, int hd, int hdp) {
   return on && (hdp & 7) == 0 && (hd & 7) == 0 && H * hd <= 2048;
 }
 
+// FmRows of a frame-major call (frames checked by the caller: groups_ok)
+static FmRows fm_rows_of(const vds_mod_groups* f, int L) { return FmRows{f->lead, f->period, (L - f->lead) / f->period}; }
+
 // NORM = false: vds_qkv_rope_fwd (launches the instances without the flag only); true: vds_qkv_rope_norm_fwd
-template <bool NORM>
+// FM = false: the plain calls (the instances without the flag only); true: vds_qkv_rope_fwd_fm / _norm_fwd_fm -- the same
+// conditions and knobs pick the form, on the instances that map the head rows
+template <bool NORM, bool FM = false>
 static int qkv_rope_fwd_impl(const void* qkv, const float* cosb, const float* sinb, const void* v0, const void* lam,
                              void* q, void* k, void* v, int32_t B, int32_t L, int32_t H, int32_t hd, int32_t hdp,
-                             float eps, vds_stream_t stream) {
+                             float eps, vds_stream_t stream, const vds_mod_groups* frames = nullptr) {
   if (!qkv || !cosb || !sinb || !q || !k || !v || (hd & 7) || hdp < hd || (hdp & 3)) return VDS_ERR_ARG;
   if (v0 && !lam) return VDS_ERR_ARG;
+  FmRows fr{0, 0, 0};
+  if constexpr (FM) {
+    if (!frames || B <= 0 || L <= 0 || H <= 0 || !groups_ok(frames, L)) return VDS_ERR_ARG;
+    fr = fm_rows_of(frames, L);
+  }
   if (((hdp - hd) >> 2) > (hd >> 3)) return VDS_ERR_UNSUPPORTED;
   const long n = (long)B * L * H * (hd >> 3);
   vdsprof::Scope ps(VDS_PROF_QKV_ROPE_FWD, (hipStream_t)stream, 0.0, (v0 ? 14.0 : 12.0) * B * L * H * hd);
   // token-tile kernel (16-byte accesses, LDS staging) for the head sizes the model builds; knob rope_tile = 0 keeps the
   // element-wise kernel (A/B), 2 | 4 | 8 picks the tokens per workgroup
   const int tile = vdscfg::geti(vdscfg::ROPE_TILE);
-  if (tile > 0 && H * hd <= 2048 && H <= 256 && L >= 8) {
+  if (tile > 0 && H * hd <= 2048 && H <= 256 && L >= 8 && (!FM || L <= (1 << 22))) {
     const long ntok = (long)B * L;
 #define ROPE_TILE(HD, HDP, T)                                                                                      \
   do {                                                                                                             \
     const int lds = ropestage::lds_bytes(T, H * HD) + (NORM ? T * 2 * H * 4 : 0); /* + the rows' rsqrt values */    \
     static bool attr = false;                                                                                      \
     if (!attr) {                                                                                                   \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qkv_rope_fwd_tile_kernel<HD, HDP, T, NORM>),        \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qkv_rope_fwd_tile_kernel<HD, HDP, T, NORM, FM>),    \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                           \
       attr = true;                                                                                                 \
     }                                                                                                              \
-    hipLaunchKernelGGL((qkv_rope_fwd_tile_kernel<HD, HDP, T, NORM>), dim3((unsigned)((ntok + T - 1) / T)),         \
+    hipLaunchKernelGGL((qkv_rope_fwd_tile_kernel<HD, HDP, T, NORM, FM>), dim3((unsigned)((ntok + T - 1) / T)),     \
                        dim3(256), lds, (hipStream_t)stream, (const bf16_t*)qkv, cosb, sinb, (const bf16_t*)v0,     \
-                       (const bf16_t*)lam, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v, ntok, L, H, eps);                   \
+                       (const bf16_t*)lam, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v, ntok, L, H, eps, fr);               \
     return ok();                                                                                                   \
   } while (0)
 #define ROPE_TILE_T(HD, HDP)                       \
@@ -2055,9 +2099,9 @@ static int qkv_rope_fwd_impl(const void* qkv, const float* cosb, const float* si
 #undef ROPE_TILE_T
 #undef ROPE_TILE
   }
-  hipLaunchKernelGGL(qkv_rope_fwd_kernel<NORM>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL((qkv_rope_fwd_kernel<NORM, FM>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)qkv, cosb, sinb, (const bf16_t*)v0, (const bf16_t*)lam, (bf16_t*)q, (bf16_t*)k,
-                     (bf16_t*)v, B, L, H, hd, hdp, eps);
+                     (bf16_t*)v, B, L, H, hd, hdp, eps, fr);
   return ok();
 }
 extern "C" int vds_qkv_rope_fwd(const void* qkv, const float* cosb, const float* sinb, const void* v0,
@@ -2071,6 +2115,19 @@ extern "C" int vds_qkv_rope_norm_fwd(const void* qkv, const float* cosb, const f
                                      int32_t hd, int32_t hdp, float eps, vds_stream_t stream) {
   if (!(eps > 0.f)) return VDS_ERR_ARG;
   return qkv_rope_fwd_impl<true>(qkv, cosb, sinb, v0, lam, q, k, v, B, L, H, hd, hdp, eps, stream);
+}
+// frame-major forms: the q / k / v head rows of token l are written, and the v0 row read, at row fm(l) (include/vds.h)
+extern "C" int vds_qkv_rope_fwd_fm(const void* qkv, const float* cosb, const float* sinb, const void* v0,
+                                   const void* lam, void* q, void* k, void* v, int32_t B, int32_t L, int32_t H,
+                                   int32_t hd, int32_t hdp, const vds_mod_groups* frames, vds_stream_t stream) {
+  return qkv_rope_fwd_impl<false, true>(qkv, cosb, sinb, v0, lam, q, k, v, B, L, H, hd, hdp, 0.f, stream, frames);
+}
+extern "C" int vds_qkv_rope_norm_fwd_fm(const void* qkv, const float* cosb, const float* sinb, const void* v0,
+                                        const void* lam, void* q, void* k, void* v, int32_t B, int32_t L, int32_t H,
+                                        int32_t hd, int32_t hdp, float eps, const vds_mod_groups* frames,
+                                        vds_stream_t stream) {
+  if (!(eps > 0.f)) return VDS_ERR_ARG;
+  return qkv_rope_fwd_impl<true, true>(qkv, cosb, sinb, v0, lam, q, k, v, B, L, H, hd, hdp, eps, stream, frames);
 }
 
 // cache forms: k / v rows (and the v0 rows read) at b * kv_sb + h * kv_sh + (l < lead ? l : l + past) * kv_sl
@@ -2169,12 +2226,18 @@ extern "C" int vds_dv0_reduce(const void* const* dv, const void* const* lam, int
   return ok();
 }
 
-template <bool NORM>
+// FM: as in qkv_rope_fwd_impl (vds_qkv_rope_bwd_fm / _norm_bwd_fm)
+template <bool NORM, bool FM = false>
 static int qkv_rope_bwd_impl(const void* dq, const void* dk, const void* dv, const float* cosb, const float* sinb,
                              const void* qkv_raw, const void* v0, const void* lam, float* dv0_acc, float* dlam,
                              void* dqkv, int32_t mix, int32_t add_dv0, int32_t B, int32_t L, int32_t H, int32_t hd,
-                             int32_t hdp, float eps, vds_stream_t stream) {
+                             int32_t hdp, float eps, vds_stream_t stream, const vds_mod_groups* frames = nullptr) {
   if (!dq || !dk || !dv || !cosb || !sinb || !dqkv || (hd & 7)) return VDS_ERR_ARG;
+  FmRows fr{0, 0, 0};
+  if constexpr (FM) {
+    if (!frames || B <= 0 || L <= 0 || H <= 0 || !groups_ok(frames, L)) return VDS_ERR_ARG;
+    fr = fm_rows_of(frames, L);
+  }
   if (mix && (!qkv_raw || !v0 || !lam || !dlam || (mix == 1 && !dv0_acc) || mix < 0 || mix > 2)) return VDS_ERR_ARG;
   if (add_dv0 && !dv0_acc) return VDS_ERR_ARG;
   const long n = (long)B * L * H * (hd >> 3);
@@ -2182,26 +2245,28 @@ static int qkv_rope_bwd_impl(const void* dq, const void* dk, const void* dv, con
   const bool tok = rope_tok_form(H, hd, hdp);
   const unsigned nblk = tok ? (unsigned)(((long)B * L + 3) / 4) : (unsigned)((n + 255) / 256);
   float* det = nullptr;  // deterministic mode: the lambda gradient as per-workgroup partials + one fixed-order sum
-  if (mix && vdsdet::on() && !(det = vdsdet::workspace(nblk, NORM ? "vds_qkv_rope_norm_bwd" : "vds_qkv_rope_bwd")))
+  if (mix && vdsdet::on() &&
+      !(det = vdsdet::workspace(nblk, FM ? (NORM ? "vds_qkv_rope_norm_bwd_fm" : "vds_qkv_rope_bwd_fm")
+                                         : (NORM ? "vds_qkv_rope_norm_bwd" : "vds_qkv_rope_bwd"))))
     return VDS_ERR_ARG;
   if (tok) {
     const int D = H * hd, lds = 4 * (4 * D + 4 * hd);
     const dim3 grid(nblk);
 #define ROPE_BWD(NI)                                                                                                \
-  hipLaunchKernelGGL((qkv_rope_bwd_tok_kernel<NI, -1, NORM>), grid, dim3(256), lds, (hipStream_t)stream,           \
+  hipLaunchKernelGGL((qkv_rope_bwd_tok_kernel<NI, -1, NORM, FM>), grid, dim3(256), lds, (hipStream_t)stream,       \
                      (const bf16_t*)dq, (const bf16_t*)dk, (const bf16_t*)dv, cosb, sinb, (const bf16_t*)qkv_raw,  \
                      (const bf16_t*)v0, (const bf16_t*)lam, dv0_acc, dlam, (bf16_t*)dqkv, mix, add_dv0, B, L, H,   \
-                     hd, hdp, QOut{}, det, eps)
+                     hd, hdp, QOut{}, det, eps, fr)
     if (D <= 512) ROPE_BWD(1);
     else if (D <= 1024) ROPE_BWD(2);
     else if (D <= 1536) ROPE_BWD(3);
     else ROPE_BWD(4);
 #undef ROPE_BWD
   } else {
-    hipLaunchKernelGGL(qkv_rope_bwd_kernel<NORM>, dim3(nblk), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL((qkv_rope_bwd_kernel<NORM, FM>), dim3(nblk), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)dq, (const bf16_t*)dk, (const bf16_t*)dv, cosb, sinb, (const bf16_t*)qkv_raw,
                        (const bf16_t*)v0, (const bf16_t*)lam, dv0_acc, dlam, (bf16_t*)dqkv, mix, add_dv0, B, L, H, hd, hdp, det,
-                       eps);
+                       eps, fr);
   }
   if (det) hipLaunchKernelGGL(det_finish_scalar_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)det, (int)nblk, dlam);
   return ok();
@@ -2221,6 +2286,24 @@ extern "C" int vds_qkv_rope_norm_bwd(const void* dq, const void* dk, const void*
   if (!qkv_raw || !(eps > 0.f)) return VDS_ERR_ARG;
   return qkv_rope_bwd_impl<true>(dq, dk, dv, cosb, sinb, qkv_raw, v0, lam, dv0_acc, dlam, dqkv, mix, add_dv0, B, L, H,
                                  hd, hdp, eps, stream);
+}
+// frame-major forms: dq / dk / dv, v0 and dv0_acc are read (dv0_acc updated) at row fm(l), dqkv row l is written
+extern "C" int vds_qkv_rope_bwd_fm(const void* dq, const void* dk, const void* dv, const float* cosb,
+                                   const float* sinb, const void* qkv_raw, const void* v0, const void* lam,
+                                   float* dv0_acc, float* dlam, void* dqkv, int32_t mix, int32_t add_dv0, int32_t B,
+                                   int32_t L, int32_t H, int32_t hd, int32_t hdp, const vds_mod_groups* frames,
+                                   vds_stream_t stream) {
+  return qkv_rope_bwd_impl<false, true>(dq, dk, dv, cosb, sinb, qkv_raw, v0, lam, dv0_acc, dlam, dqkv, mix, add_dv0, B,
+                                        L, H, hd, hdp, 0.f, stream, frames);
+}
+extern "C" int vds_qkv_rope_norm_bwd_fm(const void* dq, const void* dk, const void* dv, const float* cosb,
+                                        const float* sinb, const void* qkv_raw, const void* v0, const void* lam,
+                                        float* dv0_acc, float* dlam, void* dqkv, int32_t mix, int32_t add_dv0,
+                                        int32_t B, int32_t L, int32_t H, int32_t hd, int32_t hdp, float eps,
+                                        const vds_mod_groups* frames, vds_stream_t stream) {
+  if (!qkv_raw || !(eps > 0.f)) return VDS_ERR_ARG;
+  return qkv_rope_bwd_impl<true, true>(dq, dk, dv, cosb, sinb, qkv_raw, v0, lam, dv0_acc, dlam, dqkv, mix, add_dv0, B,
+                                       L, H, hd, hdp, eps, stream, frames);
 }
 
 // as vds_qkv_rope_bwd, the [B*L, 3D] result written as fp8 (wave-per-token kernel only)
@@ -2243,7 +2326,8 @@ extern "C" int vds_qkv_rope_bwd_fp8(const void* dq, const void* dk, const void* 
 #define ROPE_BWD_Q(NI, F)                                                                                             \
   hipLaunchKernelGGL((qkv_rope_bwd_tok_kernel<NI, F>), grid, dim3(256), lds, (hipStream_t)stream, (const bf16_t*)dq, \
                      (const bf16_t*)dk, (const bf16_t*)dv, cosb, sinb, (const bf16_t*)qkv_raw, (const bf16_t*)v0,    \
-                     (const bf16_t*)lam, dv0_acc, dlam, (bf16_t*)nullptr, mix, add_dv0, B, L, H, hd, hdp, qo, det, 0.f)
+                     (const bf16_t*)lam, dv0_acc, dlam, (bf16_t*)nullptr, mix, add_dv0, B, L, H, hd, hdp, qo, det, 0.f, \
+                     FmRows{0, 0, 0})
 #define ROPE_BWD_F(F)              \
   do {                             \
     if (D <= 512) ROPE_BWD_Q(1, F); \

@@ -351,7 +351,7 @@ class DiTBlock(nn.Module):
     drives the same two methods for all blocks inside its own whole-model node."""
 
     def __init__(self, hidden_size, cross_attn_input_size, num_heads, mlp_ratio=4.0, qkv_bias=True,
-                 residual_v=False, *, frame_causal=False, qk_norm=False):
+                 residual_v=False, *, frame_causal=False, frame_major=False, qk_norm=False):
         super().__init__()
         self.hidden_size, self.num_heads = hidden_size, num_heads
         self.head_dim = hidden_size // num_heads
@@ -364,6 +364,14 @@ class DiTBlock(nn.Module):
         # (ops.attn_fwd / attn_bwd, frames=).  Every other kernel of the block works per row and the cross-attention only
         # reads the text, so the block (and the model) is then causal over token-frames.  No parameter.
         self.frame_causal = bool(frame_causal)
+        # frame-major self-attention (with frame_causal): the head-major tensors between the qkv / RoPE
+        # kernels and the attention kernels -- q, k, v, lse, dq, dk, dv, residual-V's v_0 and its gradient -- keep a
+        # frame's rows contiguous (ops.fm_row), so the masked attention skips the key tiles no query of a tile attends.
+        # The token order of x, qkv, attn and their gradients stays (h w t); the mathematics and the parameters are those
+        # of the frame_causal block.  A cached chunk call keeps the cache's own key order and kernels.  No parameter.
+        if frame_major and not frame_causal:
+            raise ValueError("DiTBlock: frame_major=True lays out the frame-causal self-attention: it needs frame_causal=True")
+        self.frame_major = bool(frame_major)
         self.norm1 = RMSNorm(hidden_size, trainable=qkv_bias)
         self.qkv = _Linear(hidden_size, hidden_size * 3, bias=qkv_bias)
         self.attn_proj = _Linear(hidden_size, hidden_size, bias=False)
@@ -531,10 +539,12 @@ class DiTBlock(nn.Module):
                 k, v = kb, vb
             else:
                 rope_fwd = ops.qkv_rope_norm_fwd if self.qk_norm else ops.qkv_rope_fwd
-                q, k, v = rope_fwd(qkv, cos, sin, v0 if mix else None, W("lambda_param") if mix else None, B, L, H, hd, hdp)
+                fm_kw = dict(frames=frames) if self.frame_major else {}  # q, k, v (and the v0 read) in frame-major rows
+                q, k, v = rope_fwd(qkv, cos, sin, v0 if mix else None, W("lambda_param") if mix else None, B, L, H, hd, hdp,
+                                   **fm_kw)
             if cache is None and not kept_attn:
                 ops.attn_fwd(q[..., :hd], k[..., :hd], v[..., :hd], ops.heads_view(attn, B, L, H, hd), lse1,
-                             kv_pad_ones=(hdp - hd) >= 8, frames=frames)
+                             kv_pad_ones=(hdp - hd) >= 8, frames=frames, frame_major=self.frame_major)
             if a8_on and save:  # first steps: record the amax the next step quantises with
                 for j, t in enumerate((q, k, v)):
                     ops.absmax(t.view(B * H * L, hdp)[:, :hd], fp8_hist.cur(F8.ROWS * i + F8.ROW_Q + j))
@@ -825,7 +835,7 @@ class DiTBlock(nn.Module):
             delta = torch.empty(2, B, H, L, dtype=f32, device=dev)
             ops.attn_bwd(bs.q[..., :hd], bs.k[..., :hd], bs.v[..., :hd], ops.heads_view(bs.attn, B, L, H, hd), bs.lse1,
                          ops.heads_view(dattn, B, L, H, hd), dq[..., :hd], dk[..., :hd], dv[..., :hd], delta,
-                         kv_pad_ones=(hdp - hd) >= 8, frames=bs.frames)
+                         kv_pad_ones=(hdp - hd) >= 8, frames=bs.frames, frame_major=self.frame_major)
             if bs.a8_on:
                 ops.absmax(dattn, fp8_hist.cur(F8.ROWS * i + F8.ROW_DO))
         defer = getattr(sv, "dv_terms", None)  # DiT.backward: [(dv, lambda)] of the mixed blocks, summed at block 0
@@ -853,12 +863,15 @@ class DiTBlock(nn.Module):
                      Gr("lambda_param") if bs.mix else None, mix_mode, first and dv0 is not None, B, L, H, hd, hdp)
         # the qkv output gradient leaves the RoPE backward as e5m2 (a qkv bias gradient needs the bf16 tensor)
         # (QK-norm: the normed backward has no fp8-emitting form -- the quantisation pass below takes its bf16 result)
-        emit_dqkv = pemit and not G.has(pre + "qkv.bias") and hdp % 8 == 0 and D <= 2048 and not self.qk_norm
+        # (frame-major: likewise -- the fp8-emitting backward has no frame-major form)
+        emit_dqkv = (pemit and not G.has(pre + "qkv.bias") and hdp % 8 == 0 and D <= 2048 and not self.qk_norm
+                     and not self.frame_major)
         if emit_dqkv:
             fq, fs = ops.qkv_rope_bwd_fp8(*rope_args, F8.E5M2, hist.prev(F8.ROWS * i + 5), hist.part(F8.ROWS * i + 5, B * L))
             q_dqkv = F8.Q.from_rowmajor(fq, fs, True)
         else:
-            dqkv = (ops.qkv_rope_norm_bwd if self.qk_norm else ops.qkv_rope_bwd)(*rope_args)
+            fm_kw = dict(frames=bs.frames) if self.frame_major else {}  # dq, dk, dv, v0, dv0 in frame-major rows
+            dqkv = (ops.qkv_rope_norm_bwd if self.qk_norm else ops.qkv_rope_bwd)(*rope_args, **fm_kw)
         if G.has(pre + "qkv.bias"):
             ops.colsum(dqkv, Gr("qkv.bias"))
         if bs.f8:
@@ -990,7 +1003,7 @@ def grad_arena(groups, device):
 class DiT(nn.Module):
     def __init__(self, in_channels=4, patch_size=2, time_patch_size=2, hidden_size=1152, depth=28, num_heads=16,
                  mlp_ratio=4.0, cross_attn_input_size=128, residual_v=False, train_bias_and_rms=True,
-                 use_rope=True, *, frame_causal=False, qk_norm=False):
+                 use_rope=True, *, frame_causal=False, frame_major=False, qk_norm=False):
         super().__init__()
         self.qk_norm = bool(qk_norm)  # see DiTBlock: parameter-free RMSNorm of q and k in the self-attention
         # see DiTBlock: every self-attention runs with frames = (N_REG, t) -- the registers attend each other, a token of
@@ -998,6 +1011,11 @@ class DiT(nn.Module):
         # per-frame timesteps the registers are still modulated from the row maximum of the timesteps, so it is not causal
         # in the noise levels of later frames.
         self.frame_causal = bool(frame_causal)
+        # see DiTBlock: the full-sequence self-attention of every block in frame-major rows (training, rollout without a
+        # cache); the same mathematics, parameters and checkpoints as the frame_causal model
+        if frame_major and not frame_causal:
+            raise ValueError("DiT: frame_major=True lays out the frame-causal self-attention: it needs frame_causal=True")
+        self.frame_major = bool(frame_major)
         self.in_channels = self.out_channels = in_channels
         self.patch_size, self.time_patch_size = patch_size, time_patch_size
         self.hidden_size, self.num_heads, self.depth, self.mlp_ratio = hidden_size, num_heads, depth, mlp_ratio
@@ -1025,7 +1043,8 @@ class DiT(nn.Module):
         self.blocks = nn.ModuleList([
             DiTBlock(hidden_size=hidden_size, num_heads=num_heads, mlp_ratio=mlp_ratio,
                      cross_attn_input_size=cross_attn_input_size, residual_v=residual_v,
-                     qkv_bias=train_bias_and_rms, qk_norm=qk_norm, frame_causal=frame_causal) for _ in range(depth)])
+                     qkv_bias=train_bias_and_rms, qk_norm=qk_norm, frame_causal=frame_causal,
+                     frame_major=frame_major) for _ in range(depth)])
         self.final_modulation = nn.Sequential(_Act("silu"), _Linear(hidden_size, 2 * hidden_size, bias=True))
         self.final_norm = RMSNorm(hidden_size, trainable=train_bias_and_rms)
         self.final_proj = _Linear(hidden_size, patch_size * patch_size * time_patch_size * self.out_channels)

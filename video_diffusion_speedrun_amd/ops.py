@@ -276,17 +276,32 @@ def _frames(frames, kv_lens, Lq: int, Lk: int, past: int = 0):
     return C.byref(_lib.ModGroups(lead, period))
 
 
-def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=None, past: int = 0):
+def _frame_major(frame_major, frames, kv_lens, past=0) -> bool:
+    """frame_major needs frames and excludes past / kv_lens: refused here, before anything is launched"""
+    if not frame_major:
+        return False
+    if frames is None:
+        raise ValueError("attention: frame_major=True needs frames=(lead, period)")
+    if past or kv_lens is not None:
+        raise ValueError("attention: frame_major=True is the full-sequence self-attention: not with past or kv_lens")
+    return True
+
+
+def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=None, past: int = 0,
+             frame_major: bool = False):
     """q [B,H,Lq,hd], k/v [B,H,Lk,hd], o [B,H,Lq,hd] strided views (last dim contiguous); lse f32 [B,H,Lq].
     kv_pad_ones: k / v are views into qkv_rope_fwd outputs whose pad carries the ones columns.
     kv_lens: int32 CUDA tensor [B]; sample b attends its first kv_lens[b] keys only (vds_attn_fwd_kvlen).
     frames: (lead, period) -- frame-causal self-attention: row q attends row k iff mod_group_of(k) <= mod_group_of(q)
     (vds_attn_fwd_causal); not together with kv_lens.
     past (with frames): k / v hold Lk = Lq + past rows [lead rows | past cached token rows | this call's token rows]; a
-    token query also attends every past key, a lead query none of them (vds_attn_fwd_causal_past).  Forward only."""
+    token query also attends every past key, a lead query none of them (vds_attn_fwd_causal_past).  Forward only.
+    frame_major (with frames; not with past / kv_lens): q, k, v and lse rows are frame-major (fm_row), o stays token-major
+    and the key tiles no query of a tile attends are skipped (vds_attn_fwd_causal_fm)."""
     B, H, Lq, hd = q.shape
     Lk = k.shape[2]
     past = int(past)
+    fmaj = _frame_major(frame_major, frames, kv_lens, past)
     if past < 0 or (past and frames is None):
         raise ValueError(f"attention: past = {past} must be >= 0 and needs frames=(lead, period)")
     fr = _frames(frames, kv_lens, Lq, Lk, past) if frames is not None else None
@@ -298,7 +313,10 @@ def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=No
     a.o, (a.o_sb, a.o_sh, a.o_sl) = _p(o), _st(o)
     a.lse = _p(lse)
     a.kv_pad_ones = int(kv_pad_ones)  # (True = 1: self-attention layout; 2: ones in k / v only, cross-attention)
-    if fr is not None and past:
+    if fmaj:
+        check(_lib.load().vds_attn_fwd_causal_fm(C.byref(a), fr, _stream()),
+              f"vds_attn_fwd_causal_fm(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)})")
+    elif fr is not None and past:
         check(_lib.load().vds_attn_fwd_causal_past(C.byref(a), fr, past, _stream()),
               f"vds_attn_fwd_causal_past(B={B},H={H},Lq={Lq},Lk={Lk},hd={hd},frames={tuple(frames)},past={past})")
     elif fr is not None:
@@ -329,14 +347,18 @@ def attn_bwd_workspace_floats(B, H, Lq, Lk, hd, kv_pad_ones: bool = False) -> in
     return _lib.load().vds_attn_bwd_workspace_bytes(C.byref(a)) // 4
 
 
-def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = False, kv_lens=None, frames=None):
+def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = False, kv_lens=None, frames=None,
+             frame_major: bool = False):
     """delta: f32 workspace of 2*B*H*Lq elements (rowsum(dO*O), then lse*log2 e); allocated here when None
     (size from vds_attn_bwd_workspace_bytes).
     kv_lens: as in attn_fwd; rows kv_lens[b].. of dk[b] / dv[b] are written as zeros (vds_attn_bwd_kvlen).
-    frames: as in attn_fwd; a dk / dv row sums over the queries that attend it (vds_attn_bwd_causal)."""
+    frames: as in attn_fwd; a dk / dv row sums over the queries that attend it (vds_attn_bwd_causal).
+    frame_major: as in attn_fwd -- q, k, v, lse, dq, dk, dv (and the delta workspace) rows are frame-major, o and do
+    token-major (vds_attn_bwd_causal_fm)."""
     B, H, Lq, hd = q.shape
     assert lse.is_contiguous()
     Lk = k.shape[2]
+    fmaj = _frame_major(frame_major, frames, kv_lens)
     fr = _frames(frames, kv_lens, Lq, Lk) if frames is not None else None
     a = AttnArgs()
     a.B, a.H, a.Lq, a.Lk, a.head_dim = B, H, Lq, Lk, hd
@@ -356,7 +378,10 @@ def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = Fa
     a.dv, (a.dv_sb, a.dv_sh, a.dv_sl) = _p(dv), _st(dv)
     a.delta = _p(delta)
     a.kv_pad_ones = int(kv_pad_ones)
-    if fr is not None:
+    if fmaj:
+        check(_lib.load().vds_attn_bwd_causal_fm(C.byref(a), fr, _stream()),
+              f"vds_attn_bwd_causal_fm(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)})")
+    elif fr is not None:
         check(_lib.load().vds_attn_bwd_causal(C.byref(a), fr, _stream()),
               f"vds_attn_bwd_causal(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)})")
     elif kv_lens is None:
@@ -628,11 +653,64 @@ def colsum(x, out, rows_per_sample: int = 0, row_offset: int = 0):
           "vds_colsum_bf16_rows")
 
 
+# ------------------------------------------------------------------ frame-major rows ----
+# The head-major tensors of a frame-major self-attention (q, k, v, dq, dk, dv, lse, v0, dv0) keep a frame's rows
+# contiguous; the model's token order stays (h w t).  With S = (L - lead) // period rows per frame (include/vds.h):
+def fm_row(l: int, lead: int, period: int, L: int) -> int:
+    """frame-major row of token row l"""
+    if l < lead:
+        return l
+    S = (L - lead) // period
+    return lead + ((l - lead) % period) * S + (l - lead) // period
+
+
+def tok_row(r: int, lead: int, period: int, L: int) -> int:
+    """token row of frame-major row r (the inverse of fm_row)"""
+    if r < lead:
+        return r
+    S = (L - lead) // period
+    return lead + ((r - lead) % S) * period + (r - lead) // S
+
+
+def fm_group_of(r: int, lead: int, S: int) -> int:
+    """group of frame-major row r: 0 for the lead rows, then 1 + (r - lead) // S; query r attends key j iff
+    fm_group_of(j) <= fm_group_of(r) -- mod_group_of's mask, permuted"""
+    return 0 if r < lead else 1 + (r - lead) // S
+
+
+def fm_key_end(q0: int, q1: int, lead: int, S: int) -> int:
+    """first frame-major key row that no query row of [q0, q1) attends: a query tile's key loop ends here"""
+    if q1 <= lead:
+        return lead
+    return lead + ((q1 - 1 - lead) // S + 1) * S
+
+
+def fm_query_start(k0: int, lead: int, S: int) -> int:
+    """first frame-major query row that may attend a key row of [k0, ...): a key tile's query loop starts here (rounded
+    down to the query tile by the kernels)"""
+    if k0 < lead:
+        return 0
+    return lead + ((k0 - lead) // S) * S
+
+
+def _fm_frames(frames, L: int):
+    """vds_mod_groups of a frame-major qkv / RoPE call, checked against L before anything is launched"""
+    lead, period = check_mod_groups(frames, L)
+    return C.byref(_lib.ModGroups(lead, period))
+
+
 # ----------------------------------------------------------------- qkv / rope / res-V ----
-def qkv_rope_fwd(qkv, cos, sin, v0, lam, B, L, H, hd, hdp):
+def qkv_rope_fwd(qkv, cos, sin, v0, lam, B, L, H, hd, hdp, frames=None):
+    """frames=(lead, period): the q / k / v head rows of token l are written, and v0 read, at row fm_row(l)
+    (vds_qkv_rope_fwd_fm)"""
+    fr = _fm_frames(frames, L) if frames is not None else None
     q = torch.empty(B, H, L, hdp, dtype=bf16, device=qkv.device)
     k = torch.empty_like(q)
     v = torch.empty_like(q)
+    if fr is not None:
+        check(_lib.load().vds_qkv_rope_fwd_fm(_p(qkv), _p(cos), _p(sin), _p(v0), _p(lam), _p(q), _p(k), _p(v), B, L, H,
+                                              hd, hdp, fr, _stream()), "vds_qkv_rope_fwd_fm")
+        return q, k, v
     check(_lib.load().vds_qkv_rope_fwd(_p(qkv), _p(cos), _p(sin), _p(v0), _p(lam), _p(q), _p(k), _p(v), B, L, H, hd,
                                        hdp, _stream()), "vds_qkv_rope_fwd")
     return q, k, v
@@ -659,8 +737,16 @@ def qkv_rope_fwd_cache(qkv, cos, sin, v0, lam, k, v, lead, past, B, L, H, hd, hd
     return q
 
 
-def qkv_rope_bwd(dq, dk, dv, cos, sin, qkv_raw, v0, lam, dv0_acc, dlam, mix, add_dv0, B, L, H, hd, hdp):
+def qkv_rope_bwd(dq, dk, dv, cos, sin, qkv_raw, v0, lam, dv0_acc, dlam, mix, add_dv0, B, L, H, hd, hdp, frames=None):
+    """frames=(lead, period): dq / dk / dv, v0 and dv0_acc are addressed at row fm_row(l), dqkv stays token-major
+    (vds_qkv_rope_bwd_fm)"""
+    fr = _fm_frames(frames, L) if frames is not None else None
     dqkv = torch.empty(B * L, 3 * H * hd, dtype=bf16, device=dq.device)
+    if fr is not None:
+        check(_lib.load().vds_qkv_rope_bwd_fm(_p(dq), _p(dk), _p(dv), _p(cos), _p(sin), _p(qkv_raw), _p(v0), _p(lam),
+                                              _p(dv0_acc), _p(dlam), _p(dqkv), int(mix), int(add_dv0), B, L, H, hd, hdp,
+                                              fr, _stream()), "vds_qkv_rope_bwd_fm")
+        return dqkv
     check(_lib.load().vds_qkv_rope_bwd(_p(dq), _p(dk), _p(dv), _p(cos), _p(sin), _p(qkv_raw), _p(v0), _p(lam),
                                        _p(dv0_acc), _p(dlam), _p(dqkv), int(mix), int(add_dv0), B, L, H, hd, hdp,
                                        _stream()), "vds_qkv_rope_bwd")
@@ -670,12 +756,18 @@ def qkv_rope_bwd(dq, dk, dv, cos, sin, qkv_raw, v0, lam, dv0_acc, dlam, mix, add
 QK_NORM_EPS = 1e-6  # RMSNorm's eps (model.py:34-41)
 
 
-def qkv_rope_norm_fwd(qkv, cos, sin, v0, lam, B, L, H, hd, hdp, eps: float = QK_NORM_EPS):
+def qkv_rope_norm_fwd(qkv, cos, sin, v0, lam, B, L, H, hd, hdp, eps: float = QK_NORM_EPS, frames=None):
     """qkv_rope_fwd with QK-norm: every head row of q and k goes through a weightless RMSNorm (fp32 math, rounded to
-    bf16) before the rotation; v, the pad and the ones columns are qkv_rope_fwd's (vds_qkv_rope_norm_fwd)"""
+    bf16) before the rotation; v, the pad and the ones columns are qkv_rope_fwd's (vds_qkv_rope_norm_fwd).
+    frames: as in qkv_rope_fwd (vds_qkv_rope_norm_fwd_fm)"""
+    fr = _fm_frames(frames, L) if frames is not None else None
     q = torch.empty(B, H, L, hdp, dtype=bf16, device=qkv.device)
     k = torch.empty_like(q)
     v = torch.empty_like(q)
+    if fr is not None:
+        check(_lib.load().vds_qkv_rope_norm_fwd_fm(_p(qkv), _p(cos), _p(sin), _p(v0), _p(lam), _p(q), _p(k), _p(v), B, L,
+                                                   H, hd, hdp, float(eps), fr, _stream()), "vds_qkv_rope_norm_fwd_fm")
+        return q, k, v
     check(_lib.load().vds_qkv_rope_norm_fwd(_p(qkv), _p(cos), _p(sin), _p(v0), _p(lam), _p(q), _p(k), _p(v), B, L, H,
                                             hd, hdp, float(eps), _stream()), "vds_qkv_rope_norm_fwd")
     return q, k, v
@@ -692,9 +784,16 @@ def qkv_rope_norm_fwd_cache(qkv, cos, sin, v0, lam, k, v, lead, past, B, L, H, h
 
 
 def qkv_rope_norm_bwd(dq, dk, dv, cos, sin, qkv_raw, v0, lam, dv0_acc, dlam, mix, add_dv0, B, L, H, hd, hdp,
-                      eps: float = QK_NORM_EPS):
-    """backward of qkv_rope_norm_fwd; qkv_raw (the forward's qkv) is needed in every call (vds_qkv_rope_norm_bwd)"""
+                      eps: float = QK_NORM_EPS, frames=None):
+    """backward of qkv_rope_norm_fwd; qkv_raw (the forward's qkv) is needed in every call (vds_qkv_rope_norm_bwd).
+    frames: as in qkv_rope_bwd (vds_qkv_rope_norm_bwd_fm)"""
+    fr = _fm_frames(frames, L) if frames is not None else None
     dqkv = torch.empty(B * L, 3 * H * hd, dtype=bf16, device=dq.device)
+    if fr is not None:
+        check(_lib.load().vds_qkv_rope_norm_bwd_fm(_p(dq), _p(dk), _p(dv), _p(cos), _p(sin), _p(qkv_raw), _p(v0),
+                                                   _p(lam), _p(dv0_acc), _p(dlam), _p(dqkv), int(mix), int(add_dv0), B, L,
+                                                   H, hd, hdp, float(eps), fr, _stream()), "vds_qkv_rope_norm_bwd_fm")
+        return dqkv
     check(_lib.load().vds_qkv_rope_norm_bwd(_p(dq), _p(dk), _p(dv), _p(cos), _p(sin), _p(qkv_raw), _p(v0), _p(lam),
                                             _p(dv0_acc), _p(dlam), _p(dqkv), int(mix), int(add_dv0), B, L, H, hd, hdp,
                                             float(eps), _stream()), "vds_qkv_rope_norm_bwd")
