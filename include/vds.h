@@ -315,6 +315,17 @@ int vds_attn_fwd_causal_past(const vds_attn_args* args, const vds_mod_groups* fr
  * vds_attn_bwd_workspace_bytes (2 B H L floats are used). */
 int vds_attn_fwd_causal_fm(const vds_attn_args* args, const vds_mod_groups* frames, vds_stream_t stream);
 int vds_attn_bwd_causal_fm(const vds_attn_args* args, const vds_mod_groups* frames, vds_stream_t stream);
+/* Chunk-causal frame-major self-attention: the calls above with a mask that is causal over CHUNKS of `chunk` token-frames
+ * and bidirectional inside a chunk.  group(l) = 0 for l < lead, 1 + ((l - lead) % period) / chunk otherwise (token rows);
+ * in frame-major rows that is 1 + (r - lead) / G with G = chunk * S, a contiguous run, so the attended keys of a query stay
+ * a prefix and the queries of a key a suffix: the same kernel instances run with the granularity G in place of S --
+ * kend(r) = min(L, lead + ((r - lead) / G + 1) * G), qstart(j) = lead + ((j - lead) / G) * G (the lead rows as above);
+ * the layout, tok(), the skipped ranges, the variant bits and knobs, the refusals and the workspace are those of the _fm
+ * calls.  period % chunk != 0 is allowed (the last chunk is short: kend is clipped to L); chunk >= period is one token
+ * group (tokens attend every row, lead rows the lead rows).  chunk == 1 forwards to the _fm call (the same bits);
+ * chunk < 1 or frames == NULL: VDS_ERR_ARG.  chunk travels by value.  The profiler credits the visited range. */
+int vds_attn_fwd_causal_fm_chunk(const vds_attn_args* args, const vds_mod_groups* frames, int32_t chunk, vds_stream_t stream);
+int vds_attn_bwd_causal_fm_chunk(const vds_attn_args* args, const vds_mod_groups* frames, int32_t chunk, vds_stream_t stream);
 /* vds_rmsnorm_mod_fwd with mod f32 [B*G, ldmod]: the same arithmetic per row, y / rstd bit-identical to the per-sample
  * call run on the rows of one group with that group's mod row.  Every form of the dispatcher is covered. */
 int vds_rmsnorm_mod_fwd_grouped(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod,

@@ -66,6 +66,9 @@ struct AttnP {
   // frame-major rows (vds_attn_*_causal_fm): rows per frame S = (L - lead) / period (>= 1) next to fc_lead / fc_period, and
   // the heaviest-tiles-first order; by value, read by the FM instances of the kernels only
   int fm_S, fm_rev;
+  // chunk-causal granularity (vds_attn_*_causal_fm_chunk): G = c * S rows per chunk of c frames (the last one may be short);
+  // G = S (c = 1) is the frame-causal mask.  The mask bounds kend / qstart use G, the row map tok() keeps S
+  int fm_G;
 };
 
 // Keys of sample b.  KVLEN: kv_lens[b] clamped to [0, Lk] -- b is the same for the whole workgroup, so this is one
@@ -153,18 +156,25 @@ __device__ __forceinline__ void fc_zero_q(const FcMap& fm, int row0, int f, f32x
 // tiles below the largest bound of its rows only, and a sub-block below the smallest bound of a wave is attended without
 // any mask code.  o and d_o stay token-major: row r of the computation is row tok(r) of those tensors.
 // The quotient is FcMap's: trunc((r - lead + 0.5) / S) in fp32, exact while |r - lead| < 2^21.
+// Chunks (vds_attn_*_causal_fm_chunk): the groups are runs of G = c * S rows, 1 + (r - lead) / G -- c whole frames, still a
+// contiguous run, so the prefix and the suffix stay; only the two bounds take the quotient by G (the same fp32 rule) and
+// kend is clipped to L, which a short last chunk (period % c != 0) would pass.  tok() keeps S and the period.
 struct FmMap {
-  int lead, S, period;
-  float inv, hinv;
-  __device__ __forceinline__ explicit FmMap(const AttnP& p) : lead(p.fc_lead), S(p.fm_S), period(p.fc_period) {
+  int lead, S, period, G, L;
+  float inv, hinv, ginv, ghinv;
+  __device__ __forceinline__ explicit FmMap(const AttnP& p)
+      : lead(p.fc_lead), S(p.fm_S), period(p.fc_period), G(p.fm_G), L(p.Lq) {
     inv = 1.0f / (float)p.fm_S;
     hinv = 0.5f * inv;
+    ginv = 1.0f / (float)p.fm_G;
+    ghinv = 0.5f * ginv;
   }
   __device__ __forceinline__ int frame(int r) const { return (int)__builtin_fmaf((float)(r - lead), inv, hinv); }  // r >= lead
+  __device__ __forceinline__ int chunk(int r) const { return (int)__builtin_fmaf((float)(r - lead), ginv, ghinv); }  // r >= lead
   // the first key row that query row r does not attend
-  __device__ __forceinline__ int kend(int r) const { return r < lead ? lead : lead + __mul24(frame(r) + 1, S); }
+  __device__ __forceinline__ int kend(int r) const { return r < lead ? lead : min(L, lead + __mul24(chunk(r) + 1, G)); }
   // the first query row that attends key row j
-  __device__ __forceinline__ int qstart(int j) const { return j < lead ? 0 : lead + __mul24(frame(j), S); }
+  __device__ __forceinline__ int qstart(int j) const { return j < lead ? 0 : lead + __mul24(chunk(j), G); }
   // the token row of frame-major row r (o / d_o)
   __device__ __forceinline__ int tok(int r) const {
     if (r < lead) return r;
@@ -2151,6 +2161,7 @@ AttnP to_p(const vds_attn_args* a) {
   p.fc_period = 1;
   p.fc_past = 0;
   p.fm_S = 1;
+  p.fm_G = 1;
   p.fm_rev = 0;
   const bool wide_on = vdscfg::geti(vdscfg::ATTN_WIDE_STORES) != 0;  // A/B knob
   p.wide_o = wide_on && p.hd > 64 && rows16(p.o, p.o_sb, p.o_sh, p.o_sl);
@@ -2592,23 +2603,28 @@ extern "C" int vds_attn_fwd_causal_past(const vds_attn_args* a, const vds_mod_gr
 // instance of the 64-queries-per-wave 32x32 forwards nor of the ones-column 32x32 kernels: where the interleaved dispatcher
 // would take one of those, this one takes the plain 32x32x16 FM kernel.  The query range of the dK/dV kernel is never split.
 namespace {
-int fm_kend_host(int r, int lead, int S) { return r < lead ? lead : lead + ((r - lead) / S + 1) * S; }
-int fm_qstart_host(int j, int lead, int S) { return j < lead ? 0 : lead + ((j - lead) / S) * S; }
+// (G: rows per chunk, fm_G)
+int fm_kend_host(int r, int lead, int G, int L) {
+  if (r < lead) return lead;
+  const int e = lead + ((r - lead) / G + 1) * G;
+  return e < L ? e : L;
+}
+int fm_qstart_host(int j, int lead, int G) { return j < lead ? 0 : lead + ((j - lead) / G) * G; }
 // (query, key) pairs the forward / dQ kernels visit: `tile` queries per workgroup, keys [0, kend of its last query)
-double fm_pairs_q(int L, int lead, int S, int tile) {
+double fm_pairs_q(int L, int lead, int G, int tile) {
   double n = 0;
   for (int q0 = 0; q0 < L; q0 += tile) {
     const int q1 = q0 + tile < L ? q0 + tile : L;
-    n += (double)(q1 - q0) * fm_kend_host(q1 - 1, lead, S);
+    n += (double)(q1 - q0) * fm_kend_host(q1 - 1, lead, G, L);
   }
   return n;
 }
 // ... and the dK/dV kernel: `tile` keys per workgroup, queries from the 64-row tile that holds qstart of its first key
-double fm_pairs_k(int L, int lead, int S, int tile) {
+double fm_pairs_k(int L, int lead, int G, int tile) {
   double n = 0;
   for (int k0 = 0; k0 < L; k0 += tile) {
     const int k1 = k0 + tile < L ? k0 + tile : L;
-    n += (double)(k1 - k0) * (L - (fm_qstart_host(k0, lead, S) & ~63));
+    n += (double)(k1 - k0) * (L - (fm_qstart_host(k0, lead, G) & ~63));
   }
   return n;
 }
@@ -2631,7 +2647,7 @@ int run_fwd_fm(AttnP p, hipStream_t s) {
       p.n_rt = cdiv(p.Lq, 256);
       p.tail_last = tail_last_for(p.Lq, 256);
       const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
-      const double fl = 4.0 * p.B * p.H * p.hd * fm_pairs_q(p.Lq, p.fc_lead, p.fm_S, 256);
+      const double fl = 4.0 * p.B * p.H * p.hd * fm_pairs_q(p.Lq, p.fc_lead, p.fm_G, 256);
       vdsprof::Scope ps(VDS_PROF_ATTN_FWD, s, fl, 2.0 * p.B * p.H * p.hd * (2.0 * p.Lq + 2.0 * p.Lk));
       hipLaunchKernelGGL((attn_fwd16_kernel<HDP, false, false, false, true>), dim3(grid), dim3(256), LDS, s, p);
       return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
@@ -2640,7 +2656,7 @@ int run_fwd_fm(AttnP p, hipStream_t s) {
   p.n_rt = cdiv(p.Lq, 128);
   p.tail_last = tail_last_for(p.Lq, 128);
   const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
-  const double fl = 4.0 * p.B * p.H * p.hd * fm_pairs_q(p.Lq, p.fc_lead, p.fm_S, 128);
+  const double fl = 4.0 * p.B * p.H * p.hd * fm_pairs_q(p.Lq, p.fc_lead, p.fm_G, 128);
   vdsprof::Scope ps(VDS_PROF_ATTN_FWD_PLAIN, s, fl, 2.0 * p.B * p.H * p.hd * (2.0 * p.Lq + 2.0 * p.Lk));
   hipLaunchKernelGGL((attn_fwd_kernel<HDP, HDQ, 2, true, false, false, false, true>), dim3(grid), dim3(256), LDS, s, p);
   return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
@@ -2675,7 +2691,7 @@ int run_bwd_fm(AttnP p, hipStream_t s) {
     p.tail_last = tail_last_for(p.Lq, 128);
     const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
     vdsprof::Scope ps(ones ? VDS_PROF_ATTN_BWD_DQ : VDS_PROF_ATTN_BWD_DQ_PLAIN, s,
-                      2.0 * per * fm_pairs_q(p.Lq, p.fc_lead, p.fm_S, 128), (fold ? 4.0 : 3.0) * qb + 2.0 * kb);
+                      2.0 * per * fm_pairs_q(p.Lq, p.fc_lead, p.fm_G, 128), (fold ? 4.0 : 3.0) * qb + 2.0 * kb);
     if constexpr (HDP == 96 && HDQ == 80) {
       if (fold) {
         hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, true, false, false, true>), dim3(grid), dim3(256), LDS_DQ, s, p);
@@ -2703,7 +2719,7 @@ int run_bwd_fm(AttnP p, hipStream_t s) {
   {
     const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
     vdsprof::Scope ps(ones ? VDS_PROF_ATTN_BWD_DKV : VDS_PROF_ATTN_BWD_DKV_PLAIN, s,
-                      2.0 * per * fm_pairs_k(p.Lq, p.fc_lead, p.fm_S, 128), 2.0 * qb + 4.0 * kb);
+                      2.0 * per * fm_pairs_k(p.Lq, p.fc_lead, p.fm_G, 128), 2.0 * qb + 4.0 * kb);
     bool done = false;
     if constexpr (HDP == 96 && HDQ == 80) {
       if (dkv16) {
@@ -2727,11 +2743,13 @@ int fm_check(const vds_attn_args* a, const vds_mod_groups* f, bool bwd) {
   if ((int64_t)a->Lq * a->o_sl * 2 >= lim || (bwd && (int64_t)a->Lq * a->do_sl * 2 >= lim)) return VDS_ERR_UNSUPPORTED;
   return VDS_OK;
 }
-void fm_set(AttnP& p, const vds_mod_groups* f) {
+void fm_set(AttnP& p, const vds_mod_groups* f, int chunk = 1) {
   p.fc_lead = f->lead;
   p.fc_period = f->period;
   const int S = (p.Lq - f->lead) / f->period;
   p.fm_S = S > 0 ? S : 1;  // (no token rows: every row is a lead row and the quotient is never taken)
+  // chunk >= period is one token group: G = period * S = L - lead < 2^21, whatever the chunk
+  p.fm_G = (chunk < f->period ? chunk : f->period) * p.fm_S;
   p.fm_rev = vdscfg::geti(vdscfg::ATTN_FM_HEAVY_FIRST) ? 1 : 0;
 }
 }  // namespace
@@ -2761,6 +2779,50 @@ extern "C" int vds_attn_bwd_causal_fm(const vds_attn_args* a, const vds_mod_grou
   if (const int e = fm_check(a, frames, true)) return e;
   AttnP p = to_p(a);
   fm_set(p, frames);
+  hipStream_t s = (hipStream_t)stream;
+  switch (kernel_instance(a->head_dim)) {
+    case 32: return run_bwd_fm<32, 32>(p, s);
+    case 64: return run_bwd_fm<64, 64>(p, s);
+    case 80: return run_bwd_fm<96, 80>(p, s);
+    case 96: return run_bwd_fm<96, 96>(p, s);
+    case 128: return run_bwd_fm<128, 128>(p, s);
+    default: return VDS_ERR_UNSUPPORTED;
+  }
+}
+
+// ---- chunk-causal frame-major self-attention (include/vds.h) ---------------------------------------------------------
+// The FM instances above with fm_G = chunk * S: no kernel of its own.  chunk == 1 IS the _fm entry point.
+extern "C" int vds_attn_fwd_causal_fm_chunk(const vds_attn_args* a, const vds_mod_groups* frames, int32_t chunk,
+                                            vds_stream_t stream) {
+  if (!frames || chunk < 1) return VDS_ERR_ARG;
+  if (chunk == 1) return vds_attn_fwd_causal_fm(a, frames, stream);
+  if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse || a->Lq <= 0 || a->Lk <= 0) return VDS_ERR_ARG;
+  if (!strides_ok(a, false)) return VDS_ERR_ARG;
+  if (const int e = fm_check(a, frames, false)) return e;
+  AttnP p = to_p(a);
+  fm_set(p, frames, chunk);
+  hipStream_t s = (hipStream_t)stream;
+  switch (kernel_instance(a->head_dim)) {
+    case 32: return run_fwd_fm<32, 32>(p, s);
+    case 64: return run_fwd_fm<64, 64>(p, s);
+    case 80: return run_fwd_fm<96, 80>(p, s);
+    case 96: return run_fwd_fm<96, 96>(p, s);
+    case 128: return run_fwd_fm<128, 128>(p, s);
+    default: return VDS_ERR_UNSUPPORTED;
+  }
+}
+
+extern "C" int vds_attn_bwd_causal_fm_chunk(const vds_attn_args* a, const vds_mod_groups* frames, int32_t chunk,
+                                            vds_stream_t stream) {
+  if (!frames || chunk < 1) return VDS_ERR_ARG;
+  if (chunk == 1) return vds_attn_bwd_causal_fm(a, frames, stream);
+  if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse || !a->d_o || !a->dq || !a->dk || !a->dv || !a->delta || a->Lq <= 0 ||
+      a->Lk <= 0)
+    return VDS_ERR_ARG;
+  if (!strides_ok(a, true)) return VDS_ERR_ARG;
+  if (const int e = fm_check(a, frames, true)) return e;
+  AttnP p = to_p(a);
+  fm_set(p, frames, chunk);
   hipStream_t s = (hipStream_t)stream;
   switch (kernel_instance(a->head_dim)) {
     case 32: return run_bwd_fm<32, 32>(p, s);

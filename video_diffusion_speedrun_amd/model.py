@@ -341,6 +341,16 @@ _FP8_QK_NORM = ("qk_norm is not implemented for the fp8 attention producers (vds
                 "call enable_fp8(attention=False) to keep the attention products on the bf16 kernels")
 
 
+def check_frame_chunk(who: str, frame_chunk, frame_causal: bool, frame_major: bool) -> int:
+    """frame_chunk of a DiT / DiTBlock: an int >= 1; more than 1 needs the frame-major frame-causal self-attention"""
+    if isinstance(frame_chunk, bool) or not isinstance(frame_chunk, int) or frame_chunk < 1:
+        raise ValueError(f"{who}: frame_chunk = {frame_chunk!r} must be an int >= 1 (token-frames per causal chunk)")
+    if frame_chunk > 1 and not (frame_causal and frame_major):
+        raise ValueError(f"{who}: frame_chunk={frame_chunk} is a mask of the frame-major frame-causal self-attention -- build "
+                         "the model with frame_causal=True, frame_major=True (the interleaved kernels have no chunk mask)")
+    return frame_chunk
+
+
 _FP8_FRAME_CAUSAL = ("frame_causal is not implemented for the fp8 attention kernels (they have no masked instance): "
                      "call enable_fp8(attention=False) to keep the attention products on the bf16 kernels")
 
@@ -351,7 +361,7 @@ class DiTBlock(nn.Module):
     drives the same two methods for all blocks inside its own whole-model node."""
 
     def __init__(self, hidden_size, cross_attn_input_size, num_heads, mlp_ratio=4.0, qkv_bias=True,
-                 residual_v=False, *, frame_causal=False, frame_major=False, qk_norm=False):
+                 residual_v=False, *, frame_causal=False, frame_major=False, frame_chunk=1, qk_norm=False):
         super().__init__()
         self.hidden_size, self.num_heads = hidden_size, num_heads
         self.head_dim = hidden_size // num_heads
@@ -372,6 +382,12 @@ class DiTBlock(nn.Module):
         if frame_major and not frame_causal:
             raise ValueError("DiTBlock: frame_major=True lays out the frame-causal self-attention: it needs frame_causal=True")
         self.frame_major = bool(frame_major)
+        # chunk-causal mask (with frame_causal and frame_major): the self-attention is causal over chunks of
+        # frame_chunk token-frames and bidirectional inside a chunk -- token-frame f belongs to group 1 + f // frame_chunk
+        # (ops.chunk_group_of; the last chunk may be short) -- on the same frame-major kernels (ops.attn_fwd / attn_bwd,
+        # chunk=).  1 is the frame-causal mask, call for call.  A cached chunk call covers frames of ONE chunk, inside which
+        # every token attends every own key: it runs the cache's past kernel with one token group.  No parameter.
+        self.frame_chunk = check_frame_chunk("DiTBlock", frame_chunk, self.frame_causal, self.frame_major)
         self.norm1 = RMSNorm(hidden_size, trainable=qkv_bias)
         self.qkv = _Linear(hidden_size, hidden_size * 3, bias=qkv_bias)
         self.attn_proj = _Linear(hidden_size, hidden_size, bias=False)
@@ -534,8 +550,10 @@ class DiTBlock(nn.Module):
                 rope_fwd = ops.qkv_rope_norm_fwd_cache if self.qk_norm else ops.qkv_rope_fwd_cache
                 q = rope_fwd(qkv, cos, sin, v0 if mix else None, W("lambda_param") if mix else None, kb, vb, frames[0], past,
                              B, L, H, hd, hdp)
+                # (frame_chunk > 1: the call's frames are of one chunk -- one token group, frames = (lead, 1))
                 ops.attn_fwd(q[..., :hd], kb[:, :, :L + past, :hd], vb[:, :, :L + past, :hd],
-                             ops.heads_view(attn, B, L, H, hd), lse1, kv_pad_ones=(hdp - hd) >= 8, frames=frames, past=past)
+                             ops.heads_view(attn, B, L, H, hd), lse1, kv_pad_ones=(hdp - hd) >= 8,
+                             frames=(frames[0], 1) if self.frame_chunk > 1 else frames, past=past)
                 k, v = kb, vb
             else:
                 rope_fwd = ops.qkv_rope_norm_fwd if self.qk_norm else ops.qkv_rope_fwd
@@ -544,7 +562,8 @@ class DiTBlock(nn.Module):
                                    **fm_kw)
             if cache is None and not kept_attn:
                 ops.attn_fwd(q[..., :hd], k[..., :hd], v[..., :hd], ops.heads_view(attn, B, L, H, hd), lse1,
-                             kv_pad_ones=(hdp - hd) >= 8, frames=frames, frame_major=self.frame_major)
+                             kv_pad_ones=(hdp - hd) >= 8, frames=frames, frame_major=self.frame_major,
+                             **({"chunk": self.frame_chunk} if self.frame_chunk > 1 else {}))
             if a8_on and save:  # first steps: record the amax the next step quantises with
                 for j, t in enumerate((q, k, v)):
                     ops.absmax(t.view(B * H * L, hdp)[:, :hd], fp8_hist.cur(F8.ROWS * i + F8.ROW_Q + j))
@@ -835,7 +854,8 @@ class DiTBlock(nn.Module):
             delta = torch.empty(2, B, H, L, dtype=f32, device=dev)
             ops.attn_bwd(bs.q[..., :hd], bs.k[..., :hd], bs.v[..., :hd], ops.heads_view(bs.attn, B, L, H, hd), bs.lse1,
                          ops.heads_view(dattn, B, L, H, hd), dq[..., :hd], dk[..., :hd], dv[..., :hd], delta,
-                         kv_pad_ones=(hdp - hd) >= 8, frames=bs.frames, frame_major=self.frame_major)
+                         kv_pad_ones=(hdp - hd) >= 8, frames=bs.frames, frame_major=self.frame_major,
+                         **({"chunk": self.frame_chunk} if self.frame_chunk > 1 else {}))
             if bs.a8_on:
                 ops.absmax(dattn, fp8_hist.cur(F8.ROWS * i + F8.ROW_DO))
         defer = getattr(sv, "dv_terms", None)  # DiT.backward: [(dv, lambda)] of the mixed blocks, summed at block 0
@@ -1003,7 +1023,7 @@ def grad_arena(groups, device):
 class DiT(nn.Module):
     def __init__(self, in_channels=4, patch_size=2, time_patch_size=2, hidden_size=1152, depth=28, num_heads=16,
                  mlp_ratio=4.0, cross_attn_input_size=128, residual_v=False, train_bias_and_rms=True,
-                 use_rope=True, *, frame_causal=False, frame_major=False, qk_norm=False):
+                 use_rope=True, *, frame_causal=False, frame_major=False, frame_chunk=1, qk_norm=False):
         super().__init__()
         self.qk_norm = bool(qk_norm)  # see DiTBlock: parameter-free RMSNorm of q and k in the self-attention
         # see DiTBlock: every self-attention runs with frames = (N_REG, t) -- the registers attend each other, a token of
@@ -1016,6 +1036,9 @@ class DiT(nn.Module):
         if frame_major and not frame_causal:
             raise ValueError("DiT: frame_major=True lays out the frame-causal self-attention: it needs frame_causal=True")
         self.frame_major = bool(frame_major)
+        # see DiTBlock: causal over chunks of frame_chunk token-frames, bidirectional inside a chunk (1: frame-causal);
+        # the model that a rollout of frame_chunk frames at a time (generate_latents(rollout_frames=)) is trained as
+        self.frame_chunk = check_frame_chunk("DiT", frame_chunk, self.frame_causal, self.frame_major)
         self.in_channels = self.out_channels = in_channels
         self.patch_size, self.time_patch_size = patch_size, time_patch_size
         self.hidden_size, self.num_heads, self.depth, self.mlp_ratio = hidden_size, num_heads, depth, mlp_ratio
@@ -1044,7 +1067,7 @@ class DiT(nn.Module):
             DiTBlock(hidden_size=hidden_size, num_heads=num_heads, mlp_ratio=mlp_ratio,
                      cross_attn_input_size=cross_attn_input_size, residual_v=residual_v,
                      qkv_bias=train_bias_and_rms, qk_norm=qk_norm, frame_causal=frame_causal,
-                     frame_major=frame_major) for _ in range(depth)])
+                     frame_major=frame_major, frame_chunk=self.frame_chunk) for _ in range(depth)])
         self.final_modulation = nn.Sequential(_Act("silu"), _Linear(hidden_size, 2 * hidden_size, bias=True))
         self.final_norm = RMSNorm(hidden_size, trainable=train_bias_and_rms)
         self.final_proj = _Linear(hidden_size, patch_size * patch_size * time_patch_size * self.out_channels)
@@ -1291,6 +1314,12 @@ class DiT(nn.Module):
         if cache.past_frames + k > cache.frames:
             raise ValueError(f"DiT: frame_cache holds {cache.frames} token-frames, {cache.past_frames} are committed and this "
                              f"chunk brings {k}: make a larger cache (new_frame_cache(frames=...)) or reset() it")
+        c = self.frame_chunk
+        if c > 1 and (cache.past_frames % c != 0 or k > c or (k < c and cache.past_frames + k != cache.frames)):
+            raise ValueError(f"DiT: a frame_cache call on a frame_chunk={c} model covers the frames of ONE chunk: "
+                             f"{cache.past_frames} frames are committed and this call brings {k} -- commit whole chunks "
+                             f"(past_frames % {c} == 0) and pass {c} frames per call, fewer only for the short last chunk "
+                             f"of the cache's {cache.frames} frames; several chunks at once run without frame_cache")
         if rope_start is None or isinstance(rope_start, torch.Tensor):
             raise ValueError("DiT: a frame_cache call needs rope_start=(t, h, w) as host ints, t being the chunk's absolute "
                              "position: the rollout's base t + frame_cache.past_frames")

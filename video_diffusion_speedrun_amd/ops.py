@@ -276,9 +276,15 @@ def _frames(frames, kv_lens, Lq: int, Lk: int, past: int = 0):
     return C.byref(_lib.ModGroups(lead, period))
 
 
-def _frame_major(frame_major, frames, kv_lens, past=0) -> bool:
-    """frame_major needs frames and excludes past / kv_lens: refused here, before anything is launched"""
+def _frame_major(frame_major, frames, kv_lens, past=0, chunk=1) -> bool:
+    """frame_major needs frames and excludes past / kv_lens, chunk != 1 needs frame_major: refused here, before anything
+    is launched"""
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+        raise ValueError(f"attention: chunk = {chunk!r} must be an int >= 1 (token-frames per causal chunk)")
     if not frame_major:
+        if chunk != 1:
+            raise ValueError(f"attention: chunk = {chunk} needs frame_major=True -- the chunk-causal mask exists on the "
+                             "frame-major kernels only (the interleaved and the past calls are frame-causal: chunk = 1)")
         return False
     if frames is None:
         raise ValueError("attention: frame_major=True needs frames=(lead, period)")
@@ -288,7 +294,7 @@ def _frame_major(frame_major, frames, kv_lens, past=0) -> bool:
 
 
 def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=None, past: int = 0,
-             frame_major: bool = False):
+             frame_major: bool = False, chunk: int = 1):
     """q [B,H,Lq,hd], k/v [B,H,Lk,hd], o [B,H,Lq,hd] strided views (last dim contiguous); lse f32 [B,H,Lq].
     kv_pad_ones: k / v are views into qkv_rope_fwd outputs whose pad carries the ones columns.
     kv_lens: int32 CUDA tensor [B]; sample b attends its first kv_lens[b] keys only (vds_attn_fwd_kvlen).
@@ -297,11 +303,13 @@ def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=No
     past (with frames): k / v hold Lk = Lq + past rows [lead rows | past cached token rows | this call's token rows]; a
     token query also attends every past key, a lead query none of them (vds_attn_fwd_causal_past).  Forward only.
     frame_major (with frames; not with past / kv_lens): q, k, v and lse rows are frame-major (fm_row), o stays token-major
-    and the key tiles no query of a tile attends are skipped (vds_attn_fwd_causal_fm)."""
+    and the key tiles no query of a tile attends are skipped (vds_attn_fwd_causal_fm).
+    chunk (with frame_major): the mask is causal over chunks of `chunk` token-frames and bidirectional inside a chunk --
+    fm_group_of(key, chunk) <= fm_group_of(query, chunk) (vds_attn_fwd_causal_fm_chunk); 1 is the frame-causal mask."""
     B, H, Lq, hd = q.shape
     Lk = k.shape[2]
     past = int(past)
-    fmaj = _frame_major(frame_major, frames, kv_lens, past)
+    fmaj = _frame_major(frame_major, frames, kv_lens, past, chunk)
     if past < 0 or (past and frames is None):
         raise ValueError(f"attention: past = {past} must be >= 0 and needs frames=(lead, period)")
     fr = _frames(frames, kv_lens, Lq, Lk, past) if frames is not None else None
@@ -313,7 +321,10 @@ def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=No
     a.o, (a.o_sb, a.o_sh, a.o_sl) = _p(o), _st(o)
     a.lse = _p(lse)
     a.kv_pad_ones = int(kv_pad_ones)  # (True = 1: self-attention layout; 2: ones in k / v only, cross-attention)
-    if fmaj:
+    if fmaj and chunk != 1:
+        check(_lib.load().vds_attn_fwd_causal_fm_chunk(C.byref(a), fr, chunk, _stream()),
+              f"vds_attn_fwd_causal_fm_chunk(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)},chunk={chunk})")
+    elif fmaj:
         check(_lib.load().vds_attn_fwd_causal_fm(C.byref(a), fr, _stream()),
               f"vds_attn_fwd_causal_fm(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)})")
     elif fr is not None and past:
@@ -348,17 +359,18 @@ def attn_bwd_workspace_floats(B, H, Lq, Lk, hd, kv_pad_ones: bool = False) -> in
 
 
 def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = False, kv_lens=None, frames=None,
-             frame_major: bool = False):
+             frame_major: bool = False, chunk: int = 1):
     """delta: f32 workspace of 2*B*H*Lq elements (rowsum(dO*O), then lse*log2 e); allocated here when None
     (size from vds_attn_bwd_workspace_bytes).
     kv_lens: as in attn_fwd; rows kv_lens[b].. of dk[b] / dv[b] are written as zeros (vds_attn_bwd_kvlen).
     frames: as in attn_fwd; a dk / dv row sums over the queries that attend it (vds_attn_bwd_causal).
     frame_major: as in attn_fwd -- q, k, v, lse, dq, dk, dv (and the delta workspace) rows are frame-major, o and do
-    token-major (vds_attn_bwd_causal_fm)."""
+    token-major (vds_attn_bwd_causal_fm).
+    chunk: as in attn_fwd (vds_attn_bwd_causal_fm_chunk)."""
     B, H, Lq, hd = q.shape
     assert lse.is_contiguous()
     Lk = k.shape[2]
-    fmaj = _frame_major(frame_major, frames, kv_lens)
+    fmaj = _frame_major(frame_major, frames, kv_lens, 0, chunk)
     fr = _frames(frames, kv_lens, Lq, Lk) if frames is not None else None
     a = AttnArgs()
     a.B, a.H, a.Lq, a.Lk, a.head_dim = B, H, Lq, Lk, hd
@@ -378,7 +390,10 @@ def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = Fa
     a.dv, (a.dv_sb, a.dv_sh, a.dv_sl) = _p(dv), _st(dv)
     a.delta = _p(delta)
     a.kv_pad_ones = int(kv_pad_ones)
-    if fmaj:
+    if fmaj and chunk != 1:
+        check(_lib.load().vds_attn_bwd_causal_fm_chunk(C.byref(a), fr, chunk, _stream()),
+              f"vds_attn_bwd_causal_fm_chunk(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)},chunk={chunk})")
+    elif fmaj:
         check(_lib.load().vds_attn_bwd_causal_fm(C.byref(a), fr, _stream()),
               f"vds_attn_bwd_causal_fm(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)})")
     elif fr is not None:
@@ -672,25 +687,35 @@ def tok_row(r: int, lead: int, period: int, L: int) -> int:
     return lead + ((r - lead) % S) * period + (r - lead) // S
 
 
-def fm_group_of(r: int, lead: int, S: int) -> int:
-    """group of frame-major row r: 0 for the lead rows, then 1 + (r - lead) // S; query r attends key j iff
-    fm_group_of(j) <= fm_group_of(r) -- mod_group_of's mask, permuted"""
-    return 0 if r < lead else 1 + (r - lead) // S
+def fm_group_of(r: int, lead: int, S: int, chunk: int = 1) -> int:
+    """group of frame-major row r: 0 for the lead rows, then 1 + (r - lead) // (chunk * S); query r attends key j iff
+    fm_group_of(j) <= fm_group_of(r) -- mod_group_of's mask, permuted (chunk = 1), or the chunk-causal mask: causal over
+    chunks of `chunk` frames, bidirectional inside one"""
+    return 0 if r < lead else 1 + (r - lead) // (chunk * S)
 
 
-def fm_key_end(q0: int, q1: int, lead: int, S: int) -> int:
-    """first frame-major key row that no query row of [q0, q1) attends: a query tile's key loop ends here"""
+def chunk_group_of(l: int, lead: int, period: int, chunk: int = 1) -> int:
+    """fm_group_of in token rows: 0 for the lead rows, then 1 + ((l - lead) % period) // chunk"""
+    return 0 if l < lead else 1 + ((l - lead) % period) // chunk
+
+
+def fm_key_end(q0: int, q1: int, lead: int, S: int, chunk: int = 1, L=None) -> int:
+    """first frame-major key row that no query row of [q0, q1) attends: a query tile's key loop ends here.  L (rows per
+    sample): the bound is clipped to it, as the kernels do -- a short last chunk (period % chunk != 0) would pass it"""
     if q1 <= lead:
         return lead
-    return lead + ((q1 - 1 - lead) // S + 1) * S
+    G = chunk * S
+    end = lead + ((q1 - 1 - lead) // G + 1) * G
+    return end if L is None else min(end, L)
 
 
-def fm_query_start(k0: int, lead: int, S: int) -> int:
+def fm_query_start(k0: int, lead: int, S: int, chunk: int = 1) -> int:
     """first frame-major query row that may attend a key row of [k0, ...): a key tile's query loop starts here (rounded
     down to the query tile by the kernels)"""
     if k0 < lead:
         return 0
-    return lead + ((k0 - lead) // S) * S
+    G = chunk * S
+    return lead + ((k0 - lead) // G) * G
 
 
 def _fm_frames(frames, L: int):

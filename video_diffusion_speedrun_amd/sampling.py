@@ -61,6 +61,11 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
     last chunk is its own defined computation -- registers at 1.0 -- pinned by tests/helpers/frame_cache_ref.py.
     False (the default): the loop described above, call for call.
 
+    On a DiT built with frame_chunk=c > 1 (causal over chunks of c token-frames) a rollout advances by whole chunks:
+    rollout_frames must be a multiple of c and the cond_latents frames a whole number of chunks (ValueError otherwise; the
+    video's last chunk may be short).  kv_cache=True then takes rollout_frames == c -- a cached call covers one chunk --
+    and the cond_latents prefill runs one call and one commit() per chunk.
+
     cond_latents ([1,16,Tc,h,w], Tc a multiple of the model's time_patch_size; image-to-video, video extension): the
     first Tc latent frames are held at these values -- their token-frames are given t = 0 in every model call (per-frame
     timesteps, DiT.forward), the other frames the step's t, and the frames are written back into the latents and the
@@ -80,6 +85,20 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
 
         dit.load_state_dict(checkpoint.read_model_state(ckpt_dir, ema=True))
     """
+    c_model = int(getattr(model, "frame_chunk", 1))
+    if c_model > 1 and rollout_frames is not None and not isinstance(rollout_frames, bool) \
+            and int(rollout_frames) == rollout_frames and int(rollout_frames) >= 1:  # (refused before the device is touched)
+        if int(rollout_frames) % c_model != 0:
+            raise ValueError(f"frame rollout on a frame_chunk={c_model} model: rollout_frames = {rollout_frames} must be a "
+                             f"multiple of {c_model} -- a chunk's frames attend each other and are denoised together")
+        if kv_cache and int(rollout_frames) != c_model:
+            raise ValueError(f"kv_cache=True on a frame_chunk={c_model} model: a cached call covers ONE chunk, pass "
+                             f"rollout_frames={c_model} (or kv_cache=False for {rollout_frames} frames at a time)")
+        if cond_latents is not None and cond_latents.dim() == 5 \
+                and cond_latents.shape[2] % (c_model * model.time_patch_size) != 0:
+            raise ValueError(f"frame rollout on a frame_chunk={c_model} model: cond_latents must hold a whole number of "
+                             f"chunks -- a multiple of {c_model * model.time_patch_size} latent frames ({c_model} token-frames "
+                             f"of time_patch_size {model.time_patch_size}), got {cond_latents.shape[2]}")
     dev = torch.device(device)
     prompt_embeds = prompt_embeds.to(dev, bf16)
     guided = cfg_scale > 1
@@ -201,8 +220,8 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
             return model(torch.cat([x, x]) if guided else x.contiguous(), ctx, tt,
                          rope_start=(base[0] + f0, base[1], base[2]), register_timesteps=reg, frame_cache=cache, **kw)
 
-        if n_cond:
-            chunk_call(0, n_cond, 0.0)
+        for f0 in range(0, n_cond, c_model if c_model > 1 else max(n_cond, 1)):  # (frame_chunk: one call per chunk)
+            chunk_call(f0, min(f0 + c_model, n_cond) if c_model > 1 else n_cond, 0.0)
             cache.commit()
         for f0 in range(n_cond, n_frames, k_roll):
             f1 = min(f0 + k_roll, n_frames)

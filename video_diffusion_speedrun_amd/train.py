@@ -12,6 +12,7 @@ of each sample, `lens_from_mask(attention_mask)`) restricts the cross-attention 
 
 `forward(..., frame_mode="first_frame" | "independent")` trains with one noise level per token-frame (image-to-video
 conditioning, diffusion forcing): DiT.forward takes `timesteps [B, t]`, the noising and the loss work per frame.
+`frame_mode="chunk"` (a DiT built with frame_chunk=c): one noise level per chunk of c token-frames.
 """
 from __future__ import annotations
 
@@ -105,7 +106,7 @@ def frame_flow_loss(out, v, weights, time_patch: int):
     return _FrameFlowLoss.apply(out.contiguous(), v.contiguous(), weights.to(f32).contiguous(), int(time_patch))
 
 
-FRAME_MODES = (None, "first_frame", "independent")
+FRAME_MODES = (None, "first_frame", "independent", "chunk")
 
 
 def frame_group_of(l: int, n_frames: int, lead: int = 16) -> int:
@@ -114,20 +115,39 @@ def frame_group_of(l: int, n_frames: int, lead: int = 16) -> int:
     return ops.mod_group_of(l, lead, n_frames)
 
 
-def draw_frame_levels(frame_mode: str, B: int, n_frames: int, device, generator=None) -> torch.Tensor:
+def _check_chunk(chunk) -> int:
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+        raise ValueError(f"frame_mode='chunk': chunk = {chunk!r} must be an int >= 1 (the model's frame_chunk)")
+    return chunk
+
+
+def draw_frame_levels(frame_mode: str, B: int, n_frames: int, device, generator=None, chunk: int = 1) -> torch.Tensor:
     """the first random draw of a per-frame step, in bf16: "first_frame" -> t [B], the very draw of the per-sample path
-    (randn(B), time shift); "independent" -> t [B, n_frames], one level per token-frame"""
-    if frame_mode not in ("first_frame", "independent"):
+    (randn(B), time shift); "independent" -> t [B, n_frames], one level per token-frame; "chunk" -> t [B, ceil(n_frames /
+    chunk)], one level per chunk of `chunk` token-frames"""
+    if frame_mode not in ("first_frame", "independent", "chunk"):
         raise ValueError(f"frame_mode must be one of {FRAME_MODES}, got {frame_mode!r}")
-    shape = (B,) if frame_mode == "first_frame" else (B, n_frames)
+    if frame_mode == "chunk":
+        shape = (B, -(-n_frames // _check_chunk(chunk)))
+    else:
+        shape = (B,) if frame_mode == "first_frame" else (B, n_frames)
     return time_shift_from_normal(torch.randn(shape, device=device, dtype=bf16, generator=generator))
 
 
-def frame_schedule(frame_mode: str, t: torch.Tensor, n_frames: int, cond_prob: float = 0.5, generator=None):
+def frame_schedule(frame_mode: str, t: torch.Tensor, n_frames: int, cond_prob: float = 0.5, generator=None,
+                   chunk: int = 1):
     """levels from draw_frame_levels -> (timesteps [B, n_frames] in t.dtype, weights f32 [B, n_frames]).
     "first_frame": every frame of sample b at t[b]; with probability cond_prob token-frame 0 is a clean conditioning
-    frame -- t = 0 and weight 0 (out of the loss).  "independent": t as drawn, weights 1.
+    frame -- t = 0 and weight 0 (out of the loss).  "independent": t as drawn, weights 1.  "chunk": t [B, ceil(n_frames /
+    chunk)], every level repeated over the `chunk` token-frames of its chunk and cut to n_frames, weights 1.
     Only device-side elementwise work: no host sync, no boolean indexing (capturable)."""
+    if frame_mode == "chunk":
+        n_chunks = -(-n_frames // _check_chunk(chunk))
+        if t.dim() != 2 or t.shape[1] != n_chunks:
+            raise ValueError(f"frame_schedule('chunk'): t [B, {n_chunks}] expected (ceil({n_frames} / {chunk}) chunks), got "
+                             f"{tuple(t.shape)}")
+        tf = t.repeat_interleave(chunk, dim=1)[:, :n_frames].contiguous()
+        return tf, torch.ones(tf.shape, dtype=f32, device=t.device)
     if frame_mode == "independent":
         if t.dim() != 2 or t.shape[1] != n_frames:
             raise ValueError(f"frame_schedule('independent'): t [B, {n_frames}] expected, got {tuple(t.shape)}")
@@ -156,7 +176,8 @@ def forward(dit_model, batch, text_encoder, tokenizer, device, global_step, mast
             frame_timesteps=None, frame_weights=None):
     """frame_mode=None (default): one noise level per sample, the reference's step.
     frame_mode="first_frame": one level per sample, and with probability cond_prob token-frame 0 stays clean (t = 0) and
-    leaves the loss (image-to-video); "independent": one level per token-frame (diffusion forcing).  frame_timesteps
+    leaves the loss (image-to-video); "independent": one level per token-frame (diffusion forcing); "chunk": one level
+    per chunk of the model's frame_chunk token-frames (what a chunk-at-a-time rollout meets), weights 1.  frame_timesteps
     [B, t] / frame_weights [B, t] override the drawn levels / weights (t = T // time_patch_size)."""
     logger = logging.getLogger(__name__)
     vae_latent = batch["latent"].to(device).to(bf16)
@@ -188,10 +209,11 @@ def forward(dit_model, batch, text_encoder, tokenizer, device, global_step, mast
         if frame_timesteps is None:
             if frame_mode is None:
                 raise ValueError("frame_weights without frame_mode or frame_timesteps: nothing defines the per-frame levels")
-            levels = draw_frame_levels(frame_mode, B, n_frames, device, generator)
+            ckw = {"chunk": int(getattr(dit_model, "frame_chunk", 1))} if frame_mode == "chunk" else {}
+            levels = draw_frame_levels(frame_mode, B, n_frames, device, generator, **ckw)
         noise = torch.randn(vae_latent.shape, device=device, dtype=bf16, generator=generator)
         if frame_timesteps is None:
-            t, weights = frame_schedule(frame_mode, levels, n_frames, cond_prob, generator)
+            t, weights = frame_schedule(frame_mode, levels, n_frames, cond_prob, generator, **ckw)
         else:
             t = torch.as_tensor(frame_timesteps).to(device=device, dtype=bf16)
             weights = torch.ones(t.shape, dtype=f32, device=device)
