@@ -53,8 +53,12 @@ const char* vds_last_error(void);
  * activation and VDS_EPI_GATE_RES only the new residual stream, in every tiling and in the partial tiles; what is
  * stored is bit-identical to the two-output launch.  C == NULL with any other epilogue, or with C2 == NULL too, is
  * VDS_ERR_ARG.
- * Requirements: K % 8 == 0 for NT / NN (any K for TN); N % 8 == 0 (TN: M % 8 == 0 too);
- * ld* % 8 == 0; every tensor < 4 GiB. */
+ * Requirements (anything else is VDS_ERR_ARG): K % 8 == 0 for NT / NN (any K for TN); N % 8 == 0 (TN: M % 8 == 0
+ * too); lda % 8 == 0 and ldb % 8 == 0; and for every other pointer the call uses (non-NULL and read or written by
+ * its epilogue) a leading dimension that keeps 16-byte row segments aligned: ldc % 8 == 0 (ldc % 4 == 0 for the
+ * fp32 C of VDS_EPI_F32), ldc2 % 8 == 0 (BIAS_GELU, GATE_RES), ldaux % 8 == 0 (GATE_RES, DGELU), ldgate % 4 == 0
+ * (GATE_RES).  Base pointers must be 16-byte aligned (not checked); an A or B operand of 4 GiB or more is
+ * VDS_ERR_UNSUPPORTED. */
 enum { VDS_NT = 0, VDS_NN = 1, VDS_TN = 2 };
 enum { VDS_EPI_STORE = 0, VDS_EPI_BIAS_GELU = 1, VDS_EPI_GATE_RES = 2, VDS_EPI_DGELU = 3, VDS_EPI_F32 = 4 };
 

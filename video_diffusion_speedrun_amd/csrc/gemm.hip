@@ -1470,6 +1470,15 @@ extern "C" int vds_gemm_force_tile(int32_t tile) {
 static int gemm_bf16_impl(const vds_gemm_args* a, const vds_mod_groups* grp, vds_stream_t stream) {
   if (!a || !a->A || !a->B || a->M <= 0 || a->N <= 0 || a->K <= 0) return VDS_ERR_ARG;
   if ((a->N & 7) || (a->lda & 7) || (a->ldb & 7)) return VDS_ERR_ARG;
+  // the epilogues move 16-byte row segments at row * ld + column (column % 8 == 0): every leading dimension of a pointer
+  // this call uses must keep them aligned -- 8 bf16 elements, 4 floats (the fp32 C of VDS_EPI_F32, the gate table)
+  {
+    const int e = a->epilogue;
+    if (a->C && (a->ldc & (e == VDS_EPI_F32 ? 3 : 7))) return VDS_ERR_ARG;
+    if ((e == VDS_EPI_BIAS_GELU || e == VDS_EPI_GATE_RES) && a->C2 && (a->ldc2 & 7)) return VDS_ERR_ARG;
+    if ((e == VDS_EPI_GATE_RES || e == VDS_EPI_DGELU) && a->aux && (a->ldaux & 7)) return VDS_ERR_ARG;
+    if (e == VDS_EPI_GATE_RES && a->gate && (a->ldgate & 3)) return VDS_ERR_ARG;
+  }
   GemmP p;
   p.M = a->M; p.N = a->N; p.K = a->K;
   p.A = (const bf16_t*)a->A; p.lda = a->lda;
