@@ -330,6 +330,27 @@ int vds_attn_bwd_causal_fm(const vds_attn_args* args, const vds_mod_groups* fram
  * chunk < 1 or frames == NULL: VDS_ERR_ARG.  chunk travels by value.  The profiler credits the visited range. */
 int vds_attn_fwd_causal_fm_chunk(const vds_attn_args* args, const vds_mod_groups* frames, int32_t chunk, vds_stream_t stream);
 int vds_attn_bwd_causal_fm_chunk(const vds_attn_args* args, const vds_mod_groups* frames, int32_t chunk, vds_stream_t stream);
+/* Sliding-window chunk-causal frame-major self-attention: the _fm_chunk calls with a window of `window_chunks` chunks.  A
+ * lead query attends the lead keys; a token query of chunk n attends every lead key and the token keys of chunks
+ * max(0, n - window_chunks + 1) .. n.  With G = chunk * S, in frame-major rows query r attends [0, lead) and
+ * [kbeg(r), kend(r)), kbeg(r) = lead + max(0, (r - lead) / G - window_chunks + 1) * G, and key j is attended by
+ * [qstart(j), qend(j)), qend(j) = min(L, lead + ((j - lead) / G + window_chunks) * G) (L for a lead key); kend and qstart
+ * are the _fm_chunk bounds.  Every row attends its own chunk: no empty row; lead = 0 is allowed.
+ * What is skipped: a forward / dQ workgroup visits the 64-key tiles that hold lead keys and then the tiles from the one
+ * that holds kbeg of its first token query to the one below kend of its last query (never one twice); a dK/dV workgroup
+ * whose 128 keys include a lead key sweeps every query tile, any other the tiles from qstart of its first key to the one
+ * below qend of its last.  A 32 x 32 sub-block runs without mask code if its wave holds no lead query and its keys lie
+ * wholly below lead or wholly inside [kbeg of the wave's last query, kend of its first), resp. if its queries lie inside
+ * [the wave's largest qstart, its smallest qend).  The profiler credits the visited range.
+ * These are WIN instances of the frame-major kernels -- the plain 32x32x16 family at every head dim and the 16x16x32 family
+ * of the ones layout at head dim 72 -- selected by the variant bits and knobs of the _fm calls; no atomics, no workspace
+ * beyond that of the _fm calls.  window_chunks >= ceil(period / chunk) forwards to the _fm_chunk call (the same bits);
+ * window_chunks < 1, chunk < 1 or frames == NULL: VDS_ERR_ARG; the other refusals are those of the _fm calls.  chunk and
+ * window_chunks travel by value. */
+int vds_attn_fwd_causal_fm_window(const vds_attn_args* args, const vds_mod_groups* frames, int32_t chunk, int32_t window_chunks,
+                                  vds_stream_t stream);
+int vds_attn_bwd_causal_fm_window(const vds_attn_args* args, const vds_mod_groups* frames, int32_t chunk, int32_t window_chunks,
+                                  vds_stream_t stream);
 /* vds_rmsnorm_mod_fwd with mod f32 [B*G, ldmod]: the same arithmetic per row, y / rstd bit-identical to the per-sample
  * call run on the rows of one group with that group's mod row.  Every form of the dispatcher is covered. */
 int vds_rmsnorm_mod_fwd_grouped(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod,

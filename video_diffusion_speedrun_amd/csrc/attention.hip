@@ -69,7 +69,10 @@ struct AttnP {
   // chunk-causal granularity (vds_attn_*_causal_fm_chunk): G = c * S rows per chunk of c frames (the last one may be short);
   // G = S (c = 1) is the frame-causal mask.  The mask bounds kend / qstart use G, the row map tok() keeps S
   int fm_G;
+  // sliding window (vds_attn_*_causal_fm_window): W chunks, carried in fc_past -- no FM instance reads that field as a past,
+  // and the WIN instances are the only readers of the window; the struct keeps its size (its size moves the code objects)
 };
+static_assert(sizeof(AttnP) == 376, "AttnP: the kernel argument block keeps its size");
 
 // Keys of sample b.  KVLEN: kv_lens[b] clamped to [0, Lk] -- b is the same for the whole workgroup, so this is one
 // scalar load; every bound, tile count and mask of the kernel then uses it in place of the launch-wide Lk.
@@ -175,6 +178,12 @@ struct FmMap {
   __device__ __forceinline__ int kend(int r) const { return r < lead ? lead : min(L, lead + __mul24(chunk(r) + 1, G)); }
   // the first query row that attends key row j
   __device__ __forceinline__ int qstart(int j) const { return j < lead ? 0 : lead + __mul24(chunk(j), G); }
+  // window of W chunks (WIN instances): the first token key row that query row r attends (lead for a lead query: none) ...
+  __device__ __forceinline__ int kbeg(int r, int W) const {
+    return r < lead ? lead : lead + __mul24(max(chunk(r) - W + 1, 0), G);
+  }
+  // ... and the first query row past the ones that attend key row j (every query attends a lead key)
+  __device__ __forceinline__ int qend(int j, int W) const { return j < lead ? L : min(L, lead + __mul24(chunk(j) + W, G)); }
   // the token row of frame-major row r (o / d_o)
   __device__ __forceinline__ int tok(int r) const {
     if (r < lead) return r;
@@ -213,6 +222,70 @@ __device__ __forceinline__ void fm_zero_q(int row0, int qstart, f32x16& pm, f32x
 #pragma unroll
   for (int r = 0; r < 16; ++r)
     if (row0 + (r & 3) + 8 * (r >> 2) < qstart) { pm[r] = 0.f; ds[r] = 0.f; }
+}
+// Sliding window (WIN instances of the FM kernels, vds_attn_*_causal_fm_window; W = p.fc_past chunks): query r attends
+// [0, lead) and [kbeg(r), kend(r)) -- the lead rows plus one contiguous run -- and key j is attended by [qstart(j), qend(j)).
+__device__ __forceinline__ int fm_kbeg(const AttnP& p, int r) { return FmMap(p).kbeg(r, p.fc_past); }
+__device__ __forceinline__ int fm_qend(const AttnP& p, int j) { return FmMap(p).qend(j, p.fc_past); }
+// Key tiles of a forward / dQ workgroup with query rows [q0, q0 + rows), nkt = the tile count of fm_keys: the tiles that
+// hold lead keys, [0, nl), then the tiles from the one that holds kbeg of the workgroup's first token query, [jb, nkt) --
+// jb >= nl, so no tile comes twice.  The loop counts visits; tile(it) is the tile of visit it, and the prefetch of the
+// next visit follows it across the gap.
+template <bool WIN>  // (the other instances build an empty one)
+struct FmWinTiles {
+  int nl = 0, jb = 0, nit = 0;
+  __device__ __forceinline__ FmWinTiles(const AttnP& p, int q0, int rows, int nkt) {
+    if constexpr (WIN) {
+      nl = min(nkt, (p.fc_lead + 63) >> 6);
+      const int qf = max(q0, p.fc_lead);  // first token query, if the workgroup holds one
+      jb = qf < min(q0 + rows, p.Lq) ? max(nl, fm_kbeg(p, qf) >> 6) : nkt;
+      nit = nl + nkt - jb;
+    }
+  }
+  __device__ __forceinline__ int tile(int it) const { return it < nl ? it : it - nl + jb; }
+};
+// the wave-uniform open test of the WIN forward / dQ kernels: the 32 keys from k0 need no mask code if the wave holds no
+// lead query (wlead, wkend are 0 otherwise) and they lie wholly below lead or wholly inside [kbeg of the wave's last query,
+// kend of its first)
+template <bool WIN>
+struct FmWinOpen {
+  int wlead = 0, wkbeg = 0, wkend = 0;
+  __device__ __forceinline__ FmWinOpen(const AttnP& p, int wq0, int wrows) {
+    if constexpr (WIN) {
+      const bool tokens = wq0 >= p.fc_lead;
+      wlead = tokens ? p.fc_lead : 0;
+      wkend = tokens ? __builtin_amdgcn_readfirstlane(fm_kend(p, wq0)) : 0;
+      wkbeg = __builtin_amdgcn_readfirstlane(fm_kbeg(p, min(wq0 + wrows, p.Lq) - 1));
+    }
+  }
+  __device__ __forceinline__ bool open(int k0) const { return k0 + 32 <= wlead || (k0 >= wkbeg && k0 + 32 <= wkend); }
+};
+// key row `key` is masked for a query with the bounds kbeg / kend: a token key outside its run (kbeg >= lead always)
+__device__ __forceinline__ bool fm_win_masked(int key, int lead, int kbeg, int kend) {
+  return key >= kend || (key >= lead && key < kbeg);
+}
+__device__ __forceinline__ void fm_fill_win(int row0, int lead, int kbeg, int kend, f32x16& s, float fill) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    if (fm_win_masked(row0 + (r & 3) + 8 * (r >> 2), lead, kbeg, kend)) s[r] = fill;
+}
+// 32x32 accumulators with the QUERY on the registers: P and dS of the queries outside [qstart, qend) of the lane's key
+__device__ __forceinline__ void fm_zero_q_win(int row0, int qstart, int qend, f32x16& pm, f32x16& ds) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int q = row0 + (r & 3) + 8 * (r >> 2);
+    if (q < qstart || q >= qend) { pm[r] = 0.f; ds[r] = 0.f; }
+  }
+}
+// the key of a dK/dV wave (32 keys from k0) with the smallest qend: its first token key -- qend grows with the row from
+// there, and a lead key's is L -- or, in a wave of lead keys only, its last key
+__device__ __forceinline__ int fm_win_first_token_key(const AttnP& p, int k0) {
+  return min(max(k0, p.fc_lead), min(k0 + 31, p.Lk - 1));
+}
+// Query tiles of a WIN dK/dV workgroup with key rows [key0, key0 + 128): one past the last 64-row tile it sweeps -- every
+// tile if it holds a lead key, else the tiles below qend of its last key
+__device__ __forceinline__ int fm_win_qtiles(const AttnP& p, int key0, int nqt) {
+  return key0 < p.fc_lead ? nqt : (fm_qend(p, min(key0 + 127, p.Lk - 1)) + 63) >> 6;
 }
 // FM instances of the forward and dQ kernels: the row-tile order of a head is reversed, so that its longest workgroups
 // (the late query tiles) are issued first; the dK/dV kernel's natural order already starts with its longest (early keys)
@@ -544,10 +617,16 @@ struct DmaStageFm {
 // FM (vds_attn_fwd_causal_fm; without KVLEN / CAUSAL / PAST): frame-major rows.  The key loop ends at the largest kend of
 // the workgroup's queries (the K / V bounds and the tile count follow it, the way KVLEN's count does), a sub-block is
 // compared against the lane's kend unless it lies below the kend of the wave's first query, and the o row goes to tok(row).
-template <int HDP, int HDQ, int WPS, bool PIPE, bool KVLEN = false, bool CAUSAL = false, bool PAST = false, bool FM = false>
+// WIN (vds_attn_fwd_causal_fm_window; with FM): the window of p.fc_past chunks.  The key loop visits the lead tiles and
+// then the tiles from kbeg of the workgroup's first token query (FmWinTiles); a lane keeps key j iff j < lead or
+// kbeg <= j < kend, and a sub-block that FmWinOpen finds open runs without mask code.  A row whose first visited
+// sub-blocks are all masked (lead = 0) keeps m = -1e30, l = 0 and O = 0 until its window opens.
+template <int HDP, int HDQ, int WPS, bool PIPE, bool KVLEN = false, bool CAUSAL = false, bool PAST = false, bool FM = false,
+          bool WIN = false>
 __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, TILE = 64 * HDP * 2;
   static_assert(!FM || !(KVLEN || CAUSAL || PAST), "frame-major: its own mask");
+  static_assert(!WIN || FM, "the window: on frame-major rows");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int bh, qt;
   if (!decode_block(p.n_rt, p.tail_last, p.B * p.H, bh, qt)) return;
@@ -575,8 +654,16 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   dk.init(p.k_sl, p.hd, wave, lane);
   dv.init(p.v_sl, p.hd, wave, lane);
   const unsigned k_step = (unsigned)(64 * p.k_sl * 2), v_step = (unsigned)(64 * p.v_sl * 2);
+  const int nkt = (Lk + 63) / 64;
+  [[maybe_unused]] const FmWinTiles<WIN> wt(p, qt * 128, 128, nkt);  // WIN: the two tile ranges of the key loop
+  const int nit = WIN ? wt.nit : nkt;                            // visits of the key loop
+  if constexpr (WIN) {
+    dk.issue(rk, smem, (unsigned)wt.tile(0) * k_step, wave);
+    dv.issue(rv, smem + TILE, (unsigned)wt.tile(0) * v_step, wave);
+  } else {
   dk.issue(rk, smem, 0, wave);
   dv.issue(rv, smem + TILE, 0, wave);
+  }
 
   bf16x8 qf[KSQ];
 #pragma unroll
@@ -592,7 +679,6 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   for (int i = 0; i < NDB; ++i) o[i] = zero16();
   float m = -1e30f, l = 0.f;
   const float c = p.scale * LOG2E;
-  const int nkt = (Lk + 63) / 64;
   const FcMap fm(p);
   int fcq = 0;
   if constexpr (CAUSAL) fcq = fm.fq(qrow);
@@ -603,17 +689,23 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
     klim = fm_kend(p, qrow);
     wklim = wq0 >= p.fc_lead ? __builtin_amdgcn_readfirstlane(fm_kend(p, wq0)) : 0;
   }
+  // WIN: the lane's kbeg next to its kend, and the wave's open test
+  [[maybe_unused]] int kbeg = 0;
+  [[maybe_unused]] const FmWinOpen<WIN> wo(p, wq0, 32);
+  if constexpr (WIN) kbeg = fm_kbeg(p, qrow);
 #pragma unroll
   for (int ks = 0; ks < KSQ; ++ks) retire(qf[ks]);
   VDS_WAIT_VM(0);
   __syncthreads();  // tile 0 landed (DMA waited above: the compiler does not see it)
 
-  auto kv_tile = [&](int j, auto PAR) {  // unrolled by two: compile-time LDS buffer parity (see the wide kernel)
+  auto kv_tile = [&](int it, auto PAR) {  // unrolled by two: compile-time LDS buffer parity (see the wide kernel)
     constexpr int par = decltype(PAR)::value;
-    if (j + 1 < nkt) {
+    int j = it, jn = it + 1;  // this visit's key tile and the next one's (WIN: across the gap between the two ranges)
+    if constexpr (WIN) { j = wt.tile(it); jn = wt.tile(it + 1); }
+    if (it + 1 < nit) {
       char* nk = smem + (par ^ 1) * 2 * TILE;
-      dk.issue(rk, nk, (unsigned)(j + 1) * k_step, wave);
-      dv.issue(rv, nk + TILE, (unsigned)(j + 1) * v_step, wave);
+      dk.issue(rk, nk, (unsigned)jn * k_step, wave);
+      dv.issue(rv, nk + TILE, (unsigned)jn * v_step, wave);
     }
     const char* kt = smem + par * 2 * TILE;
     const char* vt = kt + TILE;
@@ -629,7 +721,10 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
       load_vfrags<HDP, NDB>(v0, vt, 0, lane);
 #pragma unroll
       for (int ks = 0; ks < KSQ; ++ks) s1 = mfma32(k1[ks], qf[ks], s1);
-      if constexpr (FM) {  // (kend <= Lk: the compare covers the ragged tile too)
+      if constexpr (WIN) {
+        if (!wo.open(j * 64)) fm_fill_win(j * 64 + 4 * h, p.fc_lead, kbeg, klim, s0, -INFINITY);
+        if (!wo.open(j * 64 + 32)) fm_fill_win(j * 64 + 32 + 4 * h, p.fc_lead, kbeg, klim, s1, -INFINITY);
+      } else if constexpr (FM) {  // (kend <= Lk: the compare covers the ragged tile too)
         if (j * 64 + 32 > wklim) fm_fill(j * 64 + 4 * h, klim, s0, -INFINITY);
         if (j * 64 + 64 > wklim) fm_fill(j * 64 + 32 + 4 * h, klim, s1, -INFINITY);
       } else {
@@ -668,7 +763,9 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
         f32x16 s = zero16();
 #pragma unroll
         for (int ks = 0; ks < KSQ; ++ks) s = mfma32(frag_row<HDP>(kt, kb * 32, ks, lane), qf[ks], s);
-        if constexpr (FM) {
+        if constexpr (WIN) {
+          if (!wo.open(j * 64 + kb * 32)) fm_fill_win(j * 64 + kb * 32 + 4 * h, p.fc_lead, kbeg, klim, s, -INFINITY);
+        } else if constexpr (FM) {
           if (j * 64 + kb * 32 + 32 > wklim) fm_fill(j * 64 + kb * 32 + 4 * h, klim, s, -INFINITY);
         } else {
         if (ragged) {
@@ -693,9 +790,9 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
     VDS_WAIT_VM(0);
     __syncthreads();  // next tile landed, everyone done reading this one
   };
-  for (int j = 0; j < nkt; j += 2) {
-    kv_tile(j, std::integral_constant<int, 0>{});
-    if (j + 1 < nkt) kv_tile(j + 1, std::integral_constant<int, 1>{});
+  for (int it = 0; it < nit; it += 2) {
+    kv_tile(it, std::integral_constant<int, 0>{});
+    if (it + 1 < nit) kv_tile(it + 1, std::integral_constant<int, 1>{});
   }
 
   const float lt = add_with_other_half(l);
@@ -1015,9 +1112,12 @@ __global__ __launch_bounds__(256) void attn_delta_tokmajor_kernel(AttnP p) {
 // FM (vds_attn_bwd_causal_fm; the plain layout only): frame-major rows -- the key sweep ends at the largest kend of the
 // workgroup's queries, dS is zeroed from the lane's kend unless the sub-block lies below the kend of the wave's first query,
 // and the dO row is that of token row tok(row); q, dq and the statistics are indexed by the frame-major row.
-template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false, bool FM = false>
+// WIN (vds_attn_bwd_causal_fm_window; with FM): the window -- the two tile ranges, the per-lane compare and the open test
+// of the forward kernel, with dS = 0 in place of -inf.
+template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false, bool FM = false, bool WIN = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, TILE = 64 * HDP * 2;
+  static_assert(!WIN || FM, "the window: on frame-major rows");
   static_assert(!ONES || (HDP == 96 && HDQ == 80), "ones columns: head_dim 72 layout");
   static_assert(!FM || !(ONES || KVLEN || CAUSAL), "frame-major: the plain layout, its own mask");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1046,8 +1146,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   dk.init(p.k_sl, hd_kv, wave, lane);
   dv.init(p.v_sl, hd_kv, wave, lane);
   const unsigned k_step = (unsigned)(64 * p.k_sl * 2), v_step = (unsigned)(64 * p.v_sl * 2);
+  const int nkt = (Lk + 63) / 64;
+  [[maybe_unused]] const FmWinTiles<WIN> wt(p, qt * 128, 128, nkt);  // WIN: as in the forward kernel
+  const int nit = WIN ? wt.nit : nkt;
+  if constexpr (WIN) {
+    dk.issue(rk, smem, (unsigned)wt.tile(0) * k_step, wave);
+    dv.issue(rv, smem + TILE, (unsigned)wt.tile(0) * v_step, wave);
+  } else {
   dk.issue(rk, smem, 0, wave);
   dv.issue(rv, smem + TILE, 0, wave);
+  }
 
   bf16x8 qf[KSQ], dof[KSQ];
 #pragma unroll
@@ -1086,7 +1194,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   f32x16 dq[NDB];
 #pragma unroll
   for (int i = 0; i < NDB; ++i) dq[i] = zero16();
-  const int nkt = (Lk + 63) / 64;
   const FcMap fm(p);
   int fcq = 0;
   if constexpr (CAUSAL) fcq = fm.fq(qrow);
@@ -1096,15 +1203,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
     klim = fm_kend(p, qrow);
     wklim = wq0 >= p.fc_lead ? __builtin_amdgcn_readfirstlane(fm_kend(p, wq0)) : 0;
   }
+  [[maybe_unused]] int kbeg = 0;  // WIN: as in the forward kernel
+  [[maybe_unused]] const FmWinOpen<WIN> wo(p, qt * 128 + wave * 32, 32);
+  if constexpr (WIN) kbeg = fm_kbeg(p, qrow);
   VDS_WAIT_VM(0);
   __syncthreads();  // tile 0 landed
 
-  auto kv_tile = [&](int j, auto PAR) {  // unrolled by two: compile-time LDS buffer parity (see the forward kernel)
+  auto kv_tile = [&](int it, auto PAR) {  // unrolled by two: compile-time LDS buffer parity (see the forward kernel)
     constexpr int par = decltype(PAR)::value;
-    if (j + 1 < nkt) {
+    int j = it, jn = it + 1;  // this visit's key tile and the next one's (WIN: across the gap)
+    if constexpr (WIN) { j = wt.tile(it); jn = wt.tile(it + 1); }
+    if (it + 1 < nit) {
       char* nk = smem + (par ^ 1) * 2 * TILE;
-      dk.issue(rk, nk, (unsigned)(j + 1) * k_step, wave);
-      dv.issue(rv, nk + TILE, (unsigned)(j + 1) * v_step, wave);
+      dk.issue(rk, nk, (unsigned)jn * k_step, wave);
+      dv.issue(rv, nk + TILE, (unsigned)jn * v_step, wave);
     }
     const char* kt = smem + par * 2 * TILE;
     const char* vt = kt + TILE;
@@ -1132,7 +1244,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
         for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r] * c - lse2) * dp[r];
       }
       if constexpr (CAUSAL) fc_fill(fm, j * 64 + kb * 32 + 4 * h, fcq, s, 0.f);
-      if constexpr (FM) {
+      if constexpr (WIN) {
+        if (!wo.open(j * 64 + kb * 32)) fm_fill_win(j * 64 + kb * 32 + 4 * h, p.fc_lead, kbeg, klim, s, 0.f);
+      } else if constexpr (FM) {
         if (j * 64 + kb * 32 + 32 > wklim) fm_fill(j * 64 + kb * 32 + 4 * h, klim, s, 0.f);
       }
 #pragma unroll
@@ -1146,9 +1260,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
     VDS_WAIT_VM(0);
     __syncthreads();
   };
-  for (int j = 0; j < nkt; j += 2) {
-    kv_tile(j, std::integral_constant<int, 0>{});
-    if (j + 1 < nkt) kv_tile(j + 1, std::integral_constant<int, 1>{});
+  for (int it = 0; it < nit; it += 2) {
+    kv_tile(it, std::integral_constant<int, 0>{});
+    if (it + 1 < nit) kv_tile(it + 1, std::integral_constant<int, 1>{});
   }
   if (qrow < p.Lq)
     store_rows<NDB>(p.dq + b * p.dq_sb + hh * p.dq_sh + (long)qrow * p.dq_sl, dq, p.scale, p.hd, h);
@@ -1171,9 +1285,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
 // FM (vds_attn_bwd_causal_fm; the plain layout, no query split): frame-major rows -- the query sweep starts at the tile
 // that holds qstart of the workgroup's first key, P and dS are zeroed before the lane's qstart unless the sub-block starts
 // at or past the qstart of the wave's last key, and the dO tile is gathered from the token rows tok(row) (DmaStageFm).
-template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false, bool FM = false>
+// WIN (vds_attn_bwd_causal_fm_window; with FM): the window -- key j is attended by [qstart(j), qend(j)).  A workgroup that
+// holds a lead key sweeps every query tile (its token keys are compared per lane); any other sweeps the tiles from qstart of
+// its first key to the one below qend of its last.  A sub-block is open from the wave's largest qstart to its smallest qend.
+template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false, bool FM = false, bool WIN = false>
 __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void attn_bwd_dkv_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, Q_TILE = 64 * HDP * 2;
+  static_assert(!WIN || FM, "the window: on frame-major rows");
   static_assert(!FM || !(ONES || KVLEN || CAUSAL), "frame-major: the plain layout, its own mask");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // LDS: [buf0: Q | dO][buf1: Q | dO][stats: 2 bufs x (lse2[64], delta[64])]
@@ -1237,13 +1355,21 @@ __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void att
   };
   // this workgroup's query tiles [j0, j1) (all of them unless the query range is split)
   const int nqt_all = (p.Lq + 63) / 64, jper = (nqt_all + p.q_split - 1) / (p.q_split > 0 ? p.q_split : 1);
-  const int j0 = fm_first_qtile<FM>(p, key0, sp * jper), j1 = min(nqt_all, j0 + jper);
+  const int j0 = fm_first_qtile<FM>(p, key0, sp * jper);
+  int j1 = min(nqt_all, j0 + jper);
+  if constexpr (WIN) j1 = fm_win_qtiles(p, key0, nqt_all);  // the sweep ends below qend of the last key (a lead key: all tiles)
   issue_tile(j0, 0);
   // FM: the lane's qstart, and the wave's largest (its last key's, the sequence's last row at most)
   [[maybe_unused]] int qlim = 0, wqlim = 0;
   if constexpr (FM) {
     qlim = fm_qstart(p, krow);
     wqlim = __builtin_amdgcn_readfirstlane(fm_qstart(p, min(key0 + wave * 32 + 31, p.Lk - 1)));
+  }
+  // WIN: the lane's qend next to its qstart, and the wave's smallest -- its first TOKEN key's (a lead key's is L)
+  [[maybe_unused]] int qhi = 0, wqhi = 0;
+  if constexpr (WIN) {
+    qhi = fm_qend(p, krow);
+    wqhi = __builtin_amdgcn_readfirstlane(fm_qend(p, fm_win_first_token_key(p, key0 + wave * 32)));
   }
 
   // this lane's key row as B-operand fragments (rows past Lk / columns past hd read as zero)
@@ -1325,7 +1451,10 @@ __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void att
         const FcMap fm(p);
         fc_zero_q(fm, j * 64 + qb * 32 + 4 * h, fm.fk(krow), pm, s);
       }
-      if constexpr (FM) {
+      if constexpr (WIN) {  // open: at or past the wave's largest qstart and wholly below its smallest qend
+        if (j * 64 + qb * 32 < wqlim || j * 64 + qb * 32 + 32 > wqhi)
+          fm_zero_q_win(j * 64 + qb * 32 + 4 * h, qlim, qhi, pm, s);
+      } else if constexpr (FM) {
         if (j * 64 + qb * 32 < wqlim) fm_zero_q(j * 64 + qb * 32 + 4 * h, qlim, pm, s);
       }
       PRIO_HI();
@@ -1417,9 +1546,11 @@ __device__ __forceinline__ bf16x8 pack2(const f32x4& a, const f32x4& b) {
 // FM (vds_attn_bwd_causal_fm, ones layout): as attn_bwd_dkv_kernel's -- the query sweep starts at the tile that holds qstart
 // of the workgroup's first key, a lane compares the query row of each register against the qstart of its two keys unless
 // the sub-block starts at or past the qstart of the wave's last key, and the dO tile is gathered from the token rows.
-template <int HDP, bool QPAD = true, bool KVLEN = false, bool CAUSAL = false, bool FM = false>
+// WIN (vds_attn_bwd_causal_fm_window; with FM): as attn_bwd_dkv_kernel's.
+template <int HDP, bool QPAD = true, bool KVLEN = false, bool CAUSAL = false, bool FM = false, bool WIN = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv16_kernel(AttnP p) {
   static_assert(HDP == 96, "head_dim 72 layout (ones columns at 72, 73)");
+  static_assert(!WIN || FM, "the window: on frame-major rows");
   static_assert(!FM || (QPAD && !KVLEN && !CAUSAL), "frame-major: the ones layout, its own mask");
   constexpr int KS = HDP / 32, NDB = 5, Q_TILE = 64 * HDP * 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1482,6 +1613,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv16_kernel(AttnP p) {
     qlim[1] = fm_qstart(p, key0 + 16 + (lane & 15));
     wqlim = __builtin_amdgcn_readfirstlane(fm_qstart(p, min(key0 + 31, p.Lk - 1)));
   }
+  // WIN: qend of the lane's two keys, and the wave's smallest -- its first TOKEN key's (a lead key's is L)
+  [[maybe_unused]] int qhi[2] = {0, 0}, wqhi = 0;
+  if constexpr (WIN) {
+    qhi[0] = fm_qend(p, key0 + (lane & 15));
+    qhi[1] = fm_qend(p, key0 + 16 + (lane & 15));
+    wqhi = __builtin_amdgcn_readfirstlane(fm_qend(p, fm_win_first_token_key(p, key0)));
+  }
 
   // the two 16-key blocks of this wave as B operands: lane (c = l & 15, g) holds columns 32 ks + 8 g .. + 7 of key c
   bf16x8 kf[2][KS], vf[2][KS];
@@ -1513,7 +1651,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv16_kernel(AttnP p) {
   for (int i = 0; i < NDB; ++i)
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) { dk[i][cb] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[i][cb] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-  const int nqt = (p.Lq + 63) / 64;
+  int nqt = (p.Lq + 63) / 64;  // one past the last query tile of the sweep
+  if constexpr (WIN) nqt = fm_win_qtiles(p, kt_idx * 128, nqt);
   VDS_WAIT_VM(0);
   __syncthreads();  // tile 0 landed
 
@@ -1577,7 +1716,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv16_kernel(AttnP p) {
               if (xq < fck[cb]) { s[rb][cb][r] = 0.f; dp[rb][cb][r] = 0.f; }
           }
       }
-      if constexpr (FM) {
+      if constexpr (WIN) {  // open: at or past the wave's largest qstart and wholly below its smallest qend
+        if (j * 64 + qb * 32 < wqlim || j * 64 + qb * 32 + 32 > wqhi) {
+#pragma unroll
+          for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int qr = j * 64 + qb * 32 + rb * 16 + 4 * g + r;
+#pragma unroll
+              for (int cb = 0; cb < NKB; ++cb)
+                if (qr < qlim[cb] || qr >= qhi[cb]) { s[rb][cb][r] = 0.f; dp[rb][cb][r] = 0.f; }
+            }
+        }
+      } else if constexpr (FM) {
         if (j * 64 + qb * 32 < wqlim) {
 #pragma unroll
           for (int rb = 0; rb < 2; ++rb)
@@ -1665,9 +1816,12 @@ __device__ __forceinline__ float max_over_lane_groups(float x) {  // max over th
 // workgroup's 256 queries, a lane compares the key row of each register against the kend of its four queries unless the
 // sub-block lies below the kend of the wave's first query, the o row goes to tok(row), and a query's running maximum is
 // raised only when its OWN scores cross the threshold (rows of several frames share a wave).
-template <int HDP, bool KVLEN = false, bool CAUSAL = false, bool PAST = false, bool FM = false>
+// WIN (vds_attn_fwd_causal_fm_window; with FM): as attn_fwd_kernel's -- the two tile ranges, the per-lane compare
+// against [kbeg, kend) of the lane's four queries, the open test -- and a first maximum per query (see `unset`).
+template <int HDP, bool KVLEN = false, bool CAUSAL = false, bool PAST = false, bool FM = false, bool WIN = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
   static_assert(HDP == 96, "head_dim 72 layout (ones columns at 72, 73 / 72, 76)");
+  static_assert(!WIN || FM, "the window: on frame-major rows");
   static_assert(!FM || !(KVLEN || CAUSAL || PAST), "frame-major: its own mask");
   constexpr int KS = HDP / 32, NDB = 5, TILE = 64 * HDP * 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1699,8 +1853,16 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
   dk.init(p.k_sl, hd_kv, wave, lane);
   dv.init(p.v_sl, hd_kv, wave, lane);
   const unsigned k_step = (unsigned)(64 * p.k_sl * 2), v_step = (unsigned)(64 * p.v_sl * 2);
+  const int nkt = (Lk + 63) / 64;
+  [[maybe_unused]] const FmWinTiles<WIN> wt(p, qt * 256, 256, nkt);  // WIN: as in attn_fwd_kernel
+  const int nit = WIN ? wt.nit : nkt;
+  if constexpr (WIN) {
+    dk.issue(rk, smem, (unsigned)wt.tile(0) * k_step, wave);
+    dv.issue(rv, smem + TILE, (unsigned)wt.tile(0) * v_step, wave);
+  } else {
   dk.issue(rk, smem, 0, wave);
   dv.issue(rv, smem + TILE, 0, wave);
+  }
 
   const float c = p.scale * LOG2E;
   bf16x8 qf[4][KS];
@@ -1724,7 +1886,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) o[db][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m[4] = {0.f, 0.f, 0.f, 0.f};
-  const int nkt = (Lk + 63) / 64;
   const FcMap fm(p);
   int fcq[4] = {0, 0, 0, 0};
   if constexpr (CAUSAL) {
@@ -1738,6 +1899,16 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
     for (int cb = 0; cb < 4; ++cb) klim[cb] = fm_kend(p, qrow0 + 16 * cb);
     wklim = wq0 >= p.fc_lead ? __builtin_amdgcn_readfirstlane(fm_kend(p, wq0)) : 0;
   }
+  // WIN: kbeg of the lane's queries and the wave's open test.  unset[cb]: the query has met no attended key yet -- with
+  // lead = 0 the first sub-blocks a wave visits may lie before a later query's window, so each query takes its first
+  // maximum from the first sub-block that holds one of ITS keys (m stays 0 and every P is 0 until then)
+  [[maybe_unused]] int kbeg[4] = {0, 0, 0, 0};
+  [[maybe_unused]] bool unset[4] = {true, true, true, true};
+  [[maybe_unused]] const FmWinOpen<WIN> wo(p, wq0, 64);
+  if constexpr (WIN) {
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) kbeg[cb] = fm_kbeg(p, qrow0 + 16 * cb);
+  }
   VDS_WAIT_VM(0);
   __syncthreads();
 
@@ -1745,13 +1916,15 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
   // real at L = 8208), whose other waves only stage and synchronise -- that workgroup then runs at the pace of the one
   // wave that has a block instead of occupying a CU slot for the time of a full one.  Invisible at B = 12 (12.4 rounds
   // of workgroups either way), but at B = 2 the 33rd workgroup of every head opens a third round.
-  auto kv_tile = [&](int j, auto PAR, auto NCBT) {
+  auto kv_tile = [&](int it, auto PAR, auto NCBT) {
     constexpr int par = decltype(PAR)::value;
     constexpr int NCB = decltype(NCBT)::value;
-    if (j + 1 < nkt) {
+    int j = it, jn = it + 1;  // this visit's key tile and the next one's (WIN: across the gap)
+    if constexpr (WIN) { j = wt.tile(it); jn = wt.tile(it + 1); }
+    if (it + 1 < nit) {
       char* nk = smem + (par ^ 1) * 2 * TILE;
-      dk.issue(rk, nk, (unsigned)(j + 1) * k_step, wave);
-      dv.issue(rv, nk + TILE, (unsigned)(j + 1) * v_step, wave);
+      dk.issue(rk, nk, (unsigned)jn * k_step, wave);
+      dv.issue(rv, nk + TILE, (unsigned)jn * v_step, wave);
     }
     const char* kt = smem + par * 2 * TILE;
     const char* vt = kt + TILE;
@@ -1800,7 +1973,19 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
               if (xk > fcq[cb]) s[rb][cb][r] = -INFINITY;
           }
       }
-      if constexpr (FM) {
+      if constexpr (WIN) {
+        if (!wo.open(j * 64 + kb * 32)) {
+#pragma unroll
+          for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int key = j * 64 + kb * 32 + rb * 16 + 4 * g + r;
+#pragma unroll
+              for (int cb = 0; cb < NCB; ++cb)
+                if (fm_win_masked(key, p.fc_lead, kbeg[cb], klim[cb])) s[rb][cb][r] = -INFINITY;
+            }
+        }
+      } else if constexpr (FM) {
         if (j * 64 + kb * 32 + 32 > wklim) {
 #pragma unroll
           for (int rb = 0; rb < 2; ++rb)
@@ -1813,7 +1998,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
             }
         }
       }
-      const bool first = (j == 0) && (kb == 0);
+      const bool first = !WIN && (j == 0) && (kb == 0);
       float mx[4];
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) {
@@ -1827,17 +2012,27 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
 #pragma unroll
         for (int cb = 1; cb < NCB; ++cb) mxa = fmaxf(mxa, mx[cb]);
       }
-      if (first || __builtin_amdgcn_ballot_w64(mxa > LAZY_THR) != 0) {  // wave-uniform, rare after the first tile
+      bool fresh = false;  // WIN: a query of this lane meets its first attended key here
+      if constexpr (WIN) {
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb) fresh |= unset[cb] && mx[cb] > -INFINITY;
+      }
+      if (first || __builtin_amdgcn_ballot_w64(mxa > LAZY_THR || fresh) != 0) {  // wave-uniform, rare after the first tile
         asm volatile("; rescale" ::: "memory");  // keeps this a real branch (no if-conversion of the O multiplies)
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
           const float mxf = max_over_lane_groups(mx[cb]);  // all four lanes of a query agree
-          float m_new = bf2f(f2bf(m[cb] + (first ? mxf : fmaxf(mxf, 0.f))));
+          bool first_q = first;  // this query takes its first maximum here
+          if constexpr (WIN) {
+            first_q = unset[cb] && mxf > -INFINITY;
+            unset[cb] = unset[cb] && !first_q;
+          }
+          float m_new = bf2f(f2bf(m[cb] + (first_q ? mxf : fmaxf(mxf, 0.f))));
           if constexpr (FM) {
-            if (!first && !(mxf > LAZY_THR)) m_new = m[cb];  // only the query's own scores move its maximum
+            if (!first_q && !(mxf > LAZY_THR)) m_new = m[cb];  // only the query's own scores move its maximum
           }
           const float delta = m_new - m[cb];
-          const float alpha = first ? 1.0f : __builtin_amdgcn_exp2f(-delta);
+          const float alpha = first_q ? 1.0f : __builtin_amdgcn_exp2f(-delta);
           m[cb] = m_new;
 #pragma unroll
           for (int db = 0; db < NDB; ++db) o[db][cb] *= alpha;  // includes the denominator rows
@@ -1870,9 +2065,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
     __syncthreads();
   };
   auto run = [&](auto NCBT) {
-    for (int j = 0; j < nkt; j += 2) {
-      kv_tile(j, std::integral_constant<int, 0>{}, NCBT);
-      if (j + 1 < nkt) kv_tile(j + 1, std::integral_constant<int, 1>{}, NCBT);
+    for (int it = 0; it < nit; it += 2) {
+      kv_tile(it, std::integral_constant<int, 0>{}, NCBT);
+      if (it + 1 < nit) kv_tile(it + 1, std::integral_constant<int, 1>{}, NCBT);
     }
   };
   const int ncb = min(4, max(0, (p.Lq - (qt * 256 + wave * 64) + 15) >> 4));  // wave-uniform
@@ -1914,9 +2109,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(AttnP p) {
 // workgroup's queries, dS is zeroed from the kend of the lane's queries unless the sub-block lies below the kend of the wave's
 // first query, and the dO row -- with FOLD the O row too -- is that of token row tok(row); q, dq, the statistics written by
 // FOLD and the annotated q pad are indexed by the frame-major row.
-template <int HDP, bool FOLD = false, bool KVLEN = false, bool CAUSAL = false, bool FM = false>
+// WIN (vds_attn_bwd_causal_fm_window; with FM): as attn_bwd_dq_kernel's.
+template <int HDP, bool FOLD = false, bool KVLEN = false, bool CAUSAL = false, bool FM = false, bool WIN = false>
 __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
   static_assert(HDP == 96, "head_dim 72 layout");
+  static_assert(!WIN || FM, "the window: on frame-major rows");
   static_assert(!FM || !(KVLEN || CAUSAL), "frame-major: its own mask");
   constexpr int KS = HDP / 32, NDB = 5, TILE = 64 * HDP * 2, NQ = 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1950,8 +2147,16 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
   dk.init(p.k_sl, hd_kv, wave, lane);
   dv.init(p.v_sl, hd_kv, wave, lane);
   const unsigned k_step = (unsigned)(64 * p.k_sl * 2), v_step = (unsigned)(64 * p.v_sl * 2);
+  const int nkt = (Lk + 63) / 64;
+  [[maybe_unused]] const FmWinTiles<WIN> wt(p, qt * (64 * NQ), 64 * NQ, nkt);  // WIN: as in attn_fwd_kernel
+  const int nit = WIN ? wt.nit : nkt;
+  if constexpr (WIN) {
+    dk.issue(rk, smem, (unsigned)wt.tile(0) * k_step, wave);
+    dv.issue(rv, smem + TILE, (unsigned)wt.tile(0) * v_step, wave);
+  } else {
   dk.issue(rk, smem, 0, wave);
   dv.issue(rv, smem + TILE, 0, wave);
+  }
 
   const long nrows = (long)p.B * p.H * p.Lq;
   const float c = p.scale * LOG2E;
@@ -2012,7 +2217,6 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
   for (int db = 0; db < NDB; ++db)
 #pragma unroll
     for (int cb = 0; cb < NQ; ++cb) dq[db][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int nkt = (Lk + 63) / 64;
   const FcMap fm(p);
   int fcq[NQ] = {0, 0};
   if constexpr (CAUSAL) {
@@ -2026,17 +2230,25 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
     for (int cb = 0; cb < NQ; ++cb) klim[cb] = fm_kend(p, qrow0 + 16 * cb);
     wklim = wq0 >= p.fc_lead ? __builtin_amdgcn_readfirstlane(fm_kend(p, wq0)) : 0;
   }
+  [[maybe_unused]] int kbeg[NQ] = {0, 0};  // WIN: as in attn_fwd16_kernel
+  [[maybe_unused]] const FmWinOpen<WIN> wo(p, qt * (64 * NQ) + wave * (16 * NQ), 16 * NQ);
+  if constexpr (WIN) {
+#pragma unroll
+    for (int cb = 0; cb < NQ; ++cb) kbeg[cb] = fm_kbeg(p, qrow0 + 16 * cb);
+  }
   VDS_WAIT_VM(0);
   __syncthreads();  // tile 0 landed
 
   // NCB: 16-query blocks of this wave that hold queries (see attn_fwd16_kernel)
-  auto kv_tile = [&](int j, auto PAR, auto NCBT) {
+  auto kv_tile = [&](int it, auto PAR, auto NCBT) {
     constexpr int par = decltype(PAR)::value;
     constexpr int NCB = decltype(NCBT)::value;
-    if (j + 1 < nkt) {
+    int j = it, jn = it + 1;  // this visit's key tile and the next one's (WIN: across the gap)
+    if constexpr (WIN) { j = wt.tile(it); jn = wt.tile(it + 1); }
+    if (it + 1 < nit) {
       char* nk = smem + (par ^ 1) * 2 * TILE;
-      dk.issue(rk, nk, (unsigned)(j + 1) * k_step, wave);
-      dv.issue(rv, nk + TILE, (unsigned)(j + 1) * v_step, wave);
+      dk.issue(rk, nk, (unsigned)jn * k_step, wave);
+      dv.issue(rv, nk + TILE, (unsigned)jn * v_step, wave);
     }
     const char* kt = smem + par * 2 * TILE;
     const char* vt = kt + TILE;
@@ -2084,7 +2296,19 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
               if (xk > fcq[cb]) s[rb][cb][r] = 0.f;
           }
       }
-      if constexpr (FM) {
+      if constexpr (WIN) {
+        if (!wo.open(j * 64 + kb * 32)) {
+#pragma unroll
+          for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int key = j * 64 + kb * 32 + rb * 16 + 4 * g + r;
+#pragma unroll
+              for (int cb = 0; cb < NCB; ++cb)
+                if (fm_win_masked(key, p.fc_lead, kbeg[cb], klim[cb])) s[rb][cb][r] = 0.f;
+            }
+        }
+      } else if constexpr (FM) {
         if (j * 64 + kb * 32 + 32 > wklim) {
 #pragma unroll
           for (int rb = 0; rb < 2; ++rb)
@@ -2111,9 +2335,9 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq16_kernel(AttnP p) {
     __syncthreads();
   };
   auto run = [&](auto NCBT) {
-    for (int j = 0; j < nkt; j += 2) {
-      kv_tile(j, std::integral_constant<int, 0>{}, NCBT);
-      if (j + 1 < nkt) kv_tile(j + 1, std::integral_constant<int, 1>{}, NCBT);
+    for (int it = 0; it < nit; it += 2) {
+      kv_tile(it, std::integral_constant<int, 0>{}, NCBT);
+      if (it + 1 < nit) kv_tile(it + 1, std::integral_constant<int, 1>{}, NCBT);
     }
   };
   const int ncb = min(NQ, max(0, (p.Lq - (qt * (64 * NQ) + wave * (16 * NQ)) + 15) >> 4));  // wave-uniform
@@ -2610,33 +2834,54 @@ int fm_kend_host(int r, int lead, int G, int L) {
   return e < L ? e : L;
 }
 int fm_qstart_host(int j, int lead, int G) { return j < lead ? 0 : lead + ((j - lead) / G) * G; }
-// (query, key) pairs the forward / dQ kernels visit: `tile` queries per workgroup, keys [0, kend of its last query)
-double fm_pairs_q(int L, int lead, int G, int tile) {
+// window of W chunks (W = 0: none)
+int fm_kbeg_host(int r, int lead, int G, int W) {
+  if (r < lead) return lead;
+  const int n = (r - lead) / G - W + 1;
+  return lead + (n > 0 ? n : 0) * G;
+}
+int fm_qend_host(int j, int lead, int G, int L, int W) {
+  if (j < lead) return L;
+  const long e = lead + ((long)(j - lead) / G + W) * G;
+  return e < L ? (int)e : L;
+}
+// (query, key) pairs the forward / dQ kernels visit: `tile` queries per workgroup, keys [0, kend of its last query); with
+// a window, less the keys between the lead tiles and the tile that holds kbeg of its first token query
+double fm_pairs_q(int L, int lead, int G, int tile, int W = 0) {
   double n = 0;
   for (int q0 = 0; q0 < L; q0 += tile) {
     const int q1 = q0 + tile < L ? q0 + tile : L;
-    n += (double)(q1 - q0) * fm_kend_host(q1 - 1, lead, G, L);
+    int keys = fm_kend_host(q1 - 1, lead, G, L);
+    if (W > 0 && q1 > lead) {
+      const int nl = ((lead + 63) >> 6) * 64, kb = fm_kbeg_host(q0 > lead ? q0 : lead, lead, G, W) & ~63;
+      if (kb > nl) keys -= kb - nl;
+    }
+    n += (double)(q1 - q0) * keys;
   }
   return n;
 }
-// ... and the dK/dV kernel: `tile` keys per workgroup, queries from the 64-row tile that holds qstart of its first key
-double fm_pairs_k(int L, int lead, int G, int tile) {
+// ... and the dK/dV kernel: `tile` keys per workgroup, queries from the 64-row tile that holds qstart of its first key; with
+// a window, up to qend of its last key unless it holds a lead key
+double fm_pairs_k(int L, int lead, int G, int tile, int W = 0) {
   double n = 0;
   for (int k0 = 0; k0 < L; k0 += tile) {
     const int k1 = k0 + tile < L ? k0 + tile : L;
-    n += (double)(k1 - k0) * (L - (fm_qstart_host(k0, lead, G) & ~63));
+    const int qe = (W > 0 && k0 >= lead) ? fm_qend_host(k1 - 1, lead, G, L, W) : L;
+    n += (double)(k1 - k0) * (qe - (fm_qstart_host(k0, lead, G) & ~63));
   }
   return n;
 }
 
 // the profiler credits the pairs of the key range actually visited, not the unmasked L x L
-template <int HDP, int HDQ>
+// WIN: the window instances (p.fc_past = W chunks), chosen by the same rules
+template <int HDP, int HDQ, bool WIN = false>
 int run_fwd_fm(AttnP p, hipStream_t s) {
+  const int W = WIN ? p.fc_past : 0;
   constexpr int LDS = 4 * 64 * HDP * 2;
   static bool once = false;
   if (!once) {
-    set_lds(attn_fwd_kernel<HDP, HDQ, 2, true, false, false, false, true>, LDS);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd16_kernel<HDP, false, false, false, true>, LDS);
+    set_lds(attn_fwd_kernel<HDP, HDQ, 2, true, false, false, false, true, WIN>, LDS);
+    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd16_kernel<HDP, false, false, false, true, WIN>, LDS);
     once = true;
   }
   if constexpr (HDP == 96 && HDQ == 80) {
@@ -2647,33 +2892,34 @@ int run_fwd_fm(AttnP p, hipStream_t s) {
       p.n_rt = cdiv(p.Lq, 256);
       p.tail_last = tail_last_for(p.Lq, 256);
       const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
-      const double fl = 4.0 * p.B * p.H * p.hd * fm_pairs_q(p.Lq, p.fc_lead, p.fm_G, 256);
+      const double fl = 4.0 * p.B * p.H * p.hd * fm_pairs_q(p.Lq, p.fc_lead, p.fm_G, 256, W);
       vdsprof::Scope ps(VDS_PROF_ATTN_FWD, s, fl, 2.0 * p.B * p.H * p.hd * (2.0 * p.Lq + 2.0 * p.Lk));
-      hipLaunchKernelGGL((attn_fwd16_kernel<HDP, false, false, false, true>), dim3(grid), dim3(256), LDS, s, p);
+      hipLaunchKernelGGL((attn_fwd16_kernel<HDP, false, false, false, true, WIN>), dim3(grid), dim3(256), LDS, s, p);
       return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
     }
   }
   p.n_rt = cdiv(p.Lq, 128);
   p.tail_last = tail_last_for(p.Lq, 128);
   const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
-  const double fl = 4.0 * p.B * p.H * p.hd * fm_pairs_q(p.Lq, p.fc_lead, p.fm_G, 128);
+  const double fl = 4.0 * p.B * p.H * p.hd * fm_pairs_q(p.Lq, p.fc_lead, p.fm_G, 128, W);
   vdsprof::Scope ps(VDS_PROF_ATTN_FWD_PLAIN, s, fl, 2.0 * p.B * p.H * p.hd * (2.0 * p.Lq + 2.0 * p.Lk));
-  hipLaunchKernelGGL((attn_fwd_kernel<HDP, HDQ, 2, true, false, false, false, true>), dim3(grid), dim3(256), LDS, s, p);
+  hipLaunchKernelGGL((attn_fwd_kernel<HDP, HDQ, 2, true, false, false, false, true, WIN>), dim3(grid), dim3(256), LDS, s, p);
   return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
 }
 
-template <int HDP, int HDQ>
+template <int HDP, int HDQ, bool WIN = false>
 int run_bwd_fm(AttnP p, hipStream_t s) {
+  const int W = WIN ? p.fc_past : 0;
   constexpr int LDS_DQ = 4 * 64 * HDP * 2;
   constexpr int LDS_DKV = 4 * 64 * HDP * 2 + 2 * 128 * 4;
   static bool once = false;
   if (!once) {
-    set_lds(attn_bwd_dq_kernel<HDP, HDQ, false, false, false, true>, LDS_DQ);
-    set_lds(attn_bwd_dkv_kernel<HDP, HDQ, false, false, false, true>, LDS_DKV);
+    set_lds(attn_bwd_dq_kernel<HDP, HDQ, false, false, false, true, WIN>, LDS_DQ);
+    set_lds(attn_bwd_dkv_kernel<HDP, HDQ, false, false, false, true, WIN>, LDS_DKV);
     if constexpr (HDP == 96 && HDQ == 80) {
-      set_lds(attn_bwd_dkv16_kernel<HDP, true, false, false, true>, LDS_DKV);
-      set_lds(attn_bwd_dq16_kernel<HDP, false, false, false, true>, LDS_DQ);
-      set_lds(attn_bwd_dq16_kernel<HDP, true, false, false, true>, LDS_DQ);
+      set_lds(attn_bwd_dkv16_kernel<HDP, true, false, false, true, WIN>, LDS_DKV);
+      set_lds(attn_bwd_dq16_kernel<HDP, false, false, false, true, WIN>, LDS_DQ);
+      set_lds(attn_bwd_dq16_kernel<HDP, true, false, false, true, WIN>, LDS_DQ);
     }
     once = true;
   }
@@ -2691,18 +2937,18 @@ int run_bwd_fm(AttnP p, hipStream_t s) {
     p.tail_last = tail_last_for(p.Lq, 128);
     const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
     vdsprof::Scope ps(ones ? VDS_PROF_ATTN_BWD_DQ : VDS_PROF_ATTN_BWD_DQ_PLAIN, s,
-                      2.0 * per * fm_pairs_q(p.Lq, p.fc_lead, p.fm_G, 128), (fold ? 4.0 : 3.0) * qb + 2.0 * kb);
+                      2.0 * per * fm_pairs_q(p.Lq, p.fc_lead, p.fm_G, 128, W), (fold ? 4.0 : 3.0) * qb + 2.0 * kb);
     if constexpr (HDP == 96 && HDQ == 80) {
       if (fold) {
-        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, true, false, false, true>), dim3(grid), dim3(256), LDS_DQ, s, p);
+        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, true, false, false, true, WIN>), dim3(grid), dim3(256), LDS_DQ, s, p);
         return;
       }
       if (dq16) {
-        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, false, false, false, true>), dim3(grid), dim3(256), LDS_DQ, s, p);
+        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, false, false, false, true, WIN>), dim3(grid), dim3(256), LDS_DQ, s, p);
         return;
       }
     }
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, HDQ, false, false, false, true>), dim3(grid), dim3(256), LDS_DQ, s, p);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, HDQ, false, false, false, true, WIN>), dim3(grid), dim3(256), LDS_DQ, s, p);
   };
   if (fold) launch_dq();
   else {
@@ -2719,15 +2965,15 @@ int run_bwd_fm(AttnP p, hipStream_t s) {
   {
     const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
     vdsprof::Scope ps(ones ? VDS_PROF_ATTN_BWD_DKV : VDS_PROF_ATTN_BWD_DKV_PLAIN, s,
-                      2.0 * per * fm_pairs_k(p.Lq, p.fc_lead, p.fm_G, 128), 2.0 * qb + 4.0 * kb);
+                      2.0 * per * fm_pairs_k(p.Lq, p.fc_lead, p.fm_G, 128, W), 2.0 * qb + 4.0 * kb);
     bool done = false;
     if constexpr (HDP == 96 && HDQ == 80) {
       if (dkv16) {
-        hipLaunchKernelGGL((attn_bwd_dkv16_kernel<HDP, true, false, false, true>), dim3(grid), dim3(256), LDS_DKV, s, p);
+        hipLaunchKernelGGL((attn_bwd_dkv16_kernel<HDP, true, false, false, true, WIN>), dim3(grid), dim3(256), LDS_DKV, s, p);
         done = true;
       }
     }
-    if (!done) hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, false, false, false, true>), dim3(grid), dim3(256), LDS_DKV, s, p);
+    if (!done) hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, false, false, false, true, WIN>), dim3(grid), dim3(256), LDS_DKV, s, p);
   }
   if (!fold) launch_dq();
   return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
@@ -2830,6 +3076,58 @@ extern "C" int vds_attn_bwd_causal_fm_chunk(const vds_attn_args* a, const vds_mo
     case 80: return run_bwd_fm<96, 80>(p, s);
     case 96: return run_bwd_fm<96, 96>(p, s);
     case 128: return run_bwd_fm<128, 128>(p, s);
+    default: return VDS_ERR_UNSUPPORTED;
+  }
+}
+
+// ---- sliding-window chunk-causal frame-major self-attention (include/vds.h) -------------------------------------------
+// The WIN instances of the FM kernels: a token query of chunk n attends the lead keys and the token keys of chunks
+// max(0, n - window_chunks + 1) .. n.  A window that covers every chunk IS the _fm_chunk entry point.
+namespace {
+// chunks of the sequence: ceil(period / chunk)
+int fm_chunks(const vds_mod_groups* f, int chunk) { return (f->period + chunk - 1) / chunk; }
+}  // namespace
+
+extern "C" int vds_attn_fwd_causal_fm_window(const vds_attn_args* a, const vds_mod_groups* frames, int32_t chunk,
+                                             int32_t window_chunks, vds_stream_t stream) {
+  if (!frames || chunk < 1 || window_chunks < 1) return VDS_ERR_ARG;
+  if (frames->period < 1 || window_chunks >= fm_chunks(frames, chunk)) return vds_attn_fwd_causal_fm_chunk(a, frames, chunk, stream);
+  if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse || a->Lq <= 0 || a->Lk <= 0) return VDS_ERR_ARG;
+  if (!strides_ok(a, false)) return VDS_ERR_ARG;
+  if (const int e = fm_check(a, frames, false)) return e;
+  AttnP p = to_p(a);
+  fm_set(p, frames, chunk);
+  p.fc_past = window_chunks;  // (< the chunk count <= period: W * G stays below L)
+  hipStream_t s = (hipStream_t)stream;
+  switch (kernel_instance(a->head_dim)) {
+    case 32: return run_fwd_fm<32, 32, true>(p, s);
+    case 64: return run_fwd_fm<64, 64, true>(p, s);
+    case 80: return run_fwd_fm<96, 80, true>(p, s);
+    case 96: return run_fwd_fm<96, 96, true>(p, s);
+    case 128: return run_fwd_fm<128, 128, true>(p, s);
+    default: return VDS_ERR_UNSUPPORTED;
+  }
+}
+
+extern "C" int vds_attn_bwd_causal_fm_window(const vds_attn_args* a, const vds_mod_groups* frames, int32_t chunk,
+                                             int32_t window_chunks, vds_stream_t stream) {
+  if (!frames || chunk < 1 || window_chunks < 1) return VDS_ERR_ARG;
+  if (frames->period < 1 || window_chunks >= fm_chunks(frames, chunk)) return vds_attn_bwd_causal_fm_chunk(a, frames, chunk, stream);
+  if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse || !a->d_o || !a->dq || !a->dk || !a->dv || !a->delta || a->Lq <= 0 ||
+      a->Lk <= 0)
+    return VDS_ERR_ARG;
+  if (!strides_ok(a, true)) return VDS_ERR_ARG;
+  if (const int e = fm_check(a, frames, true)) return e;
+  AttnP p = to_p(a);
+  fm_set(p, frames, chunk);
+  p.fc_past = window_chunks;
+  hipStream_t s = (hipStream_t)stream;
+  switch (kernel_instance(a->head_dim)) {
+    case 32: return run_bwd_fm<32, 32, true>(p, s);
+    case 64: return run_bwd_fm<64, 64, true>(p, s);
+    case 80: return run_bwd_fm<96, 80, true>(p, s);
+    case 96: return run_bwd_fm<96, 96, true>(p, s);
+    case 128: return run_bwd_fm<128, 128, true>(p, s);
     default: return VDS_ERR_UNSUPPORTED;
   }
 }

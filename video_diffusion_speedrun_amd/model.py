@@ -351,6 +351,24 @@ def check_frame_chunk(who: str, frame_chunk, frame_causal: bool, frame_major: bo
     return frame_chunk
 
 
+def check_frame_window(who: str, frame_window, frame_chunk: int, frame_causal: bool, frame_major: bool):
+    """frame_window of a DiT / DiTBlock: None, or an int >= 1 of token-frames that is a multiple of frame_chunk, on the
+    frame-major frame-causal self-attention"""
+    if frame_window is None:
+        return None
+    if isinstance(frame_window, bool) or not isinstance(frame_window, int) or frame_window < 1:
+        raise ValueError(f"{who}: frame_window = {frame_window!r} must be an int >= 1 (token-frames a token attends, its own "
+                         "chunk included) or None (no window)")
+    if not (frame_causal and frame_major):
+        raise ValueError(f"{who}: frame_window={frame_window} is a mask of the frame-major frame-causal self-attention -- "
+                         "build the model with frame_causal=True, frame_major=True (the interleaved kernels have no "
+                         "window: it would skip no tile there)")
+    if frame_window % frame_chunk != 0:
+        raise ValueError(f"{who}: frame_window={frame_window} must be a multiple of frame_chunk={frame_chunk} -- the window "
+                         f"is a whole number of chunks; pass frame_window={-(-frame_window // frame_chunk) * frame_chunk}")
+    return frame_window
+
+
 _FP8_FRAME_CAUSAL = ("frame_causal is not implemented for the fp8 attention kernels (they have no masked instance): "
                      "call enable_fp8(attention=False) to keep the attention products on the bf16 kernels")
 
@@ -361,7 +379,8 @@ class DiTBlock(nn.Module):
     drives the same two methods for all blocks inside its own whole-model node."""
 
     def __init__(self, hidden_size, cross_attn_input_size, num_heads, mlp_ratio=4.0, qkv_bias=True,
-                 residual_v=False, *, frame_causal=False, frame_major=False, frame_chunk=1, qk_norm=False):
+                 residual_v=False, *, frame_causal=False, frame_major=False, frame_chunk=1, frame_window=None,
+                 qk_norm=False):
         super().__init__()
         self.hidden_size, self.num_heads = hidden_size, num_heads
         self.head_dim = hidden_size // num_heads
@@ -388,6 +407,12 @@ class DiTBlock(nn.Module):
         # chunk=).  1 is the frame-causal mask, call for call.  A cached chunk call covers frames of ONE chunk, inside which
         # every token attends every own key: it runs the cache's past kernel with one token group.  No parameter.
         self.frame_chunk = check_frame_chunk("DiTBlock", frame_chunk, self.frame_causal, self.frame_major)
+        # sliding window (with frame_causal and frame_major): a token of chunk n attends the registers and
+        # the token-frames of chunks n - W + 1 .. n, W = frame_window // frame_chunk -- the WIN instances of the frame-major
+        # kernels (ops.attn_fwd / attn_bwd, window=W), which also skip the key tiles BEFORE the window.  None: no window,
+        # call for call.  A cached chunk call attends whatever the ring cache holds (DiT.new_frame_cache).  No parameter.
+        self.frame_window = check_frame_window("DiTBlock", frame_window, self.frame_chunk, self.frame_causal,
+                                               self.frame_major)
         self.norm1 = RMSNorm(hidden_size, trainable=qkv_bias)
         self.qkv = _Linear(hidden_size, hidden_size * 3, bias=qkv_bias)
         self.attn_proj = _Linear(hidden_size, hidden_size, bias=False)
@@ -427,6 +452,13 @@ class DiTBlock(nn.Module):
         g.materialize(device)
         self._own_group = g
         return g, ""
+
+    def _mask_kw(self):
+        """the chunk / window keywords of the full-sequence self-attention calls (nothing for the frame-causal mask)"""
+        kw = {"chunk": self.frame_chunk} if self.frame_chunk > 1 else {}
+        if self.frame_window is not None:
+            kw["window"] = self.frame_window // self.frame_chunk
+        return kw
 
     def _check_frames(self, frames, L):
         if not self.frame_causal:
@@ -474,7 +506,9 @@ class DiTBlock(nn.Module):
         frames: (lead, period) of a frame_causal block's masked self-attention (bf16 attention kernels only), else None.
         cache: (k_buf, v_buf, past) of a cached chunk call (DiT.forward(frame_cache=)), inference only -- the block's k / v
         rows go straight to their place in its cache buffers [B,H,rows,hdp], the self-attention reads the first L + past
-        rows of them, and the returned v IS v_buf (block 0's: the v0 later blocks read through the same row map)."""
+        rows of them, and the returned v IS v_buf (block 0's: the v0 later blocks read through the same row map).
+        A ring cache (frame_window) passes (k_buf, v_buf, slot, rows): the token rows go behind `slot` cached rows, the
+        self-attention reads the first `rows` rows with one token group (FrameKVCache.ring_call)."""
         D, H, hd = self.hidden_size, self.num_heads, self.head_dim
         frames = self._check_frames(frames, L)
         if cache is not None and (save or keep is not None or replay is not None or fp8 is not None or frames is None):
@@ -546,14 +580,21 @@ class DiTBlock(nn.Module):
                                       if (pemit and fp8_lin and not _NO_ATTN_EMIT) else None)
         else:
             if cache is not None:
-                kb, vb, past = cache
+                ring = len(cache) == 4
+                if ring:  # the rows of slot n % W; the keys are [lead | the other slots' rows and this one's, in buffer order]
+                    kb, vb, slot, rows = cache
+                    past = rows - L
+                else:
+                    kb, vb, past = cache
+                    slot, rows = past, L + past
                 rope_fwd = ops.qkv_rope_norm_fwd_cache if self.qk_norm else ops.qkv_rope_fwd_cache
-                q = rope_fwd(qkv, cos, sin, v0 if mix else None, W("lambda_param") if mix else None, kb, vb, frames[0], past,
+                q = rope_fwd(qkv, cos, sin, v0 if mix else None, W("lambda_param") if mix else None, kb, vb, frames[0], slot,
                              B, L, H, hd, hdp)
-                # (frame_chunk > 1: the call's frames are of one chunk -- one token group, frames = (lead, 1))
-                ops.attn_fwd(q[..., :hd], kb[:, :, :L + past, :hd], vb[:, :, :L + past, :hd],
+                # (frame_chunk > 1 or a ring: the call's frames are of one chunk -- one token group, frames = (lead, 1), under
+                # which every token query attends every token key wherever it sits among the `rows` rows)
+                ops.attn_fwd(q[..., :hd], kb[:, :, :rows, :hd], vb[:, :, :rows, :hd],
                              ops.heads_view(attn, B, L, H, hd), lse1, kv_pad_ones=(hdp - hd) >= 8,
-                             frames=(frames[0], 1) if self.frame_chunk > 1 else frames, past=past)
+                             frames=(frames[0], 1) if (self.frame_chunk > 1 or ring) else frames, past=past)
                 k, v = kb, vb
             else:
                 rope_fwd = ops.qkv_rope_norm_fwd if self.qk_norm else ops.qkv_rope_fwd
@@ -562,8 +603,7 @@ class DiTBlock(nn.Module):
                                    **fm_kw)
             if cache is None and not kept_attn:
                 ops.attn_fwd(q[..., :hd], k[..., :hd], v[..., :hd], ops.heads_view(attn, B, L, H, hd), lse1,
-                             kv_pad_ones=(hdp - hd) >= 8, frames=frames, frame_major=self.frame_major,
-                             **({"chunk": self.frame_chunk} if self.frame_chunk > 1 else {}))
+                             kv_pad_ones=(hdp - hd) >= 8, frames=frames, frame_major=self.frame_major, **self._mask_kw())
             if a8_on and save:  # first steps: record the amax the next step quantises with
                 for j, t in enumerate((q, k, v)):
                     ops.absmax(t.view(B * H * L, hdp)[:, :hd], fp8_hist.cur(F8.ROWS * i + F8.ROW_Q + j))
@@ -854,8 +894,7 @@ class DiTBlock(nn.Module):
             delta = torch.empty(2, B, H, L, dtype=f32, device=dev)
             ops.attn_bwd(bs.q[..., :hd], bs.k[..., :hd], bs.v[..., :hd], ops.heads_view(bs.attn, B, L, H, hd), bs.lse1,
                          ops.heads_view(dattn, B, L, H, hd), dq[..., :hd], dk[..., :hd], dv[..., :hd], delta,
-                         kv_pad_ones=(hdp - hd) >= 8, frames=bs.frames, frame_major=self.frame_major,
-                         **({"chunk": self.frame_chunk} if self.frame_chunk > 1 else {}))
+                         kv_pad_ones=(hdp - hd) >= 8, frames=bs.frames, frame_major=self.frame_major, **self._mask_kw())
             if bs.a8_on:
                 ops.absmax(dattn, fp8_hist.cur(F8.ROWS * i + F8.ROW_DO))
         defer = getattr(sv, "dv_terms", None)  # DiT.backward: [(dv, lambda)] of the mixed blocks, summed at block 0
@@ -916,11 +955,15 @@ class FrameKVCache:
     """K / V rows of the finished token-frames of a cached frame rollout (DiT.new_frame_cache, DiT.forward(frame_cache=)).
     Per block one K and one V buffer [batch, H, N_REG + frames*h*w, hdp] bf16 in the padded head-major layout the qkv / RoPE
     kernel writes (ones columns included): rows [0, N_REG) the register rows of the last call, then the committed frames'
-    token rows, then the rows of the last call's chunk.  past_frames counts the committed token-frames."""
+    token rows, then the rows of the last call's chunk.  past_frames counts the committed token-frames.
+    ring = (W, c) (a frame_window model): the buffers hold N_REG + W*c*h*w rows instead -- W slots of one chunk of c
+    token-frames -- and chunk n of the video lives in slot n % W, so their size does not grow with `frames`, which stays the
+    whole video's length (the RoPE table and past_frames are absolute)."""
 
-    def __init__(self, depth, batch, heads, frames, h_tokens, w_tokens, hdp, device):
+    def __init__(self, depth, batch, heads, frames, h_tokens, w_tokens, hdp, device, ring=None):
         self.batch, self.frames, self.h_tokens, self.w_tokens = batch, frames, h_tokens, w_tokens
-        rows = N_REG + frames * h_tokens * w_tokens
+        self.ring = ring
+        rows = N_REG + (frames if ring is None else ring[0] * ring[1]) * h_tokens * w_tokens
         self.k = [torch.zeros(batch, heads, rows, hdp, dtype=bf16, device=device) for _ in range(depth)]
         self.v = [torch.zeros(batch, heads, rows, hdp, dtype=bf16, device=device) for _ in range(depth)]
         self.past_frames = 0
@@ -943,9 +986,21 @@ class FrameKVCache:
         idx = torch.cat([torch.arange(N_REG, device=dev), rows.reshape(-1)])
         return cos.index_select(0, idx), sin.index_select(0, idx)
 
+    def ring_call(self, k):
+        """(slot, rows) of a call on the k token-frames of chunk n = past_frames // c of a ring cache: the chunk's token rows
+        go behind `slot` cached rows -- slot n % W -- and the self-attention reads the first `rows` rows of the buffers:
+        the registers, the min(n, W - 1) chunks before this one and its own k frames while the ring fills (n < W: the own
+        slot is the last of them), the whole buffer once it is full (k = c then: no stale row is read)"""
+        W, c = self.ring
+        hw = self.h_tokens * self.w_tokens
+        n = self.past_frames // c
+        if n < W:
+            return n * c * hw, N_REG + n * c * hw + k * hw
+        return (n % W) * c * hw, N_REG + W * c * hw
+
     def commit(self):
         """the token rows of the last forward become part of the past: a counter increment, the rows already sit behind
-        the earlier ones"""
+        the earlier ones (a ring: in their slot)"""
         if not self.pending_frames:
             raise RuntimeError("FrameKVCache.commit: no forward(frame_cache=) has run since the last commit() / reset()")
         self.past_frames += self.pending_frames
@@ -1023,7 +1078,8 @@ def grad_arena(groups, device):
 class DiT(nn.Module):
     def __init__(self, in_channels=4, patch_size=2, time_patch_size=2, hidden_size=1152, depth=28, num_heads=16,
                  mlp_ratio=4.0, cross_attn_input_size=128, residual_v=False, train_bias_and_rms=True,
-                 use_rope=True, *, frame_causal=False, frame_major=False, frame_chunk=1, qk_norm=False):
+                 use_rope=True, *, frame_causal=False, frame_major=False, frame_chunk=1, frame_window=None,
+                 qk_norm=False):
         super().__init__()
         self.qk_norm = bool(qk_norm)  # see DiTBlock: parameter-free RMSNorm of q and k in the self-attention
         # see DiTBlock: every self-attention runs with frames = (N_REG, t) -- the registers attend each other, a token of
@@ -1039,6 +1095,9 @@ class DiT(nn.Module):
         # see DiTBlock: causal over chunks of frame_chunk token-frames, bidirectional inside a chunk (1: frame-causal);
         # the model that a rollout of frame_chunk frames at a time (generate_latents(rollout_frames=)) is trained as
         self.frame_chunk = check_frame_chunk("DiT", frame_chunk, self.frame_causal, self.frame_major)
+        # see DiTBlock: a token attends the registers and the last frame_window token-frames (whole chunks) only -- the
+        # training cost of a token and the rollout's cache (new_frame_cache: a ring) no longer grow with the video
+        self.frame_window = check_frame_window("DiT", frame_window, self.frame_chunk, self.frame_causal, self.frame_major)
         self.in_channels = self.out_channels = in_channels
         self.patch_size, self.time_patch_size = patch_size, time_patch_size
         self.hidden_size, self.num_heads, self.depth, self.mlp_ratio = hidden_size, num_heads, depth, mlp_ratio
@@ -1067,7 +1126,8 @@ class DiT(nn.Module):
             DiTBlock(hidden_size=hidden_size, num_heads=num_heads, mlp_ratio=mlp_ratio,
                      cross_attn_input_size=cross_attn_input_size, residual_v=residual_v,
                      qkv_bias=train_bias_and_rms, qk_norm=qk_norm, frame_causal=frame_causal,
-                     frame_major=frame_major, frame_chunk=self.frame_chunk) for _ in range(depth)])
+                     frame_major=frame_major, frame_chunk=self.frame_chunk, frame_window=self.frame_window)
+            for _ in range(depth)])
         self.final_modulation = nn.Sequential(_Act("silu"), _Linear(hidden_size, 2 * hidden_size, bias=True))
         self.final_norm = RMSNorm(hidden_size, trainable=train_bias_and_rms)
         self.final_proj = _Linear(hidden_size, patch_size * patch_size * time_patch_size * self.out_channels)
@@ -1272,7 +1332,11 @@ class DiT(nn.Module):
     def new_frame_cache(self, batch: int, frames: int, h_tokens: int, w_tokens: int, device=None) -> "FrameKVCache":
         """The K / V store of a cached frame rollout (forward(frame_cache=)): per block, K and V buffers
         [batch, heads, N_REG + frames*h_tokens*w_tokens, padded head dim] bf16 -- the register rows, then the token rows of
-        up to `frames` token-frames of h_tokens x w_tokens tokens, in the order the chunks are run."""
+        up to `frames` token-frames of h_tokens x w_tokens tokens, in the order the chunks are run.
+        A frame_window model gets a ring: N_REG + W*c*h_tokens*w_tokens rows per buffer (W = frame_window // frame_chunk
+        slots of one chunk of c = frame_chunk token-frames), whatever `frames` is -- `frames` stays the whole video's length
+        (the RoPE table depends on it) and may exceed anything seen in training.  A video longer than the ring (frames >
+        W*c) must consist of whole chunks: a short last chunk would leave stale rows of chunk n - W in its slot."""
         if not self.frame_causal:
             raise ValueError("DiT.new_frame_cache: a frame KV cache needs a model built with frame_causal=True (on any other "
                              "model the K / V rows of finished frames change with the frames after them)")
@@ -1281,8 +1345,17 @@ class DiT(nn.Module):
                              f"{(batch, frames, h_tokens, w_tokens)}")
         if device is None:
             device = next(self.parameters()).device
+        ring = None
+        if self.frame_window is not None:
+            c = self.frame_chunk
+            ring = (self.frame_window // c, c)
+            if int(frames) > self.frame_window and int(frames) % c != 0:
+                raise ValueError(f"DiT.new_frame_cache: {frames} token-frames wrap the ring of frame_window="
+                                 f"{self.frame_window} frames, and the short last chunk ({int(frames) % c} of {c} frames) "
+                                 f"would leave stale rows in its slot -- make the video a whole number of chunks (frames a "
+                                 f"multiple of {c}, e.g. {-(-int(frames) // c) * c})")
         return FrameKVCache(self.depth, int(batch), self.num_heads, int(frames), int(h_tokens), int(w_tokens),
-                            HDP_OF[self.head_dim], device)
+                            HDP_OF[self.head_dim], device, ring=ring)
 
     def _check_frame_cache(self, cache, b, thw, per_frame, rope_start):
         """the conditions of a cached chunk call, each with its remedy (all before the device is touched)"""
@@ -1314,7 +1387,16 @@ class DiT(nn.Module):
         if cache.past_frames + k > cache.frames:
             raise ValueError(f"DiT: frame_cache holds {cache.frames} token-frames, {cache.past_frames} are committed and this "
                              f"chunk brings {k}: make a larger cache (new_frame_cache(frames=...)) or reset() it")
+        if (cache.ring is None) != (self.frame_window is None) or (
+                cache.ring is not None and cache.ring != (self.frame_window // self.frame_chunk, self.frame_chunk)):
+            raise ValueError("DiT: frame_cache was not made by this model's new_frame_cache -- a frame_window model takes a "
+                             "ring cache of its own window and chunk, any other model an unbounded one")
         c = self.frame_chunk
+        if self.frame_window is not None and c == 1 and k != 1:
+            raise ValueError(f"DiT: a frame_cache call on a frame_window model covers ONE token group -- with frame_chunk=1 "
+                             f"that is one token-frame per call, this call brings {k}: pass the frames one at a time "
+                             "(generate_latents(rollout_frames=1, kv_cache=True)), or run several frames without "
+                             "frame_cache")
         if c > 1 and (cache.past_frames % c != 0 or k > c or (k < c and cache.past_frames + k != cache.frames)):
             raise ValueError(f"DiT: a frame_cache call on a frame_chunk={c} model covers the frames of ONE chunk: "
                              f"{cache.past_frames} frames are committed and this call brings {k} -- commit whole chunks "
@@ -1415,6 +1497,7 @@ class DiT(nn.Module):
             mods = ops.small_linear_fwd_batched(cvec, wt, bt, self.depth, 9 * D, 1)
         v0 = None
         past = cache.past_frames * h * w if cache is not None else 0
+        ring_call = cache.ring_call(t) if (cache is not None and cache.ring is not None) else None
         keep = self.recompute if (save and self.recompute != "none") else None  # blocks keep their inputs, not their work
         for i in range(self.depth):
             if fs is not None:
@@ -1424,7 +1507,8 @@ class DiT(nn.Module):
                                            (self._fp8_hist, i, self.fp8_attn, self.fp8_lin, q_ctx) if self.fp8 else None,
                                            mods[i] if mods is not None else None, keep=keep, kv_lens=kv_lens,
                                            groups=groups, frames=frames,
-                                           **({} if cache is None else {"cache": (cache.k[i], cache.v[i], past)}))
+                                           **({} if cache is None else {"cache": (cache.k[i], cache.v[i], past)}
+                                              if ring_call is None else {"cache": (cache.k[i], cache.v[i]) + ring_call}))
             if v0 is None:
                 v0 = v
             if save:

@@ -276,11 +276,18 @@ def _frames(frames, kv_lens, Lq: int, Lk: int, past: int = 0):
     return C.byref(_lib.ModGroups(lead, period))
 
 
-def _frame_major(frame_major, frames, kv_lens, past=0, chunk=1) -> bool:
-    """frame_major needs frames and excludes past / kv_lens, chunk != 1 needs frame_major: refused here, before anything
-    is launched"""
+def _frame_major(frame_major, frames, kv_lens, past=0, chunk=1, window=None) -> bool:
+    """frame_major needs frames and excludes past / kv_lens, chunk != 1 and a window need frame_major: refused here, before
+    anything is launched"""
     if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
         raise ValueError(f"attention: chunk = {chunk!r} must be an int >= 1 (token-frames per causal chunk)")
+    if window is not None:
+        if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+            raise ValueError(f"attention: window = {window!r} must be an int >= 1 (chunks a token query attends, its own "
+                             "included) or None")
+        if not frame_major or past:
+            raise ValueError(f"attention: window = {window} needs frame_major=True and no past -- the sliding window exists "
+                             "on the frame-major kernels only; a cached call attends whatever rows the cache holds")
     if not frame_major:
         if chunk != 1:
             raise ValueError(f"attention: chunk = {chunk} needs frame_major=True -- the chunk-causal mask exists on the "
@@ -294,7 +301,7 @@ def _frame_major(frame_major, frames, kv_lens, past=0, chunk=1) -> bool:
 
 
 def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=None, past: int = 0,
-             frame_major: bool = False, chunk: int = 1):
+             frame_major: bool = False, chunk: int = 1, window=None):
     """q [B,H,Lq,hd], k/v [B,H,Lk,hd], o [B,H,Lq,hd] strided views (last dim contiguous); lse f32 [B,H,Lq].
     kv_pad_ones: k / v are views into qkv_rope_fwd outputs whose pad carries the ones columns.
     kv_lens: int32 CUDA tensor [B]; sample b attends its first kv_lens[b] keys only (vds_attn_fwd_kvlen).
@@ -305,11 +312,13 @@ def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=No
     frame_major (with frames; not with past / kv_lens): q, k, v and lse rows are frame-major (fm_row), o stays token-major
     and the key tiles no query of a tile attends are skipped (vds_attn_fwd_causal_fm).
     chunk (with frame_major): the mask is causal over chunks of `chunk` token-frames and bidirectional inside a chunk --
-    fm_group_of(key, chunk) <= fm_group_of(query, chunk) (vds_attn_fwd_causal_fm_chunk); 1 is the frame-causal mask."""
+    fm_group_of(key, chunk) <= fm_group_of(query, chunk) (vds_attn_fwd_causal_fm_chunk); 1 is the frame-causal mask.
+    window (with frame_major; in chunks): a token query of chunk n attends the lead keys and the token keys of chunks
+    max(0, n - window + 1) .. n only (vds_attn_fwd_causal_fm_window); None: no window."""
     B, H, Lq, hd = q.shape
     Lk = k.shape[2]
     past = int(past)
-    fmaj = _frame_major(frame_major, frames, kv_lens, past, chunk)
+    fmaj = _frame_major(frame_major, frames, kv_lens, past, chunk, window)
     if past < 0 or (past and frames is None):
         raise ValueError(f"attention: past = {past} must be >= 0 and needs frames=(lead, period)")
     fr = _frames(frames, kv_lens, Lq, Lk, past) if frames is not None else None
@@ -321,7 +330,11 @@ def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=No
     a.o, (a.o_sb, a.o_sh, a.o_sl) = _p(o), _st(o)
     a.lse = _p(lse)
     a.kv_pad_ones = int(kv_pad_ones)  # (True = 1: self-attention layout; 2: ones in k / v only, cross-attention)
-    if fmaj and chunk != 1:
+    if fmaj and window is not None:
+        check(_lib.load().vds_attn_fwd_causal_fm_window(C.byref(a), fr, chunk, window, _stream()),
+              f"vds_attn_fwd_causal_fm_window(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)},chunk={chunk},"
+              f"window={window})")
+    elif fmaj and chunk != 1:
         check(_lib.load().vds_attn_fwd_causal_fm_chunk(C.byref(a), fr, chunk, _stream()),
               f"vds_attn_fwd_causal_fm_chunk(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)},chunk={chunk})")
     elif fmaj:
@@ -359,18 +372,19 @@ def attn_bwd_workspace_floats(B, H, Lq, Lk, hd, kv_pad_ones: bool = False) -> in
 
 
 def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = False, kv_lens=None, frames=None,
-             frame_major: bool = False, chunk: int = 1):
+             frame_major: bool = False, chunk: int = 1, window=None):
     """delta: f32 workspace of 2*B*H*Lq elements (rowsum(dO*O), then lse*log2 e); allocated here when None
     (size from vds_attn_bwd_workspace_bytes).
     kv_lens: as in attn_fwd; rows kv_lens[b].. of dk[b] / dv[b] are written as zeros (vds_attn_bwd_kvlen).
     frames: as in attn_fwd; a dk / dv row sums over the queries that attend it (vds_attn_bwd_causal).
     frame_major: as in attn_fwd -- q, k, v, lse, dq, dk, dv (and the delta workspace) rows are frame-major, o and do
     token-major (vds_attn_bwd_causal_fm).
-    chunk: as in attn_fwd (vds_attn_bwd_causal_fm_chunk)."""
+    chunk: as in attn_fwd (vds_attn_bwd_causal_fm_chunk).
+    window: as in attn_fwd (vds_attn_bwd_causal_fm_window)."""
     B, H, Lq, hd = q.shape
     assert lse.is_contiguous()
     Lk = k.shape[2]
-    fmaj = _frame_major(frame_major, frames, kv_lens, 0, chunk)
+    fmaj = _frame_major(frame_major, frames, kv_lens, 0, chunk, window)
     fr = _frames(frames, kv_lens, Lq, Lk) if frames is not None else None
     a = AttnArgs()
     a.B, a.H, a.Lq, a.Lk, a.head_dim = B, H, Lq, Lk, hd
@@ -390,7 +404,11 @@ def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = Fa
     a.dv, (a.dv_sb, a.dv_sh, a.dv_sl) = _p(dv), _st(dv)
     a.delta = _p(delta)
     a.kv_pad_ones = int(kv_pad_ones)
-    if fmaj and chunk != 1:
+    if fmaj and window is not None:
+        check(_lib.load().vds_attn_bwd_causal_fm_window(C.byref(a), fr, chunk, window, _stream()),
+              f"vds_attn_bwd_causal_fm_window(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)},chunk={chunk},"
+              f"window={window})")
+    elif fmaj and chunk != 1:
         check(_lib.load().vds_attn_bwd_causal_fm_chunk(C.byref(a), fr, chunk, _stream()),
               f"vds_attn_bwd_causal_fm_chunk(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)},chunk={chunk})")
     elif fmaj:
@@ -716,6 +734,26 @@ def fm_query_start(k0: int, lead: int, S: int, chunk: int = 1) -> int:
         return 0
     G = chunk * S
     return lead + ((k0 - lead) // G) * G
+
+
+def fm_key_begin(q0: int, lead: int, S: int, chunk: int = 1, window=None) -> int:
+    """first frame-major TOKEN key row that query row q0 attends under a window of `window` chunks (None: no window): a
+    query tile's second key range starts at the tile that holds this row for its first token query.  lead for a lead query
+    (it attends no token key)"""
+    if q0 < lead or window is None:
+        return lead
+    G = chunk * S
+    return lead + max(0, (q0 - lead) // G - window + 1) * G
+
+
+def fm_query_end(k1: int, lead: int, S: int, chunk: int = 1, window=None, L=None) -> int:
+    """first frame-major query row past the ones that attend key row k1 - 1, the last of a key tile [.., k1): a key
+    tile's query loop ends here unless the tile holds a lead key (every query attends those: L)"""
+    if window is None or k1 - 1 < lead:
+        return L
+    G = chunk * S
+    end = lead + ((k1 - 1 - lead) // G + window) * G
+    return end if L is None else min(end, L)
 
 
 def _fm_frames(frames, L: int):

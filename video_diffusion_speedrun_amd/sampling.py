@@ -65,6 +65,10 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
     rollout_frames must be a multiple of c and the cond_latents frames a whole number of chunks (ValueError otherwise; the
     video's last chunk may be short).  kv_cache=True then takes rollout_frames == c -- a cached call covers one chunk --
     and the cond_latents prefill runs one call and one commit() per chunk.
+    On a DiT built with frame_window=w the cached rollout uses the model's ring cache (new_frame_cache: w token-frames of
+    K / V whatever the video's length) without further arguments; a cached call covers one chunk -- one token-frame with
+    frame_chunk=1, so rollout_frames=1 there -- and the prefill runs chunk by chunk as above.  The uncached rollout runs
+    the windowed full-sequence model unchanged.
 
     cond_latents ([1,16,Tc,h,w], Tc a multiple of the model's time_patch_size; image-to-video, video extension): the
     first Tc latent frames are held at these values -- their token-frames are given t = 0 in every model call (per-frame
@@ -99,6 +103,11 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
             raise ValueError(f"frame rollout on a frame_chunk={c_model} model: cond_latents must hold a whole number of "
                              f"chunks -- a multiple of {c_model * model.time_patch_size} latent frames ({c_model} token-frames "
                              f"of time_patch_size {model.time_patch_size}), got {cond_latents.shape[2]}")
+    windowed = getattr(model, "frame_window", None) is not None
+    if windowed and kv_cache and c_model == 1 and rollout_frames is not None and not isinstance(rollout_frames, bool) \
+            and int(rollout_frames) == rollout_frames and int(rollout_frames) > 1:
+        raise ValueError(f"kv_cache=True on a frame_window model with frame_chunk=1: a cached call covers ONE token-frame, "
+                         f"pass rollout_frames=1 (or kv_cache=False for {rollout_frames} frames at a time)")
     dev = torch.device(device)
     prompt_embeds = prompt_embeds.to(dev, bf16)
     guided = cfg_scale > 1
@@ -220,8 +229,10 @@ def generate_latents(model, prompt_embeds: torch.Tensor, negative_embeds: Option
             return model(torch.cat([x, x]) if guided else x.contiguous(), ctx, tt,
                          rope_start=(base[0] + f0, base[1], base[2]), register_timesteps=reg, frame_cache=cache, **kw)
 
-        for f0 in range(0, n_cond, c_model if c_model > 1 else max(n_cond, 1)):  # (frame_chunk: one call per chunk)
-            chunk_call(f0, min(f0 + c_model, n_cond) if c_model > 1 else n_cond, 0.0)
+        # (frame_chunk, or a ring cache: one call and one commit per chunk)
+        per_chunk = c_model > 1 or windowed
+        for f0 in range(0, n_cond, c_model if per_chunk else max(n_cond, 1)):
+            chunk_call(f0, min(f0 + c_model, n_cond) if per_chunk else n_cond, 0.0)
             cache.commit()
         for f0 in range(n_cond, n_frames, k_roll):
             f1 = min(f0 + k_roll, n_frames)
