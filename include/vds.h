@@ -240,7 +240,9 @@ int vds_rmsnorm_mod_fwd(const void* x, int64_t ldx, const void* w, const float* 
                         int32_t shift_col, int32_t scale_col, void* y, int64_t ldy, float* rstd,
                         int32_t B, int32_t L, int32_t D, float eps, vds_stream_t stream);
 /* dx = bf16( dres + d/dx ), dmod[b, shift_col..] += sum_l dy, dmod[b, scale_col..] += sum_l dy*xhat*w,
- * dw (f32 [D], atomically +=) if w != NULL.  dres may be NULL. */
+ * dw (f32 [D], atomically +=) if w != NULL.  dres may be NULL.  Every access is a 16-byte row segment: D, lddy, ldx,
+ * lddx and (with dres != NULL) lddres must be multiples of 8, else VDS_ERR_ARG and nothing is written (the grouped
+ * call checks the same). */
 int vds_rmsnorm_mod_bwd(const void* dy, int64_t lddy, const void* x, int64_t ldx, const void* w,
                         const float* mod, int64_t ldmod, int32_t shift_col, int32_t scale_col,
                         const float* rstd, const void* dres, int64_t lddres, void* dx, int64_t lddx,
@@ -248,7 +250,9 @@ int vds_rmsnorm_mod_bwd(const void* dy, int64_t lddy, const void* x, int64_t ldx
 
 /* gate backward of  x_new = x + y*gate  (model.py:139,160,165):
  *   dy = bf16(dx_new * gate[b]),  dmod[b, gate_col + n] += sum_l dx_new*y,
- *   dbias[n] (f32, atomically +=) += sum_{b,l} dy   if dbias != NULL. */
+ *   dbias[n] (f32, atomically +=) += sum_{b,l} dy   if dbias != NULL.
+ * D, lddxn, ldy and lddy must be multiples of 8 (16-byte row segments), else VDS_ERR_ARG and nothing is written; the
+ * same holds for vds_gate_bwd_grouped and (lddxn, ldy, ldq) vds_gate_bwd_fp8. */
 int vds_gate_bwd(const void* dxn, int64_t lddxn, const void* y, int64_t ldy, const float* mod,
                  int64_t ldmod, int32_t gate_col, void* dy, int64_t lddy, float* dmod, float* dbias,
                  int32_t B, int32_t L, int32_t D, vds_stream_t stream);

@@ -1864,6 +1864,7 @@ extern "C" int vds_rmsnorm_mod_bwd(const void* dy, int64_t lddy, const void* x, 
                                    float* dmod, float* dw, int32_t B, int32_t L, int32_t D, vds_stream_t stream) {
   if (!dy || !x || !mod || !rstd || !dx || !dmod || (D & 7) || (lddy & 7) || (ldx & 7) || (lddx & 7)) return VDS_ERR_ARG;
   if (w && !dw) return VDS_ERR_ARG;
+  if (dres && (lddres & 7)) return VDS_ERR_ARG;  // (16-byte row segments, as every other operand)
   const int rpb = rows_per_block_for(L, B);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((L + rpb - 1) / rpb, B);
@@ -1896,7 +1897,7 @@ extern "C" int vds_rmsnorm_mod_bwd(const void* dy, int64_t lddy, const void* x, 
 extern "C" int vds_gate_bwd(const void* dxn, int64_t lddxn, const void* y, int64_t ldy, const float* mod,
                             int64_t ldmod, int32_t gate_col, void* dy, int64_t lddy, float* dmod, float* dbias,
                             int32_t B, int32_t L, int32_t D, vds_stream_t stream) {
-  if (!dxn || !y || !mod || !dy || !dmod || (D & 7)) return VDS_ERR_ARG;
+  if (!dxn || !y || !mod || !dy || !dmod || (D & 7) || (lddxn & 7) || (ldy & 7) || (lddy & 7)) return VDS_ERR_ARG;
   const int rpb = rows_per_block_for(L, B);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((L + rpb - 1) / rpb, B);
@@ -1927,7 +1928,7 @@ extern "C" int vds_rmsnorm_mod_bwd_grouped(const void* dy, int64_t lddy, const v
     return vds_rmsnorm_mod_bwd(dy, lddy, x, ldx, w, mod, ldmod, shift_col, scale_col, rstd, dres, lddres, dx, lddx, dmod, dw,
                                B, L, D, stream);
   if (!dy || !x || !mod || !rstd || !dx || !dmod || (D & 7) || (lddy & 7) || (ldx & 7) || (lddx & 7)) return VDS_ERR_ARG;
-  if ((w && !dw) || B < 1 || L < 1 || !groups_ok(groups, L)) return VDS_ERR_ARG;
+  if ((w && !dw) || B < 1 || L < 1 || !groups_ok(groups, L) || (dres && (lddres & 7))) return VDS_ERR_ARG;
   const long BG = (long)B * (1 + groups->period);
   if (BG > 65535) return VDS_ERR_ARG;  // (the modulation rows are the grid's y dimension)
   const MGrp mg{groups->lead, groups->period};
@@ -1967,7 +1968,9 @@ extern "C" int vds_gate_bwd_grouped(const void* dxn, int64_t lddxn, const void* 
                                     int64_t ldmod, int32_t gate_col, void* dy, int64_t lddy, float* dmod, float* dbias,
                                     int32_t B, int32_t L, int32_t D, const vds_mod_groups* groups, vds_stream_t stream) {
   if (!groups) return vds_gate_bwd(dxn, lddxn, y, ldy, mod, ldmod, gate_col, dy, lddy, dmod, dbias, B, L, D, stream);
-  if (!dxn || !y || !mod || !dy || !dmod || (D & 7) || B < 1 || L < 1 || !groups_ok(groups, L)) return VDS_ERR_ARG;
+  if (!dxn || !y || !mod || !dy || !dmod || (D & 7) || (lddxn & 7) || (ldy & 7) || (lddy & 7) || B < 1 || L < 1 ||
+      !groups_ok(groups, L))
+    return VDS_ERR_ARG;
   const long BG = (long)B * (1 + groups->period);
   if (BG > 65535) return VDS_ERR_ARG;  // (the modulation rows are the grid's y dimension)
   const MGrp mg{groups->lead, groups->period};
@@ -1995,7 +1998,7 @@ extern "C" int vds_gate_bwd_fp8(const void* dxn, int64_t lddxn, const void* y, i
                                 int64_t ldmod, int32_t gate_col, void* q, int64_t ldq, int32_t fmt,
                                 const float* amax_in, float* amax_part, float* dq_out, float* dmod, float* dbias,
                                 int32_t B, int32_t L, int32_t D, vds_stream_t stream) {
-  if (!dxn || !y || !mod || !dmod || (D & 7) || !qout_ok(q, ldq, fmt, amax_in)) return VDS_ERR_ARG;
+  if (!dxn || !y || !mod || !dmod || (D & 7) || (lddxn & 7) || (ldy & 7) || !qout_ok(q, ldq, fmt, amax_in)) return VDS_ERR_ARG;
   const int rpb = rows_per_block_for(L, B);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((L + rpb - 1) / rpb, B);
