@@ -209,6 +209,7 @@ typedef struct vds_attn_args {
 } vds_attn_args;
 
 int vds_attn_fwd(const vds_attn_args* args, vds_stream_t stream);
+/* Lq <= 0 or Lk <= 0: VDS_ERR_ARG before anything is launched, as in vds_attn_fwd and every masked call below. */
 int vds_attn_bwd(const vds_attn_args* args, vds_stream_t stream);
 /* The same two calls with per-sample key counts: kv_lens = device pointer to B int32, each in [0, Lk] (values outside
  * are clamped); the kernels read it, never the host, so a captured graph replays with new lengths.  Sample b attends

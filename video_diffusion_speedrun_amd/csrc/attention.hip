@@ -2420,72 +2420,167 @@ bool strides_ok(const vds_attn_args* a, bool bwd) {
 constexpr int ATTN_VARIANT_DEFAULT = 7;
 int attn_variant() { return vdscfg::geti(vdscfg::ATTN_MFMA16) & 7; }
 
-template <typename K>
-void set_lds(K kern, int bytes) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+// ---- which mask ---------------------------------------------------------------------------------------------------------
+// A call travels: entry point (its forwarding rule) -> attn_call: validate -> to_p, apply_mask -> with_head_dim -> a runner
+// -> launch.  A mask is one enumerator, the bool template flags of the kernel instances that implement it (flags_of), the
+// values it carries (MaskV), its refusals (validate) and the AttnP fields it sets (apply_mask).
+//   KVLEN  (vds_attn_*_kvlen): the instances that read p.kv_lens.  The choices and the launch geometry are functions of Lk,
+//          never of the device-side lengths.
+//   CAUSAL (vds_attn_*_causal): the instances that read p.fc_lead / p.fc_period, same choices and geometry.
+//   PAST   (vds_attn_fwd_causal_past): the CAUSAL forward instances that also read p.fc_past.
+//   FM     (vds_attn_*_causal_fm, _fm_chunk): the frame-major instances; a chunk is the granularity p.fm_G, no kernel of its own.
+//   FM_WIN (vds_attn_*_causal_fm_window): the WIN instances of the FM kernels (p.fc_past = W chunks).
+enum class Mask { NONE, KVLEN, CAUSAL, PAST, FM, FM_WIN };
+struct MaskFlags {
+  bool kvlen, causal, past, fm, win;
+};
+constexpr MaskFlags flags_of(Mask m) {
+  return {m == Mask::KVLEN, m == Mask::CAUSAL || m == Mask::PAST, m == Mask::PAST, m == Mask::FM || m == Mask::FM_WIN,
+          m == Mask::FM_WIN};
 }
+template <Mask M>
+constexpr MaskFlags FLAGS = flags_of(M);
 
-// knob attn_tail_last = 0 keeps the head-major order for ragged lengths too (A/B)
-static int tail_last_for(int L, int tile) {
-  return (vdscfg::geti(vdscfg::ATTN_TAIL_LAST) && L > tile && (L % tile) != 0) ? 1 : 0;
-}
+struct MaskV {
+  const int32_t* kv_lens = nullptr;        // KVLEN: B int32 on the device
+  const vds_mod_groups* frames = nullptr;  // CAUSAL, PAST, FM, FM_WIN
+  int past = 0;                            // PAST: cached key rows behind the lead rows
+  int chunk = 1;                           // FM, FM_WIN: token-frames per causal chunk
+  int window_chunks = 0;                   // FM_WIN
+};
 
-// KVLEN (vds_attn_*_kvlen): the same choices and launch geometry -- functions of Lk, never of the device-side lengths --
-// on the kernel instances that read p.kv_lens
-// CAUSAL (vds_attn_*_causal): likewise -- the same choices and geometry on the instances that read p.fc_lead / p.fc_period.
-// (The profiler credits a frame-causal call with the unmasked FLOPs: in the (h w t) row order no tile is skipped, so
-// that is the work executed.)
-// PAST (vds_attn_fwd_causal_past): likewise, on the instances that also read p.fc_past; the FLOPs credited are those of
-// all Lq x Lk pairs.
-template <int HDP, int HDQ, bool KVLEN = false, bool CAUSAL = false, bool PAST = false>
-int run_fwd(AttnP p, hipStream_t s) {
-  constexpr int LDS = 4 * 64 * HDP * 2;
-  static bool once = false;
-  if (!once) {
-    set_lds(attn_fwd_kernel<HDP, HDQ, 2, true, KVLEN, CAUSAL, PAST>, LDS);
-    if constexpr (HDP <= 96) set_lds(attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN, CAUSAL, PAST>, LDS);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd_wide_kernel<HDP, HDQ, true, KVLEN, CAUSAL, PAST>, LDS);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd16_kernel<HDP, KVLEN, CAUSAL, PAST>, LDS);
-    once = true;
+// The refusals of one call, in this order: NULL pointers and non-positive lengths, strides, the mask's own conditions
+// (VDS_ERR_ARG before VDS_ERR_UNSUPPORTED), the head dim.  Nothing is launched before it returns VDS_OK.
+int validate(const vds_attn_args* a, Mask kind, const MaskV& m, bool bwd) {
+  if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse || a->Lq <= 0 || a->Lk <= 0 ||
+      (bwd && (!a->d_o || !a->dq || !a->dk || !a->dv || !a->delta)))
+    return VDS_ERR_ARG;
+  if (!strides_ok(a, bwd)) return VDS_ERR_ARG;
+  const MaskFlags f = flags_of(kind);
+  if (f.kvlen && a->kv_pad_ones == 1) return VDS_ERR_ARG;  // self-attention on annotated q rows: no lengths
+  if (f.causal || f.fm) {
+    // self-attention only: the keys are the queries' own rows, behind m.past cached ones (see fc_past_row for that mask)
+    const vds_mod_groups* fr = m.frames;
+    if (!fr || (int64_t)a->Lk != (int64_t)a->Lq + m.past || a->kv_pad_ones == 2) return VDS_ERR_ARG;
+    if (fr->lead < 0 || fr->period < 1 || a->Lq < fr->lead || (a->Lq - fr->lead) % fr->period != 0) return VDS_ERR_ARG;
+    if (a->Lk > (1 << 21)) return VDS_ERR_UNSUPPORTED;  // FcMap / FmMap: the fp32 quotient is exact below 2^21 rows
   }
+  if (f.fm) {
+    // the token rows of o / d_o are reached through 32-bit byte offsets (tok(r) * row stride * 2): a (b, h) slice of them
+    // has to stay below 4 GiB
+    const int64_t lim = (int64_t)1 << 32;
+    if ((int64_t)a->Lq * a->o_sl * 2 >= lim || (bwd && (int64_t)a->Lq * a->do_sl * 2 >= lim)) return VDS_ERR_UNSUPPORTED;
+  }
+  return kernel_instance(a->head_dim) ? VDS_OK : VDS_ERR_UNSUPPORTED;
+}
+
+// the mask's values into the kernel arguments (to_p leaves the fields of "no mask")
+void apply_mask(AttnP& p, Mask kind, const MaskV& m) {
+  const MaskFlags f = flags_of(kind);
+  if (f.kvlen) p.kv_lens = m.kv_lens;
+  if (f.causal || f.fm) {
+    p.fc_lead = m.frames->lead;
+    p.fc_period = m.frames->period;
+  }
+  if (f.past) p.fc_past = m.past;
+  if (f.fm) {
+    const int S = (p.Lq - p.fc_lead) / p.fc_period;
+    p.fm_S = S > 0 ? S : 1;  // (no token rows: every row is a lead row and the quotient is never taken)
+    // chunk >= period is one token group: G = period * S = L - lead < 2^21, whatever the chunk
+    p.fm_G = (m.chunk < p.fc_period ? m.chunk : p.fc_period) * p.fm_S;
+    p.fm_rev = vdscfg::geti(vdscfg::ATTN_FM_HEAVY_FIRST) ? 1 : 0;
+  }
+  if (f.win) p.fc_past = m.window_chunks;  // (< the chunk count <= period: W * G stays below L)
+}
+
+// The one place that maps a head dim to its instance <HDP, HDQ>: f(HDP, HDQ) with both as std::integral_constant.
+template <typename F>
+int with_head_dim(int hd, F&& f) {
+  using std::integral_constant;
+  switch (kernel_instance(hd)) {
+    // (32: the reference's own smoke test, width 512 / 16 heads, model.py:545-565)
+    case 32: return f(integral_constant<int, 32>{}, integral_constant<int, 32>{});
+    case 64: return f(integral_constant<int, 64>{}, integral_constant<int, 64>{});
+    case 80: return f(integral_constant<int, 96>{}, integral_constant<int, 80>{});
+    case 96: return f(integral_constant<int, 96>{}, integral_constant<int, 96>{});
+    case 128: return f(integral_constant<int, 128>{}, integral_constant<int, 128>{});
+    default: return VDS_ERR_UNSUPPORTED;
+  }
+}
+
+// ---- launching ----------------------------------------------------------------------------------------------------------
+// One launch of 256-thread workgroups.  The kernel is a template argument, so the limit on its dynamic LDS is raised where it
+// is launched, before its first launch and once per instantiation (the initialisation of a function-local static is done
+// exactly once, also under concurrent callers): an instance that has a launch site has the attribute.  The tiles of head dim
+// 128 take 64 KiB and more, past the default limit.
+template <auto KERNEL, int LDS>
+void launch(unsigned grid, hipStream_t s, const AttnP& p) {
+  if constexpr (LDS > 0) {
+    static const hipError_t raised =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    (void)raised;
+  }
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), LDS, s, p);
+}
+
+// what every runner returns after its last launch
+int launched() { return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH; }
+
+// The geometry of a kernel whose workgroups hold `tile` of the L rows of its stationary operand: p.n_rt and p.tail_last,
+// and the grid -- the (b, h) pairs rounded up to a multiple of 8, times the row tiles.
+// (knob attn_tail_last = 0 keeps the head-major order for ragged lengths too (A/B))
+unsigned tile_grid(AttnP& p, int L, int tile) {
+  p.n_rt = cdiv(L, tile);
+  p.tail_last = (vdscfg::geti(vdscfg::ATTN_TAIL_LAST) && L > tile && (L % tile) != 0) ? 1 : 0;
+  return (unsigned)(cdiv(p.B * p.H, 8) * 8 * p.n_rt);
+}
+
+// the preprocess of the backward (delta = rowsum(dO * O), lse * log2 e): one read of token-major o / d_o rows where the
+// layout allows it.  FM: o / d_o rows by tok(r).
+template <bool FM>
+void launch_delta(const AttnP& p, hipStream_t s) {
+  const long rows = (long)p.B * p.H * p.Lq;
+  vdsprof::Scope ps(VDS_PROF_ATTN_BWD_DELTA, s, 2.0 * rows * p.hd, 2.0 * (2.0 * p.B * p.H * p.hd * (double)p.Lq));
+  const bool tokmajor = p.o_sh == p.hd && p.do_sh == p.hd && p.o_sl == (long)p.H * p.hd && p.do_sl == p.o_sl &&
+                        (p.o_sl & 7) == 0 && (p.o_sb & 7) == 0 && (p.do_sb & 7) == 0 && p.H * p.hd <= 1536 && p.H <= 64;
+  if (tokmajor) launch<attn_delta_tokmajor_kernel<FM>, 0>((unsigned)(((long)p.B * p.Lq + 3) / 4), s, p);
+  else launch<attn_delta_kernel<FM>, 0>((unsigned)((rows + 3) / 4), s, p);
+}
+
+// ---- the runners of the interleaved masks (NONE, KVLEN, CAUSAL, PAST) ---------------------------------------------------
+// (KVLEN: the host does not know the lengths -- the profiler credits the work of all Lk keys, here and in run_bwd, so its
+// FLOP/s and byte rates of a masked call are overstated by Lk / mean length.  CAUSAL: the profiler credits the unmasked
+// FLOPs: in the (h w t) row order no tile is skipped, so that is the work executed.  PAST: those of all Lq x Lk pairs.)
+template <int HDP, int HDQ, Mask M>
+int run_fwd(AttnP p, hipStream_t s) {
+  constexpr bool KVLEN = FLAGS<M>.kvlen, CAUSAL = FLAGS<M>.causal, PAST = FLAGS<M>.past;
+  constexpr int LDS = 4 * 64 * HDP * 2;
   const int wide = vdscfg::geti(vdscfg::ATTN_FWD_WIDE);  // 0 / 1 forces (experiments); 2 (default): head_dim 64 / 72, long query sequences
   bool use_wide = false;
-  if constexpr (HDP == 96) use_wide = wide == 1 || (wide == 2 && p.Lq >= 2048);
-  if constexpr (HDP == 64) use_wide = wide == 1 || (wide == 2 && p.Lq >= 2048);  // +2.7 % at head_dim 64
-  p.n_rt = cdiv(p.Lq, use_wide ? 256 : 128);
-  p.tail_last = tail_last_for(p.Lq, use_wide ? 256 : 128);
-  const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
-  // (KVLEN: the host does not know the lengths -- the profiler credits the work of all Lk keys, here and in run_bwd, so
-  // its FLOP/s and byte rates of a masked call are overstated by Lk / mean length)
+  if constexpr (HDP == 96 || HDP == 64) use_wide = wide == 1 || (wide == 2 && p.Lq >= 2048);  // (+2.7 % at head_dim 64)
+  const unsigned grid = tile_grid(p, p.Lq, use_wide ? 256 : 128);
   const double fl = 4.0 * p.B * p.H * (double)p.Lq * p.Lk * p.hd;
   const bool ones_fwd = HDP == 96 && HDQ == 80 && use_wide && p.kv_pad_ones && p.hd == 72;
   // (kv_pad_ones == 2: cross-attention on the ones-column kernels -- keeps its own profiler class)
   vdsprof::Scope ps(ones_fwd && p.kv_pad_ones == 1 ? VDS_PROF_ATTN_FWD : VDS_PROF_ATTN_FWD_PLAIN, s, fl,
                     2.0 * p.B * p.H * p.hd * (2.0 * p.Lq + 2.0 * p.Lk));
-  if constexpr (HDP == 64) {
-    if (use_wide) {
-      hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN, CAUSAL, PAST>), dim3(grid), dim3(256), LDS, s, p);
-      return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
+  if constexpr (HDP == 96 && HDQ == 80) {
+    if (ones_fwd) {
+      // (round 5 measured a form of this kernel software-pipelined inside the wave: +9.5 % slower, removed in round 6;
+      // profiles/r05/attn_fwd_software_pipelined.log)
+      if (attn_variant() & 4) launch<attn_fwd16_kernel<HDP, KVLEN, CAUSAL, PAST>, LDS>(grid, s, p);
+      else launch<attn_fwd_wide_kernel<HDP, HDQ, true, KVLEN, CAUSAL, PAST>, LDS>(grid, s, p);
+      return launched();
     }
   }
-  if constexpr (HDP == 96) {
+  if constexpr (HDP == 96 || HDP == 64) {
     if (use_wide) {
-      bool done = false;
-      if constexpr (HDQ == 80) {
-        if (p.kv_pad_ones && p.hd == 72) {
-          // (round 5 measured a form of this kernel software-pipelined inside the wave: +9.5 % slower, removed in round 6;
-          // profiles/r05/attn_fwd_software_pipelined.log)
-          if (attn_variant() & 4) hipLaunchKernelGGL((attn_fwd16_kernel<HDP, KVLEN, CAUSAL, PAST>), dim3(grid), dim3(256), LDS, s, p);
-          else hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, true, KVLEN, CAUSAL, PAST>), dim3(grid), dim3(256), LDS, s, p);
-          done = true;
-        }
-      }
-      if (!done) hipLaunchKernelGGL((attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN, CAUSAL, PAST>), dim3(grid), dim3(256), LDS, s, p);
-      return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
+      launch<attn_fwd_wide_kernel<HDP, HDQ, false, KVLEN, CAUSAL, PAST>, LDS>(grid, s, p);
+      return launched();
     }
   }
-  hipLaunchKernelGGL((attn_fwd_kernel<HDP, HDQ, 2, true, KVLEN, CAUSAL, PAST>), dim3(grid), dim3(256), LDS, s, p);
-  return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
+  launch<attn_fwd_kernel<HDP, HDQ, 2, true, KVLEN, CAUSAL, PAST>, LDS>(grid, s, p);
+  return launched();
 }
 
 // query-range split of the plain dK/dV kernel: target ~3 rounds of the 512 co-resident workgroups, each range at
@@ -2499,22 +2594,12 @@ int dkv_qsplit(int B, int H, int Lq, int Lk) {
   return (int)(sp < 1 ? 1 : sp > 16 ? 16 : sp);
 }
 
-template <int HDP, int HDQ, bool KVLEN = false, bool CAUSAL = false>
+template <int HDP, int HDQ, Mask M>
 int run_bwd(AttnP p, hipStream_t s, size_t ws_floats) {
+  constexpr bool KVLEN = FLAGS<M>.kvlen, CAUSAL = FLAGS<M>.causal;
+  constexpr bool HD72 = HDP == 96 && HDQ == 80;  // the instance of the ones-column kernels
   constexpr int LDS_DQ = 4 * 64 * HDP * 2;
   constexpr int LDS_DKV = 4 * 64 * HDP * 2 + 2 * 128 * 4;
-  static bool once = false;
-  if (!once) {
-    set_lds(attn_bwd_dq_kernel<HDP, HDQ, false, KVLEN, CAUSAL>, LDS_DQ);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dq_kernel<HDP, HDQ, true, KVLEN, CAUSAL>, LDS_DQ);
-    set_lds(attn_bwd_dkv_kernel<HDP, HDQ, false, KVLEN, CAUSAL>, LDS_DKV);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dkv_kernel<HDP, HDQ, true, false, CAUSAL>, LDS_DKV);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dkv16_kernel<HDP, true, false, CAUSAL>, LDS_DKV);
-    if constexpr (HDP == 96 && HDQ == 80 && !CAUSAL) set_lds(attn_bwd_dkv16_kernel<HDP, false, KVLEN>, LDS_DKV);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dq16_kernel<HDP, false, KVLEN, CAUSAL>, LDS_DQ);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_bwd_dq16_kernel<HDP, true, KVLEN, CAUSAL>, LDS_DQ);
-    once = true;
-  }
   const long rows = (long)p.B * p.H * p.Lq;
   // ALGORITHMIC backward = 2 x forward = 4 products of 2*Lq*Lk*hd (train step = 3 x forward FLOPs, no
   // credit for the recomputed S, nor for the dP the split backward computes twice): dK/dV kernel 2 (dV, dK), dQ
@@ -2523,64 +2608,47 @@ int run_bwd(AttnP p, hipStream_t s, size_t ws_floats) {
   const double qb = 2.0 * p.B * p.H * p.hd * (double)p.Lq, kb = 2.0 * p.B * p.H * p.hd * (double)p.Lk;
   // the 16x16x32 dQ kernel of the ones-column path computes the statistics itself and runs first (attn_bwd_dq16_kernel, FOLD)
   bool fold = false;
-  if constexpr (HDP == 96 && HDQ == 80) fold = p.kv_pad_ones && p.hd == 72 && (attn_variant() & 2) && vdscfg::geti(vdscfg::ATTN_DELTA_FOLD);
+  if constexpr (HD72) fold = p.kv_pad_ones && p.hd == 72 && (attn_variant() & 2) && vdscfg::geti(vdscfg::ATTN_DELTA_FOLD);
   auto launch_dq = [&]() {
-    p.n_rt = cdiv(p.Lq, 128);
-    p.tail_last = tail_last_for(p.Lq, 128);
-    const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
+    const unsigned grid = tile_grid(p, p.Lq, 128);
     bool ones = false;
-    if constexpr (HDP == 96 && HDQ == 80) ones = p.kv_pad_ones && p.hd == 72;
+    if constexpr (HD72) ones = p.kv_pad_ones && p.hd == 72;
     vdsprof::Scope ps(ones && p.kv_pad_ones == 1 ? VDS_PROF_ATTN_BWD_DQ : VDS_PROF_ATTN_BWD_DQ_PLAIN, s, 2.0 * prod,
                       (fold ? 4.0 : 3.0) * qb + 2.0 * kb);
-    if constexpr (HDP == 96 && HDQ == 80) {
+    if constexpr (HD72) {
       // (48 queries per wave -- every fragment read feeds 3 MFMAs, two waves per SIMD instead of three -- measured 2-6 %
       // slower in round 5, removed in round 6; profiles/r05/attn_dq_three_blocks_per_wave.log)
-      if (fold)
-        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, true, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS_DQ, s, p);
-      else if (ones && (attn_variant() & 2))
-        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, false, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS_DQ, s, p);
-      else if (ones)
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, HDQ, true, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS_DQ, s, p);
+      if (fold) launch<attn_bwd_dq16_kernel<HDP, true, KVLEN, CAUSAL>, LDS_DQ>(grid, s, p);
+      else if (ones && (attn_variant() & 2)) launch<attn_bwd_dq16_kernel<HDP, false, KVLEN, CAUSAL>, LDS_DQ>(grid, s, p);
+      else if (ones) launch<attn_bwd_dq_kernel<HDP, HDQ, true, KVLEN, CAUSAL>, LDS_DQ>(grid, s, p);
     }
-    if (!ones) hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, HDQ, false, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS_DQ, s, p);
+    if (!ones) launch<attn_bwd_dq_kernel<HDP, HDQ, false, KVLEN, CAUSAL>, LDS_DQ>(grid, s, p);
   };
   if (fold) launch_dq();
-  else {
-    vdsprof::Scope ps(VDS_PROF_ATTN_BWD_DELTA, s, 2.0 * rows * p.hd, 2.0 * qb);
-    const bool tokmajor = p.o_sh == p.hd && p.do_sh == p.hd && p.o_sl == (long)p.H * p.hd && p.do_sl == p.o_sl &&
-                          (p.o_sl & 7) == 0 && (p.o_sb & 7) == 0 && (p.do_sb & 7) == 0 && p.H * p.hd <= 1536 && p.H <= 64;
-    if (tokmajor)
-      hipLaunchKernelGGL(attn_delta_tokmajor_kernel<false>, dim3((unsigned)(((long)p.B * p.Lq + 3) / 4)), dim3(256), 0, s, p);
-    else
-      hipLaunchKernelGGL(attn_delta_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, p);
-  }
+  else launch_delta<false>(p, s);
   // (a 64-keys-per-wave, one-wave-per-SIMD variant of this kernel -- half the LDS reads per MFMA -- was
   // measured at 0.55-0.8x: hipcc's single-wave schedule does not overlap the VALU softmax with the MFMAs)
-  p.n_rt = cdiv(p.Lk, 128);
-  p.tail_last = tail_last_for(p.Lk, 128);
-  int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
+  const unsigned grid = tile_grid(p, p.Lk, 128);
   {
     bool ones_kv = false;
     // (kv_pad_ones == 2: the q rows carry no annotated pad -- token-major cross-attention queries -- so the dK/dV pass takes
     // the plain kernel, which stages -lse2 itself and masks the K / V pad columns)
-    if constexpr (HDP == 96 && HDQ == 80) ones_kv = p.kv_pad_ones == 1 && p.hd == 72;
+    if constexpr (HD72) ones_kv = p.kv_pad_ones == 1 && p.hd == 72;
     vdsprof::Scope ps(ones_kv ? VDS_PROF_ATTN_BWD_DKV : VDS_PROF_ATTN_BWD_DKV_PLAIN, s, 2.0 * prod, 2.0 * qb + 4.0 * kb);
-    if constexpr (HDP == 96 && HDQ == 80) {
+    if constexpr (HD72) {
       // (round 6 measured this kernel as an explicit MFMA / VALU ping-pong -- one 512-thread workgroup per CU, the two wave
       // groups in alternating MFMA and VALU / LDS segments under s_barrier: bit-identical, +5 % slower; the kernel executes 77 %
       // of what a bare MFMA loop reaches at the board's power limit.  profiles/r06/negative_attn_dkv_pingpong.log)
-      if (ones_kv && (attn_variant() & 1))
-        hipLaunchKernelGGL((attn_bwd_dkv16_kernel<HDP, true, false, CAUSAL>), dim3(grid), dim3(256), LDS_DKV, s, p);
-      else if (ones_kv)
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, true, false, CAUSAL>), dim3(grid), dim3(256), LDS_DKV, s, p);
+      if (ones_kv && (attn_variant() & 1)) launch<attn_bwd_dkv16_kernel<HDP, true, false, CAUSAL>, LDS_DKV>(grid, s, p);
+      else if (ones_kv) launch<attn_bwd_dkv_kernel<HDP, HDQ, true, false, CAUSAL>, LDS_DKV>(grid, s, p);
     }
     bool done16 = false;
-    if constexpr (HDP == 96 && HDQ == 80 && !CAUSAL) {
+    if constexpr (HD72 && !CAUSAL) {
       // cross-attention with padded K / V (kv_pad_ones = 2) and enough workgroups to fill the chip once (B*H*n_rt >= 512;
       // the query-range split below exists in the plain kernel only): the 16x16x32 kernel with S started from -lse2
       const int x16 = vdscfg::geti(vdscfg::CROSS_DKV16);  // 0 = plain kernel, 1 = rule, 2 = also for small grids (tests)
-      if (!ones_kv && p.kv_pad_ones == 2 && p.hd == 72 && x16 && ((long)grid >= 512 || x16 == 2) && (attn_variant() & 1)) {
-        hipLaunchKernelGGL((attn_bwd_dkv16_kernel<HDP, false, KVLEN>), dim3(grid), dim3(256), LDS_DKV, s, p);
+      if (!ones_kv && p.kv_pad_ones == 2 && p.hd == 72 && x16 && (grid >= 512 || x16 == 2) && (attn_variant() & 1)) {
+        launch<attn_bwd_dkv16_kernel<HDP, false, KVLEN>, LDS_DKV>(grid, s, p);
         done16 = true;
       }
     }
@@ -2597,236 +2665,28 @@ int run_bwd(AttnP p, hipStream_t s, size_t ws_floats) {
         p.q_split = split;
         p.dkv_part = p.delta + 2 * rows;
         p.tail_last = 0;
-        const int g2 = cdiv(p.B * p.H, 8) * 8 * p.n_rt * split;
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, false, KVLEN, CAUSAL>), dim3(g2), dim3(256), LDS_DKV, s, p);
+        launch<attn_bwd_dkv_kernel<HDP, HDQ, false, KVLEN, CAUSAL>, LDS_DKV>(grid * split, s, p);
         const long n = (long)p.B * p.H * p.Lk * 2 * (p.hd >> 2);
-        hipLaunchKernelGGL(dkv_reduce_kernel<KVLEN>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
+        launch<dkv_reduce_kernel<KVLEN>, 0>((unsigned)((n + 255) / 256), s, p);
         p.q_split = 1;
         p.dkv_part = nullptr;
       } else {
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, false, KVLEN, CAUSAL>), dim3(grid), dim3(256), LDS_DKV, s, p);
+        launch<attn_bwd_dkv_kernel<HDP, HDQ, false, KVLEN, CAUSAL>, LDS_DKV>(grid, s, p);
       }
     }
   }
   if (!fold) launch_dq();
-  return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
+  return launched();
 }
 
-}  // namespace
-
-// K / V of a cross-attention (token-major [B*Lk, ld] rows, head h at columns col0 + h*hd) -> head-major padded rows
-// [B,H,Lk,hdp] WITH the ones columns of the head_dim-72 kernels (K: 1.0 at hd, hd+1; V: 1.0 at hd, hd+4; zeros elsewhere
-// in the pad), so that the forward and dQ passes of the cross-attention run on the ones-column 16x16x32 kernels
-// (vds_attn_args.kv_pad_ones = 2).  One thread per 16-byte chunk of an output row.
-__global__ __launch_bounds__(256) void kv_pad_ones_kernel(const bf16_t* kv, long ld, int kcol0, int vcol0, bf16_t* kp,
-                                                          bf16_t* vp, int B, int Lk, int H, int hd, int hdp) {
-  const int cpr = hdp >> 3;  // chunks per output row
-  const long n = (long)B * H * Lk * cpr;
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= n) return;
-  const int which = blockIdx.y;  // 0 K, 1 V
-  const int c = (int)(gid % cpr);
-  const long row = gid / cpr;  // (b, h, l)
-  const int l = (int)(row % Lk);
-  const int h = (int)((row / Lk) % H);
-  const int b = (int)(row / ((long)Lk * H));
-  u32x4 w = {0u, 0u, 0u, 0u};
-  if (c * 8 < hd) {
-    w = *reinterpret_cast<const u32x4*>(kv + ((long)b * Lk + l) * ld + (which ? vcol0 : kcol0) + h * hd + c * 8);
-  } else if (c * 8 == hd) {
-    w[0] = which ? 0x00003f80u : 0x3f803f80u;  // K: 1.0 at hd, hd+1; V: 1.0 at hd ...
-    w[2] = which ? 0x00003f80u : 0u;           // ... and hd+4
-  }
-  *reinterpret_cast<u32x4*>((which ? vp : kp) + row * hdp + c * 8) = w;
-}
-
-extern "C" int vds_kv_pad_ones(const void* kv, int64_t ld, int32_t k_col0, int32_t v_col0, void* kp, void* vp, int32_t B,
-                               int32_t Lk, int32_t H, int32_t hd, int32_t hdp, vds_stream_t stream) {
-  if (!kv || !kp || !vp || B <= 0 || Lk <= 0 || H <= 0 || hd <= 0) return VDS_ERR_ARG;
-  if ((hd & 7) || (hdp & 7) || hdp < hd + 8 || (ld & 7) || (k_col0 & 7) || (v_col0 & 7)) return VDS_ERR_ARG;
-  const long n = (long)B * H * Lk * (hdp >> 3);
-  hipLaunchKernelGGL(kv_pad_ones_kernel, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)kv, (long)ld, k_col0, v_col0, (bf16_t*)kp, (bf16_t*)vp, B, Lk, H, hd, hdp);
-  return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
-}
-
-extern "C" int vds_attn_set_variant(int32_t mask) {
-  const int prev = attn_variant();
-  if (mask < -1 || mask > 7) return VDS_ERR_ARG;
-  vdscfg::g_val[vdscfg::ATTN_MFMA16] = mask < 0 ? ATTN_VARIANT_DEFAULT : mask;  // -1: back to the default
-  return prev;
-}
-
-extern "C" int vds_attn_fwd(const vds_attn_args* a, vds_stream_t stream) {
-  if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse || a->Lq <= 0 || a->Lk <= 0) return VDS_ERR_ARG;
-  if (!strides_ok(a, false)) return VDS_ERR_ARG;
-  AttnP p = to_p(a);
-  hipStream_t s = (hipStream_t)stream;
-  switch (kernel_instance(a->head_dim)) {
-    case 32: return run_fwd<32, 32>(p, s);  // (the reference's own smoke test: width 512 / 16 heads, model.py:545-565)
-    case 64: return run_fwd<64, 64>(p, s);
-    case 80: return run_fwd<96, 80>(p, s);
-    case 96: return run_fwd<96, 96>(p, s);
-    case 128: return run_fwd<128, 128>(p, s);
-    default: return VDS_ERR_UNSUPPORTED;
-  }
-}
-
-// per-sample key counts: the same checks, then the KVLEN instances (kv_lens == NULL: the calls above, unchanged)
-extern "C" int vds_attn_fwd_kvlen(const vds_attn_args* a, const int32_t* kv_lens, vds_stream_t stream) {
-  if (!a) return VDS_ERR_ARG;
-  if (!kv_lens) return vds_attn_fwd(a, stream);
-  if (a->kv_pad_ones == 1) return VDS_ERR_ARG;  // self-attention on annotated q rows: no lengths
-  if (!a->q || !a->k || !a->v || !a->o || !a->lse || a->Lq <= 0 || a->Lk <= 0) return VDS_ERR_ARG;
-  if (!strides_ok(a, false)) return VDS_ERR_ARG;
-  AttnP p = to_p(a);
-  p.kv_lens = kv_lens;
-  hipStream_t s = (hipStream_t)stream;
-  switch (kernel_instance(a->head_dim)) {
-    case 32: return run_fwd<32, 32, true>(p, s);
-    case 64: return run_fwd<64, 64, true>(p, s);
-    case 80: return run_fwd<96, 80, true>(p, s);
-    case 96: return run_fwd<96, 96, true>(p, s);
-    case 128: return run_fwd<128, 128, true>(p, s);
-    default: return VDS_ERR_UNSUPPORTED;
-  }
-}
-
-extern "C" size_t vds_attn_bwd_workspace_bytes(const vds_attn_args* a) {
-  if (!a || a->B <= 0 || a->H <= 0 || a->Lq <= 0) return 0;
-  size_t fl = (size_t)2 * a->B * a->H * a->Lq;
-  if (a->Lk > 0 && a->head_dim > 0 && a->kv_pad_ones != 1)  // fp32 partials of the query-split dK/dV kernel (short key sequences)
-    fl += (size_t)dkv_qsplit(a->B, a->H, a->Lq, a->Lk) * a->B * a->H * a->Lk * 2 * a->head_dim;
-  return fl * sizeof(float);
-}
-
-extern "C" int vds_attn_bwd(const vds_attn_args* a, vds_stream_t stream) {
-  if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse || !a->d_o || !a->dq || !a->dk || !a->dv || !a->delta)
-    return VDS_ERR_ARG;
-  if (!strides_ok(a, true)) return VDS_ERR_ARG;
-  AttnP p = to_p(a);
-  hipStream_t s = (hipStream_t)stream;
-  // floats in `delta`: 2*B*H*Lq when the caller does not say (ws_floats = 0: the pre-round-4 contract, no query split)
-  const size_t ws = a->ws_floats > 0 ? (size_t)a->ws_floats : (size_t)2 * a->B * a->H * a->Lq;
-  switch (kernel_instance(a->head_dim)) {
-    case 32: return run_bwd<32, 32>(p, s, ws);
-    case 64: return run_bwd<64, 64>(p, s, ws);
-    case 80: return run_bwd<96, 80>(p, s, ws);
-    case 96: return run_bwd<96, 96>(p, s, ws);
-    case 128: return run_bwd<128, 128>(p, s, ws);
-    default: return VDS_ERR_UNSUPPORTED;
-  }
-}
-
-extern "C" int vds_attn_bwd_kvlen(const vds_attn_args* a, const int32_t* kv_lens, vds_stream_t stream) {
-  if (!a) return VDS_ERR_ARG;
-  if (!kv_lens) return vds_attn_bwd(a, stream);
-  if (a->kv_pad_ones == 1) return VDS_ERR_ARG;
-  if (!a->q || !a->k || !a->v || !a->o || !a->lse || !a->d_o || !a->dq || !a->dk || !a->dv || !a->delta || a->Lq <= 0 ||
-      a->Lk <= 0)
-    return VDS_ERR_ARG;
-  if (!strides_ok(a, true)) return VDS_ERR_ARG;
-  AttnP p = to_p(a);
-  p.kv_lens = kv_lens;
-  hipStream_t s = (hipStream_t)stream;
-  const size_t ws = a->ws_floats > 0 ? (size_t)a->ws_floats : (size_t)2 * a->B * a->H * a->Lq;
-  switch (kernel_instance(a->head_dim)) {
-    case 32: return run_bwd<32, 32, true>(p, s, ws);
-    case 64: return run_bwd<64, 64, true>(p, s, ws);
-    case 80: return run_bwd<96, 80, true>(p, s, ws);
-    case 96: return run_bwd<96, 96, true>(p, s, ws);
-    case 128: return run_bwd<128, 128, true>(p, s, ws);
-    default: return VDS_ERR_UNSUPPORTED;
-  }
-}
-
-// frame-causal self-attention: the same checks, then the CAUSAL instances (frames == NULL: the plain calls, unchanged)
-static int fc_check(const vds_attn_args* a, const vds_mod_groups* f) {
-  if (a->Lq != a->Lk || a->kv_pad_ones == 2) return VDS_ERR_ARG;
-  if (f->lead < 0 || f->period < 1 || a->Lq < f->lead || (a->Lq - f->lead) % f->period != 0) return VDS_ERR_ARG;
-  if (a->Lq > (1 << 21)) return VDS_ERR_UNSUPPORTED;  // FcMap: the fp32 quotient is exact below 2^21 rows
-  return VDS_OK;
-}
-
-extern "C" int vds_attn_fwd_causal(const vds_attn_args* a, const vds_mod_groups* frames, vds_stream_t stream) {
-  if (!a) return VDS_ERR_ARG;
-  if (!frames) return vds_attn_fwd(a, stream);
-  if (!a->q || !a->k || !a->v || !a->o || !a->lse || a->Lq <= 0 || a->Lk <= 0) return VDS_ERR_ARG;
-  if (!strides_ok(a, false)) return VDS_ERR_ARG;
-  if (const int e = fc_check(a, frames)) return e;
-  AttnP p = to_p(a);
-  p.fc_lead = frames->lead;
-  p.fc_period = frames->period;
-  hipStream_t s = (hipStream_t)stream;
-  switch (kernel_instance(a->head_dim)) {
-    case 32: return run_fwd<32, 32, false, true>(p, s);
-    case 64: return run_fwd<64, 64, false, true>(p, s);
-    case 80: return run_fwd<96, 80, false, true>(p, s);
-    case 96: return run_fwd<96, 96, false, true>(p, s);
-    case 128: return run_fwd<128, 128, false, true>(p, s);
-    default: return VDS_ERR_UNSUPPORTED;
-  }
-}
-
-extern "C" int vds_attn_bwd_causal(const vds_attn_args* a, const vds_mod_groups* frames, vds_stream_t stream) {
-  if (!a) return VDS_ERR_ARG;
-  if (!frames) return vds_attn_bwd(a, stream);
-  if (!a->q || !a->k || !a->v || !a->o || !a->lse || !a->d_o || !a->dq || !a->dk || !a->dv || !a->delta || a->Lq <= 0 ||
-      a->Lk <= 0)
-    return VDS_ERR_ARG;
-  if (!strides_ok(a, true)) return VDS_ERR_ARG;
-  if (const int e = fc_check(a, frames)) return e;
-  AttnP p = to_p(a);
-  p.fc_lead = frames->lead;
-  p.fc_period = frames->period;
-  hipStream_t s = (hipStream_t)stream;
-  const size_t ws = a->ws_floats > 0 ? (size_t)a->ws_floats : (size_t)2 * a->B * a->H * a->Lq;
-  switch (kernel_instance(a->head_dim)) {
-    case 32: return run_bwd<32, 32, false, true>(p, s, ws);
-    case 64: return run_bwd<64, 64, false, true>(p, s, ws);
-    case 80: return run_bwd<96, 80, false, true>(p, s, ws);
-    case 96: return run_bwd<96, 96, false, true>(p, s, ws);
-    case 128: return run_bwd<128, 128, false, true>(p, s, ws);
-    default: return VDS_ERR_UNSUPPORTED;
-  }
-}
-
-// frame-causal forward with a past (the cached rollout): the queries are the Lq rows of one call, the keys
-// [lead rows | past cached rows | the call's own token rows]; see fc_past_row for the mask.  past == 0: the call above.
-extern "C" int vds_attn_fwd_causal_past(const vds_attn_args* a, const vds_mod_groups* frames, int32_t past,
-                                        vds_stream_t stream) {
-  if (!a || past < 0) return VDS_ERR_ARG;
-  if (past == 0) return vds_attn_fwd_causal(a, frames, stream);
-  if (!frames) return VDS_ERR_ARG;
-  if (!a->q || !a->k || !a->v || !a->o || !a->lse || a->Lq <= 0 || a->Lk <= 0) return VDS_ERR_ARG;
-  if (!strides_ok(a, false)) return VDS_ERR_ARG;
-  if ((int64_t)a->Lk != (int64_t)a->Lq + past || a->kv_pad_ones == 2) return VDS_ERR_ARG;
-  if (frames->lead < 0 || frames->period < 1 || a->Lq < frames->lead || (a->Lq - frames->lead) % frames->period != 0)
-    return VDS_ERR_ARG;
-  if (a->Lk > (1 << 21)) return VDS_ERR_UNSUPPORTED;  // FcMap: the fp32 quotient is exact below 2^21 rows
-  AttnP p = to_p(a);
-  p.fc_lead = frames->lead;
-  p.fc_period = frames->period;
-  p.fc_past = past;
-  hipStream_t s = (hipStream_t)stream;
-  switch (kernel_instance(a->head_dim)) {
-    case 32: return run_fwd<32, 32, false, true, true>(p, s);
-    case 64: return run_fwd<64, 64, false, true, true>(p, s);
-    case 80: return run_fwd<96, 80, false, true, true>(p, s);
-    case 96: return run_fwd<96, 96, false, true, true>(p, s);
-    case 128: return run_fwd<128, 128, false, true, true>(p, s);
-    default: return VDS_ERR_UNSUPPORTED;
-  }
-}
-
-// ---- frame-major self-attention (include/vds.h) -----------------------------------------------------------------------
+// ---- the runners of the frame-major masks (FM, FM_WIN; include/vds.h) ---------------------------------------------------
 // FM instances exist of the plain 32x32x16 kernels (every head dim; kv_pad_ones 0, and 1 where a 16x16x32 kernel is
 // switched off: the pad columns are not read) and, for the ones layout at head dim 72, of the 16x16x32 family --
 // attn_fwd16_kernel, attn_bwd_dq16_kernel with and without FOLD, attn_bwd_dkv16_kernel -- under the same attn_mfma16 bits
 // (vds_attn_set_variant), attn_delta_fold knob and attn_fwd_wide rule as their CAUSAL siblings.  There is no frame-major
-// instance of the 64-queries-per-wave 32x32 forwards nor of the ones-column 32x32 kernels: where the interleaved dispatcher
-// would take one of those, this one takes the plain 32x32x16 FM kernel.  The query range of the dK/dV kernel is never split.
-namespace {
+// instance of the 64-queries-per-wave 32x32 forwards nor of the ones-column 32x32 kernels: where run_fwd / run_bwd would
+// take one of those, these runners take the plain 32x32x16 FM kernel.  The query range of the dK/dV kernel is never split.
+// The profiler credits the pairs of the key range actually visited, not the unmasked L x L.
 // (G: rows per chunk, fm_G)
 int fm_kend_host(int r, int lead, int G, int L) {
   if (r < lead) return lead;
@@ -2872,58 +2732,38 @@ double fm_pairs_k(int L, int lead, int G, int tile, int W = 0) {
   return n;
 }
 
-// the profiler credits the pairs of the key range actually visited, not the unmasked L x L
-// WIN: the window instances (p.fc_past = W chunks), chosen by the same rules
-template <int HDP, int HDQ, bool WIN = false>
+template <int HDP, int HDQ, Mask M>
 int run_fwd_fm(AttnP p, hipStream_t s) {
-  const int W = WIN ? p.fc_past : 0;
+  constexpr bool WIN = FLAGS<M>.win;
   constexpr int LDS = 4 * 64 * HDP * 2;
-  static bool once = false;
-  if (!once) {
-    set_lds(attn_fwd_kernel<HDP, HDQ, 2, true, false, false, false, true, WIN>, LDS);
-    if constexpr (HDP == 96 && HDQ == 80) set_lds(attn_fwd16_kernel<HDP, false, false, false, true, WIN>, LDS);
-    once = true;
-  }
+  const int W = WIN ? p.fc_past : 0;
+  // the ones layout on the 16x16x32 forward, where run_fwd takes it: 64 queries per wave by the attn_fwd_wide rule (0 / 1
+  // forces, 2: from 2048 queries) and bit 2 of the variant mask
+  bool fwd16 = false;
   if constexpr (HDP == 96 && HDQ == 80) {
-    // the ones layout on the 16x16x32 forward, where the interleaved dispatcher takes it: 64 queries per wave by the
-    // attn_fwd_wide rule (0 / 1 forces, 2: from 2048 queries) and bit 2 of the variant mask
     const int wide = vdscfg::geti(vdscfg::ATTN_FWD_WIDE);
-    if (p.kv_pad_ones == 1 && p.hd == 72 && (attn_variant() & 4) && (wide == 1 || (wide == 2 && p.Lq >= 2048))) {
-      p.n_rt = cdiv(p.Lq, 256);
-      p.tail_last = tail_last_for(p.Lq, 256);
-      const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
-      const double fl = 4.0 * p.B * p.H * p.hd * fm_pairs_q(p.Lq, p.fc_lead, p.fm_G, 256, W);
-      vdsprof::Scope ps(VDS_PROF_ATTN_FWD, s, fl, 2.0 * p.B * p.H * p.hd * (2.0 * p.Lq + 2.0 * p.Lk));
-      hipLaunchKernelGGL((attn_fwd16_kernel<HDP, false, false, false, true, WIN>), dim3(grid), dim3(256), LDS, s, p);
-      return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
+    fwd16 = p.kv_pad_ones == 1 && p.hd == 72 && (attn_variant() & 4) && (wide == 1 || (wide == 2 && p.Lq >= 2048));
+  }
+  const int tile = fwd16 ? 256 : 128;
+  const unsigned grid = tile_grid(p, p.Lq, tile);
+  const double fl = 4.0 * p.B * p.H * p.hd * fm_pairs_q(p.Lq, p.fc_lead, p.fm_G, tile, W);
+  vdsprof::Scope ps(fwd16 ? VDS_PROF_ATTN_FWD : VDS_PROF_ATTN_FWD_PLAIN, s, fl, 2.0 * p.B * p.H * p.hd * (2.0 * p.Lq + 2.0 * p.Lk));
+  if constexpr (HDP == 96 && HDQ == 80) {
+    if (fwd16) {
+      launch<attn_fwd16_kernel<HDP, false, false, false, true, WIN>, LDS>(grid, s, p);
+      return launched();
     }
   }
-  p.n_rt = cdiv(p.Lq, 128);
-  p.tail_last = tail_last_for(p.Lq, 128);
-  const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
-  const double fl = 4.0 * p.B * p.H * p.hd * fm_pairs_q(p.Lq, p.fc_lead, p.fm_G, 128, W);
-  vdsprof::Scope ps(VDS_PROF_ATTN_FWD_PLAIN, s, fl, 2.0 * p.B * p.H * p.hd * (2.0 * p.Lq + 2.0 * p.Lk));
-  hipLaunchKernelGGL((attn_fwd_kernel<HDP, HDQ, 2, true, false, false, false, true, WIN>), dim3(grid), dim3(256), LDS, s, p);
-  return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
+  launch<attn_fwd_kernel<HDP, HDQ, 2, true, false, false, false, true, WIN>, LDS>(grid, s, p);
+  return launched();
 }
 
-template <int HDP, int HDQ, bool WIN = false>
+template <int HDP, int HDQ, Mask M>
 int run_bwd_fm(AttnP p, hipStream_t s) {
-  const int W = WIN ? p.fc_past : 0;
+  constexpr bool WIN = FLAGS<M>.win;
   constexpr int LDS_DQ = 4 * 64 * HDP * 2;
   constexpr int LDS_DKV = 4 * 64 * HDP * 2 + 2 * 128 * 4;
-  static bool once = false;
-  if (!once) {
-    set_lds(attn_bwd_dq_kernel<HDP, HDQ, false, false, false, true, WIN>, LDS_DQ);
-    set_lds(attn_bwd_dkv_kernel<HDP, HDQ, false, false, false, true, WIN>, LDS_DKV);
-    if constexpr (HDP == 96 && HDQ == 80) {
-      set_lds(attn_bwd_dkv16_kernel<HDP, true, false, false, true, WIN>, LDS_DKV);
-      set_lds(attn_bwd_dq16_kernel<HDP, false, false, false, true, WIN>, LDS_DQ);
-      set_lds(attn_bwd_dq16_kernel<HDP, true, false, false, true, WIN>, LDS_DQ);
-    }
-    once = true;
-  }
-  const long rows = (long)p.B * p.H * p.Lq;
+  const int W = WIN ? p.fc_past : 0;
   const double per = 2.0 * p.B * p.H * p.hd;  // FLOPs of one product per (query, key) pair
   const double qb = 2.0 * p.B * p.H * p.hd * (double)p.Lq, kb = qb;
   // the ones layout at head dim 72: the 16x16x32 kernels under the variant bits of their CAUSAL siblings (bit 0 dK/dV, bit 1
@@ -2933,201 +2773,187 @@ int run_bwd_fm(AttnP p, hipStream_t s) {
   const bool dq16 = ones && (attn_variant() & 2), dkv16 = ones && (attn_variant() & 1);
   const bool fold = dq16 && vdscfg::geti(vdscfg::ATTN_DELTA_FOLD);
   auto launch_dq = [&]() {
-    p.n_rt = cdiv(p.Lq, 128);
-    p.tail_last = tail_last_for(p.Lq, 128);
-    const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
+    const unsigned grid = tile_grid(p, p.Lq, 128);
     vdsprof::Scope ps(ones ? VDS_PROF_ATTN_BWD_DQ : VDS_PROF_ATTN_BWD_DQ_PLAIN, s,
                       2.0 * per * fm_pairs_q(p.Lq, p.fc_lead, p.fm_G, 128, W), (fold ? 4.0 : 3.0) * qb + 2.0 * kb);
     if constexpr (HDP == 96 && HDQ == 80) {
-      if (fold) {
-        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, true, false, false, true, WIN>), dim3(grid), dim3(256), LDS_DQ, s, p);
-        return;
-      }
-      if (dq16) {
-        hipLaunchKernelGGL((attn_bwd_dq16_kernel<HDP, false, false, false, true, WIN>), dim3(grid), dim3(256), LDS_DQ, s, p);
-        return;
-      }
+      if (fold) launch<attn_bwd_dq16_kernel<HDP, true, false, false, true, WIN>, LDS_DQ>(grid, s, p);
+      else if (dq16) launch<attn_bwd_dq16_kernel<HDP, false, false, false, true, WIN>, LDS_DQ>(grid, s, p);
     }
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, HDQ, false, false, false, true, WIN>), dim3(grid), dim3(256), LDS_DQ, s, p);
+    if (!dq16) launch<attn_bwd_dq_kernel<HDP, HDQ, false, false, false, true, WIN>, LDS_DQ>(grid, s, p);
   };
   if (fold) launch_dq();
-  else {
-    vdsprof::Scope ps(VDS_PROF_ATTN_BWD_DELTA, s, 2.0 * rows * p.hd, 2.0 * qb);
-    const bool tokmajor = p.o_sh == p.hd && p.do_sh == p.hd && p.o_sl == (long)p.H * p.hd && p.do_sl == p.o_sl &&
-                          (p.o_sl & 7) == 0 && (p.o_sb & 7) == 0 && (p.do_sb & 7) == 0 && p.H * p.hd <= 1536 && p.H <= 64;
-    if (tokmajor)
-      hipLaunchKernelGGL(attn_delta_tokmajor_kernel<true>, dim3((unsigned)(((long)p.B * p.Lq + 3) / 4)), dim3(256), 0, s, p);
-    else
-      hipLaunchKernelGGL(attn_delta_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, p);
-  }
-  p.n_rt = cdiv(p.Lk, 128);
-  p.tail_last = tail_last_for(p.Lk, 128);
+  else launch_delta<true>(p, s);
   {
-    const int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
+    const unsigned grid = tile_grid(p, p.Lk, 128);
     vdsprof::Scope ps(ones ? VDS_PROF_ATTN_BWD_DKV : VDS_PROF_ATTN_BWD_DKV_PLAIN, s,
                       2.0 * per * fm_pairs_k(p.Lq, p.fc_lead, p.fm_G, 128, W), 2.0 * qb + 4.0 * kb);
-    bool done = false;
     if constexpr (HDP == 96 && HDQ == 80) {
-      if (dkv16) {
-        hipLaunchKernelGGL((attn_bwd_dkv16_kernel<HDP, true, false, false, true, WIN>), dim3(grid), dim3(256), LDS_DKV, s, p);
-        done = true;
-      }
+      if (dkv16) launch<attn_bwd_dkv16_kernel<HDP, true, false, false, true, WIN>, LDS_DKV>(grid, s, p);
     }
-    if (!done) hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, HDQ, false, false, false, true, WIN>), dim3(grid), dim3(256), LDS_DKV, s, p);
+    if (!dkv16) launch<attn_bwd_dkv_kernel<HDP, HDQ, false, false, false, true, WIN>, LDS_DKV>(grid, s, p);
   }
   if (!fold) launch_dq();
-  return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
+  return launched();
 }
 
-int fm_check(const vds_attn_args* a, const vds_mod_groups* f, bool bwd) {
-  if (!f || a->Lq != a->Lk || a->kv_pad_ones == 2) return VDS_ERR_ARG;
-  if (f->lead < 0 || f->period < 1 || a->Lq < f->lead || (a->Lq - f->lead) % f->period != 0) return VDS_ERR_ARG;
-  if (a->Lq > (1 << 21)) return VDS_ERR_UNSUPPORTED;  // FmMap: the fp32 quotient is exact below 2^21 rows
-  // the token rows of o / d_o are reached through 32-bit byte offsets (tok(r) * row stride * 2): a (b, h) slice of them
-  // has to stay below 4 GiB
-  const int64_t lim = (int64_t)1 << 32;
-  if ((int64_t)a->Lq * a->o_sl * 2 >= lim || (bwd && (int64_t)a->Lq * a->do_sl * 2 >= lim)) return VDS_ERR_UNSUPPORTED;
-  return VDS_OK;
+// ---- the shared path of the 13 entry points -----------------------------------------------------------------------------
+template <Mask M, bool BWD>
+int attn_call(const vds_attn_args* a, const MaskV& m, vds_stream_t stream) {
+  if (const int e = validate(a, M, m, BWD)) return e;
+  AttnP p = to_p(a);
+  apply_mask(p, M, m);
+  hipStream_t s = (hipStream_t)stream;
+  return with_head_dim(a->head_dim, [&](auto hdp, auto hdq) {
+    constexpr int HDP = decltype(hdp)::value, HDQ = decltype(hdq)::value;
+    if constexpr (BWD && FLAGS<M>.fm) {
+      return run_bwd_fm<HDP, HDQ, M>(p, s);
+    } else if constexpr (BWD) {
+      // floats in `delta`: 2*B*H*Lq when the caller does not say (ws_floats = 0: the pre-round-4 contract, no query split)
+      const size_t ws = a->ws_floats > 0 ? (size_t)a->ws_floats : (size_t)2 * a->B * a->H * a->Lq;
+      return run_bwd<HDP, HDQ, M>(p, s, ws);
+    } else if constexpr (FLAGS<M>.fm) {
+      return run_fwd_fm<HDP, HDQ, M>(p, s);
+    } else {
+      return run_fwd<HDP, HDQ, M>(p, s);
+    }
+  });
 }
-void fm_set(AttnP& p, const vds_mod_groups* f, int chunk = 1) {
-  p.fc_lead = f->lead;
-  p.fc_period = f->period;
-  const int S = (p.Lq - f->lead) / f->period;
-  p.fm_S = S > 0 ? S : 1;  // (no token rows: every row is a lead row and the quotient is never taken)
-  // chunk >= period is one token group: G = period * S = L - lead < 2^21, whatever the chunk
-  p.fm_G = (chunk < f->period ? chunk : f->period) * p.fm_S;
-  p.fm_rev = vdscfg::geti(vdscfg::ATTN_FM_HEAVY_FIRST) ? 1 : 0;
-}
+
 }  // namespace
 
-extern "C" int vds_attn_fwd_causal_fm(const vds_attn_args* a, const vds_mod_groups* frames, vds_stream_t stream) {
-  if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse || a->Lq <= 0 || a->Lk <= 0) return VDS_ERR_ARG;
-  if (!strides_ok(a, false)) return VDS_ERR_ARG;
-  if (const int e = fm_check(a, frames, false)) return e;
-  AttnP p = to_p(a);
-  fm_set(p, frames);
-  hipStream_t s = (hipStream_t)stream;
-  switch (kernel_instance(a->head_dim)) {
-    case 32: return run_fwd_fm<32, 32>(p, s);
-    case 64: return run_fwd_fm<64, 64>(p, s);
-    case 80: return run_fwd_fm<96, 80>(p, s);
-    case 96: return run_fwd_fm<96, 96>(p, s);
-    case 128: return run_fwd_fm<128, 128>(p, s);
-    default: return VDS_ERR_UNSUPPORTED;
+// K / V of a cross-attention (token-major [B*Lk, ld] rows, head h at columns col0 + h*hd) -> head-major padded rows
+// [B,H,Lk,hdp] WITH the ones columns of the head_dim-72 kernels (K: 1.0 at hd, hd+1; V: 1.0 at hd, hd+4; zeros elsewhere
+// in the pad), so that the forward and dQ passes of the cross-attention run on the ones-column 16x16x32 kernels
+// (vds_attn_args.kv_pad_ones = 2).  One thread per 16-byte chunk of an output row.
+__global__ __launch_bounds__(256) void kv_pad_ones_kernel(const bf16_t* kv, long ld, int kcol0, int vcol0, bf16_t* kp,
+                                                          bf16_t* vp, int B, int Lk, int H, int hd, int hdp) {
+  const int cpr = hdp >> 3;  // chunks per output row
+  const long n = (long)B * H * Lk * cpr;
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= n) return;
+  const int which = blockIdx.y;  // 0 K, 1 V
+  const int c = (int)(gid % cpr);
+  const long row = gid / cpr;  // (b, h, l)
+  const int l = (int)(row % Lk);
+  const int h = (int)((row / Lk) % H);
+  const int b = (int)(row / ((long)Lk * H));
+  u32x4 w = {0u, 0u, 0u, 0u};
+  if (c * 8 < hd) {
+    w = *reinterpret_cast<const u32x4*>(kv + ((long)b * Lk + l) * ld + (which ? vcol0 : kcol0) + h * hd + c * 8);
+  } else if (c * 8 == hd) {
+    w[0] = which ? 0x00003f80u : 0x3f803f80u;  // K: 1.0 at hd, hd+1; V: 1.0 at hd ...
+    w[2] = which ? 0x00003f80u : 0u;           // ... and hd+4
   }
+  *reinterpret_cast<u32x4*>((which ? vp : kp) + row * hdp + c * 8) = w;
+}
+
+extern "C" int vds_kv_pad_ones(const void* kv, int64_t ld, int32_t k_col0, int32_t v_col0, void* kp, void* vp, int32_t B,
+                               int32_t Lk, int32_t H, int32_t hd, int32_t hdp, vds_stream_t stream) {
+  if (!kv || !kp || !vp || B <= 0 || Lk <= 0 || H <= 0 || hd <= 0) return VDS_ERR_ARG;
+  if ((hd & 7) || (hdp & 7) || hdp < hd + 8 || (ld & 7) || (k_col0 & 7) || (v_col0 & 7)) return VDS_ERR_ARG;
+  const long n = (long)B * H * Lk * (hdp >> 3);
+  hipLaunchKernelGGL(kv_pad_ones_kernel, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)kv, (long)ld, k_col0, v_col0, (bf16_t*)kp, (bf16_t*)vp, B, Lk, H, hd, hdp);
+  return launched();
+}
+
+extern "C" int vds_attn_set_variant(int32_t mask) {
+  const int prev = attn_variant();
+  if (mask < -1 || mask > 7) return VDS_ERR_ARG;
+  vdscfg::g_val[vdscfg::ATTN_MFMA16] = mask < 0 ? ATTN_VARIANT_DEFAULT : mask;  // -1: back to the default
+  return prev;
+}
+
+extern "C" size_t vds_attn_bwd_workspace_bytes(const vds_attn_args* a) {
+  if (!a || a->B <= 0 || a->H <= 0 || a->Lq <= 0) return 0;
+  size_t fl = (size_t)2 * a->B * a->H * a->Lq;
+  if (a->Lk > 0 && a->head_dim > 0 && a->kv_pad_ones != 1)  // fp32 partials of the query-split dK/dV kernel (short key sequences)
+    fl += (size_t)dkv_qsplit(a->B, a->H, a->Lq, a->Lk) * a->B * a->H * a->Lk * 2 * a->head_dim;
+  return fl * sizeof(float);
+}
+
+// ---- the 13 entry points: each its forwarding rule (include/vds.h), then one call into the shared path --------------------
+extern "C" int vds_attn_fwd(const vds_attn_args* a, vds_stream_t stream) {
+  return attn_call<Mask::NONE, false>(a, {}, stream);
+}
+
+// (non-positive Lq / Lk are VDS_ERR_ARG here as in every other entry point: validate)
+extern "C" int vds_attn_bwd(const vds_attn_args* a, vds_stream_t stream) {
+  return attn_call<Mask::NONE, true>(a, {}, stream);
+}
+
+// per-sample key counts (kv_lens == NULL: the calls above, unchanged)
+extern "C" int vds_attn_fwd_kvlen(const vds_attn_args* a, const int32_t* kv_lens, vds_stream_t stream) {
+  if (!kv_lens) return vds_attn_fwd(a, stream);
+  return attn_call<Mask::KVLEN, false>(a, {kv_lens}, stream);
+}
+
+extern "C" int vds_attn_bwd_kvlen(const vds_attn_args* a, const int32_t* kv_lens, vds_stream_t stream) {
+  if (!kv_lens) return vds_attn_bwd(a, stream);
+  return attn_call<Mask::KVLEN, true>(a, {kv_lens}, stream);
+}
+
+// frame-causal self-attention (frames == NULL: the plain calls, unchanged)
+extern "C" int vds_attn_fwd_causal(const vds_attn_args* a, const vds_mod_groups* frames, vds_stream_t stream) {
+  if (!frames) return vds_attn_fwd(a, stream);
+  return attn_call<Mask::CAUSAL, false>(a, {nullptr, frames}, stream);
+}
+
+extern "C" int vds_attn_bwd_causal(const vds_attn_args* a, const vds_mod_groups* frames, vds_stream_t stream) {
+  if (!frames) return vds_attn_bwd(a, stream);
+  return attn_call<Mask::CAUSAL, true>(a, {nullptr, frames}, stream);
+}
+
+// frame-causal forward with a past (the cached rollout): the queries are the Lq rows of one call, the keys
+// [lead rows | past cached rows | the call's own token rows]; see fc_past_row for the mask.  past == 0: the call above.
+extern "C" int vds_attn_fwd_causal_past(const vds_attn_args* a, const vds_mod_groups* frames, int32_t past,
+                                        vds_stream_t stream) {
+  if (past < 0) return VDS_ERR_ARG;
+  if (past == 0) return vds_attn_fwd_causal(a, frames, stream);
+  return attn_call<Mask::PAST, false>(a, {nullptr, frames, past}, stream);
+}
+
+// frame-major self-attention (frames == NULL is refused: validate)
+extern "C" int vds_attn_fwd_causal_fm(const vds_attn_args* a, const vds_mod_groups* frames, vds_stream_t stream) {
+  return attn_call<Mask::FM, false>(a, {nullptr, frames}, stream);
 }
 
 extern "C" int vds_attn_bwd_causal_fm(const vds_attn_args* a, const vds_mod_groups* frames, vds_stream_t stream) {
-  if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse || !a->d_o || !a->dq || !a->dk || !a->dv || !a->delta || a->Lq <= 0 ||
-      a->Lk <= 0)
-    return VDS_ERR_ARG;
-  if (!strides_ok(a, true)) return VDS_ERR_ARG;
-  if (const int e = fm_check(a, frames, true)) return e;
-  AttnP p = to_p(a);
-  fm_set(p, frames);
-  hipStream_t s = (hipStream_t)stream;
-  switch (kernel_instance(a->head_dim)) {
-    case 32: return run_bwd_fm<32, 32>(p, s);
-    case 64: return run_bwd_fm<64, 64>(p, s);
-    case 80: return run_bwd_fm<96, 80>(p, s);
-    case 96: return run_bwd_fm<96, 96>(p, s);
-    case 128: return run_bwd_fm<128, 128>(p, s);
-    default: return VDS_ERR_UNSUPPORTED;
-  }
+  return attn_call<Mask::FM, true>(a, {nullptr, frames}, stream);
 }
 
-// ---- chunk-causal frame-major self-attention (include/vds.h) ---------------------------------------------------------
-// The FM instances above with fm_G = chunk * S: no kernel of its own.  chunk == 1 IS the _fm entry point.
+// chunk-causal: the FM instances with fm_G = chunk * S, no kernel of its own.  chunk == 1 IS the _fm entry point.
 extern "C" int vds_attn_fwd_causal_fm_chunk(const vds_attn_args* a, const vds_mod_groups* frames, int32_t chunk,
                                             vds_stream_t stream) {
-  if (!frames || chunk < 1) return VDS_ERR_ARG;
+  if (chunk < 1) return VDS_ERR_ARG;
   if (chunk == 1) return vds_attn_fwd_causal_fm(a, frames, stream);
-  if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse || a->Lq <= 0 || a->Lk <= 0) return VDS_ERR_ARG;
-  if (!strides_ok(a, false)) return VDS_ERR_ARG;
-  if (const int e = fm_check(a, frames, false)) return e;
-  AttnP p = to_p(a);
-  fm_set(p, frames, chunk);
-  hipStream_t s = (hipStream_t)stream;
-  switch (kernel_instance(a->head_dim)) {
-    case 32: return run_fwd_fm<32, 32>(p, s);
-    case 64: return run_fwd_fm<64, 64>(p, s);
-    case 80: return run_fwd_fm<96, 80>(p, s);
-    case 96: return run_fwd_fm<96, 96>(p, s);
-    case 128: return run_fwd_fm<128, 128>(p, s);
-    default: return VDS_ERR_UNSUPPORTED;
-  }
+  return attn_call<Mask::FM, false>(a, {nullptr, frames, 0, chunk}, stream);
 }
 
 extern "C" int vds_attn_bwd_causal_fm_chunk(const vds_attn_args* a, const vds_mod_groups* frames, int32_t chunk,
                                             vds_stream_t stream) {
-  if (!frames || chunk < 1) return VDS_ERR_ARG;
+  if (chunk < 1) return VDS_ERR_ARG;
   if (chunk == 1) return vds_attn_bwd_causal_fm(a, frames, stream);
-  if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse || !a->d_o || !a->dq || !a->dk || !a->dv || !a->delta || a->Lq <= 0 ||
-      a->Lk <= 0)
-    return VDS_ERR_ARG;
-  if (!strides_ok(a, true)) return VDS_ERR_ARG;
-  if (const int e = fm_check(a, frames, true)) return e;
-  AttnP p = to_p(a);
-  fm_set(p, frames, chunk);
-  hipStream_t s = (hipStream_t)stream;
-  switch (kernel_instance(a->head_dim)) {
-    case 32: return run_bwd_fm<32, 32>(p, s);
-    case 64: return run_bwd_fm<64, 64>(p, s);
-    case 80: return run_bwd_fm<96, 80>(p, s);
-    case 96: return run_bwd_fm<96, 96>(p, s);
-    case 128: return run_bwd_fm<128, 128>(p, s);
-    default: return VDS_ERR_UNSUPPORTED;
-  }
+  return attn_call<Mask::FM, true>(a, {nullptr, frames, 0, chunk}, stream);
 }
 
-// ---- sliding-window chunk-causal frame-major self-attention (include/vds.h) -------------------------------------------
-// The WIN instances of the FM kernels: a token query of chunk n attends the lead keys and the token keys of chunks
-// max(0, n - window_chunks + 1) .. n.  A window that covers every chunk IS the _fm_chunk entry point.
-namespace {
-// chunks of the sequence: ceil(period / chunk)
-int fm_chunks(const vds_mod_groups* f, int chunk) { return (f->period + chunk - 1) / chunk; }
-}  // namespace
+// sliding window: a token query of chunk n attends the lead keys and the token keys of chunks max(0, n - window_chunks + 1)
+// .. n.  A window that covers every chunk -- ceil(period / chunk) of them -- IS the _fm_chunk entry point.
+static bool window_covers(const vds_mod_groups* f, int32_t chunk, int32_t window_chunks) {
+  return f->period < 1 || window_chunks >= (f->period + chunk - 1) / chunk;
+}
 
 extern "C" int vds_attn_fwd_causal_fm_window(const vds_attn_args* a, const vds_mod_groups* frames, int32_t chunk,
                                              int32_t window_chunks, vds_stream_t stream) {
   if (!frames || chunk < 1 || window_chunks < 1) return VDS_ERR_ARG;
-  if (frames->period < 1 || window_chunks >= fm_chunks(frames, chunk)) return vds_attn_fwd_causal_fm_chunk(a, frames, chunk, stream);
-  if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse || a->Lq <= 0 || a->Lk <= 0) return VDS_ERR_ARG;
-  if (!strides_ok(a, false)) return VDS_ERR_ARG;
-  if (const int e = fm_check(a, frames, false)) return e;
-  AttnP p = to_p(a);
-  fm_set(p, frames, chunk);
-  p.fc_past = window_chunks;  // (< the chunk count <= period: W * G stays below L)
-  hipStream_t s = (hipStream_t)stream;
-  switch (kernel_instance(a->head_dim)) {
-    case 32: return run_fwd_fm<32, 32, true>(p, s);
-    case 64: return run_fwd_fm<64, 64, true>(p, s);
-    case 80: return run_fwd_fm<96, 80, true>(p, s);
-    case 96: return run_fwd_fm<96, 96, true>(p, s);
-    case 128: return run_fwd_fm<128, 128, true>(p, s);
-    default: return VDS_ERR_UNSUPPORTED;
-  }
+  if (window_covers(frames, chunk, window_chunks)) return vds_attn_fwd_causal_fm_chunk(a, frames, chunk, stream);
+  return attn_call<Mask::FM_WIN, false>(a, {nullptr, frames, 0, chunk, window_chunks}, stream);
 }
 
 extern "C" int vds_attn_bwd_causal_fm_window(const vds_attn_args* a, const vds_mod_groups* frames, int32_t chunk,
                                              int32_t window_chunks, vds_stream_t stream) {
   if (!frames || chunk < 1 || window_chunks < 1) return VDS_ERR_ARG;
-  if (frames->period < 1 || window_chunks >= fm_chunks(frames, chunk)) return vds_attn_bwd_causal_fm_chunk(a, frames, chunk, stream);
-  if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse || !a->d_o || !a->dq || !a->dk || !a->dv || !a->delta || a->Lq <= 0 ||
-      a->Lk <= 0)
-    return VDS_ERR_ARG;
-  if (!strides_ok(a, true)) return VDS_ERR_ARG;
-  if (const int e = fm_check(a, frames, true)) return e;
-  AttnP p = to_p(a);
-  fm_set(p, frames, chunk);
-  p.fc_past = window_chunks;
-  hipStream_t s = (hipStream_t)stream;
-  switch (kernel_instance(a->head_dim)) {
-    case 32: return run_bwd_fm<32, 32, true>(p, s);
-    case 64: return run_bwd_fm<64, 64, true>(p, s);
-    case 80: return run_bwd_fm<96, 80, true>(p, s);
-    case 96: return run_bwd_fm<96, 96, true>(p, s);
-    case 128: return run_bwd_fm<128, 128, true>(p, s);
-    default: return VDS_ERR_UNSUPPORTED;
-  }
+  if (window_covers(frames, chunk, window_chunks)) return vds_attn_bwd_causal_fm_chunk(a, frames, chunk, stream);
+  return attn_call<Mask::FM_WIN, true>(a, {nullptr, frames, 0, chunk, window_chunks}, stream);
 }

@@ -300,6 +300,57 @@ def _frame_major(frame_major, frames, kv_lens, past=0, chunk=1, window=None) -> 
     return True
 
 
+def _attn_args(q, k, v, o, lse, kv_pad_ones, grads=None, delta=None) -> AttnArgs:
+    """vds_attn_args of a call.  Forward: shapes, q / k / v / o with their strides, lse; the backward adds
+    grads = (do, dq, dk, dv) with theirs and the delta workspace with its size"""
+    a = AttnArgs()
+    a.B, a.H, a.Lq, a.head_dim = q.shape
+    a.Lk = k.shape[2]
+    tensors = {"q": q, "k": k, "v": v, "o": o}
+    if grads is not None:
+        tensors.update(zip(("do", "dq", "dk", "dv"), grads))
+    for name, t in tensors.items():
+        setattr(a, "d_o" if name == "do" else name, _p(t))
+        for ax, stride in zip(("_sb", "_sh", "_sl"), _st(t)):
+            setattr(a, name + ax, stride)
+    a.lse = _p(lse)
+    a.kv_pad_ones = int(kv_pad_ones)  # (True = 1: self-attention layout; 2: ones in k / v only, cross-attention)
+    if grads is not None:
+        a.delta, a.ws_floats = _p(delta), delta.numel()
+    return a
+
+
+def _attn_entry(direction: str, a: AttnArgs, kv_lens, frames, fr, past: int, fmaj: bool, chunk: int, window):
+    """(C entry point, its arguments after vds_attn_args, the text of its error message): the one place that maps
+    (direction, kv_lens, frames, past, frame_major, chunk, window) to one of the 13 calls.  Without a flag every call is the
+    entry point it always was; fr is the vds_mod_groups of frames (_frames)"""
+    B, H, Lq, Lk, hd = a.B, a.H, a.Lq, a.Lk, a.head_dim
+    cross = f"B={B},H={H},Lq={Lq},Lk={Lk},hd={hd}"
+    self_ = f"B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)}" if fr is not None else None
+    if fmaj and window is not None:
+        name, extra, what = "_causal_fm_window", (fr, chunk, window), f"{self_},chunk={chunk},window={window}"
+    elif fmaj and chunk != 1:
+        name, extra, what = "_causal_fm_chunk", (fr, chunk), f"{self_},chunk={chunk}"
+    elif fmaj:
+        name, extra, what = "_causal_fm", (fr,), self_
+    elif fr is not None and past:
+        name, extra, what = "_causal_past", (fr, past), f"{cross},frames={tuple(frames)},past={past}"
+    elif fr is not None:
+        name, extra, what = "_causal", (fr,), self_
+    elif kv_lens is None:
+        name, extra, what = "", (), cross
+    else:
+        name, extra, what = "_kvlen", (_kv_lens_ptr(kv_lens, B),), cross
+    name = f"vds_attn_{direction}{name}"
+    return name, extra, f"{name}({what})"
+
+
+def _attn_call(direction: str, a: AttnArgs, kv_lens, frames, fr, past, fmaj, chunk, window):
+    lib = _lib.load()
+    name, extra, what = _attn_entry(direction, a, kv_lens, frames, fr, past, fmaj, chunk, window)
+    check(getattr(lib, name)(C.byref(a), *extra, _stream()), what)
+
+
 def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=None, past: int = 0,
              frame_major: bool = False, chunk: int = 1, window=None):
     """q [B,H,Lq,hd], k/v [B,H,Lk,hd], o [B,H,Lq,hd] strided views (last dim contiguous); lse f32 [B,H,Lq].
@@ -322,35 +373,8 @@ def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=No
     if past < 0 or (past and frames is None):
         raise ValueError(f"attention: past = {past} must be >= 0 and needs frames=(lead, period)")
     fr = _frames(frames, kv_lens, Lq, Lk, past) if frames is not None else None
-    a = AttnArgs()
-    a.B, a.H, a.Lq, a.Lk, a.head_dim = B, H, Lq, Lk, hd
-    a.q, (a.q_sb, a.q_sh, a.q_sl) = _p(q), _st(q)
-    a.k, (a.k_sb, a.k_sh, a.k_sl) = _p(k), _st(k)
-    a.v, (a.v_sb, a.v_sh, a.v_sl) = _p(v), _st(v)
-    a.o, (a.o_sb, a.o_sh, a.o_sl) = _p(o), _st(o)
-    a.lse = _p(lse)
-    a.kv_pad_ones = int(kv_pad_ones)  # (True = 1: self-attention layout; 2: ones in k / v only, cross-attention)
-    if fmaj and window is not None:
-        check(_lib.load().vds_attn_fwd_causal_fm_window(C.byref(a), fr, chunk, window, _stream()),
-              f"vds_attn_fwd_causal_fm_window(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)},chunk={chunk},"
-              f"window={window})")
-    elif fmaj and chunk != 1:
-        check(_lib.load().vds_attn_fwd_causal_fm_chunk(C.byref(a), fr, chunk, _stream()),
-              f"vds_attn_fwd_causal_fm_chunk(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)},chunk={chunk})")
-    elif fmaj:
-        check(_lib.load().vds_attn_fwd_causal_fm(C.byref(a), fr, _stream()),
-              f"vds_attn_fwd_causal_fm(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)})")
-    elif fr is not None and past:
-        check(_lib.load().vds_attn_fwd_causal_past(C.byref(a), fr, past, _stream()),
-              f"vds_attn_fwd_causal_past(B={B},H={H},Lq={Lq},Lk={Lk},hd={hd},frames={tuple(frames)},past={past})")
-    elif fr is not None:
-        check(_lib.load().vds_attn_fwd_causal(C.byref(a), fr, _stream()),
-              f"vds_attn_fwd_causal(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)})")
-    elif kv_lens is None:
-        check(_lib.load().vds_attn_fwd(C.byref(a), _stream()), f"vds_attn_fwd(B={B},H={H},Lq={Lq},Lk={Lk},hd={hd})")
-    else:
-        check(_lib.load().vds_attn_fwd_kvlen(C.byref(a), _kv_lens_ptr(kv_lens, B), _stream()),
-              f"vds_attn_fwd_kvlen(B={B},H={H},Lq={Lq},Lk={Lk},hd={hd})")
+    a = _attn_args(q, k, v, o, lse, kv_pad_ones)
+    _attn_call("fwd", a, kv_lens, frames, fr, past, fmaj, chunk, window)
 
 
 def kv_pad_ones(kv: torch.Tensor, B: int, Lk: int, H: int, hd: int, hdp: int, k_col0: int, v_col0: int):
@@ -386,42 +410,11 @@ def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = Fa
     Lk = k.shape[2]
     fmaj = _frame_major(frame_major, frames, kv_lens, 0, chunk, window)
     fr = _frames(frames, kv_lens, Lq, Lk) if frames is not None else None
-    a = AttnArgs()
-    a.B, a.H, a.Lq, a.Lk, a.head_dim = B, H, Lq, Lk, hd
-    a.kv_pad_ones = int(kv_pad_ones)
     if delta is None:
-        delta = torch.empty(_lib.load().vds_attn_bwd_workspace_bytes(C.byref(a)) // 4, dtype=f32, device=q.device)
+        delta = torch.empty(attn_bwd_workspace_floats(B, H, Lq, Lk, hd, kv_pad_ones), dtype=f32, device=q.device)
     assert delta.numel() >= 2 * B * H * Lq and delta.is_contiguous(), "attn_bwd: delta workspace is [2,B,H,Lq] f32"
-    a.ws_floats = delta.numel()
-    a.q, (a.q_sb, a.q_sh, a.q_sl) = _p(q), _st(q)
-    a.k, (a.k_sb, a.k_sh, a.k_sl) = _p(k), _st(k)
-    a.v, (a.v_sb, a.v_sh, a.v_sl) = _p(v), _st(v)
-    a.o, (a.o_sb, a.o_sh, a.o_sl) = _p(o), _st(o)
-    a.lse = _p(lse)
-    a.d_o, (a.do_sb, a.do_sh, a.do_sl) = _p(do), _st(do)
-    a.dq, (a.dq_sb, a.dq_sh, a.dq_sl) = _p(dq), _st(dq)
-    a.dk, (a.dk_sb, a.dk_sh, a.dk_sl) = _p(dk), _st(dk)
-    a.dv, (a.dv_sb, a.dv_sh, a.dv_sl) = _p(dv), _st(dv)
-    a.delta = _p(delta)
-    a.kv_pad_ones = int(kv_pad_ones)
-    if fmaj and window is not None:
-        check(_lib.load().vds_attn_bwd_causal_fm_window(C.byref(a), fr, chunk, window, _stream()),
-              f"vds_attn_bwd_causal_fm_window(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)},chunk={chunk},"
-              f"window={window})")
-    elif fmaj and chunk != 1:
-        check(_lib.load().vds_attn_bwd_causal_fm_chunk(C.byref(a), fr, chunk, _stream()),
-              f"vds_attn_bwd_causal_fm_chunk(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)},chunk={chunk})")
-    elif fmaj:
-        check(_lib.load().vds_attn_bwd_causal_fm(C.byref(a), fr, _stream()),
-              f"vds_attn_bwd_causal_fm(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)})")
-    elif fr is not None:
-        check(_lib.load().vds_attn_bwd_causal(C.byref(a), fr, _stream()),
-              f"vds_attn_bwd_causal(B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)})")
-    elif kv_lens is None:
-        check(_lib.load().vds_attn_bwd(C.byref(a), _stream()), f"vds_attn_bwd(B={B},H={H},Lq={Lq},Lk={Lk},hd={hd})")
-    else:
-        check(_lib.load().vds_attn_bwd_kvlen(C.byref(a), _kv_lens_ptr(kv_lens, B), _stream()),
-              f"vds_attn_bwd_kvlen(B={B},H={H},Lq={Lq},Lk={Lk},hd={hd})")
+    a = _attn_args(q, k, v, o, lse, kv_pad_ones, (do, dq, dk, dv), delta)
+    _attn_call("bwd", a, kv_lens, frames, fr, 0, fmaj, chunk, window)
 
 
 # ---------------------------------------------------------------------- fp8 attention ----
