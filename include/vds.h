@@ -112,13 +112,18 @@ int vds_set_deterministic(int32_t on, void* workspace, size_t workspace_bytes);
  * be e4m3fn), K, lda, ldb multiples of 16.  C = epilogue((sum_k A B) * *scale_a * *scale_b) with per-tensor
  * dequantisation factors read from device memory (NULL = 1).  Runs v_mfma_f32_16x16x128_f8f6f4 (2x the bf16
  * MFMA rate).  Input gradients are NT products with the transposed WEIGHT copy written by vds_quant_fp8.
+ * The epilogues, their single-output forms (C == NULL with C2 != NULL: VDS_EPI_BIAS_GELU, VDS_EPI_GATE_RES) and the
+ * requirements on ldc / ldc2 / ldaux / ldgate are those of vds_gemm_bf16: a leading dimension that breaks the epilogues'
+ * 16-byte row segments (ldc % 8, ldc % 4 for the fp32 C of VDS_EPI_F32, ldc2 % 8, ldaux % 8, ldgate % 4, each for the
+ * pointers the call uses) is VDS_ERR_ARG, and so is VDS_EPI_GATE_RES without C2.
  * layout VDS_TN (round 4; epilogue VDS_EPI_F32, a_fmt = 1 only): C[M,N] = sum_k A[k,m] B[k,n] with A [K,M] e5m2 and
  * B [K,N] e4m3, both row-major, K, M, lda, ldb multiples of 16 -- the weight gradient dW = dy^T x contracted straight
  * from the token-major fp8 copies (both operands k-major: ds_read_b64_tr_b8 fragments), split_k as vds_gemm_bf16.
  *
  * emit (may be NULL; VDS_EPI_BIAS_GELU / VDS_EPI_DGELU only): the epilogue also writes its result -- gelu(pre) resp.
  * acc * gelu'(aux), rounded to bf16 first -- as fp8 for the next GEMMs, so that no separate quantisation pass reads
- * it back: q[M,N] row-major and / or qt[N,M] transposed, scaled by fmax / *amax_in (delayed scaling: the caller
+ * it back (bit-identical to vds_quant_fp8 of the bf16 result for finite results; any M, the last M % 4 columns of qt
+ * written byte by byte): q[M,N] row-major and / or qt[N,M] transposed, scaled by fmax / *amax_in (delayed scaling: the caller
  * passes the amax recorded by the previous step), *dq_out = *amax_in / fmax, *amax_out = max(*amax_out, max |result|)
  * of this launch, colsum[n] += sum_m result[m,n] (bias gradient).  With emit, C2 (BIAS_GELU) / C (DGELU) may be NULL. */
 typedef struct vds_fp8_out {
@@ -141,11 +146,15 @@ int vds_absmax(const void* x, int64_t ldx, int32_t M, int32_t K, float* amax, vd
  * fmt 1: e5m2, fmax 57344), written row-major to q[M,K] (ldq, may be NULL) and / or transposed to qt[K,M] (ldt,
  * may be NULL); *dq_out = *amax / fmax is the factor vds_gemm_fp8 multiplies back in.  *amax == 0 -> scale 1.
  * amax_out (may be NULL): *amax_out = max(*amax_out, max |x|) -- with delayed scaling `amax` is the value a previous
- * step recorded and this call records the next one, so that no separate vds_absmax pass reads x. */
+ * step recorded and this call records the next one, so that no separate vds_absmax pass reads x.
+ * Any M >= 1 is served (K % 8 == 0, ldx % 8 == 0, ldq % 8 == 0, ldt % 4 == 0): the transposed copy is written four
+ * rows of x per store, and the last M % 4 of them byte by byte.  The cast is ONE fp32 multiply by fmax / *amax, a clamp to
+ * +-fmax and a round-to-nearest-even conversion (subnormals kept, -0 kept); tests/helpers/fp8_census.py restates it. */
 int vds_quant_fp8(const void* x, int64_t ldx, int32_t M, int32_t K, int32_t fmt, const float* amax, void* q,
                   int64_t ldq, void* qt, int64_t ldt, float* dq_out, float* amax_out, vds_stream_t stream);
 
-/* qt[k,m] = q[m,k] for a one-byte-per-element matrix q[M,K] (row stride ldq; K, ldq multiples of 16, ldt of 4): the
+/* qt[k,m] = q[m,k] for a one-byte-per-element matrix q[M,K] (row stride ldq; K, ldq multiples of 16, ldt of 4; any
+ * M >= 1, the last M % 4 columns of qt written byte by byte): the
  * k-contiguous copy of an fp8 operand whose row-major copy came straight out of its producer (the *_fp8 entry points
  * below).  1 B read + 1 B written per element against 2 + 1 + 1 of a vds_quant_fp8 pass over the bf16 tensor. */
 int vds_transpose_fp8(const void* q, int64_t ldq, int32_t M, int32_t K, void* qt, int64_t ldt, vds_stream_t stream);
@@ -153,10 +162,12 @@ int vds_transpose_fp8(const void* q, int64_t ldq, int32_t M, int32_t K, void* qt
 /* fp8-emitting forms of three producers of the fp8 GEMMs' operands (config 5): the bf16 result of the plain entry
  * point is not written; instead each value, rounded to bf16 first, is scaled by fmax / *amax_in (delayed scaling:
  * the amax the previous step recorded; 0 -> scale 1) and cast with saturation to q[rows, ldq] (fmt 0 = e4m3fn,
- * 1 = e5m2; ldq a multiple of 8) -- bit-identical to vds_quant_fp8 of the plain result.  *dq_out = *amax_in / fmax
+ * 1 = e5m2; ldq a multiple of 8) -- bit-identical to vds_quant_fp8 of the plain result for finite results (what a
+ * NaN or an infinity becomes, and what amax it records, differs from site to site: DESIGN.md 25).  *dq_out = *amax_in / fmax
  * (may be NULL).  max |result| is recorded per wave with plain stores (amax_part, f32 [B*L], may be NULL): entry w
- * receives the maximum over the rows wave w handled -- one entry per row / token for the RMSNorm and RoPE kernels, the
- * first 4 * (number of workgroups) entries for gate backward -- and the tensor's amax is the maximum over the array
+ * receives the maximum over the rows wave w handled -- one entry per row / token for the RMSNorm and RoPE kernels (one per
+ * four rows, at the first of them, for RMSNorm at D = 384 / 768 / 1152), the entry of the first row a wave walks for gate
+ * backward; the other entries are not written -- and the tensor's amax is the maximum over the array
  * (the caller zeroes it before the launch and reduces it afterwards; no atomics: ~10^5 short waves per launch).  All other arguments as in
  * vds_rmsnorm_mod_fwd / vds_gate_bwd / vds_qkv_rope_bwd (the latter needs hdp % 8 == 0 and H*hd <= 2048, else
  * VDS_ERR_UNSUPPORTED). */

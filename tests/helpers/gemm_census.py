@@ -124,6 +124,9 @@ def _seed(layout, M, N, K, salt=0):
     return (("NT", "NN", "TN").index(layout) * 1000003 + M * 7919 + N * 104729 + K * 1299709 + salt) % (2 ** 31 - 1)
 
 
+gen, seed_of = _gen, _seed   # the public names (fp8_census.py builds its cases on the same seeds)
+
+
 def ints(shape, lo, hi, seed, dtype=f64):
     return torch.randint(lo, hi + 1, tuple(shape), generator=_gen(seed)).to(dtype)
 

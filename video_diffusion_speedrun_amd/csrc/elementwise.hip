@@ -402,8 +402,10 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const bf16_t* dxn, long l
   }
   float gt[NC][8], a_g[NC][8], a_b[NC][8];
   QState<(QF < 0 ? 0 : QF)> qs;
+  // amax_part entry of a wave: the first row it walks (distinct per wave and below B * L, whatever rows_per_block is;
+  // numbering the waves of the grid instead runs past a [B * L] array when L < 4 or ew_min_rows < 4)
   if constexpr (QF >= 0)
-    qs.init(qo, blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0, ((long)blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave);
+    qs.init(qo, blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0, (long)b * L + l0 + wave);
 #pragma unroll
   for (int i = 0; i < NC; ++i) {
     const int c = lane + 64 * i;
@@ -433,7 +435,9 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const bf16_t* dxn, long l
       }
     }
   }
-  if constexpr (QF >= 0) qs.finish();
+  if constexpr (QF >= 0) {
+    if (l0 + wave < l1) qs.finish();  // (wave-uniform; a wave without rows has no entry)
+  }
   for (int pass = 0; pass < 2; ++pass) {
     if (pass == 1 && !dbias) break;
     __syncthreads();

@@ -1693,6 +1693,14 @@ extern "C" int vds_gemm_fp8(const vds_gemm_args* a, const float* scale_a, const 
   if ((a->N & 7) || (a->K & 15) || (a->lda & 15) || (a->ldb & 15)) return VDS_ERR_ARG;
   const bool tn = a->layout == VDS_TN;  // C[M,N] = sum_k A[k,m] B[k,n]: both operands [K, .] row-major (token-major)
   if (tn && (a->epilogue != VDS_EPI_F32 || a_fmt != 1 || emit || (a->M & 15))) return VDS_ERR_UNSUPPORTED;
+  // the same epilogues as the bf16 GEMM: 16-byte row segments at row * ld + column (see gemm_bf16_impl)
+  {
+    const int e = a->epilogue;
+    if (a->C && (a->ldc & (e == VDS_EPI_F32 ? 3 : 7))) return VDS_ERR_ARG;
+    if ((e == VDS_EPI_BIAS_GELU || e == VDS_EPI_GATE_RES) && a->C2 && (a->ldc2 & 7)) return VDS_ERR_ARG;
+    if ((e == VDS_EPI_GATE_RES || e == VDS_EPI_DGELU) && a->aux && (a->ldaux & 7)) return VDS_ERR_ARG;
+    if (e == VDS_EPI_GATE_RES && a->gate && (a->ldgate & 3)) return VDS_ERR_ARG;
+  }
   GemmP p;
   p.M = a->M; p.N = a->N; p.K = a->K / 2;  // the kernel addresses in 2-byte units
   p.A = (const bf16_t*)a->A; p.lda = a->lda / 2;
@@ -1731,7 +1739,12 @@ extern "C" int vds_gemm_fp8(const vds_gemm_args* a, const float* scale_a, const 
     p.e_fmt = emit->fmt; p.e_colsum = emit->colsum;
   }
   if (p.atomic && a->epilogue != VDS_EPI_F32) return VDS_ERR_ARG;
-  if (!a->C && a->epilogue != VDS_EPI_GATE_RES && !(emit && a->epilogue == VDS_EPI_DGELU)) return VDS_ERR_ARG;
+  // C == NULL: the single-output forms of vds_gemm_bf16 (GATE_RES: x_new, BIAS_GELU: the activation; both need C2) and
+  // the emit-only DGELU; GATE_RES always stores C2
+  if (!a->C && !((a->epilogue == VDS_EPI_GATE_RES || a->epilogue == VDS_EPI_BIAS_GELU) && a->C2) &&
+      !(emit && a->epilogue == VDS_EPI_DGELU))
+    return VDS_ERR_ARG;
+  if (a->epilogue == VDS_EPI_GATE_RES && !a->C2) return VDS_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (tn) {
     if (vdscfg::geti(vdscfg::DETERMINISTIC) && p.split_k > 1)
