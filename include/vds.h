@@ -818,6 +818,38 @@ int vds_cross_qkv_fp8(const void* q, const void* kv, void* q8, void* k8, void* v
                       float* amax_cur, int32_t amax_stride, float* deq, int32_t B, int32_t Lq, int32_t Lk, int32_t H,
                       int32_t hd, vds_stream_t stream);
 
+/* ------------------------------------------------------- low-rank adapters (LoRA) ----
+ * The three tall-skinny products of y += s (x A^T) B^T and its backward (csrc/lowrank.hip).  Operands bf16,
+ * accumulation fp32, no atomics: results are bit-identical run to run, with or without vds_set_deterministic.
+ * r in {16, 32, 64}.  Every ld and the row widths K / N are multiples of 8 elements and every bf16 / workspace pointer
+ * is 16-byte aligned, so every access is a 16-byte row segment; ld may exceed the row width (windows of wider parents;
+ * nothing outside the window is read or written).  NULL pointers, non-positive sizes, another r or layout, a misaligned
+ * or too small ld, a misaligned pointer or a short workspace: VDS_ERR_ARG before any launch.  The launches are credited
+ * to no profiler class.
+ *
+ * u[m, j] = bf16(scale * sum_k x[m, k] w(j, k)),  x [M, K], u [M, r].
+ *   w_layout 0: w is [r, K] (the adapter's A: u = s x A^T);  1: w is [K, r] (the adapter's B, contracted over its
+ *   rows: dU = s dY B).  x is read once; w is staged in LDS in chunks of vds_lowrank_chunk(0, r) elements of K. */
+int vds_lowrank_down(const void* x, int64_t ldx, const void* w, int64_t ldw, int32_t w_layout, void* u, int64_t ldu,
+                     int32_t M, int32_t K, int32_t r, float scale, vds_stream_t stream);
+/* y[m, n] = bf16(fma(scale, sum_j u[m, j] w(n, j), float(y[m, n]))), in place: one read and one write of y [M, N].
+ *   w_layout 0: w is [N, r] (B: y += s u B^T);  1: w is [r, N] (A: dx += dU A).  A workgroup covers 128 rows and
+ *   vds_lowrank_chunk(1, r) columns. */
+int vds_lowrank_up_add(const void* u, int64_t ldu, const void* w, int64_t ldw, int32_t w_layout, void* y, int64_t ldy,
+                       int32_t M, int32_t N, int32_t r, float scale, vds_stream_t stream);
+/* g(n, j) = fma(scale, sum_m a[m, n] u[m, j], g(n, j)) in fp32,  a [M, N], u [M, r].
+ *   g_layout 0: g is [N, r] (dB from dY and U);  1: g is [r, N] (dA from x and dU); ldg its row stride in floats.
+ * The sum over m is split into chunks of VDS_LOWRANK_WGRAD_CHUNK rows, one fp32 partial [N, r] per chunk in ws
+ * (vds_lowrank_wgrad_workspace_floats(M, N, r) floats); a second kernel adds the partials in chunk order.  a is read
+ * once. */
+#define VDS_LOWRANK_WGRAD_CHUNK 2048
+int64_t vds_lowrank_wgrad_workspace_floats(int32_t M, int32_t N, int32_t r);
+int vds_lowrank_wgrad(const void* a, int64_t lda, const void* u, int64_t ldu, float* g, int64_t ldg, int32_t g_layout,
+                      int32_t M, int32_t N, int32_t r, float scale, float* ws, int64_t ws_floats, vds_stream_t stream);
+/* the chunk sizes above for rank r (0 for another r): which = 0 K chunk of down, 1 column chunk of up_add, 2 row chunk
+ * of wgrad -- what a test needs to place its shapes across the boundaries */
+int32_t vds_lowrank_chunk(int32_t which, int32_t r);
+
 /* ------------------------------------------------------------------ live profiling ----
  * Per-kernel-class timing with HIP events recorded on the launch stream around each launch of
  * an enabled class (bench.py's roofline leg).  Off by default (no events, no overhead).

@@ -212,6 +212,11 @@ SIGNATURES = {
     "vds_qkv_rope_fwd_fp8": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32,
                              c_i32, c_i32, c_i32, c_i32, c_vp],
     "vds_cross_qkv_fp8": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
+    "vds_lowrank_down": [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp],
+    "vds_lowrank_up_add": [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp],
+    "vds_lowrank_wgrad_workspace_floats": [c_i32, c_i32, c_i32],
+    "vds_lowrank_wgrad": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_i64, c_vp],
+    "vds_lowrank_chunk": [c_i32, c_i32],
     "vds_selftest_lanemaps": [c_vp, c_vp],
     "vds_prof_enable": [C.c_uint32],
     "vds_prof_collect": [c_vp],

@@ -432,6 +432,8 @@ class DiTBlock(nn.Module):
         self.adaLN_modulation[-1].weight.data.zero_()
         self.adaLN_modulation[-1].bias.data.zero_()
 
+    lora_scale: Optional[float] = None  # s = alpha / rank of the adapters DiT.add_lora put on this block's linears
+
     # ---- stand-alone call (reference signature, model.py:96-167) ---------------------------------------
     _own_group: Optional[FlatGroup] = None
 
@@ -529,6 +531,17 @@ class DiTBlock(nn.Module):
         W = lambda n: G.w(pre + n)
         Wo = lambda n: G.w(pre + n) if G.has(pre + n) else None
         dev = X.device
+        s_lora = self.lora_scale
+
+        def lora(name, x, y):
+            """y += s (x A^T) B^T, in place, when the linear `name` carries an adapter (DiT.add_lora); returns u = x A^T"""
+            if s_lora is None or not G.has(pre + name + ".lora_A"):
+                return None
+            u = ops.lowrank_down(x, W(name + ".lora_A"))
+            ops.lowrank_up_add(u, W(name + ".lora_B"), y, s_lora)
+            return u
+
+        u_qkv = u_qc = u_ckv = None
         R0 = F8.ROWS * i
         moved = bool(getattr(G, "recast", True))  # fp8: this group's weights changed outside the fused optimizer
         if mod is None:  # (DiT.forward computes the modulation of all blocks in one batched launch and passes it in)
@@ -555,6 +568,7 @@ class DiTBlock(nn.Module):
             F8.fwd(q_xn1, q_wqkv, qkv, Wo("qkv.bias"))
         else:
             qkv = ops.linear_fwd(xn1, W("qkv.weight"), Wo("qkv.bias"))
+            u_qkv = lora("qkv", xn1, qkv)
         mix = self.residual_v and v0 is not None
         kept_attn = replay is not None and getattr(replay, "attn", None) is not None
         if kept_attn:
@@ -638,7 +652,9 @@ class DiTBlock(nn.Module):
                 F8.fwd(q_ctx, q_wkv, ckv, Wo("context_kv.bias"))
             else:
                 qc = ops.linear_fwd(xn2, W("q_cross.weight"), Wo("q_cross.bias"))
+                u_qc = lora("q_cross", xn2, qc)
                 ckv = ops.linear_fwd(ctx2d, W("context_kv.weight"), Wo("context_kv.bias"))
+                u_ckv = lora("context_kv", ctx2d, ckv)
             catt = torch.empty(B * L, D, dtype=bf16, device=dev)
             lse2 = torch.empty(B, H, L, dtype=f32, device=dev)
             # fp8 cross-attention: the same kernels as the self-attention (Lk = context length), operands quantised by
@@ -723,6 +739,7 @@ class DiTBlock(nn.Module):
                 bs.v = None  # (block 0's bf16 v lives on as v_0; the backward contracts the fp8 copies)
             bs.mix, bs.has_cross = mix, has_cross
             bs.frames = frames
+            bs.u_qkv, bs.u_qc, bs.u_ckv = u_qkv, u_qc, u_ckv  # the adapters' x A^T (None without an adapter)
             if has_cross:
                 bs.xn2, bs.rstd2, bs.qc, bs.ckv, bs.catt, bs.lse2, bs.y_ca = xn2, rstd2, qc, ckv, catt, lse2, y_ca
                 bs.c8, bs.c8_on, bs.qc8, bs.kc8, bs.vc8, bs.deqc = c8, c8_on, qc8, kc8, vc8, deqc
@@ -763,7 +780,34 @@ class DiTBlock(nn.Module):
         batched_adaln = dmod is not None  # DiT.backward: the adaLN weight gradients of all blocks in one launch at the end
         # (round 5 measured the weight-gradient GEMMs on a second stream: +3.3 % slower -- two MFMA kernels with different LDS
         # footprints fragment the CUs; removed in round 6, profiles/r05/wgrad_side_stream_ab.log)
-        wgrad, wgrad8 = ops.linear_wgrad, F8.wgrad
+        # a frozen parameter (requires_grad False) gets no weight-gradient GEMM and no separate column-sum pass; a launch
+        # that also produces a data gradient stays, its parameter result is simply not published (FlatGroup.publish_grads)
+        T = lambda n: G.has(pre + n) and G.params[pre + n].requires_grad
+
+        def wgrad(dy, x, n):
+            if T(n):
+                ops.linear_wgrad(dy, x, Gr(n))
+
+        def wgrad8(qdy, qx, n):
+            if T(n):
+                F8.wgrad(qdy, qx, Gr(n))
+
+        s_lora = self.lora_scale
+
+        def lora_bwd(name, dY, x, u, dx):
+            """backward of `lora` in _fwd on dY = the gradient of the linear's output: dB = s dY^T u and dA = dU^T x with dU
+            = s dY B into the adapter's gradients, and dx += dU A (dx None: the linear's input is data)"""
+            if u is None:
+                return
+            tA, tB = T(name + ".lora_A"), T(name + ".lora_B")
+            if tB:
+                ops.lowrank_wgrad(dY, u, Gr(name + ".lora_B"), s_lora, 0)
+            if tA or dx is not None:
+                dU = ops.lowrank_down(dY, W(name + ".lora_B"), s_lora, layout=1)
+                if tA:
+                    ops.lowrank_wgrad(x, dU, Gr(name + ".lora_A"), 1.0, 1)
+                if dx is not None:
+                    ops.lowrank_up_add(dU, W(name + ".lora_A"), dx, 1.0, layout=1)
         if dmod is None:
             dmod = torch.zeros(mod.shape[0], 9 * D, dtype=f32, device=dev)
         # --- MLP
@@ -782,7 +826,7 @@ class DiTBlock(nn.Module):
         if bs.f8:
             if not pemit:
                 q_dy = F8.Q(dy, F8.E5M2, True, True, hist, F8.ROWS * i + 4)
-            wgrad8(q_dy, bs.q_hact, Gr("mlp.2.weight"))
+            wgrad8(q_dy, bs.q_hact, "mlp.2.weight")
             if emit:  # the fc2 input gradient leaves the GEMM as e5m2 (+ transposed, + bias gradient)
                 dh = None
                 q_dh = F8.dgrad_gelu_emit(q_dy, bs.q_w2, bs.hpre, hist.prev(F8.ROWS * i + 1), hist.cur(F8.ROWS * i + 1),
@@ -790,14 +834,15 @@ class DiTBlock(nn.Module):
             else:
                 dh = F8.dgrad(q_dy, bs.q_w2, pre=bs.hpre)
                 q_dh = F8.Q(dh, F8.E5M2, True, True, hist, F8.ROWS * i + 1)
-                ops.colsum(dh, Gr("mlp.0.bias"))
-            wgrad8(q_dh, bs.q_xn3, Gr("mlp.0.weight"))
+                if T("mlp.0.bias"):
+                    ops.colsum(dh, Gr("mlp.0.bias"))
+            wgrad8(q_dh, bs.q_xn3, "mlp.0.weight")
             dxn = F8.dgrad(q_dh, bs.q_w1)
             del q_dy, q_dh
         else:
-            wgrad(dy, bs.hact, Gr("mlp.2.weight"))
+            wgrad(dy, bs.hact, "mlp.2.weight")
             dh = ops.linear_dgrad(dy, W("mlp.2.weight"), pre=bs.hpre, colsum=Gr("mlp.0.bias"))  # + fc1 bias gradient
-            wgrad(dh, bs.xn3, Gr("mlp.0.weight"))
+            wgrad(dh, bs.xn3, "mlp.0.weight")
             dxn = ops.linear_dgrad(dh, W("mlp.0.weight"))
         del dh
         dX2 = _norm_bwd(groups, dxn, bs.X2, Wo("norm3.weight"), mod, 6 * D, 7 * D, bs.rstd3, dX, dmod,
@@ -813,12 +858,12 @@ class DiTBlock(nn.Module):
         if bs.has_cross:
             if bs.f8c:
                 q_dy = gate_bwd_q(dX2, bs.y_ca, 5 * D, R0 + F8.ROW_DY_CP)
-                wgrad8(q_dy, bs.q_catt, Gr("cross_proj.weight"))
+                wgrad8(q_dy, bs.q_catt, "cross_proj.weight")
                 dcatt = F8.dgrad(q_dy, bs.q_wcp)
                 del q_dy
             else:
                 dy = _gate_bwd(groups, dX2, bs.y_ca, mod, 5 * D, dmod, None, B, L)
-                wgrad(dy, bs.catt, Gr("cross_proj.weight"))
+                wgrad(dy, bs.catt, "cross_proj.weight")
                 dcatt = ops.linear_dgrad(dy, W("cross_proj.weight"))
             # fp8 cross-attention + fp8 q_cross: dQ leaves the attention kernel as e5m2 (and as bf16 only for a bias gradient)
             emit_dqc = bs.c8 and bs.f8c and pemit and not _NO_ATTN_EMIT
@@ -850,22 +895,24 @@ class DiTBlock(nn.Module):
                              kv_pad_ones=ones, kv_lens=sv.kv_lens)
                 if bs.c8_on:
                     ops.absmax(dcatt, fp8_hist.cur(R0 + F8.ROW_DOC))
-            if G.has(pre + "context_kv.bias"):
+            if T("context_kv.bias"):
                 ops.colsum(dckv, Gr("context_kv.bias"))
-            if G.has(pre + "q_cross.bias"):
+            if T("q_cross.bias"):
                 ops.colsum(dqc, Gr("q_cross.bias"))
             if bs.f8c:
                 q_dckv = F8.Q(dckv, F8.E5M2, F8.TN, not F8.TN, hist, R0 + F8.ROW_DCKV)  # (a weight-gradient operand only)
-                wgrad8(q_dckv, q_ctx, Gr("context_kv.weight"))
+                wgrad8(q_dckv, q_ctx, "context_kv.weight")
                 q_dqc = (F8.Q.from_rowmajor(*e_dqc, True) if e_dqc is not None else
                          F8.Q(dqc, F8.E5M2, True, True, hist, R0 + F8.ROW_DQC))
-                wgrad8(q_dqc, bs.q_xn2, Gr("q_cross.weight"))
+                wgrad8(q_dqc, bs.q_xn2, "q_cross.weight")
                 dxn = F8.dgrad(q_dqc, bs.q_wqc)
                 del q_dckv, q_dqc
             else:
-                wgrad(dckv, sv.ctx2d, Gr("context_kv.weight"))
-                wgrad(dqc, bs.xn2, Gr("q_cross.weight"))
+                wgrad(dckv, sv.ctx2d, "context_kv.weight")
+                wgrad(dqc, bs.xn2, "q_cross.weight")
                 dxn = ops.linear_dgrad(dqc, W("q_cross.weight"))
+                lora_bwd("context_kv", dckv, sv.ctx2d, bs.u_ckv, None)
+                lora_bwd("q_cross", dqc, bs.xn2, bs.u_qc, dxn)
             dX1 = _norm_bwd(groups, dxn, bs.X1, Wo("norm2.weight"), mod, 3 * D, 4 * D, bs.rstd2, dX2, dmod,
                                       Go("norm2.weight"), B, L)
         else:
@@ -873,12 +920,12 @@ class DiTBlock(nn.Module):
         # --- self attention
         if bs.f8l:
             q_dy = gate_bwd_q(dX1, bs.y_sa, 2 * D, R0 + F8.ROW_DY_AP)
-            wgrad8(q_dy, bs.q_attn, Gr("attn_proj.weight"))
+            wgrad8(q_dy, bs.q_attn, "attn_proj.weight")
             dattn = F8.dgrad(q_dy, bs.q_wap)
             del q_dy
         else:
             dy = _gate_bwd(groups, dX1, bs.y_sa, mod, 2 * D, dmod, None, B, L)
-            wgrad(dy, bs.attn, Gr("attn_proj.weight"))
+            wgrad(dy, bs.attn, "attn_proj.weight")
             dattn = ops.linear_dgrad(dy, W("attn_proj.weight"))
         dq = torch.empty(B, H, L, hdp, dtype=bf16, device=dev)
         dk = torch.empty_like(dq)
@@ -931,17 +978,18 @@ class DiTBlock(nn.Module):
         else:
             fm_kw = dict(frames=bs.frames) if self.frame_major else {}  # dq, dk, dv, v0, dv0 in frame-major rows
             dqkv = (ops.qkv_rope_norm_bwd if self.qk_norm else ops.qkv_rope_bwd)(*rope_args, **fm_kw)
-        if G.has(pre + "qkv.bias"):
+        if T("qkv.bias"):
             ops.colsum(dqkv, Gr("qkv.bias"))
         if bs.f8:
             if not emit_dqkv:
                 q_dqkv = F8.Q(dqkv, F8.E5M2, True, True, fp8_hist, F8.ROWS * i + 5)
-            wgrad8(q_dqkv, bs.q_xn1, Gr("qkv.weight"))
+            wgrad8(q_dqkv, bs.q_xn1, "qkv.weight")
             dxn = F8.dgrad(q_dqkv, bs.q_wqkv)
             del q_dqkv
         else:
-            wgrad(dqkv, bs.xn1, Gr("qkv.weight"))
+            wgrad(dqkv, bs.xn1, "qkv.weight")
             dxn = ops.linear_dgrad(dqkv, W("qkv.weight"))
+            lora_bwd("qkv", dqkv, bs.xn1, bs.u_qkv, dxn)
         dX0 = _norm_bwd(groups, dxn, bs.X, Wo("norm1.weight"), mod, 0, D, bs.rstd1, dX1, dmod, Go("norm1.weight"),
                                   B, L)
         # --- adaLN modulation (model.py:89-94,107)
@@ -1016,6 +1064,9 @@ class _Saved:
     pass
 
 
+LORA_TARGETS = ("qkv", "q_cross", "context_kv")  # the linears DiT.add_lora can adapt: plain-store GEMMs, no fused epilogue
+_FP8_LORA = ("LoRA adapters are not implemented for the fp8 linears (the adapter reads the bf16 input of the linear, which "
+             "the fp8 path does not keep)")
 RECOMPUTE_MODES = ("none", "full", "selective")
 _FP8_RECOMPUTE = ("enable_fp8() and enable_recompute() cannot be combined: the fp8 producers write amax-history rows "
                   "during the forward pass, which a replayed forward would write a second time")
@@ -1056,6 +1107,11 @@ def activation_bytes(dit, B: int, latent_shape, Lc: int, mode: str = "none") -> 
     full += 2 * R * D + 4 * R            # xn3, rstd3
     full += 2 * R * Dm * 2               # hpre, hact
     full += 2 * R * D                    # y_mlp
+    lora = getattr(dit, "lora", None)
+    if lora is not None:                 # u = x A^T of every adapted linear
+        r = lora["rank"]
+        full += 2 * r * sum({"qkv": R, "q_cross": R if cross else 0, "context_kv": B * Lc if cross else 0}[t]
+                            for t in lora["targets"])
     full += mod
     per_block = {"none": full, "full": 2 * R * D + mod, "selective": 2 * R * D + mod + 2 * R * D + lse}[mode]
     return {"per_block": per_block, "kept": dit.depth * per_block, "transient": 0 if mode == "none" else full,
@@ -1146,6 +1202,8 @@ class DiT(nn.Module):
         self.fp8_attn = 0  # ... and the attention products (1: self-attention, 2: cross-attention too)
         self.fp8_lin = False   # ... and the four remaining linears of a block
         self.recompute = "none"  # enable_recompute(): what the forward keeps for the backward ("none" | "full" | "selective")
+        self.lora = None  # add_lora(): {"rank", "alpha", "targets"} of the low-rank adapters on the blocks' q/k/v linears
+        self._lora_frozen: List[str] = []  # names add_lora(freeze_base=True) froze (merge_lora un-freezes exactly these)
 
     def enable_fp8(self, on: bool = True, attention: bool = True, all_linears: bool = True,
                    cross_attention: bool = True):
@@ -1160,6 +1218,8 @@ class DiT(nn.Module):
         holds for a model built with frame_causal=True: the fp8 attention kernels have no masked instance."""
         if on and self.recompute != "none":
             raise ValueError(_FP8_RECOMPUTE)
+        if on and self.lora is not None:
+            raise NotImplementedError(_FP8_LORA + ": call merge_lora() first, or keep the model in bf16 (enable_fp8(False))")
         if on and attention and self.qk_norm:
             raise NotImplementedError(_FP8_QK_NORM)
         if on and attention and self.frame_causal:
@@ -1185,6 +1245,159 @@ class DiT(nn.Module):
         if mode != "none" and self.fp8:
             raise ValueError(_FP8_RECOMPUTE)
         self.recompute = mode
+        return self
+
+    # ---------------------------------------------------------------- low-rank adapters ----
+    def refresh_paramstatus(self):
+        """rebuild `paramstatus` (what get_mup_setup / get_muon_setup read) from the parameters as they are now: call it
+        after freezing or un-freezing parameters by hand (`p.requires_grad_(False)`); add_lora / merge_lora do."""
+        self.paramstatus = {n: {"shape": p.shape, "requires_grad": p.requires_grad} for n, p in self.named_parameters()}
+
+    def _lora_linears(self, targets=None):
+        """[(name of the linear, its _Linear)] of the blocks' linears that carry (or, with `targets`, would carry) an adapter"""
+        targets = self.lora["targets"] if targets is None else targets
+        out = []
+        for i, blk in enumerate(self.blocks):
+            for t in targets:
+                lin = getattr(blk, t, None)
+                if lin is not None:
+                    out.append((f"blocks.{i}.{t}", lin))
+        return out
+
+    def add_lora(self, rank: int = 16, alpha=None, targets=LORA_TARGETS, freeze_base: bool = True, generator=None):
+        """Low-rank adapters (LoRA) on the attention input projections of every block: a targeted linear computes
+        y = x W^T + b + s (x A^T) B^T with s = alpha / rank (alpha defaults to rank), A = `lora_A` [rank, in] drawn uniformly
+        in +-1/sqrt(in) from `generator`, B = `lora_B` [out, rank] zero -- so the model's output is unchanged until the
+        adapters are trained.  targets: any of "qkv", "q_cross", "context_kv"; the other linears of a block (attn_proj,
+        cross_proj, the MLP) run GEMMs with fused gate / GELU epilogues and take no adapter.  The adapter products are the
+        vds_lowrank_* kernels (csrc/lowrank.hip), in every path that runs the linear: training, recompute replay,
+        per-frame timesteps, frame-major / windowed attention, QK-norm, context_lens and the cached rollout.
+        freeze_base=True: every parameter that existed before the call stops training (requires_grad False) -- it gets no
+        .grad, and the backward launches none of its weight-gradient GEMMs.  get_lora_setup() returns the optimizer groups
+        of the adapters; merge_lora() folds them into the weights.  bf16 only (not with enable_fp8), unsharded only (not
+        with apply_fsdp).  Returns self."""
+        if self.lora is not None:
+            raise ValueError("add_lora: this model already carries adapters -- call merge_lora() to fold them into the "
+                             "weights first, or load other adapter values with load_lora_state_dict()")
+        if isinstance(rank, bool) or rank not in ops.LOWRANK_RANKS:
+            raise ValueError(f"add_lora: rank = {rank!r} has no kernel instance -- pass one of {ops.LOWRANK_RANKS}")
+        targets = tuple(targets)
+        bad = [t for t in targets if t not in LORA_TARGETS]
+        if bad or not targets or len(set(targets)) != len(targets):
+            raise ValueError(f"add_lora: targets = {targets!r}: pass distinct names out of {LORA_TARGETS} (attn_proj, "
+                             "cross_proj and the MLP linears have fused-epilogue GEMMs and take no adapter)")
+        if self.fp8:
+            raise NotImplementedError(_FP8_LORA + ": call enable_fp8(False) before add_lora()")
+        if self._fsdp is not None or self._world > 1:
+            raise NotImplementedError("add_lora: adapters on a model sharded with apply_fsdp are not implemented -- add them "
+                                      "to an unsharded copy of the weights (full_state_dict())")
+        alpha = float(rank if alpha is None else alpha)
+        if not alpha > 0.0 or alpha != alpha or alpha == float("inf"):
+            raise ValueError(f"add_lora: alpha = {alpha!r} must be a positive finite number (s = alpha / rank)")
+        linears = self._lora_linears(targets)
+        if not linears:
+            raise ValueError(f"add_lora: no block of this model has any of {targets} (cross_attn_input_size=None leaves "
+                             "only \"qkv\")")
+        for name, lin in linears:
+            if lin.in_features % 8 or lin.out_features % 8:
+                raise ValueError(f"add_lora: {name} is {lin.out_features} x {lin.in_features}; the low-rank kernels need "
+                                 "both to be multiples of 8 -- drop it from `targets`")
+        before = list(self.named_parameters())
+        for name, lin in linears:
+            w = lin.weight
+            a = torch.empty(rank, lin.in_features, dtype=torch.float32)
+            bound = 1.0 / math.sqrt(lin.in_features)
+            a.uniform_(-bound, bound, generator=generator)
+            lin.lora_A = nn.Parameter(a.to(device=w.device, dtype=w.dtype))
+            lin.lora_B = nn.Parameter(torch.zeros(lin.out_features, rank, device=w.device, dtype=w.dtype))
+        self._lora_frozen = []
+        if freeze_base:
+            for n, p in before:
+                if p.requires_grad:
+                    p.requires_grad_(False)
+                    self._lora_frozen.append(n)
+        self.lora = {"rank": int(rank), "alpha": alpha, "targets": targets}
+        for blk in self.blocks:
+            blk.lora_scale = alpha / rank
+        self.refresh_paramstatus()
+        self._groups = None  # the flat groups are rebuilt with the adapters as members
+        return self
+
+    def lora_parameters(self):
+        """[(name, parameter)] of the adapter tensors, in named_parameters() order"""
+        if self.lora is None:
+            return []
+        return [(n, p) for n, p in self.named_parameters() if n.endswith((".lora_A", ".lora_B"))]
+
+    def get_lora_setup(self, learning_rate, weight_decay=0.0):
+        """(optimizer param groups, {name: {"lr", "wd", "shape"}}) in get_mup_setup's format for the adapter parameters
+        only: ONE group, every trainable lora_A / lora_B at `learning_rate` and `weight_decay` (an adapter is its own
+        small model: the width-dependent muP factors of get_mup_setup, whose cascade is unchanged, do not apply)."""
+        if self.lora is None:
+            raise ValueError("get_lora_setup: this model has no adapters -- call add_lora() first")
+        group = {"params": [], "weight_decay": float(weight_decay), "lr": float(learning_rate)}
+        table = {}
+        for n, p in self.lora_parameters():
+            if not p.requires_grad:
+                continue
+            group["params"].append(p)
+            table[n] = {"lr": float(learning_rate), "wd": float(weight_decay), "shape": self.paramstatus[n]["shape"]}
+        return [group], table
+
+    def lora_state_dict(self) -> Dict[str, object]:
+        """the adapter tensors (fp32 copies, keyed like named_parameters()) plus "rank", "alpha" and "targets": what a
+        fine-tune has to ship next to the base checkpoint"""
+        if self.lora is None:
+            raise ValueError("lora_state_dict: this model has no adapters -- call add_lora() first")
+        sd: Dict[str, object] = {n: p.detach().clone() for n, p in self.lora_parameters()}
+        sd.update(rank=self.lora["rank"], alpha=self.lora["alpha"], targets=list(self.lora["targets"]))
+        return sd
+
+    def load_lora_state_dict(self, sd):
+        """load what lora_state_dict() returned into this model's adapters; the rank, alpha, targets, the set of names
+        and every shape must match (ValueError otherwise: build the adapters with the add_lora() arguments of the file)"""
+        if self.lora is None:
+            raise ValueError("load_lora_state_dict: this model has no adapters -- call add_lora(rank=sd['rank'], "
+                             "alpha=sd['alpha'], targets=sd['targets']) first")
+        meta = {k: sd.get(k) for k in ("rank", "alpha", "targets")}
+        if (meta["rank"] != self.lora["rank"] or meta["alpha"] is None or float(meta["alpha"]) != self.lora["alpha"]
+                or meta["targets"] is None or tuple(meta["targets"]) != self.lora["targets"]):
+            raise ValueError(f"load_lora_state_dict: the file holds adapters of {meta}, this model has {self.lora} -- call "
+                             "add_lora() with the file's rank, alpha and targets")
+        own = dict(self.lora_parameters())
+        keys = {k for k in sd if k not in ("rank", "alpha", "targets")}
+        if keys != set(own):
+            raise ValueError(f"load_lora_state_dict: adapter names differ: missing {sorted(set(own) - keys)}, unexpected "
+                             f"{sorted(keys - set(own))}")
+        for n, p in own.items():
+            if tuple(sd[n].shape) != tuple(p.shape):
+                raise ValueError(f"load_lora_state_dict: {n} is {tuple(sd[n].shape)} in the file, {tuple(p.shape)} here")
+        with torch.no_grad():
+            for n, p in own.items():
+                p.copy_(sd[n].to(device=p.device, dtype=p.dtype))
+        self.invalidate_compute_copy()
+
+    def merge_lora(self):
+        """fold the adapters into the weights: W += s B A in fp32 on the masters, then remove lora_A / lora_B, give back
+        requires_grad to what add_lora froze and re-cast the compute copies.  The state dict has the reference's keys
+        again; up to the bf16 rounding of the merged weight the model computes what it computed with the adapters."""
+        if self.lora is None:
+            raise ValueError("merge_lora: this model has no adapters -- call add_lora() first")
+        s = self.lora["alpha"] / self.lora["rank"]
+        with torch.no_grad():
+            for _, lin in self._lora_linears():
+                lin.weight.data.add_(lin.lora_B.data.float() @ lin.lora_A.data.float(), alpha=s)
+                del lin.lora_A, lin.lora_B
+        named = dict(self.named_parameters())
+        for n in self._lora_frozen:
+            named[n].requires_grad_(True)
+        self._lora_frozen = []
+        self.lora = None
+        for blk in self.blocks:
+            blk.lora_scale = None
+        self.refresh_paramstatus()
+        self.invalidate_compute_copy()
+        self._groups = None  # the flat groups are rebuilt without the adapters
         return self
 
     # --------------------------------------------------------------------- parameters ----
@@ -1555,8 +1768,11 @@ class DiT(nn.Module):
         dout = dout.to(bf16).contiguous()
         # final layer
         dyf = ops.unpatchify_bwd(dout, pt, p, lead_rows=N_REG)  # [B*L, P], register rows zero
-        ops.linear_wgrad(dyf, sv.xnf, R.g("final_proj.weight"))
-        ops.colsum(dyf, R.g("final_proj.bias"))
+        Tr = lambda n: R.params[n].requires_grad  # frozen parameters skip their weight-gradient GEMM / column sums
+        if Tr("final_proj.weight"):
+            ops.linear_wgrad(dyf, sv.xnf, R.g("final_proj.weight"))
+        if Tr("final_proj.bias"):
+            ops.colsum(dyf, R.g("final_proj.bias"))
         dxnf = ops.linear_dgrad(dyf, R.w("final_proj.weight"))
         # the small zero-initialised accumulators of this pass come out of ONE fill: d(final modulation) [B, 2D],
         # d(conditioning vector) [B, D], d(time-embed hidden) [B, 4D] and the adaLN modulation gradients of all blocks
@@ -1601,8 +1817,10 @@ class DiT(nn.Module):
         ops.registers_bwd(dX, L * D, R.g("register_tokens").view(N_REG, D), B, N_REG, D)
         # patch embedding: weight gradient over all B*L rows (the register rows of `patches` are zero), bias gradient
         # over the token rows only
-        ops.linear_wgrad(dX, sv.patches, R.g("patch_embed.patch_proj.weight").view(D, Pd))
-        ops.colsum(dX, R.g("patch_embed.patch_proj.bias"), rows_per_sample=L, row_offset=N_REG)
+        if Tr("patch_embed.patch_proj.weight"):
+            ops.linear_wgrad(dX, sv.patches, R.g("patch_embed.patch_proj.weight").view(D, Pd))
+        if Tr("patch_embed.patch_proj.bias"):
+            ops.colsum(dX, R.g("patch_embed.patch_proj.bias"), rows_per_sample=L, row_offset=N_REG)
         # time embed MLP
         ops.small_linear_bwd(dc, sv.h1, R.w("time_embed.2.weight"), R.g("time_embed.2.weight"),
                              R.g("time_embed.2.bias"), dh1, 1)

@@ -679,6 +679,70 @@ def colsum(x, out, rows_per_sample: int = 0, row_offset: int = 0):
           "vds_colsum_bf16_rows")
 
 
+# -------------------------------------------------------------- low-rank adapters ----
+LOWRANK_RANKS = (16, 32, 64)
+
+
+def lowrank_chunk(which: str, r: int) -> int:
+    """the kernels' chunk sizes for rank r: "down" elements of K per LDS stage, "up" columns of y per workgroup, "wgrad"
+    rows per fp32 partial"""
+    return int(_lib.load().vds_lowrank_chunk({"down": 0, "up": 1, "wgrad": 2}[which], int(r)))
+
+
+def _lowrank_operands(what: str, layout: int, **tensors):
+    """the operands of a low-rank call against the shapes and dtypes the kernel will assume: name=(tensor, dtype, shape);
+    a mismatch raises here instead of becoming an out-of-range read in the kernel"""
+    if layout not in (0, 1):
+        raise ValueError(f"{what}: layout = {layout!r} must be 0 or 1")
+    for name, (t, dtype, shape) in tensors.items():
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape):
+            got = (t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{what}: {name} must be {dtype} of shape {tuple(shape)}, got {got}")
+
+
+def lowrank_down(x, w, scale: float = 1.0, layout: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """u = bf16(scale * x w^T) for layout 0 (w [r, K], the adapter's A) or bf16(scale * x w) for layout 1 (w [K, r], the
+    adapter's B).  x [M, K] bf16 -> u [M, r] bf16."""
+    M, K = x.shape
+    r = w.shape[0] if layout == 0 else w.shape[1]
+    u = out if out is not None else torch.empty(M, r, dtype=bf16, device=x.device)
+    _lowrank_operands("lowrank_down", layout, x=(x, bf16, (M, K)), w=(w, bf16, (r, K) if layout == 0 else (K, r)),
+                      u=(u, bf16, (M, r)))
+    check(_lib.load().vds_lowrank_down(_p(x), _rows(x)[0], _p(w), _rows(w)[0], int(layout), _p(u), _rows(u)[0], M, K, r,
+                                       float(scale), _stream()), f"vds_lowrank_down(M={M},K={K},r={r},layout={layout})")
+    return u
+
+
+def lowrank_up_add(u, w, y, scale: float = 1.0, layout: int = 0) -> torch.Tensor:
+    """y += scale * u w^T in place for layout 0 (w [N, r], the adapter's B) or scale * u w for layout 1 (w [r, N], the
+    adapter's A).  u [M, r], y [M, N] bf16."""
+    M, N = y.shape
+    r = u.shape[1]
+    _lowrank_operands("lowrank_up_add", layout, u=(u, bf16, (M, r)), w=(w, bf16, (N, r) if layout == 0 else (r, N)),
+                      y=(y, bf16, (M, N)))
+    check(_lib.load().vds_lowrank_up_add(_p(u), _rows(u)[0], _p(w), _rows(w)[0], int(layout), _p(y), _rows(y)[0], M, N, r,
+                                         float(scale), _stream()), f"vds_lowrank_up_add(M={M},N={N},r={r},layout={layout})")
+    return y
+
+
+def lowrank_wgrad(a, u, g, scale: float = 1.0, layout: int = 0, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """g += scale * a^T u in fp32 for layout 0 (g [N, r]: dB from dY and U) or scale * u^T a for layout 1 (g [r, N]: dA
+    from x and dU).  a [M, N], u [M, r] bf16; ws: f32 workspace of vds_lowrank_wgrad_workspace_floats(M, N, r) floats
+    (allocated here when not given)."""
+    M, N = a.shape
+    r = u.shape[1]
+    _lowrank_operands("lowrank_wgrad", layout, a=(a, bf16, (M, N)), u=(u, bf16, (M, r)),
+                      g=(g, f32, (N, r) if layout == 0 else (r, N)))
+    if ws is None:
+        ws = torch.empty(max(1, int(_lib.load().vds_lowrank_wgrad_workspace_floats(M, N, r))), dtype=f32, device=a.device)
+    if ws.dtype != f32 or ws.dim() != 1 or not ws.is_contiguous():
+        raise ValueError(f"lowrank_wgrad: ws must be a contiguous 1-D float32 tensor, got {ws.dtype} {tuple(ws.shape)}")
+    check(_lib.load().vds_lowrank_wgrad(_p(a), _rows(a)[0], _p(u), _rows(u)[0], _p(g), _rows(g)[0], int(layout), M, N, r,
+                                        float(scale), _p(ws), ws.numel(), _stream()),
+          f"vds_lowrank_wgrad(M={M},N={N},r={r},layout={layout})")
+    return g
+
+
 # ------------------------------------------------------------------ frame-major rows ----
 # The head-major tensors of a frame-major self-attention (q, k, v, dq, dk, dv, lse, v0, dv0) keep a frame's rows
 # contiguous; the model's token order stays (h w t).  With S = (L - lead) // period rows per frame (include/vds.h):
