@@ -513,12 +513,16 @@ int vds_rope_rows_dev(const float* tab_t_cos, const float* tab_t_sin, const floa
  * y[b, n] = act_out( sum_k act_in(x[b,k]) * W[n,k] + bias[n] ), M = B rows (the per-GPU batch; any M >= 1, run
  * in chunks of <= 16 rows that stay in registers): time_embed / adaLN_modulation / final_modulation
  * (model.py:90,318-322,339-341).  x f32 [M,K]; W bf16 [N,K]; bias bf16 [N]; y f32 [M,N].  act: 0 none, 1 SiLU.
- * K % 8 == 0. */
+ * Requires M, N >= 1, K >= 8, K % 8 == 0.  x, W, y (and dW below) are read / written in 16-byte pieces: 16-byte aligned
+ * pointers; bias (may be NULL) 8-byte aligned; dy, dbias, dx 4-byte aligned.  The batched forms check the pointers they
+ * are given directly; the pointers inside the device tables must meet the same rule (they cannot be checked on the
+ * host), and y_stride % 4 == 0 when N % 16 == 0.  Anything else is VDS_ERR_ARG before any launch. */
 int vds_small_linear_fwd(const float* x, const void* W, const void* bias, float* y, int32_t M,
                          int32_t N, int32_t K, int32_t act_in, vds_stream_t stream);
 /* dW[n,k] (f32) = sum_b dy[b,n]*act_in(x[b,k]);  dbias[n] (f32) = sum_b dy[b,n]  (overwritten);
  * dx[b,k] (f32) += act_in'(x[b,k]) * sum_n dy[b,n] W[n,k]   (atomically accumulated: the
- * conditioning vector c collects a gradient from every block).  dW/dbias or dx may be NULL. */
+ * conditioning vector c collects a gradient from every block).  dW (with it dbias) or dx may be NULL; dbias may be
+ * NULL on its own; W may be NULL when dx is (dx without W is VDS_ERR_ARG, and then dW is not written either). */
 int vds_small_linear_bwd(const float* dy, const float* x, const void* W, float* dW, float* dbias,
                          float* dx, int32_t M, int32_t N, int32_t K, int32_t act_in,
                          vds_stream_t stream);
@@ -533,12 +537,14 @@ int vds_small_linear_bwd_batched(const float* dy, int64_t dy_stride, const float
                                  float* const* dW_ptrs, float* const* dbias_ptrs, float* dx, int32_t nb, int32_t M,
                                  int32_t N, int32_t K, int32_t act_in, vds_stream_t stream);
 /* sinusoid [cos | sin](t * f_i), t unscaled (model.py:12-22), rounded through bf16 like
- * the reference's .to(x.dtype): out f32 [B, D]. */
+ * the reference's .to(x.dtype): out f32 [B, D].  B >= 1, D >= 2, D % 2 == 0. */
 int vds_timestep_embedding(const float* t, float* out, int32_t B, int32_t D, vds_stream_t stream);
 
 /* ------------------------------------------------------------ patchify / unpatchify ---
  * latent [B,C,T,H,W] bf16 -> patches [B*N, C*pt*p*p] bf16, token order (h w t)
- * (Conv3d k=stride + rearrange, model.py:182-186); the GEMM with patch_proj follows. */
+ * (Conv3d k=stride + rearrange, model.py:182-186); the GEMM with patch_proj follows.
+ * All of patchify / unpatchify: B, C, T, H, W, pt, p >= 1, T % pt == 0, H % p == 0, W % p == 0 (else VDS_ERR_ARG);
+ * two-byte accesses only, no alignment beyond bf16's. */
 int vds_patchify(const void* latent, void* patches, int32_t B, int32_t C, int32_t T, int32_t H,
                  int32_t W, int32_t pt, int32_t p, vds_stream_t stream);
 /* tokens y [B*N, p*p*pt*C] bf16 (p1 p2 p3 c) -> out [B,C,T,H,W] bf16 (model.py:392-401) */
@@ -557,7 +563,8 @@ int vds_patchify_rows(const void* latent, void* patches, int32_t B, int32_t C, i
 int vds_unpatchify_rows(const void* y, void* out, int32_t B, int32_t C, int32_t T, int32_t H, int32_t W,
                         int32_t pt, int32_t p, int32_t rows_per_sample, int32_t row_offset, int32_t bwd,
                         vds_stream_t stream);
-/* x[b, 0:R] = reg[0:R] ; used to prepend the 16 register tokens (model.py:362) */
+/* x[b, 0:R] = reg[0:R] ; used to prepend the 16 register tokens (model.py:362).  x holds sample b at
+ * x + b * batch_stride (elements); B, R, D >= 1 and batch_stride >= R * D, here and in vds_registers_bwd. */
 int vds_fill_registers(const void* reg, void* x, int64_t batch_stride, int32_t B, int32_t R,
                        int32_t D, vds_stream_t stream);
 /* dreg[r,d] (f32) += sum_b dx[b, r, d] */
@@ -565,7 +572,8 @@ int vds_registers_bwd(const void* dx, int64_t batch_stride, float* dreg, int32_t
                       int32_t D, vds_stream_t stream);
 
 /* ------------------------------------------------------------ noising + loss (train.py) --
- * z_t = x(1-t) + n t ; v = x - n  in bf16 (train.py:115-117); t f32 [B] already bf16-rounded. */
+ * z_t = x(1-t) + n t ; v = x - n  in bf16 (train.py:115-117); t f32 [B] already bf16-rounded.
+ * B >= 1, per_sample >= 1; element-wise accesses, no alignment beyond the types'. */
 int vds_noise_latents(const void* x, const void* noise, const float* t, void* z_t, void* v,
                       int32_t B, int64_t per_sample, vds_stream_t stream);
 /* the same with one noise level per token-frame: x [B,C,T,HW] bf16, t f32 [B, T / time_patch] (bf16-rounded values);
@@ -582,7 +590,8 @@ int vds_flow_loss(const void* v, const void* out, float* loss_out, float* per_sa
                   float gscale, int32_t B, int64_t per_sample_n, float* workspace, vds_stream_t stream);
 /* its backward for an arbitrary upstream gradient (autograd of train.py:121-125 under `(loss * s).backward()`,
  * loss scaling, micro-batch accumulation): dout = bf16( 2 (out - v) * *gloss_dev / (B*per_sample) ), the upstream
- * scalar read from device memory (no host synchronisation; graph-capturable).  B*per_sample % 8 == 0. */
+ * scalar read from device memory (no host synchronisation; graph-capturable).  B, per_sample >= 1,
+ * B*per_sample % 8 == 0; v, out and dout are read / written in 16-byte pieces: 16-byte aligned pointers. */
 int vds_flow_loss_bwd(const void* v, const void* out, const float* gloss_dev, void* dout, int32_t B,
                       int64_t per_sample_n, vds_stream_t stream);
 
@@ -603,7 +612,8 @@ int vds_flow_loss_frames_bwd(const void* v, const void* out, const float* w, con
 
 /* ------------------------------------------------------------ sampler --
  * One Euler step of sampling/sample.py:139-146:  out = uncond + cfg_scale*(cond - uncond) in bf16
- * (uncond may be NULL: out = cond), acc (f32) += dt * out, latents = bf16(acc).  n % 8 == 0. */
+ * (uncond may be NULL: out = cond), acc (f32) += dt * out, latents = bf16(acc).  n >= 8, n % 8 == 0; cond, uncond,
+ * acc and latents are read / written in 16-byte pieces: 16-byte aligned pointers. */
 int vds_cfg_euler_step(const void* cond, const void* uncond, float* acc, void* latents, float cfg_scale,
                        float dt, int64_t n, vds_stream_t stream);
 
@@ -753,7 +763,9 @@ int vds_all_reduce_f32_avg(float* buf, int64_t n, vds_stream_t stream);
  * squared global norm is the sum of the ranks' local sums of squares) */
 int vds_all_reduce_f32_sum(float* buf, int64_t n, vds_stream_t stream);
 
-/* f32 -> bf16 cast (FSDP param_dtype cast before all-gather, model.py:516-518) */
+/* f32 -> bf16 cast (FSDP param_dtype cast before all-gather, model.py:516-518), round to nearest even.  n >= 0 (0: no
+ * launch).  Serves ANY naturally aligned pointers (optimizer shards start anywhere): 16-byte accesses when src and dst
+ * are both 16-byte aligned, one element per thread otherwise -- the same bits either way. */
 int vds_cast_f32_bf16(const float* src, void* dst, int64_t n, vds_stream_t stream);
 /* bf16 -> f32 */
 int vds_cast_bf16_f32(const void* src, float* dst, int64_t n, vds_stream_t stream);

@@ -1663,7 +1663,14 @@ __global__ void cfg_euler_kernel(const bf16_t* cond, const bf16_t* uncond, float
   *reinterpret_cast<u32x4*>(lat + i * 8) = pack8(o);
 }
 
-__global__ void cast_f32_bf16_kernel(const float* s, bf16_t* d, long n) {
+// vec: both pointers are 16-byte aligned, 8 elements per thread.  Else (an optimizer shard starts anywhere) the grid
+// has one thread per element, so a wave still reads and writes consecutive addresses.
+__global__ void cast_f32_bf16_kernel(const float* s, bf16_t* d, long n, int vec) {
+  if (!vec) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j < n) d[j] = f2bf(s[j]);
+    return;
+  }
   const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 8;
   if (i + 8 <= n) {
     float f[8];
@@ -1709,6 +1716,11 @@ __global__ void rope_rows_kernel(const float* tab_t_cos, const float* tab_t_sin,
 }
 
 inline int ok() { return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH; }
+// entry checks: an operand read or written in 16-byte pieces (8 bf16 / 4 fp32), a plain fp32 array, the bf16 bias the
+// MFMA forward reads four at a time.  Null passes: whether a pointer may be null is the entry's own question.
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool al8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+inline bool al4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 // deterministic mode: second stage of a column sum (see det_finish_kernel)
 inline void det_finish(const float* part, int n_parts, int width, float* target, long tstride, int groups, hipStream_t s) {
   const long n = (long)groups * width;
@@ -2450,7 +2462,8 @@ static bool small_linear_fwd_mfma(const float* x, const bf16_t* W, const bf16_t*
 
 extern "C" int vds_small_linear_fwd(const float* x, const void* W, const void* bias, float* y, int32_t M,
                                     int32_t N, int32_t K, int32_t act_in, vds_stream_t stream) {
-  if (!x || !W || !y || M < 1 || (K & 7)) return VDS_ERR_ARG;
+  if (!x || !W || !y || M < 1 || N < 1 || K < 8 || (K & 7)) return VDS_ERR_ARG;
+  if (!al16(x) || !al16(W) || !al16(y) || !al8(bias)) return VDS_ERR_ARG;
   const dim3 grid((N + 15) / 16);
   // the kernels keep <= 16 rows in registers: larger batches (the reference trains with up to 64 samples per rank,
   // train.py:150) run as row chunks -- rows are independent
@@ -2474,7 +2487,9 @@ extern "C" int vds_small_linear_fwd(const float* x, const void* W, const void* b
 }
 extern "C" int vds_small_linear_bwd(const float* dy, const float* x, const void* W, float* dW, float* dbias,
                                     float* dx, int32_t M, int32_t N, int32_t K, int32_t act_in, vds_stream_t stream) {
-  if (!dy || !x || M < 1 || (K & 7)) return VDS_ERR_ARG;
+  if (!dy || !x || M < 1 || N < 1 || K < 8 || (K & 7)) return VDS_ERR_ARG;
+  if (dx && !W) return VDS_ERR_ARG;  // (before the dW launch: a refused call writes nothing)
+  if (!al16(x) || !al16(W) || !al16(dW) || !al4(dy) || !al4(dbias) || !al4(dx)) return VDS_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (dW) {
     const long n = (long)((N + 3) / 4) * (K >> 3);
@@ -2510,7 +2525,9 @@ extern "C" int vds_small_linear_bwd(const float* dy, const float* x, const void*
 extern "C" int vds_small_linear_fwd_batched(const float* x, const void* const* W_ptrs, const void* const* bias_ptrs,
                                             float* y, int64_t y_stride, int32_t nb, int32_t M, int32_t N, int32_t K,
                                             int32_t act_in, vds_stream_t stream) {
-  if (!x || !W_ptrs || !y || nb < 1 || M < 1 || M > 16 || (K & 7)) return VDS_ERR_ARG;
+  if (!x || !W_ptrs || !y || nb < 1 || M < 1 || M > 16 || N < 1 || K < 8 || (K & 7)) return VDS_ERR_ARG;
+  // (the pointers in the tables are the caller's contract; the MFMA forward, N % 16 == 0, stores y in 16-byte pieces)
+  if (!al16(x) || !al16(y) || ((N & 15) == 0 && (y_stride & 3))) return VDS_ERR_ARG;
   const dim3 grid((N + 15) / 16, 1, nb);
   const SLBatch bt{W_ptrs, bias_ptrs, nullptr, nullptr, (long)y_stride};
   hipStream_t s = (hipStream_t)stream;
@@ -2524,7 +2541,9 @@ extern "C" int vds_small_linear_fwd_batched(const float* x, const void* const* W
 extern "C" int vds_small_linear_bwd_batched(const float* dy, int64_t dy_stride, const float* x, const void* const* W_ptrs,
                                             float* const* dW_ptrs, float* const* dbias_ptrs, float* dx, int32_t nb,
                                             int32_t M, int32_t N, int32_t K, int32_t act_in, vds_stream_t stream) {
-  if (!dy || !x || nb < 1 || M < 1 || M > 16 || (K & 7)) return VDS_ERR_ARG;
+  if (!dy || !x || nb < 1 || M < 1 || M > 16 || N < 1 || K < 8 || (K & 7)) return VDS_ERR_ARG;
+  if (dx && !W_ptrs) return VDS_ERR_ARG;  // (before the dW launch: a refused call writes nothing)
+  if (!al16(x) || !al4(dy) || !al4(dx)) return VDS_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (dW_ptrs) {
     const SLBatch bt{nullptr, nullptr, dW_ptrs, dbias_ptrs, (long)dy_stride};
@@ -2554,7 +2573,7 @@ extern "C" int vds_small_linear_bwd_batched(const float* dy, int64_t dy_stride, 
 }
 
 extern "C" int vds_timestep_embedding(const float* t, float* out, int32_t B, int32_t D, vds_stream_t stream) {
-  if (!t || !out || (D & 1)) return VDS_ERR_ARG;
+  if (!t || !out || B < 1 || D < 2 || (D & 1)) return VDS_ERR_ARG;
   hipLaunchKernelGGL(timestep_embedding_kernel, dim3((B * (D / 2) + 255) / 256), dim3(256), 0, (hipStream_t)stream, t, out, B, D);
   return ok();
 }
@@ -2562,7 +2581,8 @@ extern "C" int vds_timestep_embedding(const float* t, float* out, int32_t B, int
 extern "C" int vds_patchify_rows(const void* latent, void* patches, int32_t B, int32_t C, int32_t T, int32_t H,
                                  int32_t W, int32_t pt, int32_t p, int32_t rows_per_sample, int32_t row_offset,
                                  vds_stream_t stream) {
-  if (!latent || !patches || pt < 1 || p < 1) return VDS_ERR_ARG;
+  if (!latent || !patches || B < 1 || C < 1 || T < 1 || H < 1 || W < 1 || pt < 1 || p < 1) return VDS_ERR_ARG;
+  if ((T % pt) || (H % p) || (W % p)) return VDS_ERR_ARG;  // (a remainder would be dropped: as vds_unpatchify_rows)
   const int ntok = (H / p) * (W / p) * (T / pt);
   if (rows_per_sample == 0) rows_per_sample = ntok;
   if (row_offset < 0 || rows_per_sample < row_offset + ntok) return VDS_ERR_ARG;
@@ -2579,7 +2599,8 @@ extern "C" int vds_patchify(const void* latent, void* patches, int32_t B, int32_
 extern "C" int vds_unpatchify_rows(const void* y, void* out, int32_t B, int32_t C, int32_t T, int32_t H, int32_t W,
                                    int32_t pt, int32_t p, int32_t rows_per_sample, int32_t row_offset, int32_t bwd,
                                    vds_stream_t stream) {
-  if (!y || !out || (T % pt) || (H % p) || (W % p)) return VDS_ERR_ARG;
+  if (!y || !out || B < 1 || C < 1 || T < 1 || H < 1 || W < 1 || pt < 1 || p < 1) return VDS_ERR_ARG;
+  if ((T % pt) || (H % p) || (W % p)) return VDS_ERR_ARG;
   const int ntok = (H / p) * (W / p) * (T / pt);
   if (rows_per_sample == 0) rows_per_sample = ntok;
   if (row_offset < 0 || rows_per_sample < row_offset + ntok) return VDS_ERR_ARG;
@@ -2605,7 +2626,7 @@ extern "C" int vds_unpatchify_bwd(const void* dout, void* dy, int32_t B, int32_t
 
 extern "C" int vds_fill_registers(const void* reg, void* x, int64_t batch_stride, int32_t B, int32_t R, int32_t D,
                                   vds_stream_t stream) {
-  if (!reg || !x) return VDS_ERR_ARG;
+  if (!reg || !x || B < 1 || R < 1 || D < 1 || batch_stride < (int64_t)R * D) return VDS_ERR_ARG;
   const long n = (long)B * R * D;
   hipLaunchKernelGGL(fill_registers_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)reg, (bf16_t*)x, (long)batch_stride, B, R, D);
@@ -2614,7 +2635,7 @@ extern "C" int vds_fill_registers(const void* reg, void* x, int64_t batch_stride
 
 extern "C" int vds_registers_bwd(const void* dx, int64_t batch_stride, float* dreg, int32_t B, int32_t R, int32_t D,
                                  vds_stream_t stream) {
-  if (!dx || !dreg) return VDS_ERR_ARG;
+  if (!dx || !dreg || B < 1 || R < 1 || D < 1 || batch_stride < (int64_t)R * D) return VDS_ERR_ARG;
   const long n = (long)R * D;
   hipLaunchKernelGGL(registers_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)dx, (long)batch_stride, dreg, B, R, D);
@@ -2623,7 +2644,7 @@ extern "C" int vds_registers_bwd(const void* dx, int64_t batch_stride, float* dr
 
 extern "C" int vds_noise_latents(const void* x, const void* noise, const float* t, void* z_t, void* v, int32_t B,
                                  int64_t per_sample, vds_stream_t stream) {
-  if (!x || !noise || !t || !z_t || !v) return VDS_ERR_ARG;
+  if (!x || !noise || !t || !z_t || !v || B < 1 || per_sample < 1) return VDS_ERR_ARG;
   const long n = (long)B * per_sample;
   hipLaunchKernelGGL(noise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)x, (const bf16_t*)noise, t, (bf16_t*)z_t, (bf16_t*)v, B, (long)per_sample);
@@ -2711,7 +2732,8 @@ extern "C" int vds_rope_apply(const void* x, int64_t x_sb, int64_t x_sh, int64_t
 extern "C" int vds_flow_loss_bwd(const void* v, const void* out, const float* gloss_dev, void* dout, int32_t B,
                                  int64_t per_sample_n, vds_stream_t stream) {
   const long n = (long)B * per_sample_n;
-  if (!v || !out || !gloss_dev || !dout || n <= 0 || (n & 7)) return VDS_ERR_ARG;
+  if (!v || !out || !gloss_dev || !dout || B < 1 || per_sample_n < 1 || (n & 7)) return VDS_ERR_ARG;
+  if (!al16(v) || !al16(out) || !al16(dout)) return VDS_ERR_ARG;
   long blocks = (n / 8 + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(flow_loss_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
@@ -2722,6 +2744,7 @@ extern "C" int vds_flow_loss_bwd(const void* v, const void* out, const float* gl
 extern "C" int vds_cfg_euler_step(const void* cond, const void* uncond, float* acc, void* latents, float cfg_scale,
                                   float dt, int64_t n, vds_stream_t stream) {
   if (!cond || !acc || !latents || n <= 0 || (n & 7)) return VDS_ERR_ARG;
+  if (!al16(cond) || !al16(uncond) || !al16(acc) || !al16(latents)) return VDS_ERR_ARG;
   const long n8 = n / 8;
   hipLaunchKernelGGL(cfg_euler_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)cond, (const bf16_t*)uncond, acc, (bf16_t*)latents, cfg_scale, dt, n8);
@@ -2729,15 +2752,17 @@ extern "C" int vds_cfg_euler_step(const void* cond, const void* uncond, float* a
 }
 
 extern "C" int vds_cast_f32_bf16(const float* src, void* dst, int64_t n, vds_stream_t stream) {
-  if (!src || !dst) return VDS_ERR_ARG;
+  if (!src || !dst || n < 0 || !al4(src) || ((uintptr_t)dst & 1)) return VDS_ERR_ARG;
   if (n == 0) return VDS_OK;
-  const long thr = (n + 7) / 8;
-  hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, (long)n);
+  const int vec = al16(src) && al16(dst);
+  const long thr = vec ? (n + 7) / 8 : n;
+  hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, (long)n,
+                     vec);
   return ok();
 }
 
 extern "C" int vds_cast_bf16_f32(const void* src, float* dst, int64_t n, vds_stream_t stream) {
-  if (!src || !dst) return VDS_ERR_ARG;
+  if (!src || !dst || n < 0) return VDS_ERR_ARG;
   if (n == 0) return VDS_OK;
   hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, dst, (long)n);
   return ok();
