@@ -169,8 +169,9 @@ int vds_transpose_fp8(const void* q, int64_t ldq, int32_t M, int32_t K, void* qt
  * four rows, at the first of them, for RMSNorm at D = 384 / 768 / 1152), the entry of the first row a wave walks for gate
  * backward; the other entries are not written -- and the tensor's amax is the maximum over the array
  * (the caller zeroes it before the launch and reduces it afterwards; no atomics: ~10^5 short waves per launch).  All other arguments as in
- * vds_rmsnorm_mod_fwd / vds_gate_bwd / vds_qkv_rope_bwd (the latter needs hdp % 8 == 0 and H*hd <= 2048, else
- * VDS_ERR_UNSUPPORTED). */
+ * vds_rmsnorm_mod_fwd / vds_gate_bwd / vds_qkv_rope_bwd (the latter needs hdp % 8 == 0, H*hd <= 2048 and ldq >= 3*H*hd,
+ * else VDS_ERR_UNSUPPORTED), except that y / ldy, dy / lddy and dqkv are not taken; q or amax_in NULL, ldq % 8 != 0 or
+ * another fmt: VDS_ERR_ARG, as is B < 1 or L < 1 in the RMSNorm and gate forms. */
 int vds_rmsnorm_mod_fwd_fp8(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod,
                             int32_t shift_col, int32_t scale_col, void* q, int64_t ldq, int32_t fmt,
                             const float* amax_in, float* amax_part, float* dq_out, float* rstd, int32_t B, int32_t L,
@@ -247,14 +248,16 @@ size_t vds_attn_bwd_workspace_bytes(const vds_attn_args* args);
 /* ------------------------------------------------------ normalisation / modulation ---
  * y = bf16( rmsnorm(x)[*w] * (1 + scale[b]) + shift[b] ), rstd saved (model.py:34-41,123,144,164,389).
  * x,y [B*L, D] bf16; mod f32 [B, ldmod] with shift at column shift_col, scale at scale_col;
- * w bf16 [D] or NULL; rstd f32 [B*L]. */
+ * w bf16 [D] or NULL; rstd f32 [B*L].  D and ldx, ldy multiples of 8, shift_col, scale_col and ldmod multiples of 4 (the
+ * modulation row is read in 16-byte pieces).  B < 1 or L < 1: VDS_ERR_ARG, nothing is launched -- the rule of every RMSNorm and
+ * gate entry point below, plain, _grouped and _fp8 alike.  D > 2048 (no instance): VDS_ERR_UNSUPPORTED, likewise. */
 int vds_rmsnorm_mod_fwd(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod,
                         int32_t shift_col, int32_t scale_col, void* y, int64_t ldy, float* rstd,
                         int32_t B, int32_t L, int32_t D, float eps, vds_stream_t stream);
 /* dx = bf16( dres + d/dx ), dmod[b, shift_col..] += sum_l dy, dmod[b, scale_col..] += sum_l dy*xhat*w,
  * dw (f32 [D], atomically +=) if w != NULL.  dres may be NULL.  Every access is a 16-byte row segment: D, lddy, ldx,
  * lddx and (with dres != NULL) lddres must be multiples of 8, else VDS_ERR_ARG and nothing is written (the grouped
- * call checks the same). */
+ * call checks the same).  B < 1 or L < 1: VDS_ERR_ARG. */
 int vds_rmsnorm_mod_bwd(const void* dy, int64_t lddy, const void* x, int64_t ldx, const void* w,
                         const float* mod, int64_t ldmod, int32_t shift_col, int32_t scale_col,
                         const float* rstd, const void* dres, int64_t lddres, void* dx, int64_t lddx,
@@ -264,7 +267,7 @@ int vds_rmsnorm_mod_bwd(const void* dy, int64_t lddy, const void* x, int64_t ldx
  *   dy = bf16(dx_new * gate[b]),  dmod[b, gate_col + n] += sum_l dx_new*y,
  *   dbias[n] (f32, atomically +=) += sum_{b,l} dy   if dbias != NULL.
  * D, lddxn, ldy and lddy must be multiples of 8 (16-byte row segments), else VDS_ERR_ARG and nothing is written; the
- * same holds for vds_gate_bwd_grouped and (lddxn, ldy, ldq) vds_gate_bwd_fp8. */
+ * same holds for vds_gate_bwd_grouped and (lddxn, ldy, ldq) vds_gate_bwd_fp8.  B < 1 or L < 1: VDS_ERR_ARG. */
 int vds_gate_bwd(const void* dxn, int64_t lddxn, const void* y, int64_t ldy, const float* mod,
                  int64_t ldmod, int32_t gate_col, void* dy, int64_t lddy, float* dmod, float* dbias,
                  int32_t B, int32_t L, int32_t D, vds_stream_t stream);

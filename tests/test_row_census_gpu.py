@@ -26,9 +26,12 @@ Instance -> cases (the lists and their predicates are in the helper; test_row_ce
   qkv_rope_bwd_kernel                rope_tok 0, (64, 68), H hd = 2112; all with mix 0 / 0 + add_dv0 / 1 / 2,
                                      atomics and deterministic                          test_qkv_bwd
   rope_apply_kernel                  hd = 32 72 128, L = 25, forward and inverse, strided views   test_rope_apply
+  the _grouped entries               (2, 21) x D = 384 520: groups NULL = the plain entry; one group per sample = the plain
+                                     form, deterministic                                test_grouped_entries_*, test_one_group_*
   return codes                       D = 2056, D = 12, a pad the kernels cannot write, leading dimensions off 8
                                                                                         test_refusals
 Each test prints the worst rstd error in fp32 ulps / the undecided share of its generic rows."""
+import ctypes as C
 import os
 import sys
 
@@ -319,6 +322,103 @@ def test_rope_apply(lib, ops, hd, inverse):
     expect = before.clone()
     expect[:, :, 1:L + 1, :hd] = want
     assert torch.equal(G.bits(yd.cpu()), G.bits(expect)), f"rope_apply hd {hd} inverse {inverse}"
+
+
+# ---- the grouped entries against the plain ones ------------------------------------------------------------------------
+GROUPED_BL = (2, 21)       # three 8-row blocks per sample, the last of 5 rows
+GROUPED_D = (384, 520)     # the four-rows-per-wave forward; two chunks per row with one lane in the second
+
+
+def row_calls(lib, D, form):
+    """forward, backward and gate backward of the dyadic cases at GROUPED_BL x D -> every output as the caller sees it.
+    form "plain": the plain entries; None: the grouped entries with a NULL description; (lead, period) that puts all L rows of
+    a sample into ONE group: the grouped entries on tables of two rows per sample, the rows of the empty groups NaN (mod) and
+    sentinel (dmod: returned apart, they must survive).  Guard bands and gaps are checked on every output."""
+    B, L = GROUPED_BL
+    grouped = form != "plain"
+    gr = None if form in ("plain", None) else C.byref(_lib.ModGroups(*form))
+    slot, per = (0, 1) if gr is None else ((1 if form[0] == 0 else 0), 2)  # the table row of sample b: per * b + slot
+    tail = ((gr,) if grouped else ()) + (stream(),)
+    entry = (lambda n: getattr(lib, n + "_grouped")) if grouped else (lambda n: getattr(lib, n))
+
+    def table(t, fill):
+        out = G.fill_value(t.dtype, fill).repeat(per * B, t.shape[1])
+        out[slot::per] = t
+        return Win(out, fill)
+
+    def rows(win, what):
+        G.assert_outside(win.dev, win.before, win.where, what)
+        return win.got()
+
+    def flat(f, what):
+        return f.check(f.initial, what, exact=False)
+
+    def split(dmod, what, res):
+        got = rows(dmod, what)
+        res[what], res[what + " of the empty groups"] = got[slot::per], got[1 - slot::per] if per == 2 else got[:0]
+
+    res = {}
+    c = R.fwd_case(B, L, D, True)
+    x, mod, w = Win(c.x, "nan"), table(c.mod, "nan"), Flat(c.w, "nan")
+    y, rstd = out_bf16(B * L, D), Flat(blank_f32(B * L), "sentinel")
+    rc = entry("vds_rmsnorm_mod_fwd")(x.ptr, x.ld, w.ptr, mod.ptr, mod.ld, 0, 2 * D, y.ptr, y.ld, rstd.ptr, B, L, D, R.EPS,
+                                      *tail)
+    assert rc == 0, ("fwd", form, rc)
+    res["y"], res["rstd"] = rows(y, "y"), flat(rstd, "rstd")
+
+    c = R.bwd_case(B, L, D, True, True, "dyadic")
+    dy, x, mod, w = Win(c.dy, "nan"), Win(c.x, "nan"), table(c.mod, "nan"), Flat(c.w, "nan")
+    dres, rstd, dx = Win(c.dres, "nan"), Flat(c.rstd, "nan"), out_bf16(B * L, D)
+    dmod, dw = table(c.dmod0, "sentinel"), Flat(c.dw0, "sentinel")
+    rc = entry("vds_rmsnorm_mod_bwd")(dy.ptr, dy.ld, x.ptr, x.ld, w.ptr, mod.ptr, mod.ld, 0, 2 * D, rstd.ptr, dres.ptr, dres.ld,
+                                      dx.ptr, dx.ld, dmod.ptr, dw.ptr, B, L, D, *tail)
+    assert rc == 0, ("bwd", form, rc)
+    res["dx"], res["dw"] = rows(dx, "dx"), flat(dw, "dw")
+    split(dmod, "dmod", res)
+
+    c = R.gate_case(B, L, D)
+    dxn, yy, mod = Win(c.dxn, "nan"), Win(c.y, "nan"), table(c.mod, "nan")
+    dyo, dmod, dbias = out_bf16(B * L, D), table(c.dmod0, "sentinel"), Flat(c.dbias0, "sentinel")
+    rc = entry("vds_gate_bwd")(dxn.ptr, dxn.ld, yy.ptr, yy.ld, mod.ptr, mod.ld, 2 * D, dyo.ptr, dyo.ld, dmod.ptr, dbias.ptr, B, L,
+                               D, *tail)
+    assert rc == 0, ("gate", form, rc)
+    res["gate dy"], res["dbias"] = rows(dyo, "gate dy"), flat(dbias, "dbias")
+    split(dmod, "gate dmod", res)
+    torch.cuda.synchronize()
+    return res
+
+
+def same_bits(a, b, what):
+    assert sorted(a) == sorted(b)
+    for k in a:
+        assert a[k].shape == b[k].shape and torch.equal(G.bits(a[k]), G.bits(b[k])), f"{what}: {k} differs"
+
+
+@pytest.mark.parametrize("det", [False, True], ids=["atomics", "deterministic"])
+@pytest.mark.parametrize("D", GROUPED_D)
+def test_grouped_entries_without_a_description_are_the_plain_entries(ops, lib, D, det):
+    """groups == NULL forwards: every output of the three grouped entries has the plain entry's bits (dyadic cases: the column
+    sums are exact, so the atomics' order does not show)"""
+    with Deterministic(ops, det):
+        plain = row_calls(lib, D, "plain")
+        same_bits(plain, row_calls(lib, D, None), f"groups NULL, D {D}, det {det}")
+    c = R.bwd_case(*GROUPED_BL, D, True, True, "dyadic")   # and they are the census's bits
+    assert torch.equal(G.bits(plain["dmod"]), G.bits(c.want_dmod)) and torch.equal(G.bits(plain["dx"]), G.bits(c.want_dx))
+
+
+@pytest.mark.parametrize("form", [(0, 1), (GROUPED_BL[1], 1)], ids=["all_rows_in_group_1", "all_rows_in_group_0"])
+@pytest.mark.parametrize("D", GROUPED_D)
+def test_one_group_per_sample_is_the_plain_form_in_deterministic_mode(ops, lib, D, form):
+    """deterministic mode: with one non-empty group per sample the grouped grid is the plain grid plus workgroups that leave
+    zeros, and the fixed-order sums add them in place -- dmod, dw and dbias (and y, rstd, dx, dy) equal the plain form's bit
+    for bit; the dmod rows of the empty groups are not written"""
+    with Deterministic(ops, True):
+        plain, one = row_calls(lib, D, "plain"), row_calls(lib, D, form)
+    for k in ("dmod", "gate dmod"):
+        empty = one.pop(k + " of the empty groups")
+        assert empty.shape == plain[k].shape and torch.all(G.bits(empty) == G.SENTINEL_F32), f"{k}: an empty group's row changed"
+        plain.pop(k + " of the empty groups")
+    same_bits(plain, one, f"groups {form}, D {D}")
 
 
 # ---- return codes ------------------------------------------------------------------------------------------------------

@@ -2509,18 +2509,11 @@ int with_head_dim(int hd, F&& f) {
 }
 
 // ---- launching ----------------------------------------------------------------------------------------------------------
-// One launch of 256-thread workgroups.  The kernel is a template argument, so the limit on its dynamic LDS is raised where it
-// is launched, before its first launch and once per instantiation (the initialisation of a function-local static is done
-// exactly once, also under concurrent callers): an instance that has a launch site has the attribute.  The tiles of head dim
-// 128 take 64 KiB and more, past the default limit.
+// One launch of 256-thread workgroups that take exactly LDS bytes of dynamic LDS: vds_launch (common.h) raises the kernel's
+// limit to that before its first launch.  The tiles of head dim 128 take 64 KiB and more, past the default limit.
 template <auto KERNEL, int LDS>
 void launch(unsigned grid, hipStream_t s, const AttnP& p) {
-  if constexpr (LDS > 0) {
-    static const hipError_t raised =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    (void)raised;
-  }
-  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), LDS, s, p);
+  vds_launch<KERNEL, LDS>(dim3(grid), dim3(256), LDS, s, p);
 }
 
 // what every runner returns after its last launch

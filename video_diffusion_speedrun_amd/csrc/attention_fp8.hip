@@ -1210,11 +1210,6 @@ int tail_last_for(int L, int tile) {
   return (vdscfg::geti(vdscfg::ATTN_TAIL_LAST) && L > tile && (L % tile) != 0) ? 1 : 0;
 }
 
-template <typename K>
-void set_lds(K kern, int bytes) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
 bool args_ok(const vds_attn_fp8_args* a, bool bwd) {
   if (!a || !a->q || !a->k || !a->v || !a->deq || a->B <= 0 || a->H <= 0 || a->Lq <= 0 || a->Lk <= 0) return false;
   if ((long)a->Lq * ROWB > 0x7fffffffL || (long)a->Lk * ROWB > 0x7fffffffL) return false;
@@ -1267,8 +1262,6 @@ extern "C" int vds_attn_fp8_fwd(const vds_attn_fp8_args* a, vds_stream_t stream)
   if (!args_ok(a, false)) return VDS_ERR_ARG;
   if (a->head_dim != 72) return VDS_ERR_UNSUPPORTED;
   constexpr int LDS = 4 * TILE;
-  static bool once = false;
-  if (!once) { set_lds(attn8_fwd_kernel<72>, LDS); once = true; }
   Attn8P p = to_p(a);
   p.dqq = nullptr;
   p.n_rt = cdiv(p.Lq, 256);
@@ -1277,7 +1270,7 @@ extern "C" int vds_attn_fp8_fwd(const vds_attn_fp8_args* a, vds_stream_t stream)
   hipStream_t s = (hipStream_t)stream;
   vdsprof::Scope ps(VDS_PROF_ATTN_FP8_FWD, s, 4.0 * p.B * p.H * (double)p.Lq * p.Lk * p.hd,
                     (double)p.B * p.H * (ROWB * (p.Lq + 2.0 * p.Lk) + 2.0 * p.hd * p.Lq));
-  hipLaunchKernelGGL((attn8_fwd_kernel<72>), dim3(grid), dim3(256), LDS, s, p);
+  vds_launch<attn8_fwd_kernel<72>, LDS>(dim3(grid), dim3(256), LDS, s, p);
   return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
 }
 
@@ -1308,13 +1301,6 @@ extern "C" int vds_attn_fp8_bwd(const vds_attn_fp8_args* a, vds_stream_t stream)
   if (!args_ok(a, true)) return VDS_ERR_ARG;
   if (a->head_dim != 72) return VDS_ERR_UNSUPPORTED;
   constexpr int LDS_DKV = 4 * TILE + 2 * 1024, LDS_DQ = 4 * TILE;
-  static bool once = false;
-  if (!once) {
-    set_lds(attn8_bwd_dkv_kernel<72>, LDS_DKV);
-    set_lds(attn8_bwd_dq_kernel<72, 4>, LDS_DQ);
-    set_lds(attn8_bwd_dq_kernel<72, 6>, LDS_DQ);
-    once = true;
-  }
   Attn8P p = to_p(a);
   p.oq = nullptr;
   hipStream_t s = (hipStream_t)stream;
@@ -1325,7 +1311,7 @@ extern "C" int vds_attn_fp8_bwd(const vds_attn_fp8_args* a, vds_stream_t stream)
   int grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
   {
     vdsprof::Scope ps(VDS_PROF_ATTN_FP8_DKV, s, 2.0 * prod, bytes + 4.0 * p.B * p.H * p.hd * (double)p.Lk);
-    hipLaunchKernelGGL((attn8_bwd_dkv_kernel<72>), dim3(grid), dim3(256), LDS_DKV, s, p);
+    vds_launch<attn8_bwd_dkv_kernel<72>, LDS_DKV>(dim3(grid), dim3(256), LDS_DKV, s, p);
   }
   // knob attn8_dq_waves = 4 | 6 (experiments); measured (B=6, L=8208): 2.0 ms with 4 waves, 2.7 ms with 6
   const int dq_waves = vdscfg::geti(vdscfg::ATTN8_DQ_WAVES) == 6 ? 6 : 4;
@@ -1334,8 +1320,8 @@ extern "C" int vds_attn_fp8_bwd(const vds_attn_fp8_args* a, vds_stream_t stream)
   grid = cdiv(p.B * p.H, 8) * 8 * p.n_rt;
   {
     vdsprof::Scope ps(VDS_PROF_ATTN_FP8_DQ, s, 2.0 * prod, bytes + 2.0 * p.B * p.H * p.hd * (double)p.Lq);
-    if (dq_waves == 6) hipLaunchKernelGGL((attn8_bwd_dq_kernel<72, 6>), dim3(grid), dim3(384), LDS_DQ, s, p);
-    else hipLaunchKernelGGL((attn8_bwd_dq_kernel<72, 4>), dim3(grid), dim3(256), LDS_DQ, s, p);
+    if (dq_waves == 6) vds_launch<attn8_bwd_dq_kernel<72, 6>, LDS_DQ>(dim3(grid), dim3(384), LDS_DQ, s, p);
+    else vds_launch<attn8_bwd_dq_kernel<72, 4>, LDS_DQ>(dim3(grid), dim3(256), LDS_DQ, s, p);
   }
   return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
 }
@@ -1358,18 +1344,13 @@ extern "C" int vds_qkv_rope_fwd_fp8(const void* qkv, const float* cosb, const fl
   if (tile > 0 && hd == 72 && hdp == 96 && H <= 256 && L >= 8 &&
       ropestage::lds_bytes(tile == 2 ? 2 : tile == 8 ? 8 : 4, H * 72) <= 160 * 1024) {  // else: the element-wise kernel
     const long ntok = (long)B * L;
-#define ROPE8_TILE(T)                                                                                               \
-  do {                                                                                                              \
-    static bool attr = false;                                                                                       \
-    if (!attr) {                                                                                                    \
-      set_lds(qkv_rope_fwd_fp8_tile_kernel<72, 96, T>, 160 * 1024);                                                 \
-      attr = true;                                                                                                  \
-    }                                                                                                               \
-    hipLaunchKernelGGL((qkv_rope_fwd_fp8_tile_kernel<72, 96, T>), dim3((unsigned)((ntok + T - 1) / T)), dim3(256),  \
-                       ropestage::lds_bytes(T, H * 72), s, (const bf16_t*)qkv, cosb, sinb, (const bf16_t*)v0,       \
-                       (const bf16_t*)lam, (unsigned char*)q8, (unsigned char*)k8, (unsigned char*)v8,              \
-                       (bf16_t*)v_out, amax_prev, amax_cur, amax_stride, deq, ntok, L, H, 0);                       \
-    return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;                                               \
+#define ROPE8_TILE(T)                                                                                              \
+  do {                                                                                                             \
+    vds_launch<qkv_rope_fwd_fp8_tile_kernel<72, 96, T>, 160 * 1024>(                                               \
+        dim3((unsigned)((ntok + T - 1) / T)), dim3(256), ropestage::lds_bytes(T, H * 72), s, (const bf16_t*)qkv,   \
+        cosb, sinb, (const bf16_t*)v0, (const bf16_t*)lam, (unsigned char*)q8, (unsigned char*)k8,                 \
+        (unsigned char*)v8, (bf16_t*)v_out, amax_prev, amax_cur, amax_stride, deq, ntok, L, H, 0);                 \
+    return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;                                              \
   } while (0)
     if (tile == 2) ROPE8_TILE(2);
     else if (tile == 8) ROPE8_TILE(8);
@@ -1394,22 +1375,16 @@ extern "C" int vds_cross_qkv_fp8(const void* q, const void* kv, void* q8, void* 
   if (hd != 72 || H > 256 || Lq < T || Lk < T) return VDS_ERR_UNSUPPORTED;  // (a tile of T tokens spans at most two samples)
   if ((T * 4 * H * 72 + 1023) / 1024 * 1024 > 160 * 1024) return VDS_ERR_UNSUPPORTED;  // the kv rows of a tile must fit the LDS
   hipStream_t s = (hipStream_t)stream;
-  static bool attr = false;
-  if (!attr) {
-    set_lds(qkv_rope_fwd_fp8_tile_kernel<72, 96, T, 1, false>, 160 * 1024);
-    set_lds(qkv_rope_fwd_fp8_tile_kernel<72, 96, T, 2, false>, 160 * 1024);
-    attr = true;
-  }
   vdsprof::Scope ps(VDS_PROF_QKV_ROPE_FWD, s, 0.0, (double)B * H * ((double)Lq + 2.0 * Lk) * (2.0 * hd + ROWB));
   const int D = H * 72;
   const long nq = (long)B * Lq, nk = (long)B * Lk;
-  hipLaunchKernelGGL((qkv_rope_fwd_fp8_tile_kernel<72, 96, T, 1, false>), dim3((unsigned)((nq + T - 1) / T)), dim3(256),
-                     (T * 2 * D + 1023) / 1024 * 1024, s, (const bf16_t*)q, (const float*)nullptr, (const float*)nullptr,
-                     (const bf16_t*)nullptr, (const bf16_t*)nullptr, (unsigned char*)q8, (unsigned char*)k8,
-                     (unsigned char*)v8, (bf16_t*)nullptr, amax_prev, amax_cur, amax_stride, deq, nq, Lq, H, 0);
-  hipLaunchKernelGGL((qkv_rope_fwd_fp8_tile_kernel<72, 96, T, 2, false>), dim3((unsigned)((nk + T - 1) / T)), dim3(256),
-                     (T * 4 * D + 1023) / 1024 * 1024, s, (const bf16_t*)kv, (const float*)nullptr, (const float*)nullptr,
-                     (const bf16_t*)nullptr, (const bf16_t*)nullptr, (unsigned char*)q8, (unsigned char*)k8,
-                     (unsigned char*)v8, (bf16_t*)nullptr, amax_prev, amax_cur, amax_stride, deq, nk, Lk, H, 1);
+  vds_launch<qkv_rope_fwd_fp8_tile_kernel<72, 96, T, 1, false>, 160 * 1024>(
+      dim3((unsigned)((nq + T - 1) / T)), dim3(256), (T * 2 * D + 1023) / 1024 * 1024, s, (const bf16_t*)q,
+      (const float*)nullptr, (const float*)nullptr, (const bf16_t*)nullptr, (const bf16_t*)nullptr, (unsigned char*)q8,
+      (unsigned char*)k8, (unsigned char*)v8, (bf16_t*)nullptr, amax_prev, amax_cur, amax_stride, deq, nq, Lq, H, 0);
+  vds_launch<qkv_rope_fwd_fp8_tile_kernel<72, 96, T, 2, false>, 160 * 1024>(
+      dim3((unsigned)((nk + T - 1) / T)), dim3(256), (T * 4 * D + 1023) / 1024 * 1024, s, (const bf16_t*)kv,
+      (const float*)nullptr, (const float*)nullptr, (const bf16_t*)nullptr, (const bf16_t*)nullptr, (unsigned char*)q8,
+      (unsigned char*)k8, (unsigned char*)v8, (bf16_t*)nullptr, amax_prev, amax_cur, amax_stride, deq, nk, Lk, H, 1);
   return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
 }

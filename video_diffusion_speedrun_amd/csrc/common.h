@@ -205,5 +205,22 @@ const char* get();
 void clear();
 }  // namespace vdserr
 
+// ---- launching ------------------------------------------------------------------------------------------------------
+// One kernel launch.  The kernel is a template argument, so the limit on its dynamic LDS (MAX_LDS bytes; 0: the default
+// limit of 64 KiB is enough) is raised where it is launched, before its first launch and exactly once per kernel
+// instantiation: the initialisation of a function-local static is done once, also under concurrent callers.  An instance
+// that has a launch site has the attribute; none is raised for an instance that is never launched.
+template <auto KERNEL, int MAX_LDS>
+inline void vds_raise_lds_limit() {
+  static const hipError_t raised =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS);
+  (void)raised;
+}
+template <auto KERNEL, int MAX_LDS, typename... Args>
+inline void vds_launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+  if constexpr (MAX_LDS > 0) vds_raise_lds_limit<KERNEL, MAX_LDS>();
+  hipLaunchKernelGGL(KERNEL, grid, block, lds, s, args...);
+}
+
 static inline unsigned clamp_u32(size_t v) { return v > 0xffffffffull ? 0xffffffffu : (unsigned)v; }
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }

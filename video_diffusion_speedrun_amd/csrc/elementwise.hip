@@ -1760,56 +1760,66 @@ static bool rmsnorm_q4(int D) {
   return vdscfg::geti(vdscfg::RMSNORM_Q4) != 0;
 }
 
-extern "C" int vds_rmsnorm_mod_fwd(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod,
-                                   int32_t shift_col, int32_t scale_col, void* y, int64_t ldy, float* rstd,
-                                   int32_t B, int32_t L, int32_t D, float eps, vds_stream_t stream) {
-  if (!x || !mod || !y || !rstd || (D & 7) || (ldx & 7) || (ldy & 7) || (shift_col & 3) || (scale_col & 3) || (ldmod & 3))
-    return VDS_ERR_ARG;
-  const long rows = (long)B * L;
-  hipStream_t s = (hipStream_t)stream;
-  vdsprof::Scope ps(VDS_PROF_RMSNORM_FWD, s, 0.0, 4.0 * rows * D + 4.0 * rows);
-  if (rmsnorm_q4(D)) {  // DiT-S / B / XL widths: four rows per wave, every lane of every instruction at work
-#define CALLQ(NCQ)                                                                                             \
-  hipLaunchKernelGGL((rmsnorm_mod_fwd_q4_kernel<NCQ>), dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s,     \
-                     (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col,   \
-                     (bf16_t*)y, (long)ldy, rstd, B, L, eps, QOut{}, MGrp{})
-    if (D == 384) CALLQ(3);
-    else if (D == 768) CALLQ(6);
-    else CALLQ(9);
-#undef CALLQ
-    return ok();
-  }
-#define CALL(NC)                                                                                              \
-  hipLaunchKernelGGL((rmsnorm_mod_fwd_kernel<NC>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,          \
-                     (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col, \
-                     (bf16_t*)y, (long)ldy, rstd, B, L, D, eps, QOut{}, MGrp{})
-  NC_DISPATCH(D, CALL);
-#undef CALL
-  return ok();
-}
-
 // a group description that fits L rows per sample (include/vds.h: vds_mod_groups)
 static bool groups_ok(const vds_mod_groups* g, int L) {
   return g->lead >= 0 && g->period >= 1 && g->lead <= L && (L - g->lead) % g->period == 0;
 }
+static bool qout_ok(const void* q, int64_t ldq, int32_t fmt, const float* amax_in) {
+  return q && amax_in && !(ldq & 7) && (fmt == 0 || fmt == 1);
+}
 
-extern "C" int vds_rmsnorm_mod_fwd_grouped(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod,
-                                           int32_t shift_col, int32_t scale_col, void* y, int64_t ldy, float* rstd,
-                                           int32_t B, int32_t L, int32_t D, float eps, const vds_mod_groups* groups,
-                                           vds_stream_t stream) {
-  if (!groups) return vds_rmsnorm_mod_fwd(x, ldx, w, mod, ldmod, shift_col, scale_col, y, ldy, rstd, B, L, D, eps, stream);
-  if (!x || !mod || !y || !rstd || (D & 7) || (ldx & 7) || (ldy & 7) || (shift_col & 3) || (scale_col & 3) || (ldmod & 3) ||
-      B < 1 || L < 1 || !groups_ok(groups, L))
-    return VDS_ERR_ARG;
+// ---- RMSNorm / gate backward: one runner per kernel family ------------------------------------------------------------------
+// <QF, GRP> are the kernels' own flags: QF = -1 writes bf16, 0 / 1 writes fp8 (e4m3fn / e5m2) through `qo`; GRP reads the
+// modulation row of a row's group.  The instances that exist are <-1, false> (the plain entries), <-1, true> (_grouped)
+// and <0, false>, <1, false> (_fp8): an entry applies its forwarding rule (groups == NULL -> the plain form, fmt -> QF),
+// checks what only it takes (qout_ok) and makes one call.  Every runner refuses B < 1 or L < 1.
+
+// A grid of row blocks per modulation row: the plain form is the grouped one with a modulation row per sample (BG = B)
+// that holds all L rows; a grouped workgroup walks rows of ONE group, so the x dimension covers the LARGEST group (the
+// workgroups past a smaller group's end leave at once).  The deterministic partials are sized by this grid.
+struct RowGrid { long BG; int rpb; dim3 grid; MGrp mg; };
+template <bool GRP>
+static bool row_grid(int B, int L, const vds_mod_groups* groups, RowGrid& g) {
+  g.BG = B;
+  g.mg = MGrp{};
+  int nmax = L;
+  if constexpr (GRP) {
+    if (!groups_ok(groups, L)) return false;
+    g.BG = (long)B * (1 + groups->period);
+    if (g.BG > 65535) return false;  // (the modulation rows are the grid's y dimension; a kernel requirement of GRP only)
+    g.mg = MGrp{groups->lead, groups->period};
+    nmax = max(groups->lead, (L - groups->lead) / groups->period);
+  }
+  g.rpb = rows_per_block_for(nmax, (int)g.BG);
+  g.grid = dim3((nmax + g.rpb - 1) / g.rpb, (unsigned)g.BG);
+  return true;
+}
+
+// out_bytes: what the profiler credits per element (4.0: bf16 in and out; 3.0: fp8 out)
+template <int QF, bool GRP>
+static int rmsnorm_fwd_run(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod, int32_t shift_col,
+                           int32_t scale_col, void* y, int64_t ldy, float* rstd, int32_t B, int32_t L, int32_t D, float eps,
+                           const QOut& qo, const vds_mod_groups* groups, double out_bytes, vds_stream_t stream) {
+  if (!x || !mod || !rstd || (D & 7) || (ldx & 7) || B < 1 || L < 1) return VDS_ERR_ARG;
+  // the forward's own check: a row's shift and scale are read in 16-byte pieces of the fp32 table (the backward entries
+  // have never asked for this alignment and still do not: their dmod columns are reached by single-float adds)
+  if ((shift_col & 3) || (scale_col & 3) || (ldmod & 3)) return VDS_ERR_ARG;
+  if constexpr (QF < 0) {  // the fp8 forms write through qo and do not look at y / ldy
+    if (!y || (ldy & 7)) return VDS_ERR_ARG;
+  }
+  MGrp mg{};
+  if constexpr (GRP) {
+    if (!groups_ok(groups, L)) return VDS_ERR_ARG;
+    mg = MGrp{groups->lead, groups->period};
+  }
   const long rows = (long)B * L;
-  const MGrp mg{groups->lead, groups->period};
   hipStream_t s = (hipStream_t)stream;
-  vdsprof::Scope ps(VDS_PROF_RMSNORM_FWD, s, 0.0, 4.0 * rows * D + 4.0 * rows);
-  if (rmsnorm_q4(D)) {
+  vdsprof::Scope ps(VDS_PROF_RMSNORM_FWD, s, 0.0, out_bytes * rows * D + 4.0 * rows);
+  if (rmsnorm_q4(D)) {  // DiT-S / B / XL widths: four rows per wave, every lane of every instruction at work
 #define CALLQ(NCQ)                                                                                                      \
-  hipLaunchKernelGGL((rmsnorm_mod_fwd_q4_kernel<NCQ, -1, true>), dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s,      \
+  hipLaunchKernelGGL((rmsnorm_mod_fwd_q4_kernel<NCQ, QF, GRP>), dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s,     \
                      (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col, (bf16_t*)y, \
-                     (long)ldy, rstd, B, L, eps, QOut{}, mg)
+                     (long)ldy, rstd, B, L, eps, qo, mg)
     if (D == 384) CALLQ(3);
     else if (D == 768) CALLQ(6);
     else CALLQ(9);
@@ -1817,124 +1827,113 @@ extern "C" int vds_rmsnorm_mod_fwd_grouped(const void* x, int64_t ldx, const voi
     return ok();
   }
 #define CALL(NC)                                                                                                        \
-  hipLaunchKernelGGL((rmsnorm_mod_fwd_kernel<NC, -1, true>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,            \
+  hipLaunchKernelGGL((rmsnorm_mod_fwd_kernel<NC, QF, GRP>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,           \
                      (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col, (bf16_t*)y, \
-                     (long)ldy, rstd, B, L, D, eps, QOut{}, mg)
+                     (long)ldy, rstd, B, L, D, eps, qo, mg)
   NC_DISPATCH(D, CALL);
 #undef CALL
   return ok();
 }
 
-static bool qout_ok(const void* q, int64_t ldq, int32_t fmt, const float* amax_in) {
-  return q && amax_in && !(ldq & 7) && (fmt == 0 || fmt == 1);
+// name: the entry's own, for the deterministic workspace's error message
+template <bool GRP>
+static int rmsnorm_bwd_run(const void* dy, int64_t lddy, const void* x, int64_t ldx, const void* w, const float* mod,
+                           int64_t ldmod, int32_t shift_col, int32_t scale_col, const float* rstd, const void* dres,
+                           int64_t lddres, void* dx, int64_t lddx, float* dmod, float* dw, int32_t B, int32_t L, int32_t D,
+                           const vds_mod_groups* groups, const char* name, vds_stream_t stream) {
+  if (!dy || !x || !mod || !rstd || !dx || !dmod || (D & 7) || (lddy & 7) || (ldx & 7) || (lddx & 7) || B < 1 || L < 1)
+    return VDS_ERR_ARG;
+  if (w && !dw) return VDS_ERR_ARG;
+  if (dres && (lddres & 7)) return VDS_ERR_ARG;  // (16-byte row segments, as every other operand; not read without dres)
+  RowGrid g;
+  if (!row_grid<GRP>(B, L, groups, g)) return VDS_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const long plane = g.BG * g.grid.x * D;
+  float* det = nullptr;
+  if (vdsdet::on() && !(det = vdsdet::workspace((size_t)(w ? 3 : 2) * plane, name))) return VDS_ERR_ARG;
+  vdsprof::Scope ps(VDS_PROF_RMSNORM_BWD, s, 0.0, (dres ? 8.0 : 6.0) * B * L * D + 4.0 * B * L);
+#define CALL_W(NC, HAS_W)                                                                                               \
+  hipLaunchKernelGGL((rmsnorm_mod_bwd_kernel<NC, HAS_W, GRP>), g.grid, dim3(256), 0, s, (const bf16_t*)dy, (long)lddy,   \
+                     (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col, rstd,       \
+                     (const bf16_t*)dres, (long)lddres, (bf16_t*)dx, (long)lddx, dmod, w ? dw : (float*)nullptr, B, L,  \
+                     D, g.rpb, det, g.mg)
+#define CALL(NC)                 \
+  do {                           \
+    if (w) CALL_W(NC, true);     \
+    else CALL_W(NC, false);      \
+  } while (0)
+  NC_DISPATCH(D, CALL);
+#undef CALL
+#undef CALL_W
+  if (det) {
+    det_finish(det, (int)g.grid.x, D, dmod + shift_col, ldmod, (int)g.BG, s);
+    det_finish(det + plane, (int)g.grid.x, D, dmod + scale_col, ldmod, (int)g.BG, s);
+    if (w) det_finish(det + 2 * plane, (int)(g.BG * g.grid.x), D, dw, 0, 1, s);
+  }
+  return ok();
 }
 
+// bytes: what the profiler credits per element (6.0: bf16 dy out; 5.0: fp8 out)
+template <int QF, bool GRP>
+static int gate_bwd_run(const void* dxn, int64_t lddxn, const void* y, int64_t ldy, const float* mod, int64_t ldmod,
+                        int32_t gate_col, void* dy, int64_t lddy, float* dmod, float* dbias, int32_t B, int32_t L,
+                        int32_t D, const QOut& qo, const vds_mod_groups* groups, double bytes, const char* name,
+                        vds_stream_t stream) {
+  if (!dxn || !y || !mod || !dmod || (D & 7) || (lddxn & 7) || (ldy & 7) || B < 1 || L < 1) return VDS_ERR_ARG;
+  if constexpr (QF < 0) {  // the fp8 form writes through qo and does not look at dy / lddy
+    if (!dy || (lddy & 7)) return VDS_ERR_ARG;
+  }
+  RowGrid g;
+  if (!row_grid<GRP>(B, L, groups, g)) return VDS_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const long plane = g.BG * g.grid.x * D;
+  float* det = nullptr;
+  if (vdsdet::on() && !(det = vdsdet::workspace((size_t)2 * plane, name))) return VDS_ERR_ARG;
+  vdsprof::Scope ps(VDS_PROF_GATE_BWD, s, 0.0, bytes * B * L * D);
+#define CALL(NC)                                                                                                     \
+  hipLaunchKernelGGL((gate_bwd_kernel<NC, QF, GRP>), g.grid, dim3(256), 0, s, (const bf16_t*)dxn, (long)lddxn,        \
+                     (const bf16_t*)y, (long)ldy, mod, (long)ldmod, gate_col, (bf16_t*)dy, (long)lddy, dmod, dbias, B, \
+                     L, D, g.rpb, qo, det, g.mg)
+  NC_DISPATCH(D, CALL);
+#undef CALL
+  if (det) {
+    det_finish(det, (int)g.grid.x, D, dmod + gate_col, ldmod, (int)g.BG, s);
+    if (dbias) det_finish(det + plane, (int)(g.BG * g.grid.x), D, dbias, 0, 1, s);
+  }
+  return ok();
+}
+
+extern "C" int vds_rmsnorm_mod_fwd(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod,
+                                   int32_t shift_col, int32_t scale_col, void* y, int64_t ldy, float* rstd,
+                                   int32_t B, int32_t L, int32_t D, float eps, vds_stream_t stream) {
+  return rmsnorm_fwd_run<-1, false>(x, ldx, w, mod, ldmod, shift_col, scale_col, y, ldy, rstd, B, L, D, eps, QOut{}, nullptr,
+                                    4.0, stream);
+}
+extern "C" int vds_rmsnorm_mod_fwd_grouped(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod,
+                                           int32_t shift_col, int32_t scale_col, void* y, int64_t ldy, float* rstd,
+                                           int32_t B, int32_t L, int32_t D, float eps, const vds_mod_groups* groups,
+                                           vds_stream_t stream) {
+  if (!groups) return vds_rmsnorm_mod_fwd(x, ldx, w, mod, ldmod, shift_col, scale_col, y, ldy, rstd, B, L, D, eps, stream);
+  return rmsnorm_fwd_run<-1, true>(x, ldx, w, mod, ldmod, shift_col, scale_col, y, ldy, rstd, B, L, D, eps, QOut{}, groups,
+                                   4.0, stream);
+}
 extern "C" int vds_rmsnorm_mod_fwd_fp8(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod,
                                        int32_t shift_col, int32_t scale_col, void* q, int64_t ldq, int32_t fmt,
                                        const float* amax_in, float* amax_part, float* dq_out, float* rstd, int32_t B,
                                        int32_t L, int32_t D, float eps, vds_stream_t stream) {
-  if (!x || !mod || !rstd || (D & 7) || (ldx & 7) || (shift_col & 3) || (scale_col & 3) || (ldmod & 3) ||
-      !qout_ok(q, ldq, fmt, amax_in))
-    return VDS_ERR_ARG;
-  const long rows = (long)B * L;
-  hipStream_t s = (hipStream_t)stream;
+  if (!qout_ok(q, ldq, fmt, amax_in)) return VDS_ERR_ARG;
   const QOut qo{(unsigned char*)q, (long)ldq, amax_in, amax_part, dq_out};
-  vdsprof::Scope ps(VDS_PROF_RMSNORM_FWD, s, 0.0, 3.0 * rows * D + 4.0 * rows);
-  if (rmsnorm_q4(D)) {
-#define CALLQ(NCQ)                                                                                               \
-  do {                                                                                                           \
-    if (fmt == 0)                                                                                                \
-      hipLaunchKernelGGL((rmsnorm_mod_fwd_q4_kernel<NCQ, 0>), dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s, \
-                         (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col,   \
-                         (bf16_t*)nullptr, 0L, rstd, B, L, eps, qo, MGrp{});                                             \
-    else                                                                                                         \
-      hipLaunchKernelGGL((rmsnorm_mod_fwd_q4_kernel<NCQ, 1>), dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s, \
-                         (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col,   \
-                         (bf16_t*)nullptr, 0L, rstd, B, L, eps, qo, MGrp{});                                             \
-  } while (0)
-    if (D == 384) CALLQ(3);
-    else if (D == 768) CALLQ(6);
-    else CALLQ(9);
-#undef CALLQ
-    return ok();
-  }
-#define CALL(NC)                                                                                               \
-  do {                                                                                                         \
-    if (fmt == 0)                                                                                              \
-      hipLaunchKernelGGL((rmsnorm_mod_fwd_kernel<NC, 0>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,    \
-                         (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col, \
-                         (bf16_t*)nullptr, 0L, rstd, B, L, D, eps, qo, MGrp{});                                        \
-    else                                                                                                       \
-      hipLaunchKernelGGL((rmsnorm_mod_fwd_kernel<NC, 1>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,    \
-                         (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col, \
-                         (bf16_t*)nullptr, 0L, rstd, B, L, D, eps, qo, MGrp{});                                        \
-  } while (0)
-  NC_DISPATCH(D, CALL);
-#undef CALL
-  return ok();
+  return (fmt == 0 ? rmsnorm_fwd_run<0, false> : rmsnorm_fwd_run<1, false>)(
+      x, ldx, w, mod, ldmod, shift_col, scale_col, nullptr, 0, rstd, B, L, D, eps, qo, nullptr, 3.0, stream);
 }
 
 extern "C" int vds_rmsnorm_mod_bwd(const void* dy, int64_t lddy, const void* x, int64_t ldx, const void* w,
                                    const float* mod, int64_t ldmod, int32_t shift_col, int32_t scale_col,
                                    const float* rstd, const void* dres, int64_t lddres, void* dx, int64_t lddx,
                                    float* dmod, float* dw, int32_t B, int32_t L, int32_t D, vds_stream_t stream) {
-  if (!dy || !x || !mod || !rstd || !dx || !dmod || (D & 7) || (lddy & 7) || (ldx & 7) || (lddx & 7)) return VDS_ERR_ARG;
-  if (w && !dw) return VDS_ERR_ARG;
-  if (dres && (lddres & 7)) return VDS_ERR_ARG;  // (16-byte row segments, as every other operand)
-  const int rpb = rows_per_block_for(L, B);
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid((L + rpb - 1) / rpb, B);
-  float* det = nullptr;
-  if (vdsdet::on() && !(det = vdsdet::workspace((size_t)(w ? 3 : 2) * B * grid.x * D, "vds_rmsnorm_mod_bwd"))) return VDS_ERR_ARG;
-  vdsprof::Scope ps(VDS_PROF_RMSNORM_BWD, s, 0.0, (dres ? 8.0 : 6.0) * B * L * D + 4.0 * B * L);
-#define CALL(NC)                                                                                                  \
-  do {                                                                                                            \
-    if (w)                                                                                                        \
-      hipLaunchKernelGGL((rmsnorm_mod_bwd_kernel<NC, true>), grid, dim3(256), 0, s, (const bf16_t*)dy, (long)lddy, \
-                         (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col, scale_col,   \
-                         rstd, (const bf16_t*)dres, (long)lddres, (bf16_t*)dx, (long)lddx, dmod, dw, B, L, D, rpb, det, MGrp{}); \
-    else                                                                                                          \
-      hipLaunchKernelGGL((rmsnorm_mod_bwd_kernel<NC, false>), grid, dim3(256), 0, s, (const bf16_t*)dy, (long)lddy, \
-                         (const bf16_t*)x, (long)ldx, (const bf16_t*)nullptr, mod, (long)ldmod, shift_col,        \
-                         scale_col, rstd, (const bf16_t*)dres, (long)lddres, (bf16_t*)dx, (long)lddx, dmod,       \
-                         (float*)nullptr, B, L, D, rpb, det, MGrp{});                                                     \
-  } while (0)
-  NC_DISPATCH(D, CALL);
-#undef CALL
-  if (det) {
-    const long plane = (long)B * grid.x * D;
-    det_finish(det, (int)grid.x, D, dmod + shift_col, ldmod, B, s);
-    det_finish(det + plane, (int)grid.x, D, dmod + scale_col, ldmod, B, s);
-    if (w) det_finish(det + 2 * plane, (int)(B * grid.x), D, dw, 0, 1, s);
-  }
-  return ok();
+  return rmsnorm_bwd_run<false>(dy, lddy, x, ldx, w, mod, ldmod, shift_col, scale_col, rstd, dres, lddres, dx, lddx, dmod, dw,
+                                B, L, D, nullptr, "vds_rmsnorm_mod_bwd", stream);
 }
-
-extern "C" int vds_gate_bwd(const void* dxn, int64_t lddxn, const void* y, int64_t ldy, const float* mod,
-                            int64_t ldmod, int32_t gate_col, void* dy, int64_t lddy, float* dmod, float* dbias,
-                            int32_t B, int32_t L, int32_t D, vds_stream_t stream) {
-  if (!dxn || !y || !mod || !dy || !dmod || (D & 7) || (lddxn & 7) || (ldy & 7) || (lddy & 7)) return VDS_ERR_ARG;
-  const int rpb = rows_per_block_for(L, B);
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid((L + rpb - 1) / rpb, B);
-  float* det = nullptr;
-  if (vdsdet::on() && !(det = vdsdet::workspace((size_t)2 * B * grid.x * D, "vds_gate_bwd"))) return VDS_ERR_ARG;
-  vdsprof::Scope ps(VDS_PROF_GATE_BWD, s, 0.0, 6.0 * B * L * D);
-#define CALL(NC)                                                                                             \
-  hipLaunchKernelGGL((gate_bwd_kernel<NC>), grid, dim3(256), 0, s, (const bf16_t*)dxn, (long)lddxn,           \
-                     (const bf16_t*)y, (long)ldy, mod, (long)ldmod, gate_col, (bf16_t*)dy, (long)lddy, dmod, \
-                     dbias, B, L, D, rpb, QOut{}, det, MGrp{})
-  NC_DISPATCH(D, CALL);
-#undef CALL
-  if (det) {
-    det_finish(det, (int)grid.x, D, dmod + gate_col, ldmod, B, s);
-    if (dbias) det_finish(det + (long)B * grid.x * D, (int)(B * grid.x), D, dbias, 0, 1, s);
-  }
-  return ok();
-}
-
-// the grouped backward calls: blockIdx.y = modulation row b * G + g, blockIdx.x = row chunks of the LARGEST group (the
-// workgroups past a smaller group's end leave at once); the deterministic partials are sized by this grid
 extern "C" int vds_rmsnorm_mod_bwd_grouped(const void* dy, int64_t lddy, const void* x, int64_t ldx, const void* w,
                                            const float* mod, int64_t ldmod, int32_t shift_col, int32_t scale_col,
                                            const float* rstd, const void* dres, int64_t lddres, void* dx, int64_t lddx,
@@ -1943,103 +1942,31 @@ extern "C" int vds_rmsnorm_mod_bwd_grouped(const void* dy, int64_t lddy, const v
   if (!groups)
     return vds_rmsnorm_mod_bwd(dy, lddy, x, ldx, w, mod, ldmod, shift_col, scale_col, rstd, dres, lddres, dx, lddx, dmod, dw,
                                B, L, D, stream);
-  if (!dy || !x || !mod || !rstd || !dx || !dmod || (D & 7) || (lddy & 7) || (ldx & 7) || (lddx & 7)) return VDS_ERR_ARG;
-  if ((w && !dw) || B < 1 || L < 1 || !groups_ok(groups, L) || (dres && (lddres & 7))) return VDS_ERR_ARG;
-  const long BG = (long)B * (1 + groups->period);
-  if (BG > 65535) return VDS_ERR_ARG;  // (the modulation rows are the grid's y dimension)
-  const MGrp mg{groups->lead, groups->period};
-  const int nmax = max(groups->lead, (L - groups->lead) / groups->period);
-  const int rpb = rows_per_block_for(nmax, (int)BG);
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid((nmax + rpb - 1) / rpb, (unsigned)BG);
-  float* det = nullptr;
-  if (vdsdet::on() && !(det = vdsdet::workspace((size_t)(w ? 3 : 2) * BG * grid.x * D, "vds_rmsnorm_mod_bwd_grouped")))
-    return VDS_ERR_ARG;
-  vdsprof::Scope ps(VDS_PROF_RMSNORM_BWD, s, 0.0, (dres ? 8.0 : 6.0) * B * L * D + 4.0 * B * L);
-#define CALL(NC)                                                                                                       \
-  do {                                                                                                                 \
-    if (w)                                                                                                             \
-      hipLaunchKernelGGL((rmsnorm_mod_bwd_kernel<NC, true, true>), grid, dim3(256), 0, s, (const bf16_t*)dy,          \
-                         (long)lddy, (const bf16_t*)x, (long)ldx, (const bf16_t*)w, mod, (long)ldmod, shift_col,       \
-                         scale_col, rstd, (const bf16_t*)dres, (long)lddres, (bf16_t*)dx, (long)lddx, dmod, dw, B, L,  \
-                         D, rpb, det, mg);                                                   \
-    else                                                                                                               \
-      hipLaunchKernelGGL((rmsnorm_mod_bwd_kernel<NC, false, true>), grid, dim3(256), 0, s, (const bf16_t*)dy,         \
-                         (long)lddy, (const bf16_t*)x, (long)ldx, (const bf16_t*)nullptr, mod, (long)ldmod, shift_col, \
-                         scale_col, rstd, (const bf16_t*)dres, (long)lddres, (bf16_t*)dx, (long)lddx, dmod,            \
-                         (float*)nullptr, B, L, D, rpb, det, mg);                            \
-  } while (0)
-  NC_DISPATCH(D, CALL);
-#undef CALL
-  if (det) {
-    const long plane = BG * grid.x * D;
-    det_finish(det, (int)grid.x, D, dmod + shift_col, ldmod, (int)BG, s);
-    det_finish(det + plane, (int)grid.x, D, dmod + scale_col, ldmod, (int)BG, s);
-    if (w) det_finish(det + 2 * plane, (int)(BG * grid.x), D, dw, 0, 1, s);
-  }
-  return ok();
+  return rmsnorm_bwd_run<true>(dy, lddy, x, ldx, w, mod, ldmod, shift_col, scale_col, rstd, dres, lddres, dx, lddx, dmod, dw,
+                               B, L, D, groups, "vds_rmsnorm_mod_bwd_grouped", stream);
 }
 
+extern "C" int vds_gate_bwd(const void* dxn, int64_t lddxn, const void* y, int64_t ldy, const float* mod,
+                            int64_t ldmod, int32_t gate_col, void* dy, int64_t lddy, float* dmod, float* dbias,
+                            int32_t B, int32_t L, int32_t D, vds_stream_t stream) {
+  return gate_bwd_run<-1, false>(dxn, lddxn, y, ldy, mod, ldmod, gate_col, dy, lddy, dmod, dbias, B, L, D, QOut{}, nullptr,
+                                 6.0, "vds_gate_bwd", stream);
+}
 extern "C" int vds_gate_bwd_grouped(const void* dxn, int64_t lddxn, const void* y, int64_t ldy, const float* mod,
                                     int64_t ldmod, int32_t gate_col, void* dy, int64_t lddy, float* dmod, float* dbias,
                                     int32_t B, int32_t L, int32_t D, const vds_mod_groups* groups, vds_stream_t stream) {
   if (!groups) return vds_gate_bwd(dxn, lddxn, y, ldy, mod, ldmod, gate_col, dy, lddy, dmod, dbias, B, L, D, stream);
-  if (!dxn || !y || !mod || !dy || !dmod || (D & 7) || (lddxn & 7) || (ldy & 7) || (lddy & 7) || B < 1 || L < 1 ||
-      !groups_ok(groups, L))
-    return VDS_ERR_ARG;
-  const long BG = (long)B * (1 + groups->period);
-  if (BG > 65535) return VDS_ERR_ARG;  // (the modulation rows are the grid's y dimension)
-  const MGrp mg{groups->lead, groups->period};
-  const int nmax = max(groups->lead, (L - groups->lead) / groups->period);
-  const int rpb = rows_per_block_for(nmax, (int)BG);
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid((nmax + rpb - 1) / rpb, (unsigned)BG);
-  float* det = nullptr;
-  if (vdsdet::on() && !(det = vdsdet::workspace((size_t)2 * BG * grid.x * D, "vds_gate_bwd_grouped"))) return VDS_ERR_ARG;
-  vdsprof::Scope ps(VDS_PROF_GATE_BWD, s, 0.0, 6.0 * B * L * D);
-#define CALL(NC)                                                                                                     \
-  hipLaunchKernelGGL((gate_bwd_kernel<NC, -1, true>), grid, dim3(256), 0, s, (const bf16_t*)dxn, (long)lddxn,           \
-                     (const bf16_t*)y, (long)ldy, mod, (long)ldmod, gate_col, (bf16_t*)dy, (long)lddy, dmod, dbias, B, \
-                     L, D, rpb, QOut{}, det, mg)
-  NC_DISPATCH(D, CALL);
-#undef CALL
-  if (det) {
-    det_finish(det, (int)grid.x, D, dmod + gate_col, ldmod, (int)BG, s);
-    if (dbias) det_finish(det + BG * grid.x * D, (int)(BG * grid.x), D, dbias, 0, 1, s);
-  }
-  return ok();
+  return gate_bwd_run<-1, true>(dxn, lddxn, y, ldy, mod, ldmod, gate_col, dy, lddy, dmod, dbias, B, L, D, QOut{}, groups, 6.0,
+                                "vds_gate_bwd_grouped", stream);
 }
-
 extern "C" int vds_gate_bwd_fp8(const void* dxn, int64_t lddxn, const void* y, int64_t ldy, const float* mod,
                                 int64_t ldmod, int32_t gate_col, void* q, int64_t ldq, int32_t fmt,
                                 const float* amax_in, float* amax_part, float* dq_out, float* dmod, float* dbias,
                                 int32_t B, int32_t L, int32_t D, vds_stream_t stream) {
-  if (!dxn || !y || !mod || !dmod || (D & 7) || (lddxn & 7) || (ldy & 7) || !qout_ok(q, ldq, fmt, amax_in)) return VDS_ERR_ARG;
-  const int rpb = rows_per_block_for(L, B);
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid((L + rpb - 1) / rpb, B);
+  if (!qout_ok(q, ldq, fmt, amax_in)) return VDS_ERR_ARG;
   const QOut qo{(unsigned char*)q, (long)ldq, amax_in, amax_part, dq_out};
-  float* det = nullptr;
-  if (vdsdet::on() && !(det = vdsdet::workspace((size_t)2 * B * grid.x * D, "vds_gate_bwd_fp8"))) return VDS_ERR_ARG;
-  vdsprof::Scope ps(VDS_PROF_GATE_BWD, s, 0.0, 5.0 * B * L * D);
-#define CALL(NC)                                                                                                   \
-  do {                                                                                                             \
-    if (fmt == 0)                                                                                                  \
-      hipLaunchKernelGGL((gate_bwd_kernel<NC, 0>), grid, dim3(256), 0, s, (const bf16_t*)dxn, (long)lddxn,          \
-                         (const bf16_t*)y, (long)ldy, mod, (long)ldmod, gate_col, (bf16_t*)nullptr, 0L, dmod, dbias, \
-                         B, L, D, rpb, qo, det, MGrp{});                                                                   \
-    else                                                                                                           \
-      hipLaunchKernelGGL((gate_bwd_kernel<NC, 1>), grid, dim3(256), 0, s, (const bf16_t*)dxn, (long)lddxn,          \
-                         (const bf16_t*)y, (long)ldy, mod, (long)ldmod, gate_col, (bf16_t*)nullptr, 0L, dmod, dbias, \
-                         B, L, D, rpb, qo, det, MGrp{});                                                                   \
-  } while (0)
-  NC_DISPATCH(D, CALL);
-#undef CALL
-  if (det) {
-    det_finish(det, (int)grid.x, D, dmod + gate_col, ldmod, B, s);
-    if (dbias) det_finish(det + (long)B * grid.x * D, (int)(B * grid.x), D, dbias, 0, 1, s);
-  }
-  return ok();
+  return (fmt == 0 ? gate_bwd_run<0, false> : gate_bwd_run<1, false>)(
+      dxn, lddxn, y, ldy, mod, ldmod, gate_col, nullptr, 0, dmod, dbias, B, L, D, qo, nullptr, 5.0, "vds_gate_bwd_fp8", stream);
 }
 
 extern "C" int vds_colsum_bf16_rows(const void* x, int64_t ldx, float* out, int32_t M, int32_t N,
@@ -2067,6 +1994,21 @@ static bool rope_tok_form(int H, int hd, int hdp) {
 
 // FmRows of a frame-major call (frames checked by the caller: groups_ok)
 static FmRows fm_rows_of(const vds_mod_groups* f, int L) { return FmRows{f->lead, f->period, (L - f->lead) / f->period}; }
+// what the frame-major forms (forward and backward) refuse of their own
+static bool fm_ok(const vds_mod_groups* frames, int B, int L, int H) {
+  return frames && B > 0 && L > 0 && H > 0 && groups_ok(frames, L);
+}
+
+// What every qkv / RoPE forward checks.  own_ok: the refusals only the calling form has (frames, cache strides), made by
+// the caller and placed here before the pad check: VDS_ERR_ARG wins over VDS_ERR_UNSUPPORTED.
+static int qkv_rope_fwd_check(const void* qkv, const float* cosb, const float* sinb, const void* v0, const void* lam,
+                              const void* q, const void* k, const void* v, int hd, int hdp, bool own_ok) {
+  if (!qkv || !cosb || !sinb || !q || !k || !v || (hd & 7) || hdp < hd || (hdp & 3)) return VDS_ERR_ARG;
+  if (v0 && !lam) return VDS_ERR_ARG;
+  if (!own_ok) return VDS_ERR_ARG;
+  if (((hdp - hd) >> 2) > (hd >> 3)) return VDS_ERR_UNSUPPORTED;
+  return VDS_OK;
+}
 
 // NORM = false: vds_qkv_rope_fwd (launches the instances without the flag only); true: vds_qkv_rope_norm_fwd
 // FM = false: the plain calls (the instances without the flag only); true: vds_qkv_rope_fwd_fm / _norm_fwd_fm -- the same
@@ -2075,14 +2017,9 @@ template <bool NORM, bool FM = false>
 static int qkv_rope_fwd_impl(const void* qkv, const float* cosb, const float* sinb, const void* v0, const void* lam,
                              void* q, void* k, void* v, int32_t B, int32_t L, int32_t H, int32_t hd, int32_t hdp,
                              float eps, vds_stream_t stream, const vds_mod_groups* frames = nullptr) {
-  if (!qkv || !cosb || !sinb || !q || !k || !v || (hd & 7) || hdp < hd || (hdp & 3)) return VDS_ERR_ARG;
-  if (v0 && !lam) return VDS_ERR_ARG;
+  if (const int rc = qkv_rope_fwd_check(qkv, cosb, sinb, v0, lam, q, k, v, hd, hdp, !FM || fm_ok(frames, B, L, H))) return rc;
   FmRows fr{0, 0, 0};
-  if constexpr (FM) {
-    if (!frames || B <= 0 || L <= 0 || H <= 0 || !groups_ok(frames, L)) return VDS_ERR_ARG;
-    fr = fm_rows_of(frames, L);
-  }
-  if (((hdp - hd) >> 2) > (hd >> 3)) return VDS_ERR_UNSUPPORTED;
+  if constexpr (FM) fr = fm_rows_of(frames, L);
   const long n = (long)B * L * H * (hd >> 3);
   vdsprof::Scope ps(VDS_PROF_QKV_ROPE_FWD, (hipStream_t)stream, 0.0, (v0 ? 14.0 : 12.0) * B * L * H * hd);
   // token-tile kernel (16-byte accesses, LDS staging) for the head sizes the model builds; knob rope_tile = 0 keeps the
@@ -2090,19 +2027,13 @@ static int qkv_rope_fwd_impl(const void* qkv, const float* cosb, const float* si
   const int tile = vdscfg::geti(vdscfg::ROPE_TILE);
   if (tile > 0 && H * hd <= 2048 && H <= 256 && L >= 8 && (!FM || L <= (1 << 22))) {
     const long ntok = (long)B * L;
-#define ROPE_TILE(HD, HDP, T)                                                                                      \
-  do {                                                                                                             \
-    const int lds = ropestage::lds_bytes(T, H * HD) + (NORM ? T * 2 * H * 4 : 0); /* + the rows' rsqrt values */    \
-    static bool attr = false;                                                                                      \
-    if (!attr) {                                                                                                   \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qkv_rope_fwd_tile_kernel<HD, HDP, T, NORM, FM>),    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                           \
-      attr = true;                                                                                                 \
-    }                                                                                                              \
-    hipLaunchKernelGGL((qkv_rope_fwd_tile_kernel<HD, HDP, T, NORM, FM>), dim3((unsigned)((ntok + T - 1) / T)),     \
-                       dim3(256), lds, (hipStream_t)stream, (const bf16_t*)qkv, cosb, sinb, (const bf16_t*)v0,     \
-                       (const bf16_t*)lam, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v, ntok, L, H, eps, fr);               \
-    return ok();                                                                                                   \
+#define ROPE_TILE(HD, HDP, T)                                                                                         \
+  do {                                                                                                                \
+    const int lds = ropestage::lds_bytes(T, H * HD) + (NORM ? T * 2 * H * 4 : 0); /* + the rows' rsqrt values */       \
+    vds_launch<qkv_rope_fwd_tile_kernel<HD, HDP, T, NORM, FM>, 160 * 1024>(                                           \
+        dim3((unsigned)((ntok + T - 1) / T)), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)qkv, cosb, sinb,    \
+        (const bf16_t*)v0, (const bf16_t*)lam, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v, ntok, L, H, eps, fr);             \
+    return ok();                                                                                                      \
   } while (0)
 #define ROPE_TILE_T(HD, HDP)                       \
   do {                                             \
@@ -2155,11 +2086,10 @@ static int qkv_rope_fwd_cache_impl(const void* qkv, const float* cosb, const flo
                                    void* q, void* k, void* v, int64_t kv_sb, int64_t kv_sh, int64_t kv_sl, int32_t lead,
                                    int32_t past, int32_t B, int32_t L, int32_t H, int32_t hd, int32_t hdp, float eps,
                                    vds_stream_t stream) {
-  if (!qkv || !cosb || !sinb || !q || !k || !v || (hd & 7) || hdp < hd || (hdp & 3)) return VDS_ERR_ARG;
-  if (v0 && !lam) return VDS_ERR_ARG;
-  if (B <= 0 || L <= 0 || H <= 0 || lead < 0 || lead > L || past < 0) return VDS_ERR_ARG;
-  if ((kv_sb & 3) || (kv_sh & 3) || (kv_sl & 3) || kv_sl < hdp) return VDS_ERR_ARG;
-  if (((hdp - hd) >> 2) > (hd >> 3)) return VDS_ERR_UNSUPPORTED;
+  // of its own: the row map (lead, past) and the cache strides -- 8-byte accesses, a row no shorter than hdp
+  const bool own_ok = B > 0 && L > 0 && H > 0 && lead >= 0 && lead <= L && past >= 0 && !(kv_sb & 3) && !(kv_sh & 3) &&
+                      !(kv_sl & 3) && kv_sl >= hdp;
+  if (const int rc = qkv_rope_fwd_check(qkv, cosb, sinb, v0, lam, q, k, v, hd, hdp, own_ok)) return rc;
   const long n = (long)B * L * H * (hd >> 3);
   vdsprof::Scope ps(VDS_PROF_QKV_ROPE_FWD, (hipStream_t)stream, 0.0, (v0 ? 14.0 : 12.0) * B * L * H * hd);
   hipLaunchKernelGGL(qkv_rope_fwd_cache_kernel<NORM>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
@@ -2245,43 +2175,45 @@ extern "C" int vds_dv0_reduce(const void* const* dv, const void* const* lam, int
   return ok();
 }
 
-// FM: as in qkv_rope_fwd_impl (vds_qkv_rope_bwd_fm / _norm_bwd_fm)
-template <bool NORM, bool FM = false>
+// FM: as in qkv_rope_fwd_impl (vds_qkv_rope_bwd_fm / _norm_bwd_fm).  QF = 0 / 1: vds_qkv_rope_bwd_fp8 -- the [B*L, 3D] result
+// leaves as fp8 through `qo` (dqkv is not looked at), on the wave-per-token kernel only: what that kernel cannot take is
+// refused, and knob rope_tok is not consulted.  name: the entry's own, for the deterministic workspace's error message.
+template <bool NORM, bool FM = false, int QF = -1>
 static int qkv_rope_bwd_impl(const void* dq, const void* dk, const void* dv, const float* cosb, const float* sinb,
                              const void* qkv_raw, const void* v0, const void* lam, float* dv0_acc, float* dlam,
                              void* dqkv, int32_t mix, int32_t add_dv0, int32_t B, int32_t L, int32_t H, int32_t hd,
-                             int32_t hdp, float eps, vds_stream_t stream, const vds_mod_groups* frames = nullptr) {
-  if (!dq || !dk || !dv || !cosb || !sinb || !dqkv || (hd & 7)) return VDS_ERR_ARG;
+                             int32_t hdp, float eps, const char* name, vds_stream_t stream,
+                             const vds_mod_groups* frames = nullptr, const QOut& qo = QOut{}) {
+  if (!dq || !dk || !dv || !cosb || !sinb || (QF < 0 && !dqkv) || (hd & 7)) return VDS_ERR_ARG;
   FmRows fr{0, 0, 0};
   if constexpr (FM) {
-    if (!frames || B <= 0 || L <= 0 || H <= 0 || !groups_ok(frames, L)) return VDS_ERR_ARG;
+    if (!fm_ok(frames, B, L, H)) return VDS_ERR_ARG;
     fr = fm_rows_of(frames, L);
   }
   if (mix && (!qkv_raw || !v0 || !lam || !dlam || (mix == 1 && !dv0_acc) || mix < 0 || mix > 2)) return VDS_ERR_ARG;
   if (add_dv0 && !dv0_acc) return VDS_ERR_ARG;
+  if (QF >= 0 && ((hdp & 7) || H * hd > 2048 || qo.ldq < 3 * H * hd)) return VDS_ERR_UNSUPPORTED;
   const long n = (long)B * L * H * (hd >> 3);
-  vdsprof::Scope ps(VDS_PROF_QKV_ROPE_BWD, (hipStream_t)stream, 0.0, (mix ? 24.0 : 12.0) * B * L * H * hd);
-  const bool tok = rope_tok_form(H, hd, hdp);
+  vdsprof::Scope ps(VDS_PROF_QKV_ROPE_BWD, (hipStream_t)stream, 0.0,
+                    (QF >= 0 ? (mix ? 21.0 : 9.0) : (mix ? 24.0 : 12.0)) * B * L * H * hd);
+  const bool tok = QF >= 0 || rope_tok_form(H, hd, hdp);
   const unsigned nblk = tok ? (unsigned)(((long)B * L + 3) / 4) : (unsigned)((n + 255) / 256);
   float* det = nullptr;  // deterministic mode: the lambda gradient as per-workgroup partials + one fixed-order sum
-  if (mix && vdsdet::on() &&
-      !(det = vdsdet::workspace(nblk, FM ? (NORM ? "vds_qkv_rope_norm_bwd_fm" : "vds_qkv_rope_bwd_fm")
-                                         : (NORM ? "vds_qkv_rope_norm_bwd" : "vds_qkv_rope_bwd"))))
-    return VDS_ERR_ARG;
+  if (mix && vdsdet::on() && !(det = vdsdet::workspace(nblk, name))) return VDS_ERR_ARG;
   if (tok) {
     const int D = H * hd, lds = 4 * (4 * D + 4 * hd);
     const dim3 grid(nblk);
 #define ROPE_BWD(NI)                                                                                                \
-  hipLaunchKernelGGL((qkv_rope_bwd_tok_kernel<NI, -1, NORM, FM>), grid, dim3(256), lds, (hipStream_t)stream,       \
+  hipLaunchKernelGGL((qkv_rope_bwd_tok_kernel<NI, QF, NORM, FM>), grid, dim3(256), lds, (hipStream_t)stream,       \
                      (const bf16_t*)dq, (const bf16_t*)dk, (const bf16_t*)dv, cosb, sinb, (const bf16_t*)qkv_raw,  \
                      (const bf16_t*)v0, (const bf16_t*)lam, dv0_acc, dlam, (bf16_t*)dqkv, mix, add_dv0, B, L, H,   \
-                     hd, hdp, QOut{}, det, eps, fr)
+                     hd, hdp, qo, det, eps, fr)
     if (D <= 512) ROPE_BWD(1);
     else if (D <= 1024) ROPE_BWD(2);
     else if (D <= 1536) ROPE_BWD(3);
     else ROPE_BWD(4);
 #undef ROPE_BWD
-  } else {
+  } else if constexpr (QF < 0) {
     hipLaunchKernelGGL((qkv_rope_bwd_kernel<NORM, FM>), dim3(nblk), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)dq, (const bf16_t*)dk, (const bf16_t*)dv, cosb, sinb, (const bf16_t*)qkv_raw,
                        (const bf16_t*)v0, (const bf16_t*)lam, dv0_acc, dlam, (bf16_t*)dqkv, mix, add_dv0, B, L, H, hd, hdp, det,
@@ -2295,7 +2227,7 @@ extern "C" int vds_qkv_rope_bwd(const void* dq, const void* dk, const void* dv, 
                                 float* dv0_acc, float* dlam, void* dqkv, int32_t mix, int32_t add_dv0, int32_t B,
                                 int32_t L, int32_t H, int32_t hd, int32_t hdp, vds_stream_t stream) {
   return qkv_rope_bwd_impl<false>(dq, dk, dv, cosb, sinb, qkv_raw, v0, lam, dv0_acc, dlam, dqkv, mix, add_dv0, B, L, H,
-                                  hd, hdp, 0.f, stream);
+                                  hd, hdp, 0.f, "vds_qkv_rope_bwd", stream);
 }
 // backward of vds_qkv_rope_norm_fwd: qkv_raw (the forward's input) is read for the norm in every call
 extern "C" int vds_qkv_rope_norm_bwd(const void* dq, const void* dk, const void* dv, const float* cosb,
@@ -2304,7 +2236,7 @@ extern "C" int vds_qkv_rope_norm_bwd(const void* dq, const void* dk, const void*
                                      int32_t L, int32_t H, int32_t hd, int32_t hdp, float eps, vds_stream_t stream) {
   if (!qkv_raw || !(eps > 0.f)) return VDS_ERR_ARG;
   return qkv_rope_bwd_impl<true>(dq, dk, dv, cosb, sinb, qkv_raw, v0, lam, dv0_acc, dlam, dqkv, mix, add_dv0, B, L, H,
-                                 hd, hdp, eps, stream);
+                                 hd, hdp, eps, "vds_qkv_rope_norm_bwd", stream);
 }
 // frame-major forms: dq / dk / dv, v0 and dv0_acc are read (dv0_acc updated) at row fm(l), dqkv row l is written
 extern "C" int vds_qkv_rope_bwd_fm(const void* dq, const void* dk, const void* dv, const float* cosb,
@@ -2313,7 +2245,7 @@ extern "C" int vds_qkv_rope_bwd_fm(const void* dq, const void* dk, const void* d
                                    int32_t L, int32_t H, int32_t hd, int32_t hdp, const vds_mod_groups* frames,
                                    vds_stream_t stream) {
   return qkv_rope_bwd_impl<false, true>(dq, dk, dv, cosb, sinb, qkv_raw, v0, lam, dv0_acc, dlam, dqkv, mix, add_dv0, B,
-                                        L, H, hd, hdp, 0.f, stream, frames);
+                                        L, H, hd, hdp, 0.f, "vds_qkv_rope_bwd_fm", stream, frames);
 }
 extern "C" int vds_qkv_rope_norm_bwd_fm(const void* dq, const void* dk, const void* dv, const float* cosb,
                                         const float* sinb, const void* qkv_raw, const void* v0, const void* lam,
@@ -2322,44 +2254,20 @@ extern "C" int vds_qkv_rope_norm_bwd_fm(const void* dq, const void* dk, const vo
                                         const vds_mod_groups* frames, vds_stream_t stream) {
   if (!qkv_raw || !(eps > 0.f)) return VDS_ERR_ARG;
   return qkv_rope_bwd_impl<true, true>(dq, dk, dv, cosb, sinb, qkv_raw, v0, lam, dv0_acc, dlam, dqkv, mix, add_dv0, B,
-                                       L, H, hd, hdp, eps, stream, frames);
+                                       L, H, hd, hdp, eps, "vds_qkv_rope_norm_bwd_fm", stream, frames);
 }
-
-// as vds_qkv_rope_bwd, the [B*L, 3D] result written as fp8 (wave-per-token kernel only)
+// as vds_qkv_rope_bwd, the [B*L, 3D] result written as fp8
 extern "C" int vds_qkv_rope_bwd_fp8(const void* dq, const void* dk, const void* dv, const float* cosb,
                                     const float* sinb, const void* qkv_raw, const void* v0, const void* lam,
                                     float* dv0_acc, float* dlam, void* q, int64_t ldq, int32_t fmt,
                                     const float* amax_in, float* amax_part, float* dq_out, int32_t mix,
                                     int32_t add_dv0, int32_t B, int32_t L, int32_t H, int32_t hd, int32_t hdp,
                                     vds_stream_t stream) {
-  if (!dq || !dk || !dv || !cosb || !sinb || (hd & 7) || !qout_ok(q, ldq, fmt, amax_in)) return VDS_ERR_ARG;
-  if (mix && (!qkv_raw || !v0 || !lam || !dlam || (mix == 1 && !dv0_acc) || mix < 0 || mix > 2)) return VDS_ERR_ARG;
-  if (add_dv0 && !dv0_acc) return VDS_ERR_ARG;
-  if ((hdp & 7) || H * hd > 2048 || ldq < 3 * H * hd) return VDS_ERR_UNSUPPORTED;
-  vdsprof::Scope ps(VDS_PROF_QKV_ROPE_BWD, (hipStream_t)stream, 0.0, (mix ? 21.0 : 9.0) * B * L * H * hd);
-  const int D = H * hd, lds = 4 * (4 * D + 4 * hd);
-  const dim3 grid((unsigned)(((long)B * L + 3) / 4));
+  if (!qout_ok(q, ldq, fmt, amax_in)) return VDS_ERR_ARG;
   const QOut qo{(unsigned char*)q, (long)ldq, amax_in, amax_part, dq_out};
-  float* det = nullptr;
-  if (mix && vdsdet::on() && !(det = vdsdet::workspace(grid.x, "vds_qkv_rope_bwd_fp8"))) return VDS_ERR_ARG;
-#define ROPE_BWD_Q(NI, F)                                                                                             \
-  hipLaunchKernelGGL((qkv_rope_bwd_tok_kernel<NI, F>), grid, dim3(256), lds, (hipStream_t)stream, (const bf16_t*)dq, \
-                     (const bf16_t*)dk, (const bf16_t*)dv, cosb, sinb, (const bf16_t*)qkv_raw, (const bf16_t*)v0,    \
-                     (const bf16_t*)lam, dv0_acc, dlam, (bf16_t*)nullptr, mix, add_dv0, B, L, H, hd, hdp, qo, det, 0.f, \
-                     FmRows{0, 0, 0})
-#define ROPE_BWD_F(F)              \
-  do {                             \
-    if (D <= 512) ROPE_BWD_Q(1, F); \
-    else if (D <= 1024) ROPE_BWD_Q(2, F); \
-    else if (D <= 1536) ROPE_BWD_Q(3, F); \
-    else ROPE_BWD_Q(4, F);          \
-  } while (0)
-  if (fmt == 0) ROPE_BWD_F(0);
-  else ROPE_BWD_F(1);
-#undef ROPE_BWD_F
-#undef ROPE_BWD_Q
-  if (det) hipLaunchKernelGGL(det_finish_scalar_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)det, (int)grid.x, dlam);
-  return ok();
+  return (fmt == 0 ? qkv_rope_bwd_impl<false, false, 0> : qkv_rope_bwd_impl<false, false, 1>)(
+      dq, dk, dv, cosb, sinb, qkv_raw, v0, lam, dv0_acc, dlam, nullptr, mix, add_dv0, B, L, H, hd, hdp, 0.f,
+      "vds_qkv_rope_bwd_fp8", stream, nullptr, qo);
 }
 
 // ---- round 4: the batched adaLN linears as streaming kernels -----------------------------------------------------
@@ -2449,14 +2357,8 @@ static bool small_linear_fwd_mfma(const float* x, const bf16_t* W, const bf16_t*
   const int mfma_on = vdscfg::geti(vdscfg::ADALN_MFMA);
   const size_t lds = (size_t)SL_FWD_TERMS * 16 * (K * 2 + 16);
   if (!mfma_on || M > 16 || (K & 31) || (N & 15) || lds > 160 * 1024 || N < 1024) return false;  // (small N: the row kernel's finer grid)
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_linear_fwd_mfma_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
-  hipLaunchKernelGGL(small_linear_fwd_mfma_kernel, dim3((N / 16 + SL_FWD_WAVES - 1) / SL_FWD_WAVES, 1, nb),
-                     dim3(64 * SL_FWD_WAVES), lds, s, x, W, bias, y, M, N, K, act_in, bt);
+  vds_launch<small_linear_fwd_mfma_kernel, 160 * 1024>(dim3((N / 16 + SL_FWD_WAVES - 1) / SL_FWD_WAVES, 1, nb),
+                                                       dim3(64 * SL_FWD_WAVES), lds, s, x, W, bias, y, M, N, K, act_in, bt);
   return true;
 }
 

@@ -558,47 +558,72 @@ def _groups(groups, L: int, mod: torch.Tensor, B: int):
     return C.byref(_lib.ModGroups(lead, period))
 
 
-def rmsnorm_mod_fwd_grouped(x, w, mod, shift_col, scale_col, B, L, groups, eps=1e-6):
-    """rmsnorm_mod_fwd with mod f32 [B*G, ld]: row l of sample b reads modulation row b*G + mod_group_of(l)"""
-    D = x.shape[1]
-    y = torch.empty(B * L, D, dtype=bf16, device=x.device)
+def _grouped_tables(mod, dmod):
+    assert dmod.shape[0] == mod.shape[0] and dmod.stride(0) == mod.stride(0)
+
+
+# One marshalling helper per kernel family.  `entry` is the C entry point the public wrapper reaches; `out` the arguments
+# of its output -- (y, ldy) of a bf16 result, (q, ldq, fmt, amax_in, amax_part, dq_out) of an fp8 one --; `tail` what the
+# entry takes after D (eps) and the shape (groups).
+def _rmsnorm_fwd(entry, x, w, mod, shift_col, scale_col, out, B, L, eps, tail=()):
     rstd = torch.empty(B * L, dtype=f32, device=x.device)
-    check(_lib.load().vds_rmsnorm_mod_fwd_grouped(_p(x), x.stride(0), _p(w), _p(mod), mod.stride(0), shift_col, scale_col,
-                                                  _p(y), D, _p(rstd), B, L, D, eps, _groups(groups, L, mod, B),
-                                                  _stream()), "vds_rmsnorm_mod_fwd_grouped")
-    return y, rstd
+    check(getattr(_lib.load(), entry)(_p(x), x.stride(0), _p(w), _p(mod), mod.stride(0), shift_col, scale_col, *out,
+                                      _p(rstd), B, L, x.shape[1], eps, *tail, _stream()), entry)
+    return rstd
 
 
-def rmsnorm_mod_bwd_grouped(dy, x, w, mod, shift_col, scale_col, rstd, dres, dmod, dw, B, L, groups):
-    """rmsnorm_mod_bwd with mod / dmod [B*G, ld]: dmod row b*G + g accumulates the sums over the rows of that group"""
+def _rmsnorm_bwd(entry, dy, x, w, mod, shift_col, scale_col, rstd, dres, dmod, dw, B, L, tail=()):
     D = x.shape[1]
     dx = torch.empty(B * L, D, dtype=bf16, device=x.device)
-    assert dmod.shape[0] == mod.shape[0] and dmod.stride(0) == mod.stride(0)
-    check(_lib.load().vds_rmsnorm_mod_bwd_grouped(_p(dy), dy.stride(0), _p(x), x.stride(0), _p(w), _p(mod), mod.stride(0),
-                                                  shift_col, scale_col, _p(rstd), _p(dres),
-                                                  dres.stride(0) if dres is not None else 0, _p(dx), D, _p(dmod), _p(dw),
-                                                  B, L, D, _groups(groups, L, mod, B), _stream()),
-          "vds_rmsnorm_mod_bwd_grouped")
+    check(getattr(_lib.load(), entry)(_p(dy), dy.stride(0), _p(x), x.stride(0), _p(w), _p(mod), mod.stride(0), shift_col,
+                                      scale_col, _p(rstd), _p(dres), dres.stride(0) if dres is not None else 0, _p(dx), D,
+                                      _p(dmod), _p(dw), B, L, D, *tail, _stream()), entry)
     return dx
 
 
-def gate_bwd_grouped(dxn, y, mod, gate_col, dmod, dbias, B, L, groups):
-    D = y.shape[1]
-    dy = torch.empty(B * L, D, dtype=bf16, device=y.device)
-    assert dmod.shape[0] == mod.shape[0] and dmod.stride(0) == mod.stride(0)
-    check(_lib.load().vds_gate_bwd_grouped(_p(dxn), dxn.stride(0), _p(y), y.stride(0), _p(mod), mod.stride(0), gate_col,
-                                           _p(dy), D, _p(dmod), _p(dbias), B, L, D, _groups(groups, L, mod, B), _stream()),
-          "vds_gate_bwd_grouped")
-    return dy
+def _gate_bwd(entry, dxn, y, mod, gate_col, out, dmod, dbias, B, L, tail=()):
+    check(getattr(_lib.load(), entry)(_p(dxn), dxn.stride(0), _p(y), y.stride(0), _p(mod), mod.stride(0), gate_col, *out,
+                                      _p(dmod), _p(dbias), B, L, y.shape[1], *tail, _stream()), entry)
 
 
 def rmsnorm_mod_fwd(x, w, mod, shift_col, scale_col, B, L, eps=1e-6):
     D = x.shape[1]
     y = torch.empty(B * L, D, dtype=bf16, device=x.device)
-    rstd = torch.empty(B * L, dtype=f32, device=x.device)
-    check(_lib.load().vds_rmsnorm_mod_fwd(_p(x), x.stride(0), _p(w), _p(mod), mod.stride(0), shift_col, scale_col,
-                                          _p(y), D, _p(rstd), B, L, D, eps, _stream()), "vds_rmsnorm_mod_fwd")
-    return y, rstd
+    return y, _rmsnorm_fwd("vds_rmsnorm_mod_fwd", x, w, mod, shift_col, scale_col, (_p(y), D), B, L, eps)
+
+
+def rmsnorm_mod_fwd_grouped(x, w, mod, shift_col, scale_col, B, L, groups, eps=1e-6):
+    """rmsnorm_mod_fwd with mod f32 [B*G, ld]: row l of sample b reads modulation row b*G + mod_group_of(l)"""
+    D = x.shape[1]
+    y = torch.empty(B * L, D, dtype=bf16, device=x.device)
+    return y, _rmsnorm_fwd("vds_rmsnorm_mod_fwd_grouped", x, w, mod, shift_col, scale_col, (_p(y), D), B, L, eps,
+                           (_groups(groups, L, mod, B),))
+
+
+def rmsnorm_mod_bwd(dy, x, w, mod, shift_col, scale_col, rstd, dres, dmod, dw, B, L):
+    return _rmsnorm_bwd("vds_rmsnorm_mod_bwd", dy, x, w, mod, shift_col, scale_col, rstd, dres, dmod, dw, B, L)
+
+
+def rmsnorm_mod_bwd_grouped(dy, x, w, mod, shift_col, scale_col, rstd, dres, dmod, dw, B, L, groups):
+    """rmsnorm_mod_bwd with mod / dmod [B*G, ld]: dmod row b*G + g accumulates the sums over the rows of that group"""
+    _grouped_tables(mod, dmod)
+    return _rmsnorm_bwd("vds_rmsnorm_mod_bwd_grouped", dy, x, w, mod, shift_col, scale_col, rstd, dres, dmod, dw, B, L,
+                        (_groups(groups, L, mod, B),))
+
+
+def gate_bwd(dxn, y, mod, gate_col, dmod, dbias, B, L):
+    D = y.shape[1]
+    dy = torch.empty(B * L, D, dtype=bf16, device=y.device)
+    _gate_bwd("vds_gate_bwd", dxn, y, mod, gate_col, (_p(dy), D), dmod, dbias, B, L)
+    return dy
+
+
+def gate_bwd_grouped(dxn, y, mod, gate_col, dmod, dbias, B, L, groups):
+    D = y.shape[1]
+    dy = torch.empty(B * L, D, dtype=bf16, device=y.device)
+    _grouped_tables(mod, dmod)
+    _gate_bwd("vds_gate_bwd_grouped", dxn, y, mod, gate_col, (_p(dy), D), dmod, dbias, B, L, (_groups(groups, L, mod, B),))
+    return dy
 
 
 def _fp8_out(rows, cols, fmt, device):
@@ -618,27 +643,24 @@ def _part_ok(t, rows):
     assert t is None or (t.dtype == f32 and t.is_contiguous() and t.numel() >= rows)
 
 
+def _fp8_rows(rows, cols, fmt, amax_in, amax_part, device):
+    """(q, dq f32[1]) of an fp8-emitting call and the `out` arguments that describe them"""
+    _part_ok(amax_part, rows)
+    q, dq = _fp8_out(rows, cols, fmt, device)
+    return q, dq, (_p(q), cols, fmt, _p(amax_in), _p(amax_part), _p(dq))
+
+
 def rmsnorm_mod_fwd_fp8(x, w, mod, shift_col, scale_col, B, L, fmt, amax_in, amax_part, eps=1e-6):
     """rmsnorm_mod_fwd whose result leaves the kernel as fp8 (row-major) -> (q, dq f32[1], rstd);
     amax_part: f32 [>= B*L], zeroed by the caller: per-wave maxima of |result|; its maximum is the tensor's amax (or None)"""
-    _part_ok(amax_part, B * L)
-    D = x.shape[1]
-    q, dq = _fp8_out(B * L, D, fmt, x.device)
-    rstd = torch.empty(B * L, dtype=f32, device=x.device)
-    check(_lib.load().vds_rmsnorm_mod_fwd_fp8(_p(x), x.stride(0), _p(w), _p(mod), mod.stride(0), shift_col, scale_col,
-                                              _p(q), D, fmt, _p(amax_in), _p(amax_part), _p(dq), _p(rstd), B, L, D,
-                                              eps, _stream()), "vds_rmsnorm_mod_fwd_fp8")
-    return q, dq, rstd
+    q, dq, out = _fp8_rows(B * L, x.shape[1], fmt, amax_in, amax_part, x.device)
+    return q, dq, _rmsnorm_fwd("vds_rmsnorm_mod_fwd_fp8", x, w, mod, shift_col, scale_col, out, B, L, eps)
 
 
 def gate_bwd_fp8(dxn, y, mod, gate_col, dmod, dbias, B, L, fmt, amax_in, amax_part):
     """gate_bwd whose dy leaves the kernel as fp8 (row-major) -> (q, dq f32[1])"""
-    _part_ok(amax_part, B * L)
-    D = y.shape[1]
-    q, dq = _fp8_out(B * L, D, fmt, y.device)
-    check(_lib.load().vds_gate_bwd_fp8(_p(dxn), dxn.stride(0), _p(y), y.stride(0), _p(mod), mod.stride(0), gate_col,
-                                       _p(q), D, fmt, _p(amax_in), _p(amax_part), _p(dq), _p(dmod), _p(dbias), B, L, D,
-                                       _stream()), "vds_gate_bwd_fp8")
+    q, dq, out = _fp8_rows(B * L, y.shape[1], fmt, amax_in, amax_part, y.device)
+    _gate_bwd("vds_gate_bwd_fp8", dxn, y, mod, gate_col, out, dmod, dbias, B, L)
     return q, dq
 
 
@@ -652,24 +674,6 @@ def qkv_rope_bwd_fp8(dq, dk, dv, cos, sin, qkv_raw, v0, lam, dv0_acc, dlam, mix,
                                            _p(s), int(mix), int(add_dv0), B, L, H, hd, hdp, _stream()),
           "vds_qkv_rope_bwd_fp8")
     return q, s
-
-
-def rmsnorm_mod_bwd(dy, x, w, mod, shift_col, scale_col, rstd, dres, dmod, dw, B, L):
-    D = x.shape[1]
-    dx = torch.empty(B * L, D, dtype=bf16, device=x.device)
-    check(_lib.load().vds_rmsnorm_mod_bwd(_p(dy), dy.stride(0), _p(x), x.stride(0), _p(w), _p(mod), mod.stride(0),
-                                          shift_col, scale_col, _p(rstd), _p(dres),
-                                          dres.stride(0) if dres is not None else 0, _p(dx), D, _p(dmod), _p(dw),
-                                          B, L, D, _stream()), "vds_rmsnorm_mod_bwd")
-    return dx
-
-
-def gate_bwd(dxn, y, mod, gate_col, dmod, dbias, B, L):
-    D = y.shape[1]
-    dy = torch.empty(B * L, D, dtype=bf16, device=y.device)
-    check(_lib.load().vds_gate_bwd(_p(dxn), dxn.stride(0), _p(y), y.stride(0), _p(mod), mod.stride(0), gate_col,
-                                   _p(dy), D, _p(dmod), _p(dbias), B, L, D, _stream()), "vds_gate_bwd")
-    return dy
 
 
 def colsum(x, out, rows_per_sample: int = 0, row_offset: int = 0):
@@ -820,20 +824,61 @@ def _fm_frames(frames, L: int):
 
 
 # ----------------------------------------------------------------- qkv / rope / res-V ----
-def qkv_rope_fwd(qkv, cos, sin, v0, lam, B, L, H, hd, hdp, frames=None):
-    """frames=(lead, period): the q / k / v head rows of token l are written, and v0 read, at row fm_row(l)
-    (vds_qkv_rope_fwd_fm)"""
-    fr = _fm_frames(frames, L) if frames is not None else None
+QK_NORM_EPS = 1e-6  # RMSNorm's eps (model.py:34-41)
+
+
+def _fm_entry(entry, frames, L: int, tail):
+    """the entry point and its arguments after hdp: with frames=(lead, period) the _fm form, which takes them last"""
+    if frames is None:
+        return entry, tail
+    return entry + "_fm", tail + (_fm_frames(frames, L),)
+
+
+def _qkv_rope_fwd(entry, qkv, cos, sin, v0, lam, B, L, H, hd, hdp, frames, tail=()):
+    entry, tail = _fm_entry(entry, frames, L, tail)
     q = torch.empty(B, H, L, hdp, dtype=bf16, device=qkv.device)
     k = torch.empty_like(q)
     v = torch.empty_like(q)
-    if fr is not None:
-        check(_lib.load().vds_qkv_rope_fwd_fm(_p(qkv), _p(cos), _p(sin), _p(v0), _p(lam), _p(q), _p(k), _p(v), B, L, H,
-                                              hd, hdp, fr, _stream()), "vds_qkv_rope_fwd_fm")
-        return q, k, v
-    check(_lib.load().vds_qkv_rope_fwd(_p(qkv), _p(cos), _p(sin), _p(v0), _p(lam), _p(q), _p(k), _p(v), B, L, H, hd,
-                                       hdp, _stream()), "vds_qkv_rope_fwd")
+    check(getattr(_lib.load(), entry)(_p(qkv), _p(cos), _p(sin), _p(v0), _p(lam), _p(q), _p(k), _p(v), B, L, H, hd, hdp,
+                                      *tail, _stream()), entry)
     return q, k, v
+
+
+def _qkv_rope_bwd(entry, dq, dk, dv, cos, sin, qkv_raw, v0, lam, dv0_acc, dlam, mix, add_dv0, B, L, H, hd, hdp, frames,
+                  tail=()):
+    entry, tail = _fm_entry(entry, frames, L, tail)
+    dqkv = torch.empty(B * L, 3 * H * hd, dtype=bf16, device=dq.device)
+    check(getattr(_lib.load(), entry)(_p(dq), _p(dk), _p(dv), _p(cos), _p(sin), _p(qkv_raw), _p(v0), _p(lam), _p(dv0_acc),
+                                      _p(dlam), _p(dqkv), int(mix), int(add_dv0), B, L, H, hd, hdp, *tail, _stream()), entry)
+    return dqkv
+
+
+def qkv_rope_fwd(qkv, cos, sin, v0, lam, B, L, H, hd, hdp, frames=None):
+    """frames=(lead, period): the q / k / v head rows of token l are written, and v0 read, at row fm_row(l)
+    (vds_qkv_rope_fwd_fm)"""
+    return _qkv_rope_fwd("vds_qkv_rope_fwd", qkv, cos, sin, v0, lam, B, L, H, hd, hdp, frames)
+
+
+def qkv_rope_bwd(dq, dk, dv, cos, sin, qkv_raw, v0, lam, dv0_acc, dlam, mix, add_dv0, B, L, H, hd, hdp, frames=None):
+    """frames=(lead, period): dq / dk / dv, v0 and dv0_acc are addressed at row fm_row(l), dqkv stays token-major
+    (vds_qkv_rope_bwd_fm)"""
+    return _qkv_rope_bwd("vds_qkv_rope_bwd", dq, dk, dv, cos, sin, qkv_raw, v0, lam, dv0_acc, dlam, mix, add_dv0, B, L, H,
+                         hd, hdp, frames)
+
+
+def qkv_rope_norm_fwd(qkv, cos, sin, v0, lam, B, L, H, hd, hdp, eps: float = QK_NORM_EPS, frames=None):
+    """qkv_rope_fwd with QK-norm: every head row of q and k goes through a weightless RMSNorm (fp32 math, rounded to
+    bf16) before the rotation; v, the pad and the ones columns are qkv_rope_fwd's (vds_qkv_rope_norm_fwd).
+    frames: as in qkv_rope_fwd (vds_qkv_rope_norm_fwd_fm)"""
+    return _qkv_rope_fwd("vds_qkv_rope_norm_fwd", qkv, cos, sin, v0, lam, B, L, H, hd, hdp, frames, (float(eps),))
+
+
+def qkv_rope_norm_bwd(dq, dk, dv, cos, sin, qkv_raw, v0, lam, dv0_acc, dlam, mix, add_dv0, B, L, H, hd, hdp,
+                      eps: float = QK_NORM_EPS, frames=None):
+    """backward of qkv_rope_norm_fwd; qkv_raw (the forward's qkv) is needed in every call (vds_qkv_rope_norm_bwd).
+    frames: as in qkv_rope_bwd (vds_qkv_rope_norm_bwd_fm)"""
+    return _qkv_rope_bwd("vds_qkv_rope_norm_bwd", dq, dk, dv, cos, sin, qkv_raw, v0, lam, dv0_acc, dlam, mix, add_dv0, B, L,
+                         H, hd, hdp, frames, (float(eps),))
 
 
 def _kv_cache_args(k, v, v0, B, H, hdp, lead, past, L):
@@ -847,77 +892,24 @@ def _kv_cache_args(k, v, v0, B, H, hdp, lead, past, L):
     return k.stride(0), k.stride(1), k.stride(2)
 
 
-def qkv_rope_fwd_cache(qkv, cos, sin, v0, lam, k, v, lead, past, B, L, H, hd, hdp):
-    """qkv_rope_fwd whose k / v rows go to row (l < lead ? l : l + past) of the cache buffers k, v [B,H,rows,hdp]; v0 is
-    block 0's cache v buffer, read through the same map (vds_qkv_rope_fwd_cache).  Returns q [B,H,L,hdp]."""
+def _qkv_rope_fwd_cache(entry, qkv, cos, sin, v0, lam, k, v, lead, past, B, L, H, hd, hdp, tail=()):
     st = _kv_cache_args(k, v, v0, B, H, hdp, lead, past, L)
     q = torch.empty(B, H, L, hdp, dtype=bf16, device=qkv.device)
-    check(_lib.load().vds_qkv_rope_fwd_cache(_p(qkv), _p(cos), _p(sin), _p(v0), _p(lam), _p(q), _p(k), _p(v), *st, lead,
-                                             past, B, L, H, hd, hdp, _stream()), "vds_qkv_rope_fwd_cache")
+    check(getattr(_lib.load(), entry)(_p(qkv), _p(cos), _p(sin), _p(v0), _p(lam), _p(q), _p(k), _p(v), *st, lead, past, B,
+                                      L, H, hd, hdp, *tail, _stream()), entry)
     return q
 
 
-def qkv_rope_bwd(dq, dk, dv, cos, sin, qkv_raw, v0, lam, dv0_acc, dlam, mix, add_dv0, B, L, H, hd, hdp, frames=None):
-    """frames=(lead, period): dq / dk / dv, v0 and dv0_acc are addressed at row fm_row(l), dqkv stays token-major
-    (vds_qkv_rope_bwd_fm)"""
-    fr = _fm_frames(frames, L) if frames is not None else None
-    dqkv = torch.empty(B * L, 3 * H * hd, dtype=bf16, device=dq.device)
-    if fr is not None:
-        check(_lib.load().vds_qkv_rope_bwd_fm(_p(dq), _p(dk), _p(dv), _p(cos), _p(sin), _p(qkv_raw), _p(v0), _p(lam),
-                                              _p(dv0_acc), _p(dlam), _p(dqkv), int(mix), int(add_dv0), B, L, H, hd, hdp,
-                                              fr, _stream()), "vds_qkv_rope_bwd_fm")
-        return dqkv
-    check(_lib.load().vds_qkv_rope_bwd(_p(dq), _p(dk), _p(dv), _p(cos), _p(sin), _p(qkv_raw), _p(v0), _p(lam),
-                                       _p(dv0_acc), _p(dlam), _p(dqkv), int(mix), int(add_dv0), B, L, H, hd, hdp,
-                                       _stream()), "vds_qkv_rope_bwd")
-    return dqkv
-
-
-QK_NORM_EPS = 1e-6  # RMSNorm's eps (model.py:34-41)
-
-
-def qkv_rope_norm_fwd(qkv, cos, sin, v0, lam, B, L, H, hd, hdp, eps: float = QK_NORM_EPS, frames=None):
-    """qkv_rope_fwd with QK-norm: every head row of q and k goes through a weightless RMSNorm (fp32 math, rounded to
-    bf16) before the rotation; v, the pad and the ones columns are qkv_rope_fwd's (vds_qkv_rope_norm_fwd).
-    frames: as in qkv_rope_fwd (vds_qkv_rope_norm_fwd_fm)"""
-    fr = _fm_frames(frames, L) if frames is not None else None
-    q = torch.empty(B, H, L, hdp, dtype=bf16, device=qkv.device)
-    k = torch.empty_like(q)
-    v = torch.empty_like(q)
-    if fr is not None:
-        check(_lib.load().vds_qkv_rope_norm_fwd_fm(_p(qkv), _p(cos), _p(sin), _p(v0), _p(lam), _p(q), _p(k), _p(v), B, L,
-                                                   H, hd, hdp, float(eps), fr, _stream()), "vds_qkv_rope_norm_fwd_fm")
-        return q, k, v
-    check(_lib.load().vds_qkv_rope_norm_fwd(_p(qkv), _p(cos), _p(sin), _p(v0), _p(lam), _p(q), _p(k), _p(v), B, L, H,
-                                            hd, hdp, float(eps), _stream()), "vds_qkv_rope_norm_fwd")
-    return q, k, v
+def qkv_rope_fwd_cache(qkv, cos, sin, v0, lam, k, v, lead, past, B, L, H, hd, hdp):
+    """qkv_rope_fwd whose k / v rows go to row (l < lead ? l : l + past) of the cache buffers k, v [B,H,rows,hdp]; v0 is
+    block 0's cache v buffer, read through the same map (vds_qkv_rope_fwd_cache).  Returns q [B,H,L,hdp]."""
+    return _qkv_rope_fwd_cache("vds_qkv_rope_fwd_cache", qkv, cos, sin, v0, lam, k, v, lead, past, B, L, H, hd, hdp)
 
 
 def qkv_rope_norm_fwd_cache(qkv, cos, sin, v0, lam, k, v, lead, past, B, L, H, hd, hdp, eps: float = QK_NORM_EPS):
     """qkv_rope_fwd_cache with QK-norm (vds_qkv_rope_norm_fwd_cache)"""
-    st = _kv_cache_args(k, v, v0, B, H, hdp, lead, past, L)
-    q = torch.empty(B, H, L, hdp, dtype=bf16, device=qkv.device)
-    check(_lib.load().vds_qkv_rope_norm_fwd_cache(_p(qkv), _p(cos), _p(sin), _p(v0), _p(lam), _p(q), _p(k), _p(v), *st,
-                                                  lead, past, B, L, H, hd, hdp, float(eps), _stream()),
-          "vds_qkv_rope_norm_fwd_cache")
-    return q
-
-
-def qkv_rope_norm_bwd(dq, dk, dv, cos, sin, qkv_raw, v0, lam, dv0_acc, dlam, mix, add_dv0, B, L, H, hd, hdp,
-                      eps: float = QK_NORM_EPS, frames=None):
-    """backward of qkv_rope_norm_fwd; qkv_raw (the forward's qkv) is needed in every call (vds_qkv_rope_norm_bwd).
-    frames: as in qkv_rope_bwd (vds_qkv_rope_norm_bwd_fm)"""
-    fr = _fm_frames(frames, L) if frames is not None else None
-    dqkv = torch.empty(B * L, 3 * H * hd, dtype=bf16, device=dq.device)
-    if fr is not None:
-        check(_lib.load().vds_qkv_rope_norm_bwd_fm(_p(dq), _p(dk), _p(dv), _p(cos), _p(sin), _p(qkv_raw), _p(v0),
-                                                   _p(lam), _p(dv0_acc), _p(dlam), _p(dqkv), int(mix), int(add_dv0), B, L,
-                                                   H, hd, hdp, float(eps), fr, _stream()), "vds_qkv_rope_norm_bwd_fm")
-        return dqkv
-    check(_lib.load().vds_qkv_rope_norm_bwd(_p(dq), _p(dk), _p(dv), _p(cos), _p(sin), _p(qkv_raw), _p(v0), _p(lam),
-                                            _p(dv0_acc), _p(dlam), _p(dqkv), int(mix), int(add_dv0), B, L, H, hd, hdp,
-                                            float(eps), _stream()), "vds_qkv_rope_norm_bwd")
-    return dqkv
+    return _qkv_rope_fwd_cache("vds_qkv_rope_norm_fwd_cache", qkv, cos, sin, v0, lam, k, v, lead, past, B, L, H, hd, hdp,
+                               (float(eps),))
 
 
 def dv0_reduce(dvs, lams, out, B, H, L, hd, hdp, accumulate: bool = False):
