@@ -865,6 +865,25 @@ int vds_lowrank_wgrad(const void* a, int64_t lda, const void* u, int64_t ldu, fl
  * of wgrad -- what a test needs to place its shapes across the boundaries */
 int32_t vds_lowrank_chunk(int32_t which, int32_t r);
 
+/* ------------------------------------------------- head RMS-norm (QK-norm in cross-attention) ----
+ * The weightless RMSNorm of QK-norm on head rows outside the qkv / RoPE kernels (csrc/headnorm.hip), in place: the
+ * q_cross output and the k columns of the context_kv output.  The operand is a window [M, H * hd] of a bf16 parent with
+ * a row stride of ld elements; head h of row m sits at columns h * hd .. h * hd + hd - 1.  fp32 math, no atomics: results
+ * are bit-identical run to run, with or without vds_set_deterministic.  hd is a multiple of 8 up to 128, every ld a
+ * multiple of 8 and at least H * hd, every bf16 pointer 16-byte aligned (every access to the rows is a 16-byte row
+ * segment; nothing outside the window is read or written), rstd 4-byte aligned, H at most 65536.  NULL pointers,
+ * non-positive sizes, another hd, a misaligned or too small ld, a misaligned pointer, eps <= 0 or not finite:
+ * VDS_ERR_ARG before any launch.  The launches are credited to no profiler class.
+ *
+ * forward:  r = rsqrt(mean_d(float(x)^2) + eps);  x[m, h, :] = bf16(float(x[m, h, :]) * r);  rstd[m * H + h] = r.
+ *   One rounding, the one of vds_qkv_rope_norm_fwd's normed rows.  A zero row: r = rsqrt(eps), output 0. */
+int vds_head_rmsnorm_fwd(void* x, int64_t ldx, float* rstd, int32_t M, int32_t H, int32_t hd, float eps,
+                         vds_stream_t stream);
+/* backward: y = the forward's output rows, rstd = the forward's;  with g = float(dy), yf = float(y), r = rstd[m * H + h]:
+ *   dy[m, h, :] = bf16(r * (g - yf * mean_d(g * yf))), rounded once.  The raw rows are not needed. */
+int vds_head_rmsnorm_bwd(void* dy, int64_t lddy, const void* y, int64_t ldy, const float* rstd, int32_t M, int32_t H,
+                         int32_t hd, vds_stream_t stream);
+
 /* ------------------------------------------------------------------ live profiling ----
  * Per-kernel-class timing with HIP events recorded on the launch stream around each launch of
  * an enabled class (bench.py's roofline leg).  Off by default (no events, no overhead).

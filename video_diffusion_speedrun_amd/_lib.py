@@ -217,6 +217,8 @@ SIGNATURES = {
     "vds_lowrank_wgrad_workspace_floats": [c_i32, c_i32, c_i32],
     "vds_lowrank_wgrad": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_i64, c_vp],
     "vds_lowrank_chunk": [c_i32, c_i32],
+    "vds_head_rmsnorm_fwd": [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp],
+    "vds_head_rmsnorm_bwd": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp],
     "vds_selftest_lanemaps": [c_vp, c_vp],
     "vds_prof_enable": [C.c_uint32],
     "vds_prof_collect": [c_vp],

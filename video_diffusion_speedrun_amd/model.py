@@ -341,6 +341,11 @@ _FP8_QK_NORM = ("qk_norm is not implemented for the fp8 attention producers (vds
                 "call enable_fp8(attention=False) to keep the attention products on the bf16 kernels")
 
 
+def _qk_norm_all(qk_norm) -> bool:
+    """qk_norm="all": self-attention as True plus the cross-attention; every other value is its bool()"""
+    return isinstance(qk_norm, str) and qk_norm == "all"
+
+
 def check_frame_chunk(who: str, frame_chunk, frame_causal: bool, frame_major: bool) -> int:
     """frame_chunk of a DiT / DiTBlock: an int >= 1; more than 1 needs the frame-major frame-causal self-attention"""
     if isinstance(frame_chunk, bool) or not isinstance(frame_chunk, int) or frame_chunk < 1:
@@ -388,6 +393,10 @@ class DiTBlock(nn.Module):
         # QK-norm (no reference counterpart): a weightless RMSNorm on every head row of the self-attention's q and k
         # before the rotation, inside the qkv / RoPE kernels (ops.qkv_rope_norm_fwd / _bwd).  No parameter.
         self.qk_norm = bool(qk_norm)
+        # qk_norm="all" (exactly that string): the same norm on the cross-attention's q and k head rows as well -- the
+        # q_cross output and the k columns of the context_kv output, in place right behind their linears
+        # (ops.head_rmsnorm_fwd / _bwd).  v is not normed.  No parameter.  Without cross-attention: as True.
+        self.qk_norm_cross = _qk_norm_all(qk_norm) and cross_attn_input_size is not None
         # frame-causal self-attention (no reference counterpart): row q attends row k iff ops.mod_group_of(k) <=
         # ops.mod_group_of(q) for the frames = (lead, period) of the call -- the masked attention kernels
         # (ops.attn_fwd / attn_bwd, frames=).  Every other kernel of the block works per row and the cross-attention only
@@ -655,6 +664,10 @@ class DiTBlock(nn.Module):
                 u_qc = lora("q_cross", xn2, qc)
                 ckv = ops.linear_fwd(ctx2d, W("context_kv.weight"), Wo("context_kv.bias"))
                 u_ckv = lora("context_kv", ctx2d, ckv)
+            rstd_qc = rstd_kc = None
+            if self.qk_norm_cross:  # in place, before anything reads qc / ckv: from here on they hold the normed rows
+                rstd_qc = ops.head_rmsnorm_fwd(qc, H, hd)
+                rstd_kc = ops.head_rmsnorm_fwd(ckv[:, :D], H, hd)
             catt = torch.empty(B * L, D, dtype=bf16, device=dev)
             lse2 = torch.empty(B, H, L, dtype=f32, device=dev)
             # fp8 cross-attention: the same kernels as the self-attention (Lk = context length), operands quantised by
@@ -742,6 +755,7 @@ class DiTBlock(nn.Module):
             bs.u_qkv, bs.u_qc, bs.u_ckv = u_qkv, u_qc, u_ckv  # the adapters' x A^T (None without an adapter)
             if has_cross:
                 bs.xn2, bs.rstd2, bs.qc, bs.ckv, bs.catt, bs.lse2, bs.y_ca = xn2, rstd2, qc, ckv, catt, lse2, y_ca
+                bs.rstd_qc, bs.rstd_kc = rstd_qc, rstd_kc  # (qk_norm="all": bs.qc / bs.ckv hold the normed rows)
                 bs.c8, bs.c8_on, bs.qc8, bs.kc8, bs.vc8, bs.deqc = c8, c8_on, qc8, kc8, vc8, deqc
                 if c8:
                     bs.qc = bs.ckv = None  # the backward contracts the fp8 rows
@@ -895,6 +909,9 @@ class DiTBlock(nn.Module):
                              kv_pad_ones=ones, kv_lens=sv.kv_lens)
                 if bs.c8_on:
                     ops.absmax(dcatt, fp8_hist.cur(R0 + F8.ROW_DOC))
+            if self.qk_norm_cross:  # the gradients w.r.t. the normed rows -> w.r.t. the linears' outputs, in place
+                ops.head_rmsnorm_bwd(dqc, bs.qc, bs.rstd_qc, H, hd)
+                ops.head_rmsnorm_bwd(dckv[:, :D], bs.ckv[:, :D], bs.rstd_kc, H, hd)
             if T("context_kv.bias"):
                 ops.colsum(dckv, Gr("context_kv.bias"))
             if T("q_cross.bias"):
@@ -1079,7 +1096,8 @@ def activation_bytes(dit, B: int, latent_shape, Lc: int, mode: str = "none") -> 
       kept        depth x per_block (+ nothing else: the root-level saves are the same in every mode)
       transient   one block's full set of intermediates -- what a replay holds between a block's second `_fwd` and
                   the end of its `_bwd` (0 in mode "none", whose `kept` already is depth x that)
-    bf16 fp8-free path; the lists mirror the `bs.*` assignments of DiTBlock._fwd.  qk_norm changes nothing here: its
+    bf16 fp8-free path; the lists mirror the `bs.*` assignments of DiTBlock._fwd.  qk_norm="all" adds the two rstd tensors
+    of the cross-attention's head norm (4 H bytes per token row and per context row).  qk_norm=True changes nothing: its
     backward reads the qkv GEMM output (3 D bf16 elements per token row), which every block -- block 0, which mixes no
     v_0, included -- already keeps and this sum already counts."""
     if mode not in RECOMPUTE_MODES:
@@ -1102,6 +1120,8 @@ def activation_bytes(dit, B: int, latent_shape, Lc: int, mode: str = "none") -> 
     if cross:
         full += 2 * R * D * 4 + 4 * R + lse  # xn2, qc, catt, y_ca, rstd2, lse2
         full += 2 * B * Lc * 2 * D           # ckv
+        if getattr(dit, "qk_norm_cross", False):
+            full += 4 * H * (R + B * Lc)     # rstd_qc, rstd_kc (qk_norm="all")
     else:
         full -= 2 * R * D                # (no X2 of its own)
     full += 2 * R * D + 4 * R            # xn3, rstd3
@@ -1138,6 +1158,8 @@ class DiT(nn.Module):
                  qk_norm=False):
         super().__init__()
         self.qk_norm = bool(qk_norm)  # see DiTBlock: parameter-free RMSNorm of q and k in the self-attention
+        # see DiTBlock: qk_norm="all" norms the cross-attention's q and k too (a model without cross-attention: as True)
+        self.qk_norm_cross = _qk_norm_all(qk_norm) and cross_attn_input_size is not None
         # see DiTBlock: every self-attention runs with frames = (N_REG, t) -- the registers attend each other, a token of
         # frame f the registers and frames 0 .. f.  The model is then causal over token-frames in the LATENTS; with
         # per-frame timesteps the registers are still modulated from the row maximum of the timesteps, so it is not causal

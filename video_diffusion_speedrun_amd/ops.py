@@ -912,6 +912,54 @@ def qkv_rope_norm_fwd_cache(qkv, cos, sin, v0, lam, k, v, lead, past, B, L, H, h
                                (float(eps),))
 
 
+def _head_rows(what: str, name: str, t, H: int, hd: int):
+    """a head-norm operand: a bf16 [M, H * hd] tensor or column window whose rows are 16-byte segments of a parent"""
+    if not isinstance(t, torch.Tensor) or t.dtype != bf16 or t.dim() != 2 or t.shape[1] != H * hd:
+        got = (t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{what}: {name} must be bfloat16 of shape [M, H * hd = {H * hd}], got {got}")
+    if t.shape[0] < 1 or t.stride(1) != 1 or t.stride(0) % 8 != 0 or t.stride(0) < H * hd:
+        raise ValueError(f"{what}: {name} {tuple(t.shape)} with strides {t.stride()} is no window of rows -- at least one "
+                         f"row, contiguous columns and a row stride that is a multiple of 8 and at least {H * hd}")
+
+
+def _head_dims(what: str, H, hd):
+    if not (isinstance(H, int) and isinstance(hd, int)) or H < 1 or hd < 8 or hd % 8 != 0 or hd > 128:
+        raise ValueError(f"{what}: H = {H!r} must be an int >= 1 and hd = {hd!r} a multiple of 8 up to 128")
+
+
+def head_rmsnorm_fwd(x, H: int, hd: int, eps: float = QK_NORM_EPS) -> torch.Tensor:
+    """QK-norm of the head rows of x [M, H * hd] bf16 (a tensor or a column window such as ckv[:, :D]), IN PLACE:
+    x[m, h] <- bf16(float(x[m, h]) * r), r = rsqrt(mean_d(x^2) + eps) -> rstd [M, H] f32 (vds_head_rmsnorm_fwd)"""
+    _head_dims("head_rmsnorm_fwd", H, hd)
+    _head_rows("head_rmsnorm_fwd", "x", x, H, hd)
+    eps = float(eps)
+    if not (0.0 < eps < float("inf")):
+        raise ValueError(f"head_rmsnorm_fwd: eps = {eps!r} must be positive and finite")
+    M = x.shape[0]
+    rstd = torch.empty(M, H, dtype=f32, device=x.device)
+    check(_lib.load().vds_head_rmsnorm_fwd(_p(x), x.stride(0), _p(rstd), M, H, hd, eps, _stream()),
+          f"vds_head_rmsnorm_fwd(M={M},H={H},hd={hd})")
+    return rstd
+
+
+def head_rmsnorm_bwd(dy, y, rstd, H: int, hd: int) -> torch.Tensor:
+    """backward of head_rmsnorm_fwd, IN PLACE on dy [M, H * hd] bf16: dy[m, h] <- bf16(r (g - y mean_d(g y))) with y the
+    forward's output rows and rstd [M, H] f32 the forward's (vds_head_rmsnorm_bwd); dy and y may be column windows"""
+    _head_dims("head_rmsnorm_bwd", H, hd)
+    _head_rows("head_rmsnorm_bwd", "dy", dy, H, hd)
+    _head_rows("head_rmsnorm_bwd", "y", y, H, hd)
+    M = dy.shape[0]
+    if y.shape[0] != M or y.device != dy.device:
+        raise ValueError(f"head_rmsnorm_bwd: y has {y.shape[0]} rows on {y.device}, dy {M} on {dy.device}")
+    if (not isinstance(rstd, torch.Tensor) or rstd.dtype != f32 or tuple(rstd.shape) != (M, H) or not rstd.is_contiguous()
+            or rstd.device != dy.device):
+        got = (rstd.dtype, tuple(rstd.shape)) if isinstance(rstd, torch.Tensor) else type(rstd).__name__
+        raise ValueError(f"head_rmsnorm_bwd: rstd must be contiguous float32 of shape ({M}, {H}) on dy's device, got {got}")
+    check(_lib.load().vds_head_rmsnorm_bwd(_p(dy), dy.stride(0), _p(y), y.stride(0), _p(rstd), M, H, hd, _stream()),
+          f"vds_head_rmsnorm_bwd(M={M},H={H},hd={hd})")
+    return dy
+
+
 def dv0_reduce(dvs, lams, out, B, H, L, hd, hdp, accumulate: bool = False):
     """out[B,H,L,hdp] f32 (+)= sum_i (1 - lam_i) dvs[i][..., :hd]: the residual-V gradient of v_0 from all mixed blocks in one
     pass (vds_dv0_reduce; the blocks' RoPE backward then runs with mix = 2)"""
