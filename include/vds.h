@@ -58,7 +58,10 @@ const char* vds_last_error(void);
  * its epilogue) a leading dimension that keeps 16-byte row segments aligned: ldc % 8 == 0 (ldc % 4 == 0 for the
  * fp32 C of VDS_EPI_F32), ldc2 % 8 == 0 (BIAS_GELU, GATE_RES), ldaux % 8 == 0 (GATE_RES, DGELU), ldgate % 4 == 0
  * (GATE_RES).  Base pointers must be 16-byte aligned (not checked); an A or B operand of 4 GiB or more is
- * VDS_ERR_UNSUPPORTED. */
+ * VDS_ERR_UNSUPPORTED.
+ * Six (layout, epilogue) pairs exist: NT + STORE, NT + BIAS_GELU, NT + GATE_RES, NN + STORE, NN + DGELU, TN + F32.  Any
+ * other pair is VDS_ERR_UNSUPPORTED -- in every tiling, with or without colsum, before anything is chosen or launched --
+ * unless the call also breaks a requirement above: VDS_ERR_ARG wins. */
 enum { VDS_NT = 0, VDS_NN = 1, VDS_TN = 2 };
 enum { VDS_EPI_STORE = 0, VDS_EPI_BIAS_GELU = 1, VDS_EPI_GATE_RES = 2, VDS_EPI_DGELU = 3, VDS_EPI_F32 = 4 };
 
@@ -87,6 +90,7 @@ int vds_gemm_bf16(const vds_gemm_args* args, vds_stream_t stream);
  * values.  Knob "gemm_tile" (VDS_GEMM_TILE sets the initial value).  Results are identical across tilings up
  * to fp32 summation order. */
 int vds_gemm_force_tile(int32_t tile);
+/* (vds_gemm_plan, below vds_gemm_bf16_grouped, reports the tiling and grid a call would get.) */
 /* ------------------------------------------------------------ process-wide settings -----
  * Every tuning knob of the library lives in ONE table (csrc/config.h lists them with their defaults) that is filled from
  * the environment once, when the library is loaded; no entry point reads the environment afterwards.  vds_knob_set
@@ -395,6 +399,21 @@ int vds_gate_bwd_grouped(const void* dxn, int64_t lddxn, const void* y, int64_t 
  * path of a rows_per_batch = 1 launch with an expanded [M, N] gate table, to which the result is bit-identical.
  * Any other layout / epilogue with groups != NULL: VDS_ERR_ARG. */
 int vds_gemm_bf16_grouped(const vds_gemm_args* args, const vds_mod_groups* groups, vds_stream_t stream);
+/* Tests / experiments: what vds_gemm_bf16 (groups == NULL) / vds_gemm_bf16_grouped would do with these arguments under
+ * the current knobs and deterministic mode, without launching anything.  Runs the same argument check and the same
+ * planning function as the launching entries: returns the code they would refuse the call with (*info is then left
+ * alone), else VDS_OK with *info filled.  info == NULL is VDS_ERR_ARG.  In deterministic mode split_k is the count
+ * asked of the split-K launch; that launch still lowers it until its slabs fit the workspace. */
+typedef struct vds_gemm_plan_info {
+  int32_t tiling;            /* 128 = 128x128 tiles, 2 = 256x128, 256 = 256x256 (the values of vds_gemm_force_tile) */
+  int32_t tiles_m, tiles_n;  /* the grid is tiles_m * tiles_n x split_k workgroups */
+  int32_t split_k, atomic;   /* K splits (1 = none); the epilogue accumulates into C with fp32 atomics */
+  int32_t group_m;           /* row tiles per group of the grouped tile order */
+  int32_t joint_xcd;         /* split-K: XCD-aware order over the joint (split, tile) list */
+  int32_t narrow;            /* 256x256: the last tile column runs the 256 x 128 body */
+  int32_t colsum;            /* args->colsum: 0 absent, 1 fused into the epilogue, 2 a vds_colsum_bf16 pass after the GEMM */
+} vds_gemm_plan_info;
+int vds_gemm_plan(const vds_gemm_args* args, const vds_mod_groups* groups, vds_gemm_plan_info* info);
 
 /* column sums: out[n] (f32, atomically +=) += sum_m x[m,n]  (bias gradients). */
 int vds_colsum_bf16(const void* x, int64_t ldx, float* out, int32_t M, int32_t N, vds_stream_t stream);

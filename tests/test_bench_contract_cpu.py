@@ -48,6 +48,10 @@ def test_gpus_n_starts_n_ranks_itself():
     """`python bench.py --gpus 2` with no launcher environment must start 2 ranks (child torch.distributed.run) and
     relay their exit code; here, without a GPU, every rank refuses to run -- which proves they were started"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    # torch.distributed.run polls its ranks every 0.1 s and sends SIGTERM to the others when one has failed: on a loaded
+    # machine the second rank can still be inside `import torch` then and never prints its refusal.  Its own setting (the
+    # --monitor-interval option, read from this variable) makes it look every 2 s, so both ranks get to their check.
+    env["PET_MONITOR_INTERVAL"] = "2"
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                          capture_output=True, text=True, env=env, timeout=300)
     text = out.stderr + out.stdout

@@ -291,8 +291,48 @@ def test_dgelu_bounded_and_column_sums(ops, tile, embedded, parity_log):
                table_bound=table, worst_error_over_bound=worst, colsum_worst_error_over_bound=worst_cs)
 
 
+@pytest.mark.parametrize("mode", ["default", "deterministic"])
+def test_dgelu_column_sums_in_every_tiling_and_mode(ops, tile, mode):
+    """NN DGELU with `colsum` at 264 x 328 x 328 (ragged rows, a narrow ragged last column on the 256-wide tiling, 5.1 K
+    tiles) under every tiling, in the default mode (fused into the 256^2 epilogue, a vds_colsum_bf16 pass after the other
+    tilings) and in deterministic mode (the pass after every tiling): C within dgelu_bound of the float64 expectation,
+    the same C bits with and without colsum, and colsum - c0 within the bound derived in
+    test_dgelu_bounded_and_column_sums of the float64 column sums of the stored C.  Operands embedded: NaN past M."""
+    M, N, K = shape = (264, 328, 328)
+    assert shape in G.SHAPES_NN
+    dg = G.dgelu_case(M, N, K)
+    A, B, aux = src(dg.A, True), src(dg.B, True), src(dg.aux, True)
+    c0 = G.ints((N,), 1, 3, 77 + N) * (G.ints((N,), 0, 1, 78 + N) * 2 - 1)
+    what = tag(f"DGELU colsum {mode}", tile, True, shape)
+    if mode == "deterministic":
+        ops.set_deterministic(True, 64 << 20)
+    try:
+        out, out2 = dst(M, N, bf16, True), dst(M, N, bf16, True)
+        cs = dst(1, N, f32, True, init=c0.to(f32).view(1, N))
+        gemm(ops, NN, _lib.EPI_DGELU, M, N, K, A, B, out, aux=aux)
+        gemm(ops, NN, _lib.EPI_DGELU, M, N, K, A, B, out2, aux=aux, colsum=cs)
+        torch.cuda.synchronize()
+    finally:
+        if mode == "deterministic":
+            ops.set_deterministic(False)
+    out.contained(what)
+    got = out.value()
+    err = (got.double() - dg.want64).abs()
+    bound = G.dgelu_bound(dg.want64, dg.acc, tile in (0, 256))
+    print(f"{what}: worst error / bound {float((err / bound.clamp(min=1e-300))[bound > 0].max()):.4f}")
+    assert not (~(err <= bound)).any(), what
+    out2.exact(got, what + "C with colsum against C without")
+    cs.contained(what + "colsum")
+    got_cs = cs.value()[0].double()
+    c64 = got.double()
+    cs_err = (got_cs - c0 - c64.sum(0)).abs()
+    cs_bound = M * 2.0 ** -24 * c64.abs().sum(0) + -(-M // 64) * 2.0 ** -24 * c0.abs()
+    print(f"{what}: colsum worst error / bound {float((cs_err / cs_bound).max()):.4f}")
+    assert torch.isfinite(got_cs).all() and not (~(cs_err <= cs_bound)).any(), (what, "colsum")
+
+
 # ---- TN F32 ------------------------------------------------------------------------------------------------------------
-SPLITS = (1, 3, 5, 0, -1, -2)   # none | 3 | 5 (more splits than K tiles on most shapes) | the auto forms | accumulate
+SPLITS =(1, 3, 5, 0, -1, -2)   # none | 3 | 5 (more splits than K tiles on most shapes) | the auto forms | accumulate
 
 
 def _tn_census(ops, tile, embedded, mode, two_slabs=False):

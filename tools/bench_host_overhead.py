@@ -28,3 +28,15 @@ y = torch.zeros(64, 64, dtype=torch.float32, device="cuda")
 torch.cuda.synchronize()
 print("ops.cast_f32_bf16 (one tiny launch, queue not drained): %.2f us" % t(lambda: ops.cast_f32_bf16(y.view(-1), x.view(-1)), 20000))
 torch.cuda.synchronize()
+# vds_gemm_bf16 on a 64^3 problem (NT, STORE): through ops.linear_fwd, and the C entry alone on prebuilt arguments -- its
+# check, plan and launch
+import ctypes as C
+w = torch.zeros(64, 64, dtype=torch.bfloat16, device="cuda")
+out = torch.empty(64, 64, dtype=torch.bfloat16, device="cuda")
+print("ops.linear_fwd 64x64x64 (vds_gemm_bf16, queue not drained): %.2f us" % t(lambda: ops.linear_fwd(x, w, out=out), 20000))
+torch.cuda.synchronize()
+a = _lib.GemmArgs(_lib.VDS_NT, _lib.EPI_STORE, 64, 64, 64, x.data_ptr(), 64, w.data_ptr(), 64, out.data_ptr(), 64)
+a.split_k = 1
+ref, stream = C.byref(a), torch._C._cuda_getCurrentRawStream(0)
+print("lib.vds_gemm_bf16 64x64x64 (the C entry alone)            : %.2f us" % t(lambda: lib.vds_gemm_bf16(ref, stream), 20000))
+torch.cuda.synchronize()

@@ -61,6 +61,11 @@ class ModGroups(C.Structure):  # vds_mod_groups
     _fields_ = [("lead", c_i32), ("period", c_i32)]
 
 
+class GemmPlanInfo(C.Structure):  # vds_gemm_plan_info
+    _fields_ = [(n, c_i32) for n in ("tiling", "tiles_m", "tiles_n", "split_k", "atomic", "group_m", "joint_xcd", "narrow",
+                                     "colsum")]
+
+
 class ProfStat(C.Structure):
     _fields_ = [("launches", c_i64), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -120,6 +125,7 @@ SIGNATURES = {
     "vds_gate_bwd_grouped": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32,
                              c_i32, c_vp, c_vp],
     "vds_gemm_bf16_grouped": [C.POINTER(GemmArgs), c_vp, c_vp],
+    "vds_gemm_plan": [C.POINTER(GemmArgs), c_vp, C.POINTER(GemmPlanInfo)],
     "vds_colsum_bf16": [c_vp, c_i64, c_vp, c_i32, c_i32, c_vp],
     "vds_colsum_bf16_rows": [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp],
     "vds_qkv_rope_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],

@@ -1147,28 +1147,6 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel(GemmP p) {
   gemm_tile<LAYOUT, EPI, FMT, 256>(p, smem, m0, n0, kt_begin, kt_end);
 }
 
-template <int LAYOUT, int EPI, int FMT = 0>
-int launch(const GemmP& p, hipStream_t s) {
-  constexpr bool USE_LUT = EPI == VDS_EPI_BIAS_GELU || EPI == VDS_EPI_DGELU;
-  constexpr int LDS_TOTAL = LDS_BYTES + (USE_LUT ? LUT_BYTES : 0);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<LAYOUT, EPI, FMT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-    attr_set = true;
-  }
-  if constexpr (USE_LUT) {
-    if (!ensure_gelu_lut()) return VDS_ERR_LAUNCH;
-  }
-  dim3 grid(p.tiles_m * p.tiles_n, p.split_k > 1 ? p.split_k : 1, 1);
-  const double k = FMT != 0 ? p.prof_k : (double)p.K;
-  vdsprof::Scope ps(FMT != 0 ? VDS_PROF_GEMM_FP8 : LAYOUT == VDS_NT ? VDS_PROF_GEMM_NT : LAYOUT == VDS_NN ? VDS_PROF_GEMM_NN
-                                                                                                       : VDS_PROF_GEMM_TN,
-                    s, 2.0 * p.M * p.N * k, (FMT != 0 ? 1.0 : 2.0) * ((double)p.M * k + (double)p.N * k) + 2.0 * (double)p.M * p.N);
-  hipLaunchKernelGGL((gemm_kernel<LAYOUT, EPI, FMT>), grid, dim3(512), LDS_TOTAL, s, p);
-  return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
-}
-
 }  // namespace big
 
 // =====================================================================================
@@ -1364,39 +1342,83 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmP p) {
   }
 }
 
-template <int LAYOUT, int EPI>
-int launch(const GemmP& p, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<LAYOUT, EPI>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    attr_set = true;
-  }
-  dim3 grid(p.tiles_m * p.tiles_n, p.split_k > 1 ? p.split_k : 1, 1);
-  vdsprof::Scope ps(LAYOUT == VDS_NT ? VDS_PROF_GEMM_NT : LAYOUT == VDS_NN ? VDS_PROF_GEMM_NN : VDS_PROF_GEMM_TN, s,
-                    2.0 * p.M * p.N * p.K, 2.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N));
-  hipLaunchKernelGGL((gemm_kernel<LAYOUT, EPI>), grid, dim3(256), LDS_BYTES, s, p);
-  return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
-}
 }  // namespace mid
 
-thread_local char g_err[256] = "";
-
-template <int LAYOUT, int EPI>
-int launch(const GemmP& p, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<LAYOUT, EPI>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    attr_set = true;
-  }
-  dim3 grid(p.tiles_m * p.tiles_n, p.split_k > 1 ? p.split_k : 1, 1);
-  vdsprof::Scope ps(LAYOUT == VDS_NT ? VDS_PROF_GEMM_NT : LAYOUT == VDS_NN ? VDS_PROF_GEMM_NN : VDS_PROF_GEMM_TN, s,
-                    2.0 * p.M * p.N * p.K, 2.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N));
-  hipLaunchKernelGGL((gemm_kernel<LAYOUT, EPI>), grid, dim3(256), LDS_BYTES, s, p);
+// ---- launching (host) ---------------------------------------------------------------------------------------------------
+// One launch of a GEMM kernel on the grid tiles_m * tiles_n x splits: vds_launch (common.h) raises the kernel's dynamic-LDS
+// limit to LDS before its first launch.  `cls`, `flops`, `bytes`: the profiler scope of the launch (prof.h).
+template <auto KERNEL, int LDS, int THREADS>
+int launch_gemm(const GemmP& p, hipStream_t s, int cls, double flops, double bytes) {
+  vdsprof::Scope ps(cls, s, flops, bytes);
+  vds_launch<KERNEL, LDS>(dim3(p.tiles_m * p.tiles_n, p.split_k > 1 ? p.split_k : 1, 1), dim3(THREADS), LDS, s, p);
   return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
 }
 
+// The three tilings as tags: the kernel of a (layout, epilogue, format) triple, its dynamic LDS, its workgroup size, its
+// K-tile depth, and the value vds_gemm_force_tile / vds_gemm_plan_info.tiling names it with.
+struct Small {  // 128 x 128 x 64
+  static constexpr int TILING = 128, THREADS = 256, K_TILE = BK;
+  template <int EPI> static constexpr bool LUT = false;
+  template <int EPI> static constexpr int LDS = LDS_BYTES;
+  template <int LAYOUT, int EPI, int FMT> static constexpr auto kernel = gemm_kernel<LAYOUT, EPI>;
+};
+struct Mid {  // 256 x 128 x 32
+  static constexpr int TILING = 2, THREADS = 256, K_TILE = mid::BK;
+  template <int EPI> static constexpr bool LUT = false;
+  template <int EPI> static constexpr int LDS = mid::LDS_BYTES;
+  template <int LAYOUT, int EPI, int FMT> static constexpr auto kernel = mid::gemm_kernel<LAYOUT, EPI>;
+};
+struct Big {  // 256 x 256 x 64; the GELU epilogues read gelu / gelu' from a table in LDS.  No bf16 TN kernel; fp8: FMT != 0
+  static constexpr int TILING = 256, THREADS = 512, K_TILE = BK;
+  template <int EPI> static constexpr bool LUT = EPI == VDS_EPI_BIAS_GELU || EPI == VDS_EPI_DGELU;
+  template <int EPI> static constexpr int LDS = big::LDS_BYTES + (LUT<EPI> ? LUT_BYTES : 0);
+  template <int LAYOUT, int EPI, int FMT> static constexpr auto kernel = big::gemm_kernel<LAYOUT, EPI, FMT>;
+};
+
+// The code object holds the kernels in the order they are instantiated, and the three table-reading instances of the 256^2
+// kernel address g_gelu_lut relative to their own position.  With the 128^2 weight-gradient kernel instantiated here, ahead
+// of the 256^2 ones (run_bf16 and vds_gemm_fp8 name the rest in table order), every kernel keeps the address it had before
+// the host side was rewritten, and the device code compares byte for byte (profiles/gemm_dispatch/).  Nothing but that
+// comparison depends on it.
+template __global__ void gemm_kernel<VDS_TN, VDS_EPI_F32>(GemmP);
+
+// the instance of tiling T for one (layout, epilogue, format): FMT 0 = bf16 operands, 1 / 2 = fp8 NT with A e4m3 / e5m2,
+// 3 = fp8 TN (one byte per element, p.K counts 2-byte units: the profiler is given p.prof_k)
+template <class T, int LAYOUT, int EPI, int FMT = 0>
+int launch_instance(const GemmP& p, hipStream_t s) {
+  if constexpr (LAYOUT == VDS_TN && FMT == 0 && std::is_same_v<T, Big>) {
+    return VDS_ERR_UNSUPPORTED;  // (never planned: plan_bf16 keeps TN off the 256^2 tiling)
+  } else {
+    if constexpr (T::template LUT<EPI>) {
+      if (!ensure_gelu_lut()) return VDS_ERR_LAUNCH;
+    }
+    const double k = p.prof_k;
+    return launch_gemm<T::template kernel<LAYOUT, EPI, FMT>, T::template LDS<EPI>, T::THREADS>(
+        p, s, FMT != 0 ? VDS_PROF_GEMM_FP8 : LAYOUT == VDS_NT ? VDS_PROF_GEMM_NT : LAYOUT == VDS_NN ? VDS_PROF_GEMM_NN
+                                                                                                   : VDS_PROF_GEMM_TN,
+        2.0 * p.M * p.N * k, (FMT != 0 ? 1.0 : 2.0) * ((double)p.M * k + (double)p.N * k) + 2.0 * (double)p.M * p.N);
+  }
+}
+
+// THE table of the bf16 GEMM: its six (layout, epilogue) pairs, f(layout, epilogue) as integral constants for the one
+// given, VDS_ERR_UNSUPPORTED for any other.  The grouped form of GATE_RES (vds_gemm_bf16_grouped) is an epilogue id of
+// its own, mapped here and nowhere else.
+template <int V> using ic = std::integral_constant<int, V>;
+constexpr int pair_key(int layout, int epilogue) { return layout * 8 + epilogue; }  // (both in range: checked first)
+template <typename F>
+int with_pair(int layout, int epilogue, bool grouped, F f) {
+  if (layout < VDS_NT || layout > VDS_TN || epilogue < VDS_EPI_STORE || epilogue > VDS_EPI_F32) return VDS_ERR_UNSUPPORTED;
+  switch (pair_key(layout, epilogue)) {
+    case pair_key(VDS_NT, VDS_EPI_STORE): return f(ic<VDS_NT>{}, ic<VDS_EPI_STORE>{});
+    case pair_key(VDS_NT, VDS_EPI_BIAS_GELU): return f(ic<VDS_NT>{}, ic<VDS_EPI_BIAS_GELU>{});
+    case pair_key(VDS_NT, VDS_EPI_GATE_RES):
+      return grouped ? f(ic<VDS_NT>{}, ic<EPI_GATE_RES_G>{}) : f(ic<VDS_NT>{}, ic<VDS_EPI_GATE_RES>{});
+    case pair_key(VDS_NN, VDS_EPI_STORE): return f(ic<VDS_NN>{}, ic<VDS_EPI_STORE>{});
+    case pair_key(VDS_NN, VDS_EPI_DGELU): return f(ic<VDS_NN>{}, ic<VDS_EPI_DGELU>{});
+    case pair_key(VDS_TN, VDS_EPI_F32): return f(ic<VDS_TN>{}, ic<VDS_EPI_F32>{});
+    default: return VDS_ERR_UNSUPPORTED;
+  }
+}
 
 // ---- fixed-order split-K (deterministic mode, round 6) --------------------------------------------------------------------
 // vds_set_deterministic(1, workspace, bytes): a split-K weight gradient writes one dense fp32 slab [M, N] per split into the
@@ -1467,81 +1489,93 @@ extern "C" int vds_gemm_force_tile(int32_t tile) {
   return prev;
 }
 
-static int gemm_bf16_impl(const vds_gemm_args* a, const vds_mod_groups* grp, vds_stream_t stream) {
-  if (!a || !a->A || !a->B || a->M <= 0 || a->N <= 0 || a->K <= 0) return VDS_ERR_ARG;
-  if ((a->N & 7) || (a->lda & 7) || (a->ldb & 7)) return VDS_ERR_ARG;
-  // the epilogues move 16-byte row segments at row * ld + column (column % 8 == 0): every leading dimension of a pointer
-  // this call uses must keep them aligned -- 8 bf16 elements, 4 floats (the fp32 C of VDS_EPI_F32, the gate table)
-  {
-    const int e = a->epilogue;
-    if (a->C && (a->ldc & (e == VDS_EPI_F32 ? 3 : 7))) return VDS_ERR_ARG;
-    if ((e == VDS_EPI_BIAS_GELU || e == VDS_EPI_GATE_RES) && a->C2 && (a->ldc2 & 7)) return VDS_ERR_ARG;
-    if ((e == VDS_EPI_GATE_RES || e == VDS_EPI_DGELU) && a->aux && (a->ldaux & 7)) return VDS_ERR_ARG;
-    if (e == VDS_EPI_GATE_RES && a->gate && (a->ldgate & 3)) return VDS_ERR_ARG;
-  }
-  GemmP p;
-  p.M = a->M; p.N = a->N; p.K = a->K;
-  p.A = (const bf16_t*)a->A; p.lda = a->lda;
-  p.B = (const bf16_t*)a->B; p.ldb = a->ldb;
+// ---- argument handling shared by vds_gemm_bf16, vds_gemm_bf16_grouped and vds_gemm_fp8 -----------------------------------
+namespace {
+
+// the epilogues move 16-byte row segments at row * ld + column (column % 8 == 0): every leading dimension of a pointer
+// the call uses must keep them aligned -- 8 bf16 elements, 4 floats (the fp32 C of VDS_EPI_F32, the gate table)
+int check_epilogue_ld(const vds_gemm_args* a) {
+  const int e = a->epilogue;
+  if (a->C && (a->ldc & (e == VDS_EPI_F32 ? 3 : 7))) return VDS_ERR_ARG;
+  if ((e == VDS_EPI_BIAS_GELU || e == VDS_EPI_GATE_RES) && a->C2 && (a->ldc2 & 7)) return VDS_ERR_ARG;
+  if ((e == VDS_EPI_GATE_RES || e == VDS_EPI_DGELU) && a->aux && (a->ldaux & 7)) return VDS_ERR_ARG;
+  if (e == VDS_EPI_GATE_RES && a->gate && (a->ldgate & 3)) return VDS_ERR_ARG;
+  return VDS_OK;
+}
+
+// The kernel arguments that come straight from vds_gemm_args; every other member starts as 0 / NULL.  `esz`: bytes per
+// operand element (2 = bf16, 1 = fp8; the kernels address the operands in 2-byte units).
+// split_k: > 1 that many K splits (atomic accumulation into a pre-zeroed C); 1 none; <= -2: |split_k| splits and
+// atomic accumulation; 0 / -1 (bf16 TN + F32 only): the library picks tiling and split count itself (-1: and always
+// accumulates, so that several calls can sum into one C) -- plan_bf16 overwrites both members for them
+GemmP gemm_params(const vds_gemm_args* a, int esz) {
+  GemmP p{};
+  p.M = a->M; p.N = a->N; p.K = a->K * esz / 2;
+  p.A = (const bf16_t*)a->A; p.lda = a->lda * esz / 2;
+  p.B = (const bf16_t*)a->B; p.ldb = a->ldb * esz / 2;
   p.C = a->C; p.ldc = a->ldc; p.C2 = a->C2; p.ldc2 = a->ldc2;
   p.bias = (const bf16_t*)a->bias;
   p.aux = (const bf16_t*)a->aux; p.ldaux = a->ldaux;
   p.gate = a->gate; p.ldgate = a->ldgate;
   p.rows_per_batch = a->rows_per_batch > 0 ? a->rows_per_batch : a->M;
-  p.row_base = 0;
-  p.g_lead = p.g_period = 0;
-  if (grp) {  // one gate row per modulation group: rows_per_batch is L, the rows of one sample
-    if (a->epilogue != VDS_EPI_GATE_RES || a->layout != VDS_NT || a->rows_per_batch <= 0 || a->M % a->rows_per_batch != 0 ||
-        grp->lead < 0 || grp->period < 1 || grp->lead > a->rows_per_batch || (a->rows_per_batch - grp->lead) % grp->period != 0)
-      return VDS_ERR_ARG;
-    p.g_lead = grp->lead;
-    p.g_period = grp->period;
-  }
-  p.slab_stride = 0;
-  // split_k: > 1 that many K splits (atomic accumulation into a pre-zeroed C); 1 none; <= -2: |split_k| splits and
-  // atomic accumulation; 0 / -1 (TN + F32 only): the library picks tiling and split count itself (-1: and always
-  // accumulates, so that several calls can sum into one C)
-  const bool auto_split = (a->split_k == 0 || a->split_k == -1) && a->layout == VDS_TN && a->epilogue == VDS_EPI_F32;
   p.split_k = a->split_k > 1 ? a->split_k : (a->split_k < -1 ? -a->split_k : 1);
   p.atomic = (a->split_k > 1 || a->split_k < 0) ? 1 : 0;
-  p.sa = p.sb = nullptr;
   p.prof_k = a->K;
-  p.e_q = p.e_qt = nullptr; p.e_ldq = p.e_ldqt = 0;
-  p.e_amax_in = nullptr; p.e_amax_out = p.e_dq_out = p.e_colsum = nullptr; p.e_fmt = 0;
-  p.narrow = 0;
-  if (a->colsum && !(a->epilogue == VDS_EPI_DGELU && a->C)) return VDS_ERR_ARG;
-  p.tiles_m = cdiv(a->M, BM);
-  p.tiles_n = cdiv(a->N, BN);
-  size_t abytes, bbytes;
-  switch (a->layout) {
-    case VDS_NT:
-      if (a->K & 7) return VDS_ERR_ARG;
-      abytes = ((size_t)(a->M - 1) * a->lda + a->K) * 2;
-      bbytes = ((size_t)(a->N - 1) * a->ldb + a->K) * 2;
-      break;
-    case VDS_NN:
-      if (a->K & 7) return VDS_ERR_ARG;
-      abytes = ((size_t)(a->M - 1) * a->lda + a->K) * 2;
-      bbytes = ((size_t)(a->K - 1) * a->ldb + a->N) * 2;
-      break;
-    case VDS_TN:
-      if (a->M & 7) return VDS_ERR_ARG;
-      abytes = ((size_t)(a->K - 1) * a->lda + a->M) * 2;
-      bbytes = ((size_t)(a->K - 1) * a->ldb + a->N) * 2;
-      break;
-    default:
-      return VDS_ERR_ARG;
-  }
+  return p;
+}
+
+// p.a_bytes / p.b_bytes (the SRD ranges: rows past the end read as zero) from the extent of each operand, rows x cols of
+// `esz`-byte elements with the k-major ones [K, .]; an operand of 4 GiB or more is VDS_ERR_UNSUPPORTED
+int operand_extents(const vds_gemm_args* a, int esz, GemmP& p) {
+  const bool a_km = a->layout == VDS_TN, b_km = a->layout != VDS_NT;
+  const size_t abytes = ((size_t)((a_km ? a->K : a->M) - 1) * a->lda + (a_km ? a->M : a->K)) * esz;
+  const size_t bbytes = ((size_t)((b_km ? a->K : a->N) - 1) * a->ldb + (b_km ? a->N : a->K)) * esz;
   if (abytes >= (1ull << 32) || bbytes >= (1ull << 32)) return VDS_ERR_UNSUPPORTED;
   p.a_bytes = (unsigned)abytes;
   p.b_bytes = (unsigned)bbytes;
-  hipStream_t s = (hipStream_t)stream;
+  return VDS_OK;
+}
+
+// ---- vds_gemm_bf16 / vds_gemm_bf16_grouped: check, plan, run --------------------------------------------------------------
+// Every refusal of the two entries, and the kernel arguments that do not depend on the tiling.  VDS_ERR_ARG wins over the
+// pair outside the table (VDS_ERR_UNSUPPORTED, the last check); a 4 GiB operand is refused where it always was.
+int check_bf16(const vds_gemm_args* a, const vds_mod_groups* grp, GemmP& p) {
+  if (!a || !a->A || !a->B || a->M <= 0 || a->N <= 0 || a->K <= 0) return VDS_ERR_ARG;
+  if ((a->N & 7) || (a->lda & 7) || (a->ldb & 7)) return VDS_ERR_ARG;
+  if (check_epilogue_ld(a) != VDS_OK) return VDS_ERR_ARG;
+  // one gate row per modulation group: rows_per_batch is L, the rows of one sample
+  if (grp && (a->epilogue != VDS_EPI_GATE_RES || a->layout != VDS_NT || a->rows_per_batch <= 0 ||
+              a->M % a->rows_per_batch != 0 || grp->lead < 0 || grp->period < 1 || grp->lead > a->rows_per_batch ||
+              (a->rows_per_batch - grp->lead) % grp->period != 0))
+    return VDS_ERR_ARG;
+  if (a->colsum && !(a->epilogue == VDS_EPI_DGELU && a->C)) return VDS_ERR_ARG;
+  if (a->layout < VDS_NT || a->layout > VDS_TN) return VDS_ERR_ARG;
+  if ((a->layout == VDS_TN ? a->M : a->K) & 7) return VDS_ERR_ARG;  // the dimension the k-contiguous / k-major rows run along
+  p = gemm_params(a, 2);
+  if (grp) {
+    p.g_lead = grp->lead;
+    p.g_period = grp->period;
+  }
+  if (operand_extents(a, 2, p) != VDS_OK) return VDS_ERR_UNSUPPORTED;
   if (p.atomic && !(a->layout == VDS_TN && a->epilogue == VDS_EPI_F32)) return VDS_ERR_ARG;
   // C == NULL: the two-output epilogues store their second output only (GATE_RES: x_new, BIAS_GELU: the activation)
   if (!a->C && !((a->epilogue == VDS_EPI_GATE_RES || a->epilogue == VDS_EPI_BIAS_GELU) && a->C2)) return VDS_ERR_ARG;
-  const bool det = vdscfg::geti(vdscfg::DETERMINISTIC) != 0;
-  // deterministic mode: the fc1 bias gradient is a separate fixed-order column sum, not the epilogue's per-tile atomics
-  const float* fused_colsum = det ? nullptr : a->colsum;
+  return with_pair(a->layout, a->epilogue, grp != nullptr, [](auto, auto) { return (int)VDS_OK; });
+}
+
+enum { COLSUM_NONE = 0, COLSUM_FUSED = 1, COLSUM_PASS = 2 };  // vds_gemm_plan_info.colsum
+using GemmPlan = vds_gemm_plan_info;
+
+// Tiling, grid, K split and tile order of a checked call: arithmetic on the arguments, the knobs (config.h) and the
+// deterministic flag alone, no HIP call.  vds_gemm_plan reports exactly this.
+GemmPlan plan_bf16(const vds_gemm_args* a, const GemmP& p, bool det) {
+  GemmPlan pl{};
+  pl.split_k = p.split_k;
+  pl.atomic = p.atomic;
+  const bool auto_split = (a->split_k == 0 || a->split_k == -1) && a->layout == VDS_TN && a->epilogue == VDS_EPI_F32;
+  // the smaller tilings have no fused column sums: a pass over the result follows the GEMM.  Deterministic mode: the fc1
+  // bias gradient is that separate fixed-order column sum in every tiling, not the epilogue's per-tile atomics
+  pl.colsum = a->colsum ? COLSUM_PASS : COLSUM_NONE;
   // tile choice: 256^2 (one workgroup per CU, deep LDS-DMA pipeline) for problems that fill the chip
   // with such tiles; 128^2 otherwise.  vds_gemm_force_tile / VDS_GEMM_TILE = 128 | 256 | 2 forces one (experiments).
   const int ft = force_tile();
@@ -1549,27 +1583,25 @@ static int gemm_bf16_impl(const vds_gemm_args* a, const vds_mod_groups* grp, vds
   // workgroups; compare the number of rounds each tiling needs (wave quantisation dominates at
   // these sizes).  Weight gradients (TN, split-K) run on the 256 x 128 or the 128^2 kernel.
   const int tm = cdiv(a->M, 256), tn = cdiv(a->N, 256);
+  const int tiles_m_small = cdiv(a->M, BM), tiles_n_small = cdiv(a->N, BN);
   const long rounds_big = ((long)tm * tn + 255) / 256;
-  const long rounds_small = ((long)p.tiles_m * p.tiles_n + 511) / 512;
+  const long rounds_small = ((long)tiles_m_small * tiles_n_small + 511) / 512;
   bool use_big = a->layout != VDS_TN && a->K >= 256 && (double)rounds_big * (2.0 / 1.24) < (double)rounds_small;
   if (ft == 128) use_big = false;
   if (ft == 256 && a->layout != VDS_TN) use_big = true;
-  p.group_m = vdscfg::geti(vdscfg::GEMM_GROUP_M);  // groups of 4 row tiles (1024 rows) measured best at the DiT shapes
-  if (p.group_m < 1) p.group_m = 4;
-  p.joint_xcd = 0;
+  pl.group_m = vdscfg::geti(vdscfg::GEMM_GROUP_M);  // groups of 4 row tiles (1024 rows) measured best at the DiT shapes
+  if (pl.group_m < 1) pl.group_m = 4;
   const int group_m_tn = vdscfg::geti(vdscfg::GEMM_GROUP_M_TN) > 0 ? vdscfg::geti(vdscfg::GEMM_GROUP_M_TN) : 0;
   if (a->layout == VDS_TN) {
     // weight gradients: few output tiles, every tile of a split streams the same token range.  Fixed groups of 2 row
     // tiles measured 4-5 % faster than 4 at the DiT-XL shapes (106.4 -> 101.5 ms per step); 0 (default) = sized at the
     // launch so that one XCD's chunk of the joint (split, tile) list is one group (below): 97 ms
-    p.group_m = group_m_tn ? group_m_tn : 2;
-    p.joint_xcd = vdscfg::geti(vdscfg::GEMM_TN_JOINT);
+    pl.group_m = group_m_tn ? group_m_tn : 2;
+    pl.joint_xcd = vdscfg::geti(vdscfg::GEMM_TN_JOINT);
   }
-  // the split-K launch of a weight gradient: atomics (default) or slabs + fixed-order reduction (deterministic mode)
-  auto launch_tn = [&](int bk, auto fn) -> int {
-    if (det && p.split_k > 1) return launch_split_det(p, (float*)a->C, a->ldc, s, bk, fn);
-    return fn(p);
-  };
+  pl.tiling = Small::TILING;
+  pl.tiles_m = tiles_m_small;
+  pl.tiles_n = tiles_n_small;
   if (auto_split) {
     // weight gradient dW[M = out features, N = in features] = dy^T x over K = tokens: few output tiles, long K.
     // Candidates: 128^2 tiles (two workgroups per CU) and 256 x 128 tiles (two per CU, ~mid_tn x the per-CU rate:
@@ -1593,21 +1625,21 @@ static int gemm_bf16_impl(const vds_gemm_args* a, const vds_mod_groups* grp, vds
         if (cost < best - 1e-9) { best = cost; best_tile = cand == 0 ? 128 : 2; best_s = sp; }
       }
     }
-    p.split_k = best_s;
-    p.atomic = (best_s > 1 || a->split_k == -1) ? 1 : 0;
+    pl.split_k = best_s;
+    pl.atomic = (best_s > 1 || a->split_k == -1) ? 1 : 0;
     if (best_tile == 2) {
-      p.tiles_m = cdiv(a->M, 256);
-      p.tiles_n = cdiv(a->N, 128);
-      if (p.joint_xcd && !group_m_tn) {
+      pl.tiling = Mid::TILING;
+      pl.tiles_m = cdiv(a->M, 256);
+      pl.tiles_n = cdiv(a->N, 128);
+      if (pl.joint_xcd && !group_m_tn) {
         // one XCD's chunk = (tiles x splits) / 8 consecutive entries of the split-major list: make it a block of
         // whole tile rows of one split (qkv weight gradient: 14 x 9 tiles x 4 splits -> 7 rows x 9 columns per XCD)
-        const long chunk = ((long)p.tiles_m * p.tiles_n * p.split_k + 7) / 8;
-        long g = (chunk + p.tiles_n / 2) / p.tiles_n;
-        p.group_m = (int)(g < 1 ? 1 : (g > p.tiles_m ? p.tiles_m : g));
+        const long chunk = ((long)pl.tiles_m * pl.tiles_n * pl.split_k + 7) / 8;
+        long g = (chunk + pl.tiles_n / 2) / pl.tiles_n;
+        pl.group_m = (int)(g < 1 ? 1 : (g > pl.tiles_m ? pl.tiles_m : g));
       }
-      return launch_tn(mid::BK, [&](GemmP& q) { return mid::launch<VDS_TN, VDS_EPI_F32>(q, s); });
     }
-    return launch_tn(BK, [&](GemmP& q) { return launch<VDS_TN, VDS_EPI_F32>(q, s); });
+    return pl;
   }
   // 256 x 128 tiles, two workgroups per CU: no padded half tile when N is a multiple of 128 but not of 256, and the
   // epilogue of one workgroup runs under the main loop of the other.  Measured (tools/bench_gemm_tiles.py, DiT-XL
@@ -1615,73 +1647,71 @@ static int gemm_bf16_impl(const vds_gemm_args* a, const vds_mod_groups* grp, vds
   // it at ~0.8x the 256^2 kernel on NT / NN problems, so a round of 512 such tiles is priced at 1.3 rounds of 256^2
   // tiles and it only wins where tile quantisation is severe; on weight gradients (TN) it beats the 128^2 kernel
   // by 7-24 % (see auto_split above).  tile = 2 forces it.
-  {
-    const int tmm = cdiv(a->M, 256), tnm = cdiv(a->N, 128);
-    const double cost_mid = (double)(((long)tmm * tnm + 511) / 512) * vdscfg::get(vdscfg::GEMM_MID_FACTOR);
-    const double cost_big = (double)rounds_big, cost_small = (double)rounds_small * (1.24 / 2.0);
-    bool use_mid = a->K >= 128 && cost_mid < (use_big ? cost_big : cost_small) && a->layout != VDS_TN;
-    if (ft == 2) use_mid = true;
-    if (a->colsum && a->layout != VDS_NN) use_mid = false;
-    if (ft == 128 || ft == 256) use_mid = false;
-    if (use_mid) {
-      p.tiles_m = tmm;
-      p.tiles_n = tnm;
-      if (a->colsum) {  // no fused column sums in this tiling: a pass over the result follows the GEMM
-        const int rc = mid::launch<VDS_NN, VDS_EPI_DGELU>(p, s);
-        return rc != VDS_OK ? rc : vds_colsum_bf16(a->C, a->ldc, a->colsum, a->M, a->N, stream);
-      }
-#define GOM(L, E) if (a->layout == L && a->epilogue == E) return mid::launch<L, E>(p, s);
-      GOM(VDS_NT, VDS_EPI_STORE)
-      GOM(VDS_NT, VDS_EPI_BIAS_GELU)
-      if (grp) return mid::launch<VDS_NT, EPI_GATE_RES_G>(p, s);
-      GOM(VDS_NT, VDS_EPI_GATE_RES)
-      GOM(VDS_NN, VDS_EPI_STORE)
-      GOM(VDS_NN, VDS_EPI_DGELU)
-#undef GOM
-      if (a->layout == VDS_TN && a->epilogue == VDS_EPI_F32)
-        return launch_tn(mid::BK, [&](GemmP& q) { return mid::launch<VDS_TN, VDS_EPI_F32>(q, s); });
-    }
+  const int tmm = cdiv(a->M, 256), tnm = cdiv(a->N, 128);
+  const double cost_mid = (double)(((long)tmm * tnm + 511) / 512) * vdscfg::get(vdscfg::GEMM_MID_FACTOR);
+  const double cost_big = (double)rounds_big, cost_small = (double)rounds_small * (1.24 / 2.0);
+  bool use_mid = a->K >= 128 && cost_mid < (use_big ? cost_big : cost_small) && a->layout != VDS_TN;
+  if (ft == 2) use_mid = true;
+  if (a->colsum && a->layout != VDS_NN) use_mid = false;
+  if (ft == 128 || ft == 256) use_mid = false;
+  if (use_mid) {
+    pl.tiling = Mid::TILING;
+    pl.tiles_m = tmm;
+    pl.tiles_n = tnm;
+  } else if (use_big) {
+    pl.tiling = Big::TILING;
+    pl.tiles_m = tm;
+    pl.tiles_n = tn;
+    pl.narrow = narrow_last_column(a->N);
+    if (a->colsum && !det) pl.colsum = COLSUM_FUSED;  // DGELU only (checked): column sums of the result in the epilogue
   }
-  if (use_big) {
-    p.tiles_m = tm;
-    p.tiles_n = tn;
-    p.narrow = narrow_last_column(a->N);
-    p.e_colsum = const_cast<float*>(fused_colsum);  // DGELU only (checked above): column sums of the result in the epilogue
-    int rc = VDS_ERR_UNSUPPORTED;
-#define GOB(L, E) if (a->layout == L && a->epilogue == E) rc = big::launch<L, E>(p, s);
-    GOB(VDS_NT, VDS_EPI_STORE)
-    GOB(VDS_NT, VDS_EPI_BIAS_GELU)
-    if (grp) rc = big::launch<VDS_NT, EPI_GATE_RES_G>(p, s);
-    else GOB(VDS_NT, VDS_EPI_GATE_RES)
-    GOB(VDS_NN, VDS_EPI_STORE)
-    GOB(VDS_NN, VDS_EPI_DGELU)
-#undef GOB
-    if (rc == VDS_OK && a->colsum && !fused_colsum) return vds_colsum_bf16(a->C, a->ldc, a->colsum, a->M, a->N, stream);
-    return rc;
-  }
-  p.tiles_m = cdiv(a->M, BM);
-  p.tiles_n = cdiv(a->N, BN);
-  if (a->colsum) {  // the smaller tilings have no fused column sums: a pass over the result follows the GEMM
-    const int rc = launch<VDS_NN, VDS_EPI_DGELU>(p, s);
-    return rc != VDS_OK ? rc : vds_colsum_bf16(a->C, a->ldc, a->colsum, a->M, a->N, stream);
-  }
-#define GO(L, E) if (a->layout == L && a->epilogue == E) return launch<L, E>(p, s);
-  GO(VDS_NT, VDS_EPI_STORE)
-  GO(VDS_NT, VDS_EPI_BIAS_GELU)
-  if (grp) return launch<VDS_NT, EPI_GATE_RES_G>(p, s);
-  GO(VDS_NT, VDS_EPI_GATE_RES)
-  GO(VDS_NN, VDS_EPI_STORE)
-  GO(VDS_NN, VDS_EPI_DGELU)
-#undef GO
-  if (a->layout == VDS_TN && a->epilogue == VDS_EPI_F32)
-    return launch_tn(BK, [&](GemmP& q) { return launch<VDS_TN, VDS_EPI_F32>(q, s); });
-  return VDS_ERR_UNSUPPORTED;
+  return pl;
 }
 
-extern "C" int vds_gemm_bf16(const vds_gemm_args* a, vds_stream_t stream) { return gemm_bf16_impl(a, nullptr, stream); }
+// the launches of a checked and planned call: the GEMM -- through launch_split_det for a split-K in deterministic mode
+// (slabs + fixed-order reduction instead of atomics) -- and the column-sum pass where the plan has one
+int run_bf16(const vds_gemm_args* a, const vds_mod_groups* grp, GemmP& p, const GemmPlan& pl, bool det, vds_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n;
+  p.split_k = pl.split_k; p.atomic = pl.atomic;
+  p.group_m = pl.group_m; p.joint_xcd = pl.joint_xcd; p.narrow = pl.narrow;
+  p.e_colsum = pl.colsum == COLSUM_FUSED ? a->colsum : nullptr;
+  auto with_tiling = [&](auto f) { return pl.tiling == Mid::TILING ? f(Mid{}) : pl.tiling == Big::TILING ? f(Big{}) : f(Small{}); };
+  auto launch = [&](GemmP& q) {
+    return with_tiling([&](auto tiling) {
+      return with_pair(a->layout, a->epilogue, grp != nullptr, [&](auto layout, auto epilogue) {
+        return launch_instance<decltype(tiling), decltype(layout)::value, decltype(epilogue)::value>(q, s);
+      });
+    });
+  };
+  const int k_tile = with_tiling([](auto tiling) { return (int)decltype(tiling)::K_TILE; });
+  const int rc = det && p.split_k > 1 ? launch_split_det(p, (float*)a->C, a->ldc, s, k_tile, launch) : launch(p);
+  if (rc != VDS_OK || pl.colsum != COLSUM_PASS) return rc;
+  return vds_colsum_bf16(a->C, a->ldc, a->colsum, a->M, a->N, stream);
+}
+
+int gemm_bf16(const vds_gemm_args* a, const vds_mod_groups* grp, vds_stream_t stream) {
+  GemmP p;
+  const int rc = check_bf16(a, grp, p);
+  if (rc != VDS_OK) return rc;
+  const bool det = vdscfg::geti(vdscfg::DETERMINISTIC) != 0;
+  return run_bf16(a, grp, p, plan_bf16(a, p, det), det, stream);
+}
+
+}  // namespace
+
+extern "C" int vds_gemm_bf16(const vds_gemm_args* a, vds_stream_t stream) { return gemm_bf16(a, nullptr, stream); }
 // GATE_RES (NT) with the gate row looked up per output row through a group description; NULL: vds_gemm_bf16
 extern "C" int vds_gemm_bf16_grouped(const vds_gemm_args* a, const vds_mod_groups* groups, vds_stream_t stream) {
-  return gemm_bf16_impl(a, groups, stream);
+  return gemm_bf16(a, groups, stream);
+}
+// what the two entries above would do with these arguments: the same check, the same plan, no launch
+extern "C" int vds_gemm_plan(const vds_gemm_args* a, const vds_mod_groups* groups, vds_gemm_plan_info* info) {
+  if (!info) return VDS_ERR_ARG;
+  GemmP p;
+  const int rc = check_bf16(a, groups, p);
+  if (rc == VDS_OK) *info = plan_bf16(a, p, vdscfg::geti(vdscfg::DETERMINISTIC) != 0);
+  return rc;
 }
 
 // OCP fp8 GEMM, NT only: C[M,N] = (sum_k A[m,k] B[n,k]) * scale_a * scale_b with A, B one byte per element
@@ -1693,42 +1723,14 @@ extern "C" int vds_gemm_fp8(const vds_gemm_args* a, const float* scale_a, const 
   if ((a->N & 7) || (a->K & 15) || (a->lda & 15) || (a->ldb & 15)) return VDS_ERR_ARG;
   const bool tn = a->layout == VDS_TN;  // C[M,N] = sum_k A[k,m] B[k,n]: both operands [K, .] row-major (token-major)
   if (tn && (a->epilogue != VDS_EPI_F32 || a_fmt != 1 || emit || (a->M & 15))) return VDS_ERR_UNSUPPORTED;
-  // the same epilogues as the bf16 GEMM: 16-byte row segments at row * ld + column (see gemm_bf16_impl)
-  {
-    const int e = a->epilogue;
-    if (a->C && (a->ldc & (e == VDS_EPI_F32 ? 3 : 7))) return VDS_ERR_ARG;
-    if ((e == VDS_EPI_BIAS_GELU || e == VDS_EPI_GATE_RES) && a->C2 && (a->ldc2 & 7)) return VDS_ERR_ARG;
-    if ((e == VDS_EPI_GATE_RES || e == VDS_EPI_DGELU) && a->aux && (a->ldaux & 7)) return VDS_ERR_ARG;
-    if (e == VDS_EPI_GATE_RES && a->gate && (a->ldgate & 3)) return VDS_ERR_ARG;
-  }
-  GemmP p;
-  p.M = a->M; p.N = a->N; p.K = a->K / 2;  // the kernel addresses in 2-byte units
-  p.A = (const bf16_t*)a->A; p.lda = a->lda / 2;
-  p.B = (const bf16_t*)a->B; p.ldb = a->ldb / 2;
-  p.C = a->C; p.ldc = a->ldc; p.C2 = a->C2; p.ldc2 = a->ldc2;
-  p.bias = (const bf16_t*)a->bias;
-  p.aux = (const bf16_t*)a->aux; p.ldaux = a->ldaux;
-  p.gate = a->gate; p.ldgate = a->ldgate;
-  p.rows_per_batch = a->rows_per_batch > 0 ? a->rows_per_batch : a->M;
-  p.row_base = 0;
-  p.g_lead = p.g_period = 0;
-  p.slab_stride = 0;
-  p.split_k = a->split_k > 1 ? a->split_k : (a->split_k < -1 ? -a->split_k : 1);
-  p.atomic = (a->split_k > 1 || a->split_k < 0) ? 1 : 0;
+  if (check_epilogue_ld(a) != VDS_OK) return VDS_ERR_ARG;  // the same epilogues as the bf16 GEMM
+  GemmP p = gemm_params(a, 1);
+  if (operand_extents(a, 1, p) != VDS_OK) return VDS_ERR_UNSUPPORTED;
   p.sa = scale_a; p.sb = scale_b;
-  p.prof_k = a->K;
   p.tiles_m = cdiv(a->M, 256);
   p.tiles_n = cdiv(a->N, 256);
-  const size_t abytes = tn ? (size_t)(a->K - 1) * a->lda + a->M : (size_t)(a->M - 1) * a->lda + a->K;
-  const size_t bbytes = tn ? (size_t)(a->K - 1) * a->ldb + a->N : (size_t)(a->N - 1) * a->ldb + a->K;
-  if (abytes >= (1ull << 32) || bbytes >= (1ull << 32)) return VDS_ERR_UNSUPPORTED;
-  p.a_bytes = (unsigned)abytes;
-  p.b_bytes = (unsigned)bbytes;
   p.group_m = 4;
-  p.joint_xcd = 0;
   p.narrow = narrow_last_column(a->N);
-  p.e_q = p.e_qt = nullptr; p.e_ldq = p.e_ldqt = 0;
-  p.e_amax_in = nullptr; p.e_amax_out = p.e_dq_out = p.e_colsum = nullptr; p.e_fmt = 0;
   if (emit) {
     if (a->epilogue != VDS_EPI_BIAS_GELU && a->epilogue != VDS_EPI_DGELU) return VDS_ERR_ARG;
     if ((emit->q && (emit->ldq & 7)) || (emit->qt && (emit->ldqt & 3)) || (emit->fmt != 0 && emit->fmt != 1)) return VDS_ERR_ARG;
@@ -1746,20 +1748,22 @@ extern "C" int vds_gemm_fp8(const vds_gemm_args* a, const float* scale_a, const 
     return VDS_ERR_ARG;
   if (a->epilogue == VDS_EPI_GATE_RES && !a->C2) return VDS_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
+  const bool det = vdscfg::geti(vdscfg::DETERMINISTIC) != 0;
   if (tn) {
-    if (vdscfg::geti(vdscfg::DETERMINISTIC) && p.split_k > 1)
-      return launch_split_det(p, (float*)a->C, a->ldc, s, BK, [&](GemmP& q) { return big::launch<VDS_TN, VDS_EPI_F32, 3>(q, s); });
-    return big::launch<VDS_TN, VDS_EPI_F32, 3>(p, s);
+    auto launch = [&](GemmP& q) { return launch_instance<Big, VDS_TN, VDS_EPI_F32, 3>(q, s); };
+    return det && p.split_k > 1 ? launch_split_det(p, (float*)a->C, a->ldc, s, Big::K_TILE, launch) : launch(p);
   }
-  if (vdscfg::geti(vdscfg::DETERMINISTIC) && p.e_colsum) return VDS_ERR_UNSUPPORTED;  // (fused column sums are atomic)
-#define GOF(E, F) if (a->epilogue == E && a_fmt == F - 1) return big::launch<VDS_NT, E, F>(p, s);
-  GOF(VDS_EPI_STORE, 1)
-  GOF(VDS_EPI_BIAS_GELU, 1)
-  GOF(VDS_EPI_GATE_RES, 1)
-  GOF(VDS_EPI_STORE, 2)
-  GOF(VDS_EPI_DGELU, 2)
-  GOF(VDS_EPI_F32, 2)
-  GOF(VDS_EPI_F32, 1)
-#undef GOF
-  return VDS_ERR_UNSUPPORTED;
+  if (det && p.e_colsum) return VDS_ERR_UNSUPPORTED;  // (fused column sums are atomic)
+  // the table of the fp8 NT GEMM: (epilogue, format of A) -> the instance with FMT = 1 + a_fmt
+  constexpr auto key = [](int epilogue, int fmt) { return epilogue * 2 + fmt; };  // (a_fmt is 0 or 1: checked)
+  switch (key(a->epilogue, a_fmt)) {
+    case key(VDS_EPI_STORE, 0): return launch_instance<Big, VDS_NT, VDS_EPI_STORE, 1>(p, s);
+    case key(VDS_EPI_BIAS_GELU, 0): return launch_instance<Big, VDS_NT, VDS_EPI_BIAS_GELU, 1>(p, s);
+    case key(VDS_EPI_GATE_RES, 0): return launch_instance<Big, VDS_NT, VDS_EPI_GATE_RES, 1>(p, s);
+    case key(VDS_EPI_STORE, 1): return launch_instance<Big, VDS_NT, VDS_EPI_STORE, 2>(p, s);
+    case key(VDS_EPI_DGELU, 1): return launch_instance<Big, VDS_NT, VDS_EPI_DGELU, 2>(p, s);
+    case key(VDS_EPI_F32, 1): return launch_instance<Big, VDS_NT, VDS_EPI_F32, 2>(p, s);
+    case key(VDS_EPI_F32, 0): return launch_instance<Big, VDS_NT, VDS_EPI_F32, 1>(p, s);
+    default: return VDS_ERR_UNSUPPORTED;
+  }
 }

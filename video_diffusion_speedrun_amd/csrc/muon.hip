@@ -364,14 +364,8 @@ __global__ __launch_bounds__(256, 2) void ns_gemm_kernel(NsP p) {
 
 template <bool B_KM, bool SYM>
 int launch_ns(const NsP& p, int nmat, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ns_gemm_kernel<B_KM, SYM>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    attr_set = true;
-  }
   const int tiles = SYM ? p.tiles_n * (p.tiles_n + 1) / 2 : p.tiles_m * p.tiles_n;
-  hipLaunchKernelGGL((ns_gemm_kernel<B_KM, SYM>), dim3(tiles, nmat), dim3(256), LDS_BYTES, s, p);
+  vds_launch<ns_gemm_kernel<B_KM, SYM>, LDS_BYTES>(dim3(tiles, nmat), dim3(256), LDS_BYTES, s, p);
   return hipGetLastError() == hipSuccess ? VDS_OK : VDS_ERR_LAUNCH;
 }
 

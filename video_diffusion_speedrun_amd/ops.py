@@ -46,11 +46,18 @@ def _rows(t: torch.Tensor) -> Tuple[int, int]:
 
 
 # ------------------------------------------------------------------------------- GEMM ----
+def _gemm_args(layout: int, epi: int, M: int, N: int, K: int, A, lda, B, ldb, Cp=None, ldc=0, C2=None, ldc2=0, bias=None,
+               aux=None, ldaux=0, gate=None, ldgate=0, rows_per_batch=0, split_k=1, colsum=None):
+    """vds_gemm_args (by reference) from tensors and leading dimensions: the one place that knows the field order"""
+    return C.byref(GemmArgs(layout, epi, M, N, K, _p(A), lda, _p(B), ldb, _p(Cp), ldc, _p(C2), ldc2, _p(bias), _p(aux),
+                            ldaux, _p(gate), ldgate, rows_per_batch, split_k, _p(colsum)))
+
+
 def gemm(layout: int, epi: int, M: int, N: int, K: int, A, lda, B, ldb, Cp=None, ldc=0, C2=None, ldc2=0,
          bias=None, aux=None, ldaux=0, gate=None, ldgate=0, rows_per_batch=0, split_k=1, colsum=None):
-    a = GemmArgs(layout, epi, M, N, K, _p(A), lda, _p(B), ldb, _p(Cp), ldc, _p(C2), ldc2, _p(bias), _p(aux),
-                 ldaux, _p(gate), ldgate, rows_per_batch, split_k, _p(colsum))
-    check(_lib.load().vds_gemm_bf16(C.byref(a), _stream()), f"vds_gemm_bf16(layout={layout},epi={epi},M={M},N={N},K={K})")
+    a = _gemm_args(layout, epi, M, N, K, A, lda, B, ldb, Cp, ldc, C2, ldc2, bias, aux, ldaux, gate, ldgate, rows_per_batch,
+                   split_k, colsum)
+    check(_lib.load().vds_gemm_bf16(a, _stream()), f"vds_gemm_bf16(layout={layout},epi={epi},M={M},N={N},K={K})")
 
 
 def gemm_force_tile(tile: int) -> int:
@@ -145,9 +152,9 @@ def linear_fwd_gate_res_grouped(x, W, bias, mod, gate_col: int, res, L: int, gro
     y = torch.empty(M, N, dtype=bf16, device=x.device) if want_y else None
     xn = torch.empty(M, N, dtype=bf16, device=x.device)
     gate = mod[:, gate_col:]
-    a = GemmArgs(VDS_NT, EPI_GATE_RES, M, N, K, _p(x), x.stride(0), _p(W), W.stride(0), _p(y), N, _p(xn), N, _p(bias),
-                 _p(res), res.stride(0), _p(gate), mod.stride(0), L, 1, None)
-    check(_lib.load().vds_gemm_bf16_grouped(C.byref(a), _groups(groups, L, mod, M // L), _stream()),
+    a = _gemm_args(VDS_NT, EPI_GATE_RES, M, N, K, x, x.stride(0), W, W.stride(0), y, N, xn, N, bias=bias, aux=res,
+                   ldaux=res.stride(0), gate=gate, ldgate=mod.stride(0), rows_per_batch=L)
+    check(_lib.load().vds_gemm_bf16_grouped(a, _groups(groups, L, mod, M // L), _stream()),
           f"vds_gemm_bf16_grouped(M={M},N={N},K={K},L={L},groups={tuple(groups)})")
     return y, xn
 
@@ -202,24 +209,18 @@ def gemm_fp8(epi: int, M: int, N: int, K: int, A, B, sa, sb, a_fmt: int, Cp=None
     tn: C[M,N] = sum_k A[k,m] B[k,n] with A [K,M] (e5m2) and B [K,N] (e4m3) row-major -- the weight gradient read
     straight from the token-major fp8 copies (EPI_F32 only).
     emit = dict(q=, qt=, amax_in=, amax_out=, dq_out=, fmt=, colsum=): fp8 copies of the epilogue result (vds_fp8_out)."""
-    if tn:
-        assert A.is_contiguous() and B.is_contiguous() and A.shape == (K, M) and B.shape == (K, N) and emit is None
-        a = GemmArgs(VDS_TN, epi, M, N, K, _p(A), M, _p(B), N, _p(Cp), ldc, _p(C2), ldc2, _p(bias), _p(aux), ldaux,
-                     _p(gate), ldgate, rows_per_batch, split_k, None)
-        check(_lib.load().vds_gemm_fp8(C.byref(a), _p(sa), _p(sb), a_fmt, 0, None, _stream()),
-              f"vds_gemm_fp8(tn,M={M},N={N},K={K})")
-        return
-    assert A.is_contiguous() and B.is_contiguous() and A.shape == (M, K) and B.shape == (N, K)
-    a = GemmArgs(VDS_NT, epi, M, N, K, _p(A), K, _p(B), K, _p(Cp), ldc, _p(C2), ldc2, _p(bias), _p(aux), ldaux,
-                 _p(gate), ldgate, rows_per_batch, split_k, None)
+    assert A.is_contiguous() and B.is_contiguous()
+    assert (A.shape == (K, M) and B.shape == (K, N) and emit is None) if tn else (A.shape == (M, K) and B.shape == (N, K))
+    a = _gemm_args(VDS_TN if tn else VDS_NT, epi, M, N, K, A, M if tn else K, B, N if tn else K, Cp, ldc, C2, ldc2, bias, aux,
+                   ldaux, gate, ldgate, rows_per_batch, split_k)
     e = None
     if emit is not None:
         q, qt = emit.get("q"), emit.get("qt")
         assert (q is None or q.shape == (M, N)) and (qt is None or qt.shape == (N, M))
         e = C.byref(_lib.Fp8Out(_p(q), N, _p(qt), M, _p(emit.get("amax_in")), _p(emit.get("amax_out")),
                                 _p(emit.get("dq_out")), int(emit.get("fmt", 0)), _p(emit.get("colsum"))))
-    check(_lib.load().vds_gemm_fp8(C.byref(a), _p(sa), _p(sb), a_fmt, 0, e, _stream()),
-          f"vds_gemm_fp8(epi={epi},M={M},N={N},K={K})")
+    check(_lib.load().vds_gemm_fp8(a, _p(sa), _p(sb), a_fmt, 0, e, _stream()),
+          f"vds_gemm_fp8({'tn' if tn else f'epi={epi}'},M={M},N={N},K={K})")
 
 
 def _wgrad_split(tiles: int, kt: int, slots: int) -> int:
