@@ -374,6 +374,27 @@ int vds_attn_fwd_causal_fm_window(const vds_attn_args* args, const vds_mod_group
                                   vds_stream_t stream);
 int vds_attn_bwd_causal_fm_window(const vds_attn_args* args, const vds_mod_groups* frames, int32_t chunk, int32_t window_chunks,
                                   vds_stream_t stream);
+/* Teacher forcing: frame-major self-attention over [lead rows | n clean token-frames | their n noisy copies], frames->period
+ * = 2n.  With S = (L - lead) / period rows per frame, G = min(chunk, n) * S and base = lead + n * S, the chunks of G rows
+ * restart at base (the last chunk of each half may be short), and query r attends key j iff j < lead, or r and j are clean
+ * and chunk(j) <= chunk(r) (the _fm_chunk mask on the first base rows), or r is noisy and j is clean with chunk(j) <
+ * chunk(r), or r and j are noisy with chunk(j) == chunk(r).  A lead query attends the lead keys only.
+ * Seen from a query the attended keys are [0, pend(r)) plus [kbeg(r), kend(r)):
+ *   clean r: pend = min(base, lead + (chunk + 1) G), no run;   noisy r: pend = lead + chunk G, run [base + chunk G,
+ *   min(L, base + (chunk + 1) G)).
+ * Seen from a key the readers are [qstart(j), qend(j)) plus [q2(j), L): a lead key [0, L); a clean key [lead + chunk G, base)
+ * and [base + (chunk + 1) G, L) -- a hole --; a noisy key its own chunk [base + chunk G, min(L, base + (chunk + 1) G)).
+ * What is skipped: a forward / dQ workgroup (128 queries) visits the 64-key tiles below its largest pend and then those from
+ * its smallest kbeg to its largest kend, never one twice; a dK/dV workgroup (128 keys) with a lead key sweeps every 64-row
+ * query tile, any other the tiles from qstart of its first key to qend of its last and then from q2 of its first key to L.
+ * Excluded pairs get P = 0 exactly and never enter a running maximum.  The profiler credits the visited tiles.
+ * These are TF instances of the plain 32x32x16 frame-major kernels at every head dim of the dispatcher, for kv_pad_ones 0
+ * and 1 (the pad columns are not read); the 16x16x32 family has no TF instance.  Layout, tok() (with the period 2n),
+ * workspace and the other refusals are those of the _fm calls; no atomics, bit-identical run to run.
+ * frames == NULL, an odd period, chunk < 1, (L - lead) % period != 0, Lq != Lk, kv_pad_ones == 2: VDS_ERR_ARG; L > 2^21 rows
+ * or a head dim without instance: VDS_ERR_UNSUPPORTED.  lead, period and chunk travel by value. */
+int vds_teacher_attn_fwd(const vds_attn_args* args, const vds_mod_groups* frames, int32_t chunk, vds_stream_t stream);
+int vds_teacher_attn_bwd(const vds_attn_args* args, const vds_mod_groups* frames, int32_t chunk, vds_stream_t stream);
 /* vds_rmsnorm_mod_fwd with mod f32 [B*G, ldmod]: the same arithmetic per row, y / rstd bit-identical to the per-sample
  * call run on the rows of one group with that group's mod row.  Every form of the dispatcher is covered. */
 int vds_rmsnorm_mod_fwd_grouped(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod,

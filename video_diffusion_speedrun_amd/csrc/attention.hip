@@ -191,6 +191,40 @@ struct FmMap {
     return lead + __mul24(r - lead - __mul24(f, S), period) + f;
   }
 };
+// Teacher forcing (TF instances of the FM kernels, vds_teacher_attn_*).  The period is 2n token-frames: frames 0 .. n-1 are
+// clean, frames n .. 2n-1 their noisy copies, base = lead + n * S is the first noisy row, and chunks of G rows restart at
+// base.  Query r attends [0, pend(r)) plus [kbeg(r), kend(r)) -- the WIN form with a per-row prefix end in place of lead:
+//   lead query    pend = lead,                              empty run
+//   clean query   pend = min(base, lead + (chunk + 1) G),   empty run         (the chunk-causal mask of the first base rows)
+//   noisy query   pend = lead + chunk G,                    [base + chunk G, min(L, base + (chunk + 1) G))
+// an empty run is kbeg = kend = pend, so that "key >= kend or pend <= key < kbeg" is the one compare of every row.
+// Seen from a key, the readers are [qstart(j), qend(j)) plus [q2(j), L) -- a clean key's readers have a hole:
+//   lead key      [0, L),                                   q2 = L
+//   clean key     [lead + chunk G, base),                   q2 = min(L, base + (chunk + 1) G)
+//   noisy key     [base + chunk G, min(L, base + (chunk + 1) G)),   q2 = L
+// qstart and q2 (from lead on) grow with the row, and so do pend, kbeg and kend inside a half.  The quotient is FcMap's
+// fp32 rule on the row's offset inside its half (< 2^21).
+struct TfMap {
+  int lead, base, G, L;
+  float ginv, ghinv;
+  __device__ __forceinline__ explicit TfMap(const AttnP& p)
+      : lead(p.fc_lead), base(p.fc_lead + __mul24(p.fc_period >> 1, p.fm_S)), G(p.fm_G), L(p.Lq) {
+    ginv = 1.0f / (float)p.fm_G;
+    ghinv = 0.5f * ginv;
+  }
+  // first row of the chunk of row r inside its half, as an offset from the half's first row (r >= lead)
+  __device__ __forceinline__ int cg(int r) const {
+    return __mul24((int)__builtin_fmaf((float)(r - (r >= base ? base : lead)), ginv, ghinv), G);
+  }
+  __device__ __forceinline__ int pend(int r) const {
+    return r < lead ? lead : (r < base ? min(base, lead + cg(r) + G) : lead + cg(r));
+  }
+  __device__ __forceinline__ int kbeg(int r) const { return r < base ? pend(r) : base + cg(r); }
+  __device__ __forceinline__ int kend(int r) const { return r < base ? pend(r) : min(L, base + cg(r) + G); }
+  __device__ __forceinline__ int qstart(int j) const { return j < lead ? 0 : (j < base ? lead : base) + cg(j); }
+  __device__ __forceinline__ int qend(int j) const { return j < lead ? L : (j < base ? base : min(L, base + cg(j) + G)); }
+  __device__ __forceinline__ int q2(int j) const { return (j >= lead && j < base) ? min(L, base + cg(j) + G) : L; }
+};
 __device__ __forceinline__ int fm_kend(const AttnP& p, int r) { return FmMap(p).kend(r); }
 __device__ __forceinline__ int fm_qstart(const AttnP& p, int j) { return FmMap(p).qstart(j); }
 // row of o / d_o that holds row r of the computation: tok(r) in the FM instances, r itself otherwise
@@ -200,9 +234,11 @@ __device__ __forceinline__ int out_row(const AttnP& p, int r) {
   else return r;
 }
 // keys of the workgroup whose query rows are [q0, q0 + rows): FM -- the largest kend of its rows (<= L); else Lk
-template <bool FM>
+// (TF: kend of the last row is the largest bound of either range -- a noisy row's run ends past base, where no prefix reaches)
+template <bool FM, bool TF = false>
 __device__ __forceinline__ int fm_keys(const AttnP& p, int q0, int rows, int Lk) {
-  if constexpr (FM) return fm_kend(p, min(q0 + rows, p.Lq) - 1);
+  if constexpr (TF) return TfMap(p).kend(min(q0 + rows, p.Lq) - 1);
+  else if constexpr (FM) return fm_kend(p, min(q0 + rows, p.Lq) - 1);
   else return Lk;
 }
 // first 64-row query tile of the workgroup whose first key row is k0: FM -- the tile that holds qstart(k0); else dflt
@@ -231,11 +267,21 @@ __device__ __forceinline__ int fm_qend(const AttnP& p, int j) { return FmMap(p).
 // hold lead keys, [0, nl), then the tiles from the one that holds kbeg of the workgroup's first token query, [jb, nkt) --
 // jb >= nl, so no tile comes twice.  The loop counts visits; tile(it) is the tile of visit it, and the prefetch of the
 // next visit follows it across the gap.
-template <bool WIN>  // (the other instances build an empty one)
+// TF: the tiles below the workgroup's largest pend, [0, nl), then those from its smallest kbeg to its largest kend,
+// [jb, nkt) -- jb >= nl again, also in the workgroup that straddles base (TfMap).
+template <bool WIN, bool TF = false>  // (the other instances build an empty one)
 struct FmWinTiles {
   int nl = 0, jb = 0, nit = 0;
   __device__ __forceinline__ FmWinTiles(const AttnP& p, int q0, int rows, int nkt) {
-    if constexpr (WIN) {
+    if constexpr (TF) {
+      const TfMap tf(p);
+      const int q1 = min(q0 + rows, p.Lq);
+      // the largest pend: that of the last clean (or lead) row if there is one -- base for the straddling workgroup, which
+      // no noisy row's prefix reaches -- else the last row's
+      nl = (tf.pend(q0 < tf.base ? min(q1, tf.base) - 1 : q1 - 1) + 63) >> 6;
+      jb = q1 > tf.base ? max(nl, tf.kbeg(max(q0, tf.base)) >> 6) : nkt;
+      nit = nl + nkt - jb;
+    } else if constexpr (WIN) {
       nl = min(nkt, (p.fc_lead + 63) >> 6);
       const int qf = max(q0, p.fc_lead);  // first token query, if the workgroup holds one
       jb = qf < min(q0 + rows, p.Lq) ? max(nl, fm_kbeg(p, qf) >> 6) : nkt;
@@ -247,11 +293,20 @@ struct FmWinTiles {
 // the wave-uniform open test of the WIN forward / dQ kernels: the 32 keys from k0 need no mask code if the wave holds no
 // lead query (wlead, wkend are 0 otherwise) and they lie wholly below lead or wholly inside [kbeg of the wave's last query,
 // kend of its first)
-template <bool WIN>
+// TF: wlead is the wave's smallest pend (its first query's) and the run that of a wave of noisy queries only; a wave of
+// clean queries only has no run, and a wave with a lead query or with queries of both halves has nothing open.
+template <bool WIN, bool TF = false>
 struct FmWinOpen {
   int wlead = 0, wkbeg = 0, wkend = 0;
   __device__ __forceinline__ FmWinOpen(const AttnP& p, int wq0, int wrows) {
-    if constexpr (WIN) {
+    if constexpr (TF) {
+      const TfMap tf(p);
+      const int wq1 = min(wq0 + wrows, p.Lq) - 1;  // the wave's last query
+      const bool noisy = wq0 >= tf.base, clean = wq0 >= tf.lead && wq1 < tf.base;
+      wlead = (noisy || clean) ? __builtin_amdgcn_readfirstlane(tf.pend(wq0)) : 0;
+      wkbeg = noisy ? __builtin_amdgcn_readfirstlane(tf.kbeg(wq1)) : 0;
+      wkend = noisy ? __builtin_amdgcn_readfirstlane(tf.kend(wq0)) : 0;
+    } else if constexpr (WIN) {
       const bool tokens = wq0 >= p.fc_lead;
       wlead = tokens ? p.fc_lead : 0;
       wkend = tokens ? __builtin_amdgcn_readfirstlane(fm_kend(p, wq0)) : 0;
@@ -286,6 +341,37 @@ __device__ __forceinline__ int fm_win_first_token_key(const AttnP& p, int k0) {
 // tile if it holds a lead key, else the tiles below qend of its last key
 __device__ __forceinline__ int fm_win_qtiles(const AttnP& p, int key0, int nqt) {
   return key0 < p.fc_lead ? nqt : (fm_qend(p, min(key0 + 127, p.Lk - 1)) + 63) >> 6;
+}
+// Query tiles (64 rows) of a TF dK/dV workgroup with key rows [key0, key0 + 128): [a0, a1) from qstart of its first key to
+// qend of its last, then [b0, nqt) from q2 of its first key -- b0 >= a1, no tile twice.  A workgroup with a lead key sweeps
+// every tile; one of noisy keys only has q2 = L: it sweeps the tiles of its own chunks and nothing else.
+template <bool TF>
+struct TfQTiles {
+  int a0 = 0, na = 0, b0 = 0, nit = 0;
+  __device__ __forceinline__ TfQTiles(const AttnP& p, int key0, int nqt) {
+    if constexpr (TF) {
+      const TfMap tf(p);
+      int a1 = nqt;
+      b0 = nqt;
+      if (key0 >= tf.lead) {
+        a0 = tf.qstart(key0) >> 6;
+        a1 = (tf.qend(min(key0 + 127, p.Lk - 1)) + 63) >> 6;
+        const int q2 = tf.q2(key0);
+        b0 = q2 >= p.Lq ? nqt : max(a1, q2 >> 6);
+      }
+      na = a1 - a0;
+      nit = na + nqt - b0;
+    }
+  }
+  __device__ __forceinline__ int tile(int it) const { return it < na ? a0 + it : it - na + b0; }
+};
+// 32x32 accumulators with the QUERY on the registers: P and dS of the queries outside [qstart, qend) and below q2
+__device__ __forceinline__ void fm_zero_q_tf(int row0, int qstart, int qend, int q2, f32x16& pm, f32x16& ds) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int q = row0 + (r & 3) + 8 * (r >> 2);
+    if ((q < qstart || q >= qend) && q < q2) { pm[r] = 0.f; ds[r] = 0.f; }
+  }
 }
 // FM instances of the forward and dQ kernels: the row-tile order of a head is reversed, so that its longest workgroups
 // (the late query tiles) are issued first; the dK/dV kernel's natural order already starts with its longest (early keys)
@@ -621,12 +707,17 @@ struct DmaStageFm {
 // then the tiles from kbeg of the workgroup's first token query (FmWinTiles); a lane keeps key j iff j < lead or
 // kbeg <= j < kend, and a sub-block that FmWinOpen finds open runs without mask code.  A row whose first visited
 // sub-blocks are all masked (lead = 0) keeps m = -1e30, l = 0 and O = 0 until its window opens.
+// TF (vds_teacher_attn_fwd; with FM, without WIN): teacher forcing (TfMap).  The WIN code with the lane's pend in place of
+// lead: the key loop visits the tiles below the workgroup's largest pend, then those from its smallest kbeg to its largest
+// kend; a lane keeps key j iff j < pend or kbeg <= j < kend.
 template <int HDP, int HDQ, int WPS, bool PIPE, bool KVLEN = false, bool CAUSAL = false, bool PAST = false, bool FM = false,
-          bool WIN = false>
+          bool WIN = false, bool TF = false>
 __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, TILE = 64 * HDP * 2;
+  constexpr bool TWO = WIN || TF;  // two key-tile ranges
   static_assert(!FM || !(KVLEN || CAUSAL || PAST), "frame-major: its own mask");
   static_assert(!WIN || FM, "the window: on frame-major rows");
+  static_assert(!TF || (FM && !WIN), "teacher forcing: on frame-major rows, its own mask");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int bh, qt;
   if (!decode_block(p.n_rt, p.tail_last, p.B * p.H, bh, qt)) return;
@@ -635,7 +726,7 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qrow = qt * 128 + wave * 32 + (lane & 31);
-  const int Lk = fm_keys<FM>(p, qt * 128, 128, kv_len_of<KVLEN>(p, b));
+  const int Lk = fm_keys<FM, TF>(p, qt * 128, 128, kv_len_of<KVLEN>(p, b));
   if constexpr (KVLEN) {
     if (Lk == 0) {  // no context: O = 0, lse = 0
       if (qrow < p.Lq) {
@@ -655,9 +746,9 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   dv.init(p.v_sl, p.hd, wave, lane);
   const unsigned k_step = (unsigned)(64 * p.k_sl * 2), v_step = (unsigned)(64 * p.v_sl * 2);
   const int nkt = (Lk + 63) / 64;
-  [[maybe_unused]] const FmWinTiles<WIN> wt(p, qt * 128, 128, nkt);  // WIN: the two tile ranges of the key loop
-  const int nit = WIN ? wt.nit : nkt;                            // visits of the key loop
-  if constexpr (WIN) {
+  [[maybe_unused]] const FmWinTiles<WIN, TF> wt(p, qt * 128, 128, nkt);  // WIN, TF: the two tile ranges of the key loop
+  const int nit = TWO ? wt.nit : nkt;                                // visits of the key loop
+  if constexpr (TWO) {
     dk.issue(rk, smem, (unsigned)wt.tile(0) * k_step, wave);
     dv.issue(rv, smem + TILE, (unsigned)wt.tile(0) * v_step, wave);
   } else {
@@ -691,8 +782,15 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   }
   // WIN: the lane's kbeg next to its kend, and the wave's open test
   [[maybe_unused]] int kbeg = 0;
-  [[maybe_unused]] const FmWinOpen<WIN> wo(p, wq0, 32);
+  [[maybe_unused]] const FmWinOpen<WIN, TF> wo(p, wq0, 32);
   if constexpr (WIN) kbeg = fm_kbeg(p, qrow);
+  [[maybe_unused]] int pend = p.fc_lead;  // TF: the lane's prefix end, with its run [kbeg, klim)
+  if constexpr (TF) {
+    const TfMap tf(p);
+    pend = tf.pend(qrow);
+    kbeg = tf.kbeg(qrow);
+    klim = tf.kend(qrow);
+  }
 #pragma unroll
   for (int ks = 0; ks < KSQ; ++ks) retire(qf[ks]);
   VDS_WAIT_VM(0);
@@ -700,8 +798,8 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
 
   auto kv_tile = [&](int it, auto PAR) {  // unrolled by two: compile-time LDS buffer parity (see the wide kernel)
     constexpr int par = decltype(PAR)::value;
-    int j = it, jn = it + 1;  // this visit's key tile and the next one's (WIN: across the gap between the two ranges)
-    if constexpr (WIN) { j = wt.tile(it); jn = wt.tile(it + 1); }
+    int j = it, jn = it + 1;  // this visit's key tile and the next one's (WIN, TF: across the gap between the two ranges)
+    if constexpr (TWO) { j = wt.tile(it); jn = wt.tile(it + 1); }
     if (it + 1 < nit) {
       char* nk = smem + (par ^ 1) * 2 * TILE;
       dk.issue(rk, nk, (unsigned)jn * k_step, wave);
@@ -721,9 +819,9 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
       load_vfrags<HDP, NDB>(v0, vt, 0, lane);
 #pragma unroll
       for (int ks = 0; ks < KSQ; ++ks) s1 = mfma32(k1[ks], qf[ks], s1);
-      if constexpr (WIN) {
-        if (!wo.open(j * 64)) fm_fill_win(j * 64 + 4 * h, p.fc_lead, kbeg, klim, s0, -INFINITY);
-        if (!wo.open(j * 64 + 32)) fm_fill_win(j * 64 + 32 + 4 * h, p.fc_lead, kbeg, klim, s1, -INFINITY);
+      if constexpr (TWO) {
+        if (!wo.open(j * 64)) fm_fill_win(j * 64 + 4 * h, pend, kbeg, klim, s0, -INFINITY);
+        if (!wo.open(j * 64 + 32)) fm_fill_win(j * 64 + 32 + 4 * h, pend, kbeg, klim, s1, -INFINITY);
       } else if constexpr (FM) {  // (kend <= Lk: the compare covers the ragged tile too)
         if (j * 64 + 32 > wklim) fm_fill(j * 64 + 4 * h, klim, s0, -INFINITY);
         if (j * 64 + 64 > wklim) fm_fill(j * 64 + 32 + 4 * h, klim, s1, -INFINITY);
@@ -763,8 +861,8 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
         f32x16 s = zero16();
 #pragma unroll
         for (int ks = 0; ks < KSQ; ++ks) s = mfma32(frag_row<HDP>(kt, kb * 32, ks, lane), qf[ks], s);
-        if constexpr (WIN) {
-          if (!wo.open(j * 64 + kb * 32)) fm_fill_win(j * 64 + kb * 32 + 4 * h, p.fc_lead, kbeg, klim, s, -INFINITY);
+        if constexpr (TWO) {
+          if (!wo.open(j * 64 + kb * 32)) fm_fill_win(j * 64 + kb * 32 + 4 * h, pend, kbeg, klim, s, -INFINITY);
         } else if constexpr (FM) {
           if (j * 64 + kb * 32 + 32 > wklim) fm_fill(j * 64 + kb * 32 + 4 * h, klim, s, -INFINITY);
         } else {
@@ -1114,10 +1212,14 @@ __global__ __launch_bounds__(256) void attn_delta_tokmajor_kernel(AttnP p) {
 // and the dO row is that of token row tok(row); q, dq and the statistics are indexed by the frame-major row.
 // WIN (vds_attn_bwd_causal_fm_window; with FM): the window -- the two tile ranges, the per-lane compare and the open test
 // of the forward kernel, with dS = 0 in place of -inf.
-template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false, bool FM = false, bool WIN = false>
+// TF (vds_teacher_attn_bwd; with FM, without WIN): teacher forcing -- as the forward kernel's, with dS = 0 in place of -inf.
+template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false, bool FM = false, bool WIN = false,
+          bool TF = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, TILE = 64 * HDP * 2;
+  constexpr bool TWO = WIN || TF;  // two key-tile ranges
   static_assert(!WIN || FM, "the window: on frame-major rows");
+  static_assert(!TF || (FM && !WIN), "teacher forcing: on frame-major rows, its own mask");
   static_assert(!ONES || (HDP == 96 && HDQ == 80), "ones columns: head_dim 72 layout");
   static_assert(!FM || !(ONES || KVLEN || CAUSAL), "frame-major: the plain layout, its own mask");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1129,7 +1231,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qrow = qt * 128 + wave * 32 + (lane & 31);
   const int hd_kv = ONES ? p.hd + 8 : p.hd;
-  const int Lk = fm_keys<FM>(p, qt * 128, 128, kv_len_of<KVLEN>(p, b));
+  const int Lk = fm_keys<FM, TF>(p, qt * 128, 128, kv_len_of<KVLEN>(p, b));
   if constexpr (KVLEN) {
     if (Lk == 0) {  // no context: dQ = 0
       if (qrow < p.Lq) store_zero_rows<NDB>(p.dq + b * p.dq_sb + hh * p.dq_sh + (long)qrow * p.dq_sl, p.hd, h);
@@ -1147,9 +1249,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   dv.init(p.v_sl, hd_kv, wave, lane);
   const unsigned k_step = (unsigned)(64 * p.k_sl * 2), v_step = (unsigned)(64 * p.v_sl * 2);
   const int nkt = (Lk + 63) / 64;
-  [[maybe_unused]] const FmWinTiles<WIN> wt(p, qt * 128, 128, nkt);  // WIN: as in the forward kernel
-  const int nit = WIN ? wt.nit : nkt;
-  if constexpr (WIN) {
+  [[maybe_unused]] const FmWinTiles<WIN, TF> wt(p, qt * 128, 128, nkt);  // WIN, TF: as in the forward kernel
+  const int nit = TWO ? wt.nit : nkt;
+  if constexpr (TWO) {
     dk.issue(rk, smem, (unsigned)wt.tile(0) * k_step, wave);
     dv.issue(rv, smem + TILE, (unsigned)wt.tile(0) * v_step, wave);
   } else {
@@ -1204,15 +1306,22 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
     wklim = wq0 >= p.fc_lead ? __builtin_amdgcn_readfirstlane(fm_kend(p, wq0)) : 0;
   }
   [[maybe_unused]] int kbeg = 0;  // WIN: as in the forward kernel
-  [[maybe_unused]] const FmWinOpen<WIN> wo(p, qt * 128 + wave * 32, 32);
+  [[maybe_unused]] const FmWinOpen<WIN, TF> wo(p, qt * 128 + wave * 32, 32);
   if constexpr (WIN) kbeg = fm_kbeg(p, qrow);
+  [[maybe_unused]] int pend = p.fc_lead;  // TF: as in the forward kernel
+  if constexpr (TF) {
+    const TfMap tf(p);
+    pend = tf.pend(qrow);
+    kbeg = tf.kbeg(qrow);
+    klim = tf.kend(qrow);
+  }
   VDS_WAIT_VM(0);
   __syncthreads();  // tile 0 landed
 
   auto kv_tile = [&](int it, auto PAR) {  // unrolled by two: compile-time LDS buffer parity (see the forward kernel)
     constexpr int par = decltype(PAR)::value;
-    int j = it, jn = it + 1;  // this visit's key tile and the next one's (WIN: across the gap)
-    if constexpr (WIN) { j = wt.tile(it); jn = wt.tile(it + 1); }
+    int j = it, jn = it + 1;  // this visit's key tile and the next one's (WIN, TF: across the gap)
+    if constexpr (TWO) { j = wt.tile(it); jn = wt.tile(it + 1); }
     if (it + 1 < nit) {
       char* nk = smem + (par ^ 1) * 2 * TILE;
       dk.issue(rk, nk, (unsigned)jn * k_step, wave);
@@ -1244,8 +1353,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
         for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r] * c - lse2) * dp[r];
       }
       if constexpr (CAUSAL) fc_fill(fm, j * 64 + kb * 32 + 4 * h, fcq, s, 0.f);
-      if constexpr (WIN) {
-        if (!wo.open(j * 64 + kb * 32)) fm_fill_win(j * 64 + kb * 32 + 4 * h, p.fc_lead, kbeg, klim, s, 0.f);
+      if constexpr (TWO) {
+        if (!wo.open(j * 64 + kb * 32)) fm_fill_win(j * 64 + kb * 32 + 4 * h, pend, kbeg, klim, s, 0.f);
       } else if constexpr (FM) {
         if (j * 64 + kb * 32 + 32 > wklim) fm_fill(j * 64 + kb * 32 + 4 * h, klim, s, 0.f);
       }
@@ -1288,10 +1397,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
 // WIN (vds_attn_bwd_causal_fm_window; with FM): the window -- key j is attended by [qstart(j), qend(j)).  A workgroup that
 // holds a lead key sweeps every query tile (its token keys are compared per lane); any other sweeps the tiles from qstart of
 // its first key to the one below qend of its last.  A sub-block is open from the wave's largest qstart to its smallest qend.
-template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false, bool FM = false, bool WIN = false>
-__global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void attn_bwd_dkv_kernel(AttnP p) {
+// TF (vds_teacher_attn_bwd; with FM, without WIN): teacher forcing -- key j is attended by [qstart(j), qend(j)) and by
+// [q2(j), L) (TfMap).  The sweep visits the query tiles of TfQTiles, counted as visits like the key loop of the forward
+// kernel; a sub-block is open between the wave's largest qstart and its smallest qend, or from its largest q2.
+template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false, bool FM = false, bool WIN = false,
+          bool TF = false>
+// (head dim 64: three waves per SIMD cap the kernel at 168 VGPRs, which the TF instance's third bound and second tile range
+// do not fit without scratch -- it runs at two)
+__global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 && !TF ? 3 : 2))) void attn_bwd_dkv_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, Q_TILE = 64 * HDP * 2;
   static_assert(!WIN || FM, "the window: on frame-major rows");
+  static_assert(!TF || (FM && !WIN), "teacher forcing: on frame-major rows, its own mask");
   static_assert(!FM || !(ONES || KVLEN || CAUSAL), "frame-major: the plain layout, its own mask");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // LDS: [buf0: Q | dO][buf1: Q | dO][stats: 2 bufs x (lse2[64], delta[64])]
@@ -1355,10 +1471,12 @@ __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void att
   };
   // this workgroup's query tiles [j0, j1) (all of them unless the query range is split)
   const int nqt_all = (p.Lq + 63) / 64, jper = (nqt_all + p.q_split - 1) / (p.q_split > 0 ? p.q_split : 1);
-  const int j0 = fm_first_qtile<FM>(p, key0, sp * jper);
-  int j1 = min(nqt_all, j0 + jper);
+  [[maybe_unused]] const TfQTiles<TF> tt(p, key0, nqt_all);  // TF: the two tile ranges; j0 .. j1 then count visits
+  const int j0 = TF ? 0 : fm_first_qtile<FM>(p, key0, sp * jper);
+  int j1 = TF ? tt.nit : min(nqt_all, j0 + jper);
   if constexpr (WIN) j1 = fm_win_qtiles(p, key0, nqt_all);  // the sweep ends below qend of the last key (a lead key: all tiles)
-  issue_tile(j0, 0);
+  if constexpr (TF) issue_tile(tt.tile(0), 0);
+  else issue_tile(j0, 0);
   // FM: the lane's qstart, and the wave's largest (its last key's, the sequence's last row at most)
   [[maybe_unused]] int qlim = 0, wqlim = 0;
   if constexpr (FM) {
@@ -1370,6 +1488,19 @@ __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void att
   if constexpr (WIN) {
     qhi = fm_qend(p, krow);
     wqhi = __builtin_amdgcn_readfirstlane(fm_qend(p, fm_win_first_token_key(p, key0 + wave * 32)));
+  }
+  // TF: the lane's three reader bounds; the wave's largest qstart and q2 (its last key's; q2 = L with a lead key in the
+  // wave) and its smallest qend (its first token key's)
+  [[maybe_unused]] int q2 = 0, wq2 = 0;
+  if constexpr (TF) {
+    const TfMap tf(p);
+    const int wk0 = key0 + wave * 32, wk1 = min(wk0 + 31, p.Lk - 1);
+    qlim = tf.qstart(krow);
+    qhi = tf.qend(krow);
+    q2 = tf.q2(krow);
+    wqlim = __builtin_amdgcn_readfirstlane(tf.qstart(wk1));
+    wqhi = __builtin_amdgcn_readfirstlane(tf.qend(fm_win_first_token_key(p, wk0)));
+    wq2 = wk0 >= tf.lead ? __builtin_amdgcn_readfirstlane(tf.q2(wk1)) : p.Lq;
   }
 
   // this lane's key row as B-operand fragments (rows past Lk / columns past hd read as zero)
@@ -1400,9 +1531,11 @@ __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void att
   VDS_WAIT_VM(0);
   __syncthreads();  // tile j0 landed
 
-  auto q_tile = [&](int j, auto PAR) {  // unrolled by two: compile-time LDS buffer parity (see the forward kernel)
+  auto q_tile = [&](int it, auto PAR) {  // unrolled by two: compile-time LDS buffer parity (see the forward kernel)
     constexpr int par = decltype(PAR)::value;
-    if (j + 1 < j1) issue_tile(j + 1, par ^ 1);
+    int j = it, jn = it + 1;  // this visit's query tile and the next one's (TF: across the gap between the two ranges)
+    if constexpr (TF) { j = tt.tile(it); jn = tt.tile(it + 1); }
+    if (it + 1 < j1) issue_tile(jn, par ^ 1);
     const char* qt = qbuf + par * 2 * Q_TILE;
     const char* dot = qt + Q_TILE;
     const float* stl = reinterpret_cast<const float*>(stats + par * 512);
@@ -1451,7 +1584,10 @@ __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 ? 3 : 2))) void att
         const FcMap fm(p);
         fc_zero_q(fm, j * 64 + qb * 32 + 4 * h, fm.fk(krow), pm, s);
       }
-      if constexpr (WIN) {  // open: at or past the wave's largest qstart and wholly below its smallest qend
+      if constexpr (TF) {  // open: inside every key's first range, or at or past the wave's largest q2
+        const int s0 = j * 64 + qb * 32;
+        if ((s0 < wqlim || s0 + 32 > wqhi) && s0 < wq2) fm_zero_q_tf(s0 + 4 * h, qlim, qhi, q2, pm, s);
+      } else if constexpr (WIN) {  // open: at or past the wave's largest qstart and wholly below its smallest qend
         if (j * 64 + qb * 32 < wqlim || j * 64 + qb * 32 + 32 > wqhi)
           fm_zero_q_win(j * 64 + qb * 32 + 4 * h, qlim, qhi, pm, s);
       } else if constexpr (FM) {
@@ -2430,22 +2566,23 @@ int attn_variant() { return vdscfg::geti(vdscfg::ATTN_MFMA16) & 7; }
 //   PAST   (vds_attn_fwd_causal_past): the CAUSAL forward instances that also read p.fc_past.
 //   FM     (vds_attn_*_causal_fm, _fm_chunk): the frame-major instances; a chunk is the granularity p.fm_G, no kernel of its own.
 //   FM_WIN (vds_attn_*_causal_fm_window): the WIN instances of the FM kernels (p.fc_past = W chunks).
-enum class Mask { NONE, KVLEN, CAUSAL, PAST, FM, FM_WIN };
+//   FM_TF  (vds_teacher_attn_*): the TF instances of the plain FM kernels (the period is 2n: clean frames, noisy copies).
+enum class Mask { NONE, KVLEN, CAUSAL, PAST, FM, FM_WIN, FM_TF };
 struct MaskFlags {
-  bool kvlen, causal, past, fm, win;
+  bool kvlen, causal, past, fm, win, tf;
 };
 constexpr MaskFlags flags_of(Mask m) {
-  return {m == Mask::KVLEN, m == Mask::CAUSAL || m == Mask::PAST, m == Mask::PAST, m == Mask::FM || m == Mask::FM_WIN,
-          m == Mask::FM_WIN};
+  return {m == Mask::KVLEN, m == Mask::CAUSAL || m == Mask::PAST, m == Mask::PAST,
+          m == Mask::FM || m == Mask::FM_WIN || m == Mask::FM_TF, m == Mask::FM_WIN, m == Mask::FM_TF};
 }
 template <Mask M>
 constexpr MaskFlags FLAGS = flags_of(M);
 
 struct MaskV {
   const int32_t* kv_lens = nullptr;        // KVLEN: B int32 on the device
-  const vds_mod_groups* frames = nullptr;  // CAUSAL, PAST, FM, FM_WIN
+  const vds_mod_groups* frames = nullptr;  // CAUSAL, PAST, FM, FM_WIN, FM_TF
   int past = 0;                            // PAST: cached key rows behind the lead rows
-  int chunk = 1;                           // FM, FM_WIN: token-frames per causal chunk
+  int chunk = 1;                           // FM, FM_WIN, FM_TF: token-frames per causal chunk
   int window_chunks = 0;                   // FM_WIN
 };
 
@@ -2463,6 +2600,7 @@ int validate(const vds_attn_args* a, Mask kind, const MaskV& m, bool bwd) {
     const vds_mod_groups* fr = m.frames;
     if (!fr || (int64_t)a->Lk != (int64_t)a->Lq + m.past || a->kv_pad_ones == 2) return VDS_ERR_ARG;
     if (fr->lead < 0 || fr->period < 1 || a->Lq < fr->lead || (a->Lq - fr->lead) % fr->period != 0) return VDS_ERR_ARG;
+    if (f.tf && (fr->period & 1)) return VDS_ERR_ARG;  // clean frames and their noisy copies: an even period
     if (a->Lk > (1 << 21)) return VDS_ERR_UNSUPPORTED;  // FcMap / FmMap: the fp32 quotient is exact below 2^21 rows
   }
   if (f.fm) {
@@ -2488,6 +2626,8 @@ void apply_mask(AttnP& p, Mask kind, const MaskV& m) {
     p.fm_S = S > 0 ? S : 1;  // (no token rows: every row is a lead row and the quotient is never taken)
     // chunk >= period is one token group: G = period * S = L - lead < 2^21, whatever the chunk
     p.fm_G = (m.chunk < p.fc_period ? m.chunk : p.fc_period) * p.fm_S;
+    // teacher forcing: chunks of the n = period / 2 frames of a half (chunk >= n: one chunk per half)
+    if (f.tf) p.fm_G = (m.chunk < p.fc_period / 2 ? m.chunk : p.fc_period / 2) * p.fm_S;
     p.fm_rev = vdscfg::geti(vdscfg::ATTN_FM_HEAVY_FIRST) ? 1 : 0;
   }
   if (f.win) p.fc_past = m.window_chunks;  // (< the chunk count <= period: W * G stays below L)
@@ -2725,11 +2865,66 @@ double fm_pairs_k(int L, int lead, int G, int tile, int W = 0) {
   return n;
 }
 
+// Teacher forcing (TfMap): the bounds on the host, for the pair counts of the two-range sweeps.  base = lead + n S.
+struct TfHost {
+  int L, lead, base, G;
+  int cg(int r) const { return (r - (r >= base ? base : lead)) / G * G; }
+  int clip(long e) const { return e < L ? (int)e : L; }
+  int pend(int r) const { return r < lead ? lead : r < base ? (lead + cg(r) + G < base ? lead + cg(r) + G : base) : lead + cg(r); }
+  int kbeg(int r) const { return r < base ? pend(r) : base + cg(r); }
+  int kend(int r) const { return r < base ? pend(r) : clip((long)base + cg(r) + G); }
+  int qstart(int j) const { return j < lead ? 0 : (j < base ? lead : base) + cg(j); }
+  int qend(int j) const { return j < lead ? L : j < base ? base : clip((long)base + cg(j) + G); }
+  int q2(int j) const { return (j >= lead && j < base) ? clip((long)base + cg(j) + G) : L; }
+};
+// pairs of the key tiles (64 rows, the last one up to the workgroup's key bound) a TF forward / dQ workgroup visits
+double fm_pairs_q_tf(const TfHost& t, int tile) {
+  double n = 0;
+  for (int q0 = 0; q0 < t.L; q0 += tile) {
+    const int q1 = q0 + tile < t.L ? q0 + tile : t.L;
+    const int keys = t.kend(q1 - 1);
+    const int nl = (t.pend(q0 < t.base ? (q1 < t.base ? q1 : t.base) - 1 : q1 - 1) + 63) >> 6;
+    int skipped = 0;  // the tiles [nl, jb) between the two ranges
+    if (q1 > t.base) {
+      const int jb = t.kbeg(q0 > t.base ? q0 : t.base) >> 6;
+      if (jb > nl) skipped = (jb - nl) * 64;
+    }
+    n += (double)(q1 - q0) * (keys - skipped);
+  }
+  return n;
+}
+// ... and of the query tiles a TF dK/dV workgroup visits (rows up to L)
+double fm_pairs_k_tf(const TfHost& t, int tile) {
+  double n = 0;
+  const int nqt = (t.L + 63) >> 6;
+  for (int k0 = 0; k0 < t.L; k0 += tile) {
+    const int k1 = k0 + tile < t.L ? k0 + tile : t.L;
+    int a0 = 0, a1 = nqt, b0 = nqt;
+    if (k0 >= t.lead) {
+      a0 = t.qstart(k0) >> 6;
+      a1 = (t.qend(k1 - 1) + 63) >> 6;
+      const int q2 = t.q2(k0);
+      b0 = q2 >= t.L ? nqt : (a1 > (q2 >> 6) ? a1 : q2 >> 6);
+    }
+    auto rows = [&](int j0, int j1) { return (j1 * 64 < t.L ? j1 * 64 : t.L) - (j0 * 64 < t.L ? j0 * 64 : t.L); };
+    n += (double)(k1 - k0) * (rows(a0, a1) + rows(b0, nqt));
+  }
+  return n;
+}
+
 template <int HDP, int HDQ, Mask M>
 int run_fwd_fm(AttnP p, hipStream_t s) {
   constexpr bool WIN = FLAGS<M>.win;
   constexpr int LDS = 4 * 64 * HDP * 2;
   const int W = WIN ? p.fc_past : 0;
+  if constexpr (FLAGS<M>.tf) {  // the plain 32x32x16 TF kernel, whatever the layout (no TF instance of the 16x16x32 family)
+    const unsigned grid = tile_grid(p, p.Lq, 128);
+    const TfHost t{p.Lq, p.fc_lead, p.fc_lead + (p.fc_period / 2) * p.fm_S, p.fm_G};
+    vdsprof::Scope ps(VDS_PROF_ATTN_FWD_PLAIN, s, 4.0 * p.B * p.H * p.hd * fm_pairs_q_tf(t, 128),
+                      2.0 * p.B * p.H * p.hd * (2.0 * p.Lq + 2.0 * p.Lk));
+    launch<attn_fwd_kernel<HDP, HDQ, 2, true, false, false, false, true, false, true>, LDS>(grid, s, p);
+    return launched();
+  }
   // the ones layout on the 16x16x32 forward, where run_fwd takes it: 64 queries per wave by the attn_fwd_wide rule (0 / 1
   // forces, 2: from 2048 queries) and bit 2 of the variant mask
   bool fwd16 = false;
@@ -2759,6 +2954,19 @@ int run_bwd_fm(AttnP p, hipStream_t s) {
   const int W = WIN ? p.fc_past : 0;
   const double per = 2.0 * p.B * p.H * p.hd;  // FLOPs of one product per (query, key) pair
   const double qb = 2.0 * p.B * p.H * p.hd * (double)p.Lq, kb = qb;
+  if constexpr (FLAGS<M>.tf) {  // the plain 32x32x16 TF kernels: preprocess, dK/dV, dQ
+    const TfHost t{p.Lq, p.fc_lead, p.fc_lead + (p.fc_period / 2) * p.fm_S, p.fm_G};
+    launch_delta<true>(p, s);
+    {
+      const unsigned grid = tile_grid(p, p.Lk, 128);
+      vdsprof::Scope ps(VDS_PROF_ATTN_BWD_DKV_PLAIN, s, 2.0 * per * fm_pairs_k_tf(t, 128), 2.0 * qb + 4.0 * kb);
+      launch<attn_bwd_dkv_kernel<HDP, HDQ, false, false, false, true, false, true>, LDS_DKV>(grid, s, p);
+    }
+    const unsigned grid = tile_grid(p, p.Lq, 128);
+    vdsprof::Scope ps(VDS_PROF_ATTN_BWD_DQ_PLAIN, s, 2.0 * per * fm_pairs_q_tf(t, 128), 3.0 * qb + 2.0 * kb);
+    launch<attn_bwd_dq_kernel<HDP, HDQ, false, false, false, true, false, true>, LDS_DQ>(grid, s, p);
+    return launched();
+  }
   // the ones layout at head dim 72: the 16x16x32 kernels under the variant bits of their CAUSAL siblings (bit 0 dK/dV, bit 1
   // dQ; with attn_delta_fold the dQ kernel is its own preprocess and runs first)
   bool ones = false;
@@ -2949,4 +3157,19 @@ extern "C" int vds_attn_bwd_causal_fm_window(const vds_attn_args* a, const vds_m
   if (!frames || chunk < 1 || window_chunks < 1) return VDS_ERR_ARG;
   if (window_covers(frames, chunk, window_chunks)) return vds_attn_bwd_causal_fm_chunk(a, frames, chunk, stream);
   return attn_call<Mask::FM_WIN, true>(a, {nullptr, frames, 0, chunk, window_chunks}, stream);
+}
+
+// teacher forcing: the rows are [lead | clean frames | their noisy copies], frames->period = 2n token-frames; a noisy query
+// attends the lead keys, the clean chunks before its own and its own noisy chunk (TfMap).  Self-attention on frame-major
+// rows only; frames == NULL, an odd period and chunk < 1 are refused.
+extern "C" int vds_teacher_attn_fwd(const vds_attn_args* a, const vds_mod_groups* frames, int32_t chunk,
+                                    vds_stream_t stream) {
+  if (!frames || chunk < 1) return VDS_ERR_ARG;
+  return attn_call<Mask::FM_TF, false>(a, {nullptr, frames, 0, chunk}, stream);
+}
+
+extern "C" int vds_teacher_attn_bwd(const vds_attn_args* a, const vds_mod_groups* frames, int32_t chunk,
+                                    vds_stream_t stream) {
+  if (!frames || chunk < 1) return VDS_ERR_ARG;
+  return attn_call<Mask::FM_TF, true>(a, {nullptr, frames, 0, chunk}, stream);
 }

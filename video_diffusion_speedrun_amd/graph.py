@@ -56,8 +56,9 @@ class GraphedTrainStep:
 
     def __init__(self, dit_model, optimizer, lr_scheduler, device, eager_steps: int = 2, frame_mode=None,
                  cond_prob: float = 0.5):
-        """frame_mode / cond_prob: train.forward's per-frame timestep modes; the levels, weights and the conditioning
-        draw live on the device, so the captured step replays with new draws"""
+        """frame_mode / cond_prob: train.forward's per-frame timestep modes ("teacher" included: the doubled sequence, its
+        RoPE row gather and the teacher mask are captured like the rest of the step); the levels, weights and the
+        conditioning draw live on the device, so the captured step replays with new draws"""
         if frame_mode not in _train.FRAME_MODES:
             raise ValueError(f"frame_mode must be one of {_train.FRAME_MODES}, got {frame_mode!r}")
         self.frame_kw = {} if frame_mode is None else {"frame_mode": frame_mode, "cond_prob": cond_prob}

@@ -356,6 +356,13 @@ def check_frame_chunk(who: str, frame_chunk, frame_causal: bool, frame_major: bo
     return frame_chunk
 
 
+class TeacherFrames(tuple):
+    """frames = (lead, 2n) of a teacher-forcing call (DiT.forward(teacher_latents=)): the token-frames are n clean frames
+    and then their n noisy copies.  A plain (lead, period) pair for every per-row kernel; the self-attention calls of a
+    block run the teacher mask under it (DiTBlock._mask_kw)."""
+    __slots__ = ()
+
+
 def check_frame_window(who: str, frame_window, frame_chunk: int, frame_causal: bool, frame_major: bool):
     """frame_window of a DiT / DiTBlock: None, or an int >= 1 of token-frames that is a multiple of frame_chunk, on the
     frame-major frame-causal self-attention"""
@@ -464,8 +471,11 @@ class DiTBlock(nn.Module):
         self._own_group = g
         return g, ""
 
-    def _mask_kw(self):
-        """the chunk / window keywords of the full-sequence self-attention calls (nothing for the frame-causal mask)"""
+    def _mask_kw(self, frames=None):
+        """the chunk / window keywords of the full-sequence self-attention calls (nothing for the frame-causal mask);
+        frames a TeacherFrames: the teacher-forcing mask over chunks of frame_chunk frames (chunk 1 included)"""
+        if isinstance(frames, TeacherFrames):
+            return {"chunk": self.frame_chunk, "teacher": True}
         kw = {"chunk": self.frame_chunk} if self.frame_chunk > 1 else {}
         if self.frame_window is not None:
             kw["window"] = self.frame_window // self.frame_chunk
@@ -478,6 +488,11 @@ class DiTBlock(nn.Module):
             return None
         if frames is None:
             raise ValueError("DiTBlock: a frame_causal block needs frames=(lead, period), the row groups of its sequence")
+        if isinstance(frames, TeacherFrames):
+            if not self.frame_major or self.frame_window is not None:
+                raise ValueError("DiTBlock: a teacher-forcing call needs a block built with frame_major=True and without "
+                                 "frame_window")
+            return TeacherFrames(ops.check_mod_groups(frames, L))
         return ops.check_mod_groups(frames, L)
 
     def forward(self, x, context, c, v_0=None, rope=None, context_lens=None, frames=None):
@@ -626,7 +641,8 @@ class DiTBlock(nn.Module):
                                    **fm_kw)
             if cache is None and not kept_attn:
                 ops.attn_fwd(q[..., :hd], k[..., :hd], v[..., :hd], ops.heads_view(attn, B, L, H, hd), lse1,
-                             kv_pad_ones=(hdp - hd) >= 8, frames=frames, frame_major=self.frame_major, **self._mask_kw())
+                             kv_pad_ones=(hdp - hd) >= 8, frames=frames, frame_major=self.frame_major,
+                             **self._mask_kw(frames))
             if a8_on and save:  # first steps: record the amax the next step quantises with
                 for j, t in enumerate((q, k, v)):
                     ops.absmax(t.view(B * H * L, hdp)[:, :hd], fp8_hist.cur(F8.ROWS * i + F8.ROW_Q + j))
@@ -958,7 +974,8 @@ class DiTBlock(nn.Module):
             delta = torch.empty(2, B, H, L, dtype=f32, device=dev)
             ops.attn_bwd(bs.q[..., :hd], bs.k[..., :hd], bs.v[..., :hd], ops.heads_view(bs.attn, B, L, H, hd), bs.lse1,
                          ops.heads_view(dattn, B, L, H, hd), dq[..., :hd], dk[..., :hd], dv[..., :hd], delta,
-                         kv_pad_ones=(hdp - hd) >= 8, frames=bs.frames, frame_major=self.frame_major, **self._mask_kw())
+                         kv_pad_ones=(hdp - hd) >= 8, frames=bs.frames, frame_major=self.frame_major,
+                         **self._mask_kw(bs.frames))
             if bs.a8_on:
                 ops.absmax(dattn, fp8_hist.cur(F8.ROWS * i + F8.ROW_DO))
         defer = getattr(sv, "dv_terms", None)  # DiT.backward: [(dv, lambda)] of the mixed blocks, summed at block 0
@@ -1099,7 +1116,9 @@ def activation_bytes(dit, B: int, latent_shape, Lc: int, mode: str = "none") -> 
     bf16 fp8-free path; the lists mirror the `bs.*` assignments of DiTBlock._fwd.  qk_norm="all" adds the two rstd tensors
     of the cross-attention's head norm (4 H bytes per token row and per context row).  qk_norm=True changes nothing: its
     backward reads the qkv GEMM output (3 D bf16 elements per token row), which every block -- block 0, which mixes no
-    v_0, included -- already keeps and this sum already counts."""
+    v_0, included -- already keeps and this sum already counts.
+    A teacher-forcing call (forward(teacher_latents=)) runs the clean and the noisy frames as one sequence: call this with
+    the doubled T, latent_shape = (2 * T, H, W), for its numbers."""
     if mode not in RECOMPUTE_MODES:
         raise ValueError(f"activation_bytes: mode must be one of {RECOMPUTE_MODES}, got {mode!r}")
     D, H, hd = dit.hidden_size, dit.num_heads, dit.head_dim
@@ -1491,7 +1510,7 @@ class DiT(nn.Module):
 
     # ------------------------------------------------------------------------ forward ----
     def forward(self, x, context, timesteps, rope_start: Optional[Tuple[int, int, int]] = None, context_lens=None,
-                register_timesteps=None, frame_cache=None):
+                register_timesteps=None, frame_cache=None, teacher_latents=None):
         """x [B,C,T,H,W], context [B,Lc,Cc], timesteps [B] -> [B,C,T,H,W] bf16 (model.py:358-402).
         timesteps [B, t], t = T // time_patch_size: one noise level per token-frame (image-to-video, video extension,
         diffusion forcing).  The tokens of frame f of sample b are modulated from timesteps[b, f], the register tokens
@@ -1512,7 +1531,55 @@ class DiT(nn.Module):
         table of the whole video of frame_cache.frames frames (FrameKVCache.rope_rows), so the cache must be made for the
         video's full frame count.  Returns [B, C, k*pt, H, W].  The cached K / V are only valid if every call pins the
         same register_timesteps.  With those two, the call computes what the full-sequence call (earlier frames at t = 0,
-        later ones at any level) computes for the chunk's frames."""
+        later ones at any level) computes for the chunk's frames.
+        teacher_latents ([B,C,T,H,W], the clean latents that x is the noised copy of; a frame_causal, frame_major model
+        without frame_window; timesteps [B, t]): teacher forcing.  The model runs cat([teacher_latents, x], dim=2) as a
+        video of 2t token-frames at the levels [0 ... 0 | timesteps], the registers at register_timesteps (default 1.0 per
+        sample, the level the cached rollout pins); token-frame t + f takes the RoPE rows of token-frame f; every
+        self-attention runs the teacher mask -- a noisy chunk attends the registers, the CLEAN chunks before it and
+        itself -- so that each chunk is computed as generate_latents(rollout_frames=frame_chunk, kv_cache=True) computes it.
+        Returns the noisy half, [B,C,T,H,W]; the clean rows get their gradients through K / V."""
+        if teacher_latents is not None:
+            return self._forward_teacher(x, context, timesteps, rope_start, context_lens, register_timesteps, frame_cache,
+                                         teacher_latents)
+        return self._forward(x, context, timesteps, rope_start, context_lens, register_timesteps, frame_cache)
+
+    def _forward_teacher(self, x, context, timesteps, rope_start, context_lens, register_timesteps, frame_cache,
+                         teacher_latents):
+        # every refusal before the device is touched
+        if not (self.frame_causal and self.frame_major):
+            raise ValueError("DiT: teacher_latents needs the teacher-forcing mask of the frame-major frame-causal "
+                             "self-attention -- build the model with frame_causal=True, frame_major=True")
+        if self.frame_window is not None:
+            raise ValueError(f"DiT: teacher_latents is not built for a frame_window={self.frame_window} model (the ring's "
+                             "clean context is a different mask) -- build the model with frame_window=None, or train it "
+                             "with frame_mode='chunk'")
+        if frame_cache is not None:
+            raise ValueError("DiT: teacher_latents and frame_cache exclude each other -- a teacher-forcing call carries its "
+                             "clean context in the sequence; pass frame_cache=None (training) or drop teacher_latents "
+                             "(the cached rollout)")
+        if not isinstance(teacher_latents, torch.Tensor) or tuple(teacher_latents.shape) != tuple(x.shape):
+            got = tuple(teacher_latents.shape) if isinstance(teacher_latents, torch.Tensor) else type(teacher_latents).__name__
+            raise ValueError(f"DiT: teacher_latents must have x's shape {tuple(x.shape)} (the clean latents of the same "
+                             f"frames), got {got}")
+        b, T = x.shape[0], x.shape[2]
+        t = T // self.time_patch_size
+        if not check_timesteps(timesteps, b, t):
+            raise ValueError(f"DiT: teacher_latents takes per-frame timesteps of shape [{b}, {t}] (one level per noisy "
+                             f"token-frame, equal inside a chunk), got {tuple(timesteps.shape)} -- pass "
+                             f"timesteps[:, None].expand({b}, {t})")
+        if self.fp8:
+            raise NotImplementedError(_FP8_FRAME_TIMESTEPS)
+        if register_timesteps is None:
+            register_timesteps = torch.ones(b, dtype=f32, device=x.device)
+        if rope_start is None and self.use_rope:
+            rope_start = self.rope.draw_start((t, x.shape[3] // self.patch_size, x.shape[4] // self.patch_size))
+        x2 = torch.cat([teacher_latents.to(x.dtype), x], dim=2)
+        ts2 = torch.cat([torch.zeros_like(timesteps), timesteps], dim=1)
+        out = self._forward(x2, context, ts2, rope_start, context_lens, register_timesteps, None, teacher=True)
+        return out[:, :, T:]
+
+    def _forward(self, x, context, timesteps, rope_start, context_lens, register_timesteps, frame_cache, teacher=False):
         reg_t = None
         if register_timesteps is not None or frame_cache is not None:  # validated before the device is touched
             b = x.shape[0]
@@ -1557,9 +1624,9 @@ class DiT(nn.Module):
         if kv_lens is not None:
             kv_lens = kv_lens.to(x.device)
         if need_grad:
-            return _DiTFunction.apply(self, x, context, timesteps, rope_start, kv_lens, reg_t, *params)
+            return _DiTFunction.apply(self, x, context, timesteps, rope_start, kv_lens, reg_t, teacher, *params)
         out, _ = self._forward_impl(x, context, timesteps, rope_start, save=False, kv_lens=kv_lens, reg_t=reg_t,
-                                    cache=frame_cache)
+                                    cache=frame_cache, teacher=teacher)
         if frame_cache is not None:
             frame_cache.pending_frames = thw[0]
         return out
@@ -1655,7 +1722,8 @@ class DiT(nn.Module):
         for g in self._groups:
             g.gather(ops.cast_f32_bf16, None)
 
-    def _forward_impl(self, x, context, timesteps, rope_start, save: bool, kv_lens=None, reg_t=None, cache=None):
+    def _forward_impl(self, x, context, timesteps, rope_start, save: bool, kv_lens=None, reg_t=None, cache=None,
+                      teacher=False):
         D, H, hd = self.hidden_size, self.num_heads, self.head_dim
         pt, p = self.time_patch_size, self.patch_size
         B, C, T, Hh, Ww = x.shape
@@ -1696,6 +1764,13 @@ class DiT(nn.Module):
         ops.fill_registers(R.w("register_tokens").view(N_REG, D), X, L * D, B, N_REG, D)
         if cache is not None:
             cos, sin = cache.rope_rows(self.rope, rope_start, t)
+        elif teacher:
+            # token-frame t/2 + f takes the rows of token-frame f: the table of (t/2, h, w), its token rows ((h w t) order, t
+            # fastest) taken twice along t
+            def twice(tab):
+                tok = tab[N_REG:].view(h * w, t // 2, -1)
+                return torch.cat([tab[:N_REG], torch.cat([tok, tok], dim=1).reshape(N, -1)], dim=0).contiguous()
+            cos, sin = (twice(tab) for tab in self.rope.rows((t // 2, h, w), rope_start, N_REG))
         else:
             cos, sin = self.rope.rows((t, h, w), rope_start, N_REG)
 
@@ -1704,6 +1779,8 @@ class DiT(nn.Module):
         # group 0 (the register rows) on the sample's noisiest frame, group 1 + f (the rows of token-frame f: the token
         # order is (h w t), t fastest) on timesteps[b, f] -- and every modulated kernel looks its row up per group
         frames = (N_REG, t) if self.frame_causal else None  # [B] and [B, t] timesteps alike
+        if teacher:
+            frames = TeacherFrames(frames)  # (the blocks' self-attention: the teacher mask over t/2 clean + t/2 noisy frames)
         groups = None
         if timesteps.dim() == 2:
             groups = (N_REG, t)
@@ -2035,8 +2112,9 @@ class _DiTFunction(torch.autograd.Function):
     parameter gradients are written into the flat fp32 gradient buffers that p.grad aliases."""
 
     @staticmethod
-    def forward(ctx, model, x, context, timesteps, rope_start, kv_lens, reg_t, *params):
-        out, sv = model._forward_impl(x, context, timesteps, rope_start, save=True, kv_lens=kv_lens, reg_t=reg_t)
+    def forward(ctx, model, x, context, timesteps, rope_start, kv_lens, reg_t, teacher, *params):
+        out, sv = model._forward_impl(x, context, timesteps, rope_start, save=True, kv_lens=kv_lens, reg_t=reg_t,
+                                      teacher=teacher)
         ctx.model, ctx.sv = model, sv
         return out
 
@@ -2045,4 +2123,4 @@ class _DiTFunction(torch.autograd.Function):
         model, sv = ctx.model, ctx.sv
         ctx.sv = None
         model._backward_impl(sv, dout)
-        return (None,) * (7 + len([p for p in model.parameters() if p.requires_grad]))
+        return (None,) * (8 + len([p for p in model.parameters() if p.requires_grad]))

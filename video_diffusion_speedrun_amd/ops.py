@@ -301,6 +301,29 @@ def _frame_major(frame_major, frames, kv_lens, past=0, chunk=1, window=None) -> 
     return True
 
 
+def _teacher(teacher, frame_major, frames, kv_lens, past, window, Lq) -> bool:
+    """teacher=True (the clean-context mask of teacher forcing) needs frame_major=True and frames=(lead, 2n), and excludes
+    window, past and kv_lens: refused here, before anything is launched"""
+    if not teacher:
+        return False
+    if not frame_major or frames is None:
+        raise ValueError("attention: teacher=True needs frame_major=True and frames=(lead, 2n) -- the teacher-forcing mask "
+                         "exists on the frame-major kernels only; pass frame_major=True with frame-major q / k / v rows")
+    if window is not None:
+        raise ValueError(f"attention: teacher=True excludes window = {window} -- the sliding window over a clean context is "
+                         "not built; pass window=None")
+    if past:
+        raise ValueError(f"attention: teacher=True excludes past = {past} -- the clean context is part of the sequence "
+                         "([lead | clean frames | noisy frames]), not a cache; pass past=0")
+    if kv_lens is not None:
+        raise ValueError("attention: teacher=True is self-attention: pass kv_lens=None")
+    lead, period = frames
+    if int(period) % 2:
+        raise ValueError(f"attention: teacher=True needs an even period (n clean frames and their n noisy copies), got "
+                         f"frames = {tuple(frames)}; pass frames=(lead, 2 * n)")
+    return True
+
+
 def _attn_args(q, k, v, o, lse, kv_pad_ones, grads=None, delta=None) -> AttnArgs:
     """vds_attn_args of a call.  Forward: shapes, q / k / v / o with their strides, lse; the backward adds
     grads = (do, dq, dk, dv) with theirs and the delta workspace with its size"""
@@ -321,13 +344,18 @@ def _attn_args(q, k, v, o, lse, kv_pad_ones, grads=None, delta=None) -> AttnArgs
     return a
 
 
-def _attn_entry(direction: str, a: AttnArgs, kv_lens, frames, fr, past: int, fmaj: bool, chunk: int, window):
+def _attn_entry(direction: str, a: AttnArgs, kv_lens, frames, fr, past: int, fmaj: bool, chunk: int, window,
+                teacher: bool = False):
     """(C entry point, its arguments after vds_attn_args, the text of its error message): the one place that maps
-    (direction, kv_lens, frames, past, frame_major, chunk, window) to one of the 13 calls.  Without a flag every call is the
-    entry point it always was; fr is the vds_mod_groups of frames (_frames)"""
+    (direction, kv_lens, frames, past, frame_major, chunk, window) to one of the 13 calls, or with teacher to
+    vds_teacher_attn_fwd / _bwd.  Without a flag every call is the entry point it always was; fr is the vds_mod_groups of
+    frames (_frames)"""
     B, H, Lq, Lk, hd = a.B, a.H, a.Lq, a.Lk, a.head_dim
     cross = f"B={B},H={H},Lq={Lq},Lk={Lk},hd={hd}"
     self_ = f"B={B},H={H},L={Lq},hd={hd},frames={tuple(frames)}" if fr is not None else None
+    if teacher:
+        name = f"vds_teacher_attn_{direction}"
+        return name, (fr, chunk), f"{name}({self_},chunk={chunk})"
     if fmaj and window is not None:
         name, extra, what = "_causal_fm_window", (fr, chunk, window), f"{self_},chunk={chunk},window={window}"
     elif fmaj and chunk != 1:
@@ -346,14 +374,14 @@ def _attn_entry(direction: str, a: AttnArgs, kv_lens, frames, fr, past: int, fma
     return name, extra, f"{name}({what})"
 
 
-def _attn_call(direction: str, a: AttnArgs, kv_lens, frames, fr, past, fmaj, chunk, window):
+def _attn_call(direction: str, a: AttnArgs, kv_lens, frames, fr, past, fmaj, chunk, window, teacher=False):
     lib = _lib.load()
-    name, extra, what = _attn_entry(direction, a, kv_lens, frames, fr, past, fmaj, chunk, window)
+    name, extra, what = _attn_entry(direction, a, kv_lens, frames, fr, past, fmaj, chunk, window, teacher)
     check(getattr(lib, name)(C.byref(a), *extra, _stream()), what)
 
 
 def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=None, past: int = 0,
-             frame_major: bool = False, chunk: int = 1, window=None):
+             frame_major: bool = False, chunk: int = 1, window=None, teacher: bool = False):
     """q [B,H,Lq,hd], k/v [B,H,Lk,hd], o [B,H,Lq,hd] strided views (last dim contiguous); lse f32 [B,H,Lq].
     kv_pad_ones: k / v are views into qkv_rope_fwd outputs whose pad carries the ones columns.
     kv_lens: int32 CUDA tensor [B]; sample b attends its first kv_lens[b] keys only (vds_attn_fwd_kvlen).
@@ -366,16 +394,20 @@ def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=No
     chunk (with frame_major): the mask is causal over chunks of `chunk` token-frames and bidirectional inside a chunk --
     fm_group_of(key, chunk) <= fm_group_of(query, chunk) (vds_attn_fwd_causal_fm_chunk); 1 is the frame-causal mask.
     window (with frame_major; in chunks): a token query of chunk n attends the lead keys and the token keys of chunks
-    max(0, n - window + 1) .. n only (vds_attn_fwd_causal_fm_window); None: no window."""
+    max(0, n - window + 1) .. n only (vds_attn_fwd_causal_fm_window); None: no window.
+    teacher (with frame_major, frames=(lead, 2n); not with window / past / kv_lens): teacher forcing -- the token-frames are n
+    clean frames then their n noisy copies; a clean query attends the lead keys and the clean chunks up to its own, a noisy
+    query the lead keys, the clean chunks BEFORE its own and its own noisy chunk (vds_teacher_attn_fwd)."""
     B, H, Lq, hd = q.shape
     Lk = k.shape[2]
     past = int(past)
+    teacher = _teacher(teacher, frame_major, frames, kv_lens, past, window, Lq)
     fmaj = _frame_major(frame_major, frames, kv_lens, past, chunk, window)
     if past < 0 or (past and frames is None):
         raise ValueError(f"attention: past = {past} must be >= 0 and needs frames=(lead, period)")
     fr = _frames(frames, kv_lens, Lq, Lk, past) if frames is not None else None
     a = _attn_args(q, k, v, o, lse, kv_pad_ones)
-    _attn_call("fwd", a, kv_lens, frames, fr, past, fmaj, chunk, window)
+    _attn_call("fwd", a, kv_lens, frames, fr, past, fmaj, chunk, window, teacher)
 
 
 def kv_pad_ones(kv: torch.Tensor, B: int, Lk: int, H: int, hd: int, hdp: int, k_col0: int, v_col0: int):
@@ -397,7 +429,7 @@ def attn_bwd_workspace_floats(B, H, Lq, Lk, hd, kv_pad_ones: bool = False) -> in
 
 
 def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = False, kv_lens=None, frames=None,
-             frame_major: bool = False, chunk: int = 1, window=None):
+             frame_major: bool = False, chunk: int = 1, window=None, teacher: bool = False):
     """delta: f32 workspace of 2*B*H*Lq elements (rowsum(dO*O), then lse*log2 e); allocated here when None
     (size from vds_attn_bwd_workspace_bytes).
     kv_lens: as in attn_fwd; rows kv_lens[b].. of dk[b] / dv[b] are written as zeros (vds_attn_bwd_kvlen).
@@ -405,17 +437,19 @@ def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = Fa
     frame_major: as in attn_fwd -- q, k, v, lse, dq, dk, dv (and the delta workspace) rows are frame-major, o and do
     token-major (vds_attn_bwd_causal_fm).
     chunk: as in attn_fwd (vds_attn_bwd_causal_fm_chunk).
-    window: as in attn_fwd (vds_attn_bwd_causal_fm_window)."""
+    window: as in attn_fwd (vds_attn_bwd_causal_fm_window).
+    teacher: as in attn_fwd (vds_teacher_attn_bwd); the workspace is unchanged."""
     B, H, Lq, hd = q.shape
     assert lse.is_contiguous()
     Lk = k.shape[2]
+    teacher = _teacher(teacher, frame_major, frames, kv_lens, 0, window, Lq)
     fmaj = _frame_major(frame_major, frames, kv_lens, 0, chunk, window)
     fr = _frames(frames, kv_lens, Lq, Lk) if frames is not None else None
     if delta is None:
         delta = torch.empty(attn_bwd_workspace_floats(B, H, Lq, Lk, hd, kv_pad_ones), dtype=f32, device=q.device)
     assert delta.numel() >= 2 * B * H * Lq and delta.is_contiguous(), "attn_bwd: delta workspace is [2,B,H,Lq] f32"
     a = _attn_args(q, k, v, o, lse, kv_pad_ones, (do, dq, dk, dv), delta)
-    _attn_call("bwd", a, kv_lens, frames, fr, 0, fmaj, chunk, window)
+    _attn_call("bwd", a, kv_lens, frames, fr, 0, fmaj, chunk, window, teacher)
 
 
 # ---------------------------------------------------------------------- fp8 attention ----

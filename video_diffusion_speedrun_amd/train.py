@@ -106,7 +106,7 @@ def frame_flow_loss(out, v, weights, time_patch: int):
     return _FrameFlowLoss.apply(out.contiguous(), v.contiguous(), weights.to(f32).contiguous(), int(time_patch))
 
 
-FRAME_MODES = (None, "first_frame", "independent", "chunk")
+FRAME_MODES = (None, "first_frame", "independent", "chunk", "teacher")
 
 
 def frame_group_of(l: int, n_frames: int, lead: int = 16) -> int:
@@ -177,7 +177,11 @@ def forward(dit_model, batch, text_encoder, tokenizer, device, global_step, mast
     """frame_mode=None (default): one noise level per sample, the reference's step.
     frame_mode="first_frame": one level per sample, and with probability cond_prob token-frame 0 stays clean (t = 0) and
     leaves the loss (image-to-video); "independent": one level per token-frame (diffusion forcing); "chunk": one level
-    per chunk of the model's frame_chunk token-frames (what a chunk-at-a-time rollout meets), weights 1.  frame_timesteps
+    per chunk of the model's frame_chunk token-frames (what a chunk-at-a-time rollout meets), weights 1.
+    "teacher": teacher forcing -- the levels are drawn exactly as "chunk" draws them (the same generator draws in the same
+    order), and the model runs [registers | clean frames | noisy frames] (DiT.forward(teacher_latents=)): every noisy
+    chunk attends the registers at level 1.0, the clean chunks before it and itself, which is what the cached rollout
+    computes for that chunk; the loss is taken on the noisy half, weights 1.  frame_timesteps
     [B, t] / frame_weights [B, t] override the drawn levels / weights (t = T // time_patch_size)."""
     logger = logging.getLogger(__name__)
     vae_latent = batch["latent"].to(device).to(bf16)
@@ -206,14 +210,23 @@ def forward(dit_model, batch, text_encoder, tokenizer, device, global_step, mast
         # per-sample path does for its first two draws
         pt = dit_model.time_patch_size
         n_frames = vae_latent.shape[2] // pt
+        teacher = frame_mode == "teacher"
+        if teacher:
+            if not (getattr(dit_model, "frame_causal", False) and getattr(dit_model, "frame_major", False)) or \
+                    getattr(dit_model, "frame_window", None) is not None:
+                raise ValueError("frame_mode='teacher' needs a model built with frame_causal=True, frame_major=True and "
+                                 "frame_window=None (the teacher-forcing mask); train any other model with "
+                                 "frame_mode='chunk' or 'independent'")
+            kw = dict(kw, teacher_latents=vae_latent)
+        draw_mode = "chunk" if teacher else frame_mode  # teacher: the draws of "chunk", in the same order
         if frame_timesteps is None:
             if frame_mode is None:
                 raise ValueError("frame_weights without frame_mode or frame_timesteps: nothing defines the per-frame levels")
-            ckw = {"chunk": int(getattr(dit_model, "frame_chunk", 1))} if frame_mode == "chunk" else {}
-            levels = draw_frame_levels(frame_mode, B, n_frames, device, generator, **ckw)
+            ckw = {"chunk": int(getattr(dit_model, "frame_chunk", 1))} if frame_mode in ("chunk", "teacher") else {}
+            levels = draw_frame_levels(draw_mode, B, n_frames, device, generator, **ckw)
         noise = torch.randn(vae_latent.shape, device=device, dtype=bf16, generator=generator)
         if frame_timesteps is None:
-            t, weights = frame_schedule(frame_mode, levels, n_frames, cond_prob, generator, **ckw)
+            t, weights = frame_schedule(draw_mode, levels, n_frames, cond_prob, generator, **ckw)
         else:
             t = torch.as_tensor(frame_timesteps).to(device=device, dtype=bf16)
             weights = torch.ones(t.shape, dtype=f32, device=device)
