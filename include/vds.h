@@ -669,7 +669,11 @@ typedef struct vds_adamw_tensor {
 } vds_adamw_tensor;
 /* work list: chunk i updates elements [chunk_start[i], chunk_start[i]+chunk_elems) of tensor
  * chunk_tensor[i]; lr_mult is the LR-schedule multiplier of this step (train.py:349-364,434),
- * step counts from 1, grad_scale multiplies every gradient (1.0 normally). */
+ * step counts from 1, grad_scale multiplies every gradient (1.0 normally).  chunk_elems >= 4, any value.
+ * Alignment: every pointer needs only its natural alignment (4 bytes, 2 for the shadow).  A chunk takes the 16-byte
+ * path only when ALL of p, g, m, v (and the EMA of the guarded form, where present) are 16-byte aligned at the chunk's
+ * first element and p_bf16, where present, is 8-byte aligned there; otherwise it is served element by element.  The
+ * results are the same bits either way. */
 int vds_adamw_multi(const vds_adamw_tensor* desc_dev, const int32_t* chunk_tensor_dev,
                     const int64_t* chunk_start_dev, int32_t n_chunks, int32_t chunk_elems,
                     float beta1, float beta2, float eps, int32_t step, float lr_mult,

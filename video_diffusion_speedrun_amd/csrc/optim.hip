@@ -63,8 +63,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamT* desc, const int
 #define VDS_ST(ptr, val) (*(ptr) = (val))
 #endif
   constexpr int U = VDS_ADAMW_U;
-  const bool vec_ok = (reinterpret_cast<uintptr_t>(t.p + s0) & 15) == 0 && (!t.pb || (reinterpret_cast<uintptr_t>(t.pb + s0) & 7) == 0) &&
-                      (!GUARD || !ema || (reinterpret_cast<uintptr_t>(ema + s0) & 15) == 0);
+  // the 16-byte path needs EVERY stream of the chunk on its boundary: p, g, m, v (16 bytes), the shadow (8), the EMA (16)
+  const uintptr_t f32_bits = reinterpret_cast<uintptr_t>(t.p + s0) | reinterpret_cast<uintptr_t>(t.g + s0) |
+                             reinterpret_cast<uintptr_t>(t.m + s0) | reinterpret_cast<uintptr_t>(t.v + s0) |
+                             ((GUARD && ema) ? reinterpret_cast<uintptr_t>(ema + s0) : 0);
+  const bool vec_ok = (f32_bits & 15) == 0 && (!t.pb || (reinterpret_cast<uintptr_t>(t.pb + s0) & 7) == 0);
   long i = s0 + threadIdx.x * 4;
   if (vec_ok) {
     // U independent 16-byte vectors per thread and iteration: every load is issued before the first use
