@@ -395,6 +395,32 @@ int vds_attn_bwd_causal_fm_window(const vds_attn_args* args, const vds_mod_group
  * or a head dim without instance: VDS_ERR_UNSUPPORTED.  lead, period and chunk travel by value. */
 int vds_teacher_attn_fwd(const vds_attn_args* args, const vds_mod_groups* frames, int32_t chunk, vds_stream_t stream);
 int vds_teacher_attn_bwd(const vds_attn_args* args, const vds_mod_groups* frames, int32_t chunk, vds_stream_t stream);
+/* Frame band: frame-major self-attention for the bidirectional model -- not causal.  With S = (L - lead) / period rows per
+ * frame, G = min(chunk, period) * S and chunk(x) = (x - lead) / G (the last chunk is short when period % chunk != 0), a
+ * token row x has
+ *   lo(x) = lead + max(0, chunk(x) - band_chunks) * G,   hi(x) = min(L, lead + (chunk(x) + band_chunks + 1) * G)
+ * and query r attends key j iff r < lead, or j < lead, or lo(r) <= j < hi(r).  A lead query attends all L keys (every
+ * causal mask here gives it the lead keys only), a lead key is read by all L queries, and the relation is symmetric: the
+ * readers of token key j are [0, lead) and [lo(j), hi(j)).  No row is empty.  lead = 0 is allowed; band_chunks = 0 is "own
+ * chunk plus lead rows"; band_chunks >= ceil(period / chunk) - 1 attends every pair and runs the same instances.
+ * What is skipped: a forward / dQ workgroup with queries [q0, q1) visits every 64-key tile if q0 < lead, else the lead
+ * tiles [0, nl) and then [max(nl, lo(q0) >> 6), ceil(hi(q1 - 1) / 64)), never one twice; a dK/dV workgroup with keys
+ * [k0, k1) sweeps every 64-row query tile if k0 < lead, else the lead query tiles and then those from lo(k0) to below
+ * hi(k1 - 1).  A 32x32 sub-block runs without mask code when the wave holds no lead row and the block lies wholly below lead
+ * or wholly inside [lo of the wave's last row, hi of its first), and in a wave of lead rows only.  Excluded pairs get P = 0
+ * exactly and never enter a running maximum.  The forward and dQ workgroups run in plain tile order (the first one of a head
+ * is its heaviest; attn_fm_heavy_first does not reverse them).  The profiler credits the visited tiles.
+ * These are BAND instances of the plain 32x32x16 frame-major kernels at every head dim of the dispatcher, for kv_pad_ones 0
+ * and 1 (the pad columns are not read); the variant bits and knobs that select the 16x16x32 or 64-queries-per-wave family
+ * elsewhere select nothing here.  Layout, tok(), workspace and the stride, length and 4 GiB refusals are those of the _fm
+ * calls; no atomics, bit-identical run to run.
+ * band_chunks < 0, chunk < 1, frames == NULL, Lq != Lk, kv_pad_ones == 2, lead < 0, period < 1 or (L - lead) % period != 0:
+ * VDS_ERR_ARG; L > 2^21 rows or a head dim without instance: VDS_ERR_UNSUPPORTED (ARG first).  lead, period, chunk and
+ * band_chunks travel by value. */
+int vds_band_attn_fwd(const vds_attn_args* args, const vds_mod_groups* frames, int32_t chunk, int32_t band_chunks,
+                      vds_stream_t stream);
+int vds_band_attn_bwd(const vds_attn_args* args, const vds_mod_groups* frames, int32_t chunk, int32_t band_chunks,
+                      vds_stream_t stream);
 /* vds_rmsnorm_mod_fwd with mod f32 [B*G, ldmod]: the same arithmetic per row, y / rstd bit-identical to the per-sample
  * call run on the rows of one group with that group's mod row.  Every form of the dispatcher is covered. */
 int vds_rmsnorm_mod_fwd_grouped(const void* x, int64_t ldx, const void* w, const float* mod, int64_t ldmod,

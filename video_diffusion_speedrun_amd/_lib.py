@@ -109,6 +109,8 @@ SIGNATURES = {
     "vds_attn_bwd_causal_fm_window": [C.POINTER(AttnArgs), c_vp, c_i32, c_i32, c_vp],
     "vds_teacher_attn_fwd": [C.POINTER(AttnArgs), c_vp, c_i32, c_vp],
     "vds_teacher_attn_bwd": [C.POINTER(AttnArgs), c_vp, c_i32, c_vp],
+    "vds_band_attn_fwd": [C.POINTER(AttnArgs), c_vp, c_i32, c_i32, c_vp],
+    "vds_band_attn_bwd": [C.POINTER(AttnArgs), c_vp, c_i32, c_i32, c_vp],
     "vds_attn_fwd_causal_past": [C.POINTER(AttnArgs), c_vp, c_i32, c_vp],
     "vds_attn_set_variant": [c_i32],
     "vds_kv_pad_ones": [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],

@@ -225,6 +225,28 @@ struct TfMap {
   __device__ __forceinline__ int qend(int j) const { return j < lead ? L : (j < base ? base : min(L, base + cg(j) + G)); }
   __device__ __forceinline__ int q2(int j) const { return (j >= lead && j < base) ? min(L, base + cg(j) + G) : L; }
 };
+// Frame band (BAND instances of the FM kernels, vds_band_attn_*; b = p.fc_past chunks on each side).  Not causal: a token
+// row x of chunk n attends the lead rows and the token rows of chunks n - b .. n + b, [lo(x), hi(x)) -- the lead rows plus
+// one contiguous run, the WIN form -- and a lead row attends every row.  The relation is symmetric: the readers of token
+// key j are [0, lead) and [lo(j), hi(j)), those of a lead key [0, L).  lo and hi grow with the row from lead on.
+//   lead row    prefix end L (everything), empty run (lo = hi = L)
+//   token row   prefix end lead,           run [lead + max(0, n - b) G, min(L, lead + (n + b + 1) G))
+// so that fm_win_masked's "key >= hi or pend <= key < lo" is the one compare of every row.  The quotient is FcMap's fp32
+// rule; b is clamped to the chunk count by apply_mask, so b G stays below 2^22.
+struct BandMap {
+  int lead, G, bG, L;
+  float ginv, ghinv;
+  __device__ __forceinline__ explicit BandMap(const AttnP& p)
+      : lead(p.fc_lead), G(p.fm_G), bG(__mul24(p.fc_past, p.fm_G)), L(p.Lq) {
+    ginv = 1.0f / (float)p.fm_G;
+    ghinv = 0.5f * ginv;
+  }
+  // first row of the chunk of token row r, as an offset from lead (r >= lead)
+  __device__ __forceinline__ int cg(int r) const { return __mul24((int)__builtin_fmaf((float)(r - lead), ginv, ghinv), G); }
+  __device__ __forceinline__ int pend(int r) const { return r < lead ? L : lead; }
+  __device__ __forceinline__ int lo(int r) const { return r < lead ? L : lead + max(0, cg(r) - bG); }
+  __device__ __forceinline__ int hi(int r) const { return r < lead ? L : min(L, lead + cg(r) + bG + G); }
+};
 __device__ __forceinline__ int fm_kend(const AttnP& p, int r) { return FmMap(p).kend(r); }
 __device__ __forceinline__ int fm_qstart(const AttnP& p, int j) { return FmMap(p).qstart(j); }
 // row of o / d_o that holds row r of the computation: tok(r) in the FM instances, r itself otherwise
@@ -235,9 +257,11 @@ __device__ __forceinline__ int out_row(const AttnP& p, int r) {
 }
 // keys of the workgroup whose query rows are [q0, q0 + rows): FM -- the largest kend of its rows (<= L); else Lk
 // (TF: kend of the last row is the largest bound of either range -- a noisy row's run ends past base, where no prefix reaches)
-template <bool FM, bool TF = false>
+// (BAND: L for the workgroup that holds a lead row, else hi of its last row)
+template <bool FM, bool TF = false, bool BAND = false>
 __device__ __forceinline__ int fm_keys(const AttnP& p, int q0, int rows, int Lk) {
-  if constexpr (TF) return TfMap(p).kend(min(q0 + rows, p.Lq) - 1);
+  if constexpr (BAND) return q0 < p.fc_lead ? p.Lq : BandMap(p).hi(min(q0 + rows, p.Lq) - 1);
+  else if constexpr (TF) return TfMap(p).kend(min(q0 + rows, p.Lq) - 1);
   else if constexpr (FM) return fm_kend(p, min(q0 + rows, p.Lq) - 1);
   else return Lk;
 }
@@ -269,11 +293,17 @@ __device__ __forceinline__ int fm_qend(const AttnP& p, int j) { return FmMap(p).
 // next visit follows it across the gap.
 // TF: the tiles below the workgroup's largest pend, [0, nl), then those from its smallest kbeg to its largest kend,
 // [jb, nkt) -- jb >= nl again, also in the workgroup that straddles base (TfMap).
-template <bool WIN, bool TF = false>  // (the other instances build an empty one)
+// BAND: a workgroup with a lead row visits every tile, [0, nkt); any other the lead tiles, [0, nl), then those from lo of
+// its first row to hi of its last, [jb, nkt).
+template <bool WIN, bool TF = false, bool BAND = false>  // (the other instances build an empty one)
 struct FmWinTiles {
   int nl = 0, jb = 0, nit = 0;
   __device__ __forceinline__ FmWinTiles(const AttnP& p, int q0, int rows, int nkt) {
-    if constexpr (TF) {
+    if constexpr (BAND) {
+      nl = q0 < p.fc_lead ? nkt : min(nkt, (p.fc_lead + 63) >> 6);
+      jb = q0 < p.fc_lead ? nkt : max(nl, BandMap(p).lo(q0) >> 6);
+      nit = nl + nkt - jb;
+    } else if constexpr (TF) {
       const TfMap tf(p);
       const int q1 = min(q0 + rows, p.Lq);
       // the largest pend: that of the last clean (or lead) row if there is one -- base for the straddling workgroup, which
@@ -295,11 +325,23 @@ struct FmWinTiles {
 // kend of its first)
 // TF: wlead is the wave's smallest pend (its first query's) and the run that of a wave of noisy queries only; a wave of
 // clean queries only has no run, and a wave with a lead query or with queries of both halves has nothing open.
-template <bool WIN, bool TF = false>
+// BAND: a wave of token queries only has the WIN test on [lo of its last query, hi of its first); a wave of lead queries only
+// has everything below L open; a wave that holds both has nothing open.
+template <bool WIN, bool TF = false, bool BAND = false>
 struct FmWinOpen {
   int wlead = 0, wkbeg = 0, wkend = 0;
   __device__ __forceinline__ FmWinOpen(const AttnP& p, int wq0, int wrows) {
-    if constexpr (TF) {
+    if constexpr (BAND) {
+      const BandMap bm(p);
+      const int wq1 = min(wq0 + wrows, p.Lq) - 1;  // the wave's last query
+      if (wq1 < bm.lead) {
+        wlead = p.Lq;
+      } else if (wq0 >= bm.lead) {
+        wlead = bm.lead;
+        wkbeg = __builtin_amdgcn_readfirstlane(bm.lo(wq1));
+        wkend = __builtin_amdgcn_readfirstlane(bm.hi(wq0));
+      }
+    } else if constexpr (TF) {
       const TfMap tf(p);
       const int wq1 = min(wq0 + wrows, p.Lq) - 1;  // the wave's last query
       const bool noisy = wq0 >= tf.base, clean = wq0 >= tf.lead && wq1 < tf.base;
@@ -345,11 +387,23 @@ __device__ __forceinline__ int fm_win_qtiles(const AttnP& p, int key0, int nqt) 
 // Query tiles (64 rows) of a TF dK/dV workgroup with key rows [key0, key0 + 128): [a0, a1) from qstart of its first key to
 // qend of its last, then [b0, nqt) from q2 of its first key -- b0 >= a1, no tile twice.  A workgroup with a lead key sweeps
 // every tile; one of noisy keys only has q2 = L: it sweeps the tiles of its own chunks and nothing else.
-template <bool TF>
+// BAND: the lead query tiles, [0, a1), then the tiles from lo of the first key to below hi of the last, [b0, b1) -- a prefix
+// plus a run; a workgroup with a lead key sweeps every tile.
+template <bool TF, bool BAND = false>
 struct TfQTiles {
   int a0 = 0, na = 0, b0 = 0, nit = 0;
   __device__ __forceinline__ TfQTiles(const AttnP& p, int key0, int nqt) {
-    if constexpr (TF) {
+    if constexpr (BAND) {
+      na = nqt;
+      b0 = nqt;
+      nit = nqt;
+      if (key0 >= p.fc_lead) {
+        const BandMap bm(p);
+        na = min(nqt, (bm.lead + 63) >> 6);
+        b0 = max(na, bm.lo(key0) >> 6);
+        nit = na + ((bm.hi(min(key0 + 127, p.Lk - 1)) + 63) >> 6) - b0;
+      }
+    } else if constexpr (TF) {
       const TfMap tf(p);
       int a1 = nqt;
       b0 = nqt;
@@ -371,6 +425,15 @@ __device__ __forceinline__ void fm_zero_q_tf(int row0, int qstart, int qend, int
   for (int r = 0; r < 16; ++r) {
     const int q = row0 + (r & 3) + 8 * (r >> 2);
     if ((q < qstart || q >= qend) && q < q2) { pm[r] = 0.f; ds[r] = 0.f; }
+  }
+}
+// 32x32 accumulators with the QUERY on the registers: P and dS of the queries from pl on that lie outside [qlo, qhi) (BAND:
+// pl = lead for a token key, L for a lead key)
+__device__ __forceinline__ void fm_zero_q_band(int row0, int pl, int qlo, int qhi, f32x16& pm, f32x16& ds) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int q = row0 + (r & 3) + 8 * (r >> 2);
+    if (q >= pl && (q < qlo || q >= qhi)) { pm[r] = 0.f; ds[r] = 0.f; }
   }
 }
 // FM instances of the forward and dQ kernels: the row-tile order of a head is reversed, so that its longest workgroups
@@ -710,11 +773,14 @@ struct DmaStageFm {
 // TF (vds_teacher_attn_fwd; with FM, without WIN): teacher forcing (TfMap).  The WIN code with the lane's pend in place of
 // lead: the key loop visits the tiles below the workgroup's largest pend, then those from its smallest kbeg to its largest
 // kend; a lane keeps key j iff j < pend or kbeg <= j < kend.
+// BAND (vds_band_attn_fwd; with FM, without WIN / TF): the frame band (BandMap), not causal.  The WIN code again: a lane keeps
+// key j iff j < pend or lo <= j < hi, with pend = L for a lead query.  The workgroup that holds a lead row visits every tile.
 template <int HDP, int HDQ, int WPS, bool PIPE, bool KVLEN = false, bool CAUSAL = false, bool PAST = false, bool FM = false,
-          bool WIN = false, bool TF = false>
+          bool WIN = false, bool TF = false, bool BAND = false>
 __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, TILE = 64 * HDP * 2;
-  constexpr bool TWO = WIN || TF;  // two key-tile ranges
+  constexpr bool TWO = WIN || TF || BAND;  // two key-tile ranges
+  static_assert(!BAND || (FM && !WIN && !TF), "the frame band: on frame-major rows, its own mask");
   static_assert(!FM || !(KVLEN || CAUSAL || PAST), "frame-major: its own mask");
   static_assert(!WIN || FM, "the window: on frame-major rows");
   static_assert(!TF || (FM && !WIN), "teacher forcing: on frame-major rows, its own mask");
@@ -726,7 +792,7 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qrow = qt * 128 + wave * 32 + (lane & 31);
-  const int Lk = fm_keys<FM, TF>(p, qt * 128, 128, kv_len_of<KVLEN>(p, b));
+  const int Lk = fm_keys<FM, TF, BAND>(p, qt * 128, 128, kv_len_of<KVLEN>(p, b));
   if constexpr (KVLEN) {
     if (Lk == 0) {  // no context: O = 0, lse = 0
       if (qrow < p.Lq) {
@@ -746,7 +812,7 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   dv.init(p.v_sl, p.hd, wave, lane);
   const unsigned k_step = (unsigned)(64 * p.k_sl * 2), v_step = (unsigned)(64 * p.v_sl * 2);
   const int nkt = (Lk + 63) / 64;
-  [[maybe_unused]] const FmWinTiles<WIN, TF> wt(p, qt * 128, 128, nkt);  // WIN, TF: the two tile ranges of the key loop
+  [[maybe_unused]] const FmWinTiles<WIN, TF, BAND> wt(p, qt * 128, 128, nkt);  // WIN, TF: the two tile ranges of the key loop
   const int nit = TWO ? wt.nit : nkt;                                // visits of the key loop
   if constexpr (TWO) {
     dk.issue(rk, smem, (unsigned)wt.tile(0) * k_step, wave);
@@ -782,7 +848,7 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
   }
   // WIN: the lane's kbeg next to its kend, and the wave's open test
   [[maybe_unused]] int kbeg = 0;
-  [[maybe_unused]] const FmWinOpen<WIN, TF> wo(p, wq0, 32);
+  [[maybe_unused]] const FmWinOpen<WIN, TF, BAND> wo(p, wq0, 32);
   if constexpr (WIN) kbeg = fm_kbeg(p, qrow);
   [[maybe_unused]] int pend = p.fc_lead;  // TF: the lane's prefix end, with its run [kbeg, klim)
   if constexpr (TF) {
@@ -790,6 +856,12 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd_kernel(AttnP p) {
     pend = tf.pend(qrow);
     kbeg = tf.kbeg(qrow);
     klim = tf.kend(qrow);
+  }
+  if constexpr (BAND) {  // the lane's prefix end (L for a lead query) and its run [lo, hi)
+    const BandMap bm(p);
+    pend = bm.pend(qrow);
+    kbeg = bm.lo(qrow);
+    klim = bm.hi(qrow);
   }
 #pragma unroll
   for (int ks = 0; ks < KSQ; ++ks) retire(qf[ks]);
@@ -1213,11 +1285,13 @@ __global__ __launch_bounds__(256) void attn_delta_tokmajor_kernel(AttnP p) {
 // WIN (vds_attn_bwd_causal_fm_window; with FM): the window -- the two tile ranges, the per-lane compare and the open test
 // of the forward kernel, with dS = 0 in place of -inf.
 // TF (vds_teacher_attn_bwd; with FM, without WIN): teacher forcing -- as the forward kernel's, with dS = 0 in place of -inf.
+// BAND (vds_band_attn_bwd; with FM, without WIN / TF): the frame band -- as the forward kernel's, with dS = 0 in place of -inf.
 template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false, bool FM = false, bool WIN = false,
-          bool TF = false>
+          bool TF = false, bool BAND = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, TILE = 64 * HDP * 2;
-  constexpr bool TWO = WIN || TF;  // two key-tile ranges
+  constexpr bool TWO = WIN || TF || BAND;  // two key-tile ranges
+  static_assert(!BAND || (FM && !WIN && !TF), "the frame band: on frame-major rows, its own mask");
   static_assert(!WIN || FM, "the window: on frame-major rows");
   static_assert(!TF || (FM && !WIN), "teacher forcing: on frame-major rows, its own mask");
   static_assert(!ONES || (HDP == 96 && HDQ == 80), "ones columns: head_dim 72 layout");
@@ -1231,7 +1305,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qrow = qt * 128 + wave * 32 + (lane & 31);
   const int hd_kv = ONES ? p.hd + 8 : p.hd;
-  const int Lk = fm_keys<FM, TF>(p, qt * 128, 128, kv_len_of<KVLEN>(p, b));
+  const int Lk = fm_keys<FM, TF, BAND>(p, qt * 128, 128, kv_len_of<KVLEN>(p, b));
   if constexpr (KVLEN) {
     if (Lk == 0) {  // no context: dQ = 0
       if (qrow < p.Lq) store_zero_rows<NDB>(p.dq + b * p.dq_sb + hh * p.dq_sh + (long)qrow * p.dq_sl, p.hd, h);
@@ -1249,7 +1323,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   dv.init(p.v_sl, hd_kv, wave, lane);
   const unsigned k_step = (unsigned)(64 * p.k_sl * 2), v_step = (unsigned)(64 * p.v_sl * 2);
   const int nkt = (Lk + 63) / 64;
-  [[maybe_unused]] const FmWinTiles<WIN, TF> wt(p, qt * 128, 128, nkt);  // WIN, TF: as in the forward kernel
+  [[maybe_unused]] const FmWinTiles<WIN, TF, BAND> wt(p, qt * 128, 128, nkt);  // WIN, TF: as in the forward kernel
   const int nit = TWO ? wt.nit : nkt;
   if constexpr (TWO) {
     dk.issue(rk, smem, (unsigned)wt.tile(0) * k_step, wave);
@@ -1306,7 +1380,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
     wklim = wq0 >= p.fc_lead ? __builtin_amdgcn_readfirstlane(fm_kend(p, wq0)) : 0;
   }
   [[maybe_unused]] int kbeg = 0;  // WIN: as in the forward kernel
-  [[maybe_unused]] const FmWinOpen<WIN, TF> wo(p, qt * 128 + wave * 32, 32);
+  [[maybe_unused]] const FmWinOpen<WIN, TF, BAND> wo(p, qt * 128 + wave * 32, 32);
   if constexpr (WIN) kbeg = fm_kbeg(p, qrow);
   [[maybe_unused]] int pend = p.fc_lead;  // TF: as in the forward kernel
   if constexpr (TF) {
@@ -1314,6 +1388,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
     pend = tf.pend(qrow);
     kbeg = tf.kbeg(qrow);
     klim = tf.kend(qrow);
+  }
+  if constexpr (BAND) {  // the lane's prefix end (L for a lead query) and its run [lo, hi)
+    const BandMap bm(p);
+    pend = bm.pend(qrow);
+    kbeg = bm.lo(qrow);
+    klim = bm.hi(qrow);
   }
   VDS_WAIT_VM(0);
   __syncthreads();  // tile 0 landed
@@ -1400,12 +1480,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
 // TF (vds_teacher_attn_bwd; with FM, without WIN): teacher forcing -- key j is attended by [qstart(j), qend(j)) and by
 // [q2(j), L) (TfMap).  The sweep visits the query tiles of TfQTiles, counted as visits like the key loop of the forward
 // kernel; a sub-block is open between the wave's largest qstart and its smallest qend, or from its largest q2.
+// BAND (vds_band_attn_bwd; with FM, without WIN / TF): the frame band -- token key j is attended by [0, lead) and by
+// [lo(j), hi(j)), a lead key by every query (BandMap).  The sweep visits the query tiles of TfQTiles<.., BAND>; a sub-block
+// is open in a wave of lead keys, or, in a wave of token keys, below lead or inside [lo of its last key, hi of its first).
 template <int HDP, int HDQ, bool ONES, bool KVLEN = false, bool CAUSAL = false, bool FM = false, bool WIN = false,
-          bool TF = false>
+          bool TF = false, bool BAND = false>
 // (head dim 64: three waves per SIMD cap the kernel at 168 VGPRs, which the TF instance's third bound and second tile range
-// do not fit without scratch -- it runs at two)
-__global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 && !TF ? 3 : 2))) void attn_bwd_dkv_kernel(AttnP p) {
+// do not fit without scratch -- it runs at two, and so does the BAND instance, which carries the same three bounds)
+__global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 && !TF && !BAND ? 3 : 2))) void attn_bwd_dkv_kernel(AttnP p) {
   constexpr int KSQ = HDQ / 16, NDB = HDP / 32, Q_TILE = 64 * HDP * 2;
+  constexpr bool TWO = TF || BAND;  // two query-tile ranges, counted as visits
+  static_assert(!BAND || (FM && !WIN && !TF), "the frame band: on frame-major rows, its own mask");
   static_assert(!WIN || FM, "the window: on frame-major rows");
   static_assert(!TF || (FM && !WIN), "teacher forcing: on frame-major rows, its own mask");
   static_assert(!FM || !(ONES || KVLEN || CAUSAL), "frame-major: the plain layout, its own mask");
@@ -1471,11 +1556,11 @@ __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 && !TF ? 3 : 2))) v
   };
   // this workgroup's query tiles [j0, j1) (all of them unless the query range is split)
   const int nqt_all = (p.Lq + 63) / 64, jper = (nqt_all + p.q_split - 1) / (p.q_split > 0 ? p.q_split : 1);
-  [[maybe_unused]] const TfQTiles<TF> tt(p, key0, nqt_all);  // TF: the two tile ranges; j0 .. j1 then count visits
-  const int j0 = TF ? 0 : fm_first_qtile<FM>(p, key0, sp * jper);
-  int j1 = TF ? tt.nit : min(nqt_all, j0 + jper);
+  [[maybe_unused]] const TfQTiles<TF, BAND> tt(p, key0, nqt_all);  // TF, BAND: the two tile ranges; j0 .. j1 then count visits
+  const int j0 = TWO ? 0 : fm_first_qtile<FM>(p, key0, sp * jper);
+  int j1 = TWO ? tt.nit : min(nqt_all, j0 + jper);
   if constexpr (WIN) j1 = fm_win_qtiles(p, key0, nqt_all);  // the sweep ends below qend of the last key (a lead key: all tiles)
-  if constexpr (TF) issue_tile(tt.tile(0), 0);
+  if constexpr (TWO) issue_tile(tt.tile(0), 0);
   else issue_tile(j0, 0);
   // FM: the lane's qstart, and the wave's largest (its last key's, the sequence's last row at most)
   [[maybe_unused]] int qlim = 0, wqlim = 0;
@@ -1501,6 +1586,22 @@ __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 && !TF ? 3 : 2))) v
     wqlim = __builtin_amdgcn_readfirstlane(tf.qstart(wk1));
     wqhi = __builtin_amdgcn_readfirstlane(tf.qend(fm_win_first_token_key(p, wk0)));
     wq2 = wk0 >= tf.lead ? __builtin_amdgcn_readfirstlane(tf.q2(wk1)) : p.Lq;
+  }
+  // BAND: the lane's run [qlim, qhi) and the row its compare starts at (q2: lead, or L for a lead key); the wave's open
+  // prefix (wq2: every row for lead keys only, lead for token keys only, nothing for both) and run [wqlim, wqhi)
+  if constexpr (BAND) {
+    const BandMap bm(p);
+    const int wk0 = key0 + wave * 32, wk1 = min(wk0 + 31, p.Lk - 1);
+    qlim = bm.lo(krow);
+    qhi = bm.hi(krow);
+    q2 = bm.pend(krow);
+    if (wk1 < bm.lead) {
+      wq2 = 0x3fffffff;
+    } else if (wk0 >= bm.lead) {
+      wq2 = bm.lead;
+      wqlim = __builtin_amdgcn_readfirstlane(bm.lo(wk1));
+      wqhi = __builtin_amdgcn_readfirstlane(bm.hi(wk0));
+    }
   }
 
   // this lane's key row as B-operand fragments (rows past Lk / columns past hd read as zero)
@@ -1534,7 +1635,7 @@ __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 && !TF ? 3 : 2))) v
   auto q_tile = [&](int it, auto PAR) {  // unrolled by two: compile-time LDS buffer parity (see the forward kernel)
     constexpr int par = decltype(PAR)::value;
     int j = it, jn = it + 1;  // this visit's query tile and the next one's (TF: across the gap between the two ranges)
-    if constexpr (TF) { j = tt.tile(it); jn = tt.tile(it + 1); }
+    if constexpr (TWO) { j = tt.tile(it); jn = tt.tile(it + 1); }
     if (it + 1 < j1) issue_tile(jn, par ^ 1);
     const char* qt = qbuf + par * 2 * Q_TILE;
     const char* dot = qt + Q_TILE;
@@ -1584,7 +1685,10 @@ __global__ __launch_bounds__(256, (HDP > 96 ? 1 : (HDP == 64 && !TF ? 3 : 2))) v
         const FcMap fm(p);
         fc_zero_q(fm, j * 64 + qb * 32 + 4 * h, fm.fk(krow), pm, s);
       }
-      if constexpr (TF) {  // open: inside every key's first range, or at or past the wave's largest q2
+      if constexpr (BAND) {  // open: wholly below the wave's open prefix, or wholly inside the run every key of it shares
+        const int s0 = j * 64 + qb * 32;
+        if (s0 + 32 > wq2 && (s0 < wqlim || s0 + 32 > wqhi)) fm_zero_q_band(s0 + 4 * h, q2, qlim, qhi, pm, s);
+      } else if constexpr (TF) {  // open: inside every key's first range, or at or past the wave's largest q2
         const int s0 = j * 64 + qb * 32;
         if ((s0 < wqlim || s0 + 32 > wqhi) && s0 < wq2) fm_zero_q_tf(s0 + 4 * h, qlim, qhi, q2, pm, s);
       } else if constexpr (WIN) {  // open: at or past the wave's largest qstart and wholly below its smallest qend
@@ -2567,23 +2671,26 @@ int attn_variant() { return vdscfg::geti(vdscfg::ATTN_MFMA16) & 7; }
 //   FM     (vds_attn_*_causal_fm, _fm_chunk): the frame-major instances; a chunk is the granularity p.fm_G, no kernel of its own.
 //   FM_WIN (vds_attn_*_causal_fm_window): the WIN instances of the FM kernels (p.fc_past = W chunks).
 //   FM_TF  (vds_teacher_attn_*): the TF instances of the plain FM kernels (the period is 2n: clean frames, noisy copies).
-enum class Mask { NONE, KVLEN, CAUSAL, PAST, FM, FM_WIN, FM_TF };
+//   FM_BAND (vds_band_attn_*): the BAND instances of the plain FM kernels (p.fc_past = b chunks on each side; not causal).
+enum class Mask { NONE, KVLEN, CAUSAL, PAST, FM, FM_WIN, FM_TF, FM_BAND };
 struct MaskFlags {
-  bool kvlen, causal, past, fm, win, tf;
+  bool kvlen, causal, past, fm, win, tf, band;
 };
 constexpr MaskFlags flags_of(Mask m) {
   return {m == Mask::KVLEN, m == Mask::CAUSAL || m == Mask::PAST, m == Mask::PAST,
-          m == Mask::FM || m == Mask::FM_WIN || m == Mask::FM_TF, m == Mask::FM_WIN, m == Mask::FM_TF};
+          m == Mask::FM || m == Mask::FM_WIN || m == Mask::FM_TF || m == Mask::FM_BAND, m == Mask::FM_WIN, m == Mask::FM_TF,
+          m == Mask::FM_BAND};
 }
 template <Mask M>
 constexpr MaskFlags FLAGS = flags_of(M);
 
 struct MaskV {
   const int32_t* kv_lens = nullptr;        // KVLEN: B int32 on the device
-  const vds_mod_groups* frames = nullptr;  // CAUSAL, PAST, FM, FM_WIN, FM_TF
+  const vds_mod_groups* frames = nullptr;  // CAUSAL, PAST, FM, FM_WIN, FM_TF, FM_BAND
   int past = 0;                            // PAST: cached key rows behind the lead rows
-  int chunk = 1;                           // FM, FM_WIN, FM_TF: token-frames per causal chunk
+  int chunk = 1;                           // FM, FM_WIN, FM_TF, FM_BAND: token-frames per chunk
   int window_chunks = 0;                   // FM_WIN
+  int band_chunks = 0;                     // FM_BAND: chunks on each side of a token's own
 };
 
 // The refusals of one call, in this order: NULL pointers and non-positive lengths, strides, the mask's own conditions
@@ -2601,6 +2708,7 @@ int validate(const vds_attn_args* a, Mask kind, const MaskV& m, bool bwd) {
     if (!fr || (int64_t)a->Lk != (int64_t)a->Lq + m.past || a->kv_pad_ones == 2) return VDS_ERR_ARG;
     if (fr->lead < 0 || fr->period < 1 || a->Lq < fr->lead || (a->Lq - fr->lead) % fr->period != 0) return VDS_ERR_ARG;
     if (f.tf && (fr->period & 1)) return VDS_ERR_ARG;  // clean frames and their noisy copies: an even period
+    if (f.band && (m.chunk < 1 || m.band_chunks < 0)) return VDS_ERR_ARG;
     if (a->Lk > (1 << 21)) return VDS_ERR_UNSUPPORTED;  // FcMap / FmMap: the fp32 quotient is exact below 2^21 rows
   }
   if (f.fm) {
@@ -2631,6 +2739,12 @@ void apply_mask(AttnP& p, Mask kind, const MaskV& m) {
     p.fm_rev = vdscfg::geti(vdscfg::ATTN_FM_HEAVY_FIRST) ? 1 : 0;
   }
   if (f.win) p.fc_past = m.window_chunks;  // (< the chunk count <= period: W * G stays below L)
+  if (f.band) {
+    // b at most the chunk count (every larger band attends the same pairs): b * G <= L - lead + G stays below 2^22
+    const int nch = (p.fc_period + m.chunk - 1) / m.chunk;
+    p.fc_past = m.band_chunks < nch ? m.band_chunks : nch;
+    p.fm_rev = 0;  // the first workgroup of a head is its heaviest (the lead rows sweep everything): plain tile order
+  }
 }
 
 // The one place that maps a head dim to its instance <HDP, HDQ>: f(HDP, HDQ) with both as std::integral_constant.
@@ -2912,11 +3026,46 @@ double fm_pairs_k_tf(const TfHost& t, int tile) {
   return n;
 }
 
+// Frame band (BandMap): the bounds on the host, for the pair counts of the tiles the BAND kernels visit.  b: chunks a side.
+struct BandHost {
+  int L, lead, G, b;
+  long cg(int r) const { return (long)((r - lead) / G) * G; }
+  int lo(int r) const { const long o = cg(r) - (long)b * G; return lead + (int)(o > 0 ? o : 0); }
+  int hi(int r) const { const long e = lead + cg(r) + ((long)b + 1) * G; return e < L ? (int)e : L; }
+};
+// pairs of the 64-row tiles a BAND workgroup of `tile` rows visits -- the same count for the key tiles of the forward / dQ
+// kernels and the query tiles of the dK/dV kernel (the relation is symmetric and so are the two walks): every tile for the
+// workgroup that holds a lead row, else the lead tiles and those from lo of its first row to below hi of its last
+double fm_pairs_band(const BandHost& t, int tile) {
+  double n = 0;
+  auto rows = [&](int j0, int j1) { return (j1 * 64 < t.L ? j1 * 64 : t.L) - (j0 * 64 < t.L ? j0 * 64 : t.L); };
+  for (int r0 = 0; r0 < t.L; r0 += tile) {
+    const int r1 = r0 + tile < t.L ? r0 + tile : t.L;
+    if (r0 < t.lead) {
+      n += (double)(r1 - r0) * t.L;
+      continue;
+    }
+    const int e = (t.hi(r1 - 1) + 63) >> 6;
+    const int nl = (t.lead + 63) >> 6 < e ? (t.lead + 63) >> 6 : e;
+    const int jb = nl > (t.lo(r0) >> 6) ? nl : t.lo(r0) >> 6;
+    n += (double)(r1 - r0) * (rows(0, nl) + rows(jb, e));
+  }
+  return n;
+}
+
 template <int HDP, int HDQ, Mask M>
 int run_fwd_fm(AttnP p, hipStream_t s) {
   constexpr bool WIN = FLAGS<M>.win;
   constexpr int LDS = 4 * 64 * HDP * 2;
   const int W = WIN ? p.fc_past : 0;
+  if constexpr (FLAGS<M>.band) {  // the plain 32x32x16 BAND kernel, whatever the layout and the variant bits
+    const unsigned grid = tile_grid(p, p.Lq, 128);
+    const BandHost t{p.Lq, p.fc_lead, p.fm_G, p.fc_past};
+    vdsprof::Scope ps(VDS_PROF_ATTN_FWD_PLAIN, s, 4.0 * p.B * p.H * p.hd * fm_pairs_band(t, 128),
+                      2.0 * p.B * p.H * p.hd * (2.0 * p.Lq + 2.0 * p.Lk));
+    launch<attn_fwd_kernel<HDP, HDQ, 2, true, false, false, false, true, false, false, true>, LDS>(grid, s, p);
+    return launched();
+  }
   if constexpr (FLAGS<M>.tf) {  // the plain 32x32x16 TF kernel, whatever the layout (no TF instance of the 16x16x32 family)
     const unsigned grid = tile_grid(p, p.Lq, 128);
     const TfHost t{p.Lq, p.fc_lead, p.fc_lead + (p.fc_period / 2) * p.fm_S, p.fm_G};
@@ -2954,6 +3103,20 @@ int run_bwd_fm(AttnP p, hipStream_t s) {
   const int W = WIN ? p.fc_past : 0;
   const double per = 2.0 * p.B * p.H * p.hd;  // FLOPs of one product per (query, key) pair
   const double qb = 2.0 * p.B * p.H * p.hd * (double)p.Lq, kb = qb;
+  if constexpr (FLAGS<M>.band) {  // the plain 32x32x16 BAND kernels: preprocess, dK/dV, dQ
+    const BandHost t{p.Lq, p.fc_lead, p.fm_G, p.fc_past};
+    const double pairs = fm_pairs_band(t, 128);
+    launch_delta<true>(p, s);
+    {
+      const unsigned grid = tile_grid(p, p.Lk, 128);
+      vdsprof::Scope ps(VDS_PROF_ATTN_BWD_DKV_PLAIN, s, 2.0 * per * pairs, 2.0 * qb + 4.0 * kb);
+      launch<attn_bwd_dkv_kernel<HDP, HDQ, false, false, false, true, false, false, true>, LDS_DKV>(grid, s, p);
+    }
+    const unsigned grid = tile_grid(p, p.Lq, 128);
+    vdsprof::Scope ps(VDS_PROF_ATTN_BWD_DQ_PLAIN, s, 2.0 * per * pairs, 3.0 * qb + 2.0 * kb);
+    launch<attn_bwd_dq_kernel<HDP, HDQ, false, false, false, true, false, false, true>, LDS_DQ>(grid, s, p);
+    return launched();
+  }
   if constexpr (FLAGS<M>.tf) {  // the plain 32x32x16 TF kernels: preprocess, dK/dV, dQ
     const TfHost t{p.Lq, p.fc_lead, p.fc_lead + (p.fc_period / 2) * p.fm_S, p.fm_G};
     launch_delta<true>(p, s);
@@ -3172,4 +3335,17 @@ extern "C" int vds_teacher_attn_bwd(const vds_attn_args* a, const vds_mod_groups
                                     vds_stream_t stream) {
   if (!frames || chunk < 1) return VDS_ERR_ARG;
   return attn_call<Mask::FM_TF, true>(a, {nullptr, frames, 0, chunk}, stream);
+}
+
+// frame band (not causal): a token row of chunk n attends the lead rows and the token rows of chunks n - band_chunks ..
+// n + band_chunks, a lead row every row (BandMap).  Self-attention on frame-major rows only; the refusals are validate's.
+// A band that covers every pair runs the same instances: there is no frame-major unmasked entry to forward to.
+extern "C" int vds_band_attn_fwd(const vds_attn_args* a, const vds_mod_groups* frames, int32_t chunk, int32_t band_chunks,
+                                 vds_stream_t stream) {
+  return attn_call<Mask::FM_BAND, false>(a, {nullptr, frames, 0, chunk, 0, band_chunks}, stream);
+}
+
+extern "C" int vds_band_attn_bwd(const vds_attn_args* a, const vds_mod_groups* frames, int32_t chunk, int32_t band_chunks,
+                                 vds_stream_t stream) {
+  return attn_call<Mask::FM_BAND, true>(a, {nullptr, frames, 0, chunk, 0, band_chunks}, stream);
 }

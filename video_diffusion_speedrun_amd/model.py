@@ -381,6 +381,11 @@ def check_frame_window(who: str, frame_window, frame_chunk: int, frame_causal: b
     return frame_window
 
 
+_FP8_FRAME_BAND = ("the frame band is not implemented for the fp8 attention kernels (they have no masked instance): call "
+                   "enable_fp8(attention=False) to keep the attention products on the bf16 kernels, or "
+                   "enable_frame_band(None) to run without the band")
+_BAND_NO_CACHE = ("a frame-band model has no K / V cache (its mask is two-sided: the K / V rows of finished frames are read "
+                  "by, and change with, the frames after them)")
 _FP8_FRAME_CAUSAL = ("frame_causal is not implemented for the fp8 attention kernels (they have no masked instance): "
                      "call enable_fp8(attention=False) to keep the attention products on the bf16 kernels")
 
@@ -449,6 +454,17 @@ class DiTBlock(nn.Module):
         self.adaLN_modulation[-1].bias.data.zero_()
 
     lora_scale: Optional[float] = None  # s = alpha / rank of the adapters DiT.add_lora put on this block's linears
+    # frame band (DiT.enable_frame_band; not with frame_causal): None, or (chunk, band_chunks) -- a token of
+    # chunk n attends the registers and the token-frames of chunks n - band_chunks .. n + band_chunks, the registers attend
+    # everything: the BAND instances of the frame-major kernels (ops.band_attn_fwd / band_attn_bwd).  The block then takes
+    # frames=(lead, period) and keeps its head-major tensors in frame-major rows exactly as a frame_major block does.
+    # No parameter.
+    frame_band: Optional[Tuple[int, int]] = None
+
+    @property
+    def _fm_rows(self) -> bool:
+        """q, k, v, lse, dq, dk, dv, v_0 and its gradient in frame-major rows: a frame_major block or a band block"""
+        return self.frame_major or self.frame_band is not None
 
     # ---- stand-alone call (reference signature, model.py:96-167) ---------------------------------------
     _own_group: Optional[FlatGroup] = None
@@ -482,6 +498,11 @@ class DiTBlock(nn.Module):
         return kw
 
     def _check_frames(self, frames, L):
+        if self.frame_band is not None:
+            if frames is None or isinstance(frames, TeacherFrames):
+                raise ValueError("DiTBlock: a frame-band block needs frames=(lead, period), the row groups of its sequence "
+                                 "(lead register rows, then `period` token-frames); enable_frame_band(None) runs without")
+            return ops.check_mod_groups(frames, L)
         if not self.frame_causal:
             if frames is not None:
                 raise ValueError("DiTBlock: frames given to a block built without frame_causal=True")
@@ -546,7 +567,7 @@ class DiTBlock(nn.Module):
         if self.qk_norm and use_fp8 and fp8[2]:
             raise NotImplementedError(_FP8_QK_NORM)
         if frames is not None and use_fp8 and fp8[2]:
-            raise NotImplementedError(_FP8_FRAME_CAUSAL)
+            raise NotImplementedError(_FP8_FRAME_BAND if self.frame_band is not None else _FP8_FRAME_CAUSAL)
         if groups is not None and use_fp8:
             raise NotImplementedError(_FP8_FRAME_TIMESTEPS)
         if use_fp8 and (keep is not None or replay is not None):
@@ -636,10 +657,14 @@ class DiTBlock(nn.Module):
                 k, v = kb, vb
             else:
                 rope_fwd = ops.qkv_rope_norm_fwd if self.qk_norm else ops.qkv_rope_fwd
-                fm_kw = dict(frames=frames) if self.frame_major else {}  # q, k, v (and the v0 read) in frame-major rows
+                fm_kw = dict(frames=frames) if self._fm_rows else {}  # q, k, v (and the v0 read) in frame-major rows
                 q, k, v = rope_fwd(qkv, cos, sin, v0 if mix else None, W("lambda_param") if mix else None, B, L, H, hd, hdp,
                                    **fm_kw)
-            if cache is None and not kept_attn:
+            if cache is None and not kept_attn and self.frame_band is not None:
+                ops.band_attn_fwd(q[..., :hd], k[..., :hd], v[..., :hd], ops.heads_view(attn, B, L, H, hd), lse1,
+                                  kv_pad_ones=(hdp - hd) >= 8, frames=frames, frame_major=True, chunk=self.frame_band[0],
+                                  band=self.frame_band[1])
+            elif cache is None and not kept_attn:
                 ops.attn_fwd(q[..., :hd], k[..., :hd], v[..., :hd], ops.heads_view(attn, B, L, H, hd), lse1,
                              kv_pad_ones=(hdp - hd) >= 8, frames=frames, frame_major=self.frame_major,
                              **self._mask_kw(frames))
@@ -972,10 +997,16 @@ class DiTBlock(nn.Module):
             ops.attn_fp8_bwd(bs.q8, bs.k8, bs.v8, sv.doq, stats, bs.deq, dq[..., :hd], dk[..., :hd], dv[..., :hd], hd)
         else:
             delta = torch.empty(2, B, H, L, dtype=f32, device=dev)
-            ops.attn_bwd(bs.q[..., :hd], bs.k[..., :hd], bs.v[..., :hd], ops.heads_view(bs.attn, B, L, H, hd), bs.lse1,
-                         ops.heads_view(dattn, B, L, H, hd), dq[..., :hd], dk[..., :hd], dv[..., :hd], delta,
-                         kv_pad_ones=(hdp - hd) >= 8, frames=bs.frames, frame_major=self.frame_major,
-                         **self._mask_kw(bs.frames))
+            if self.frame_band is not None:
+                ops.band_attn_bwd(bs.q[..., :hd], bs.k[..., :hd], bs.v[..., :hd], ops.heads_view(bs.attn, B, L, H, hd),
+                                  bs.lse1, ops.heads_view(dattn, B, L, H, hd), dq[..., :hd], dk[..., :hd], dv[..., :hd],
+                                  delta, kv_pad_ones=(hdp - hd) >= 8, frames=bs.frames, frame_major=True,
+                                  chunk=self.frame_band[0], band=self.frame_band[1])
+            else:
+                ops.attn_bwd(bs.q[..., :hd], bs.k[..., :hd], bs.v[..., :hd], ops.heads_view(bs.attn, B, L, H, hd), bs.lse1,
+                             ops.heads_view(dattn, B, L, H, hd), dq[..., :hd], dk[..., :hd], dv[..., :hd], delta,
+                             kv_pad_ones=(hdp - hd) >= 8, frames=bs.frames, frame_major=self.frame_major,
+                             **self._mask_kw(bs.frames))
             if bs.a8_on:
                 ops.absmax(dattn, fp8_hist.cur(F8.ROWS * i + F8.ROW_DO))
         defer = getattr(sv, "dv_terms", None)  # DiT.backward: [(dv, lambda)] of the mixed blocks, summed at block 0
@@ -1005,12 +1036,12 @@ class DiTBlock(nn.Module):
         # (QK-norm: the normed backward has no fp8-emitting form -- the quantisation pass below takes its bf16 result)
         # (frame-major: likewise -- the fp8-emitting backward has no frame-major form)
         emit_dqkv = (pemit and not G.has(pre + "qkv.bias") and hdp % 8 == 0 and D <= 2048 and not self.qk_norm
-                     and not self.frame_major)
+                     and not self._fm_rows)
         if emit_dqkv:
             fq, fs = ops.qkv_rope_bwd_fp8(*rope_args, F8.E5M2, hist.prev(F8.ROWS * i + 5), hist.part(F8.ROWS * i + 5, B * L))
             q_dqkv = F8.Q.from_rowmajor(fq, fs, True)
         else:
-            fm_kw = dict(frames=bs.frames) if self.frame_major else {}  # dq, dk, dv, v0, dv0 in frame-major rows
+            fm_kw = dict(frames=bs.frames) if self._fm_rows else {}  # dq, dk, dv, v0, dv0 in frame-major rows
             dqkv = (ops.qkv_rope_norm_bwd if self.qk_norm else ops.qkv_rope_bwd)(*rope_args, **fm_kw)
         if T("qkv.bias"):
             ops.colsum(dqkv, Gr("qkv.bias"))
@@ -1244,6 +1275,7 @@ class DiT(nn.Module):
         self.fp8_lin = False   # ... and the four remaining linears of a block
         self.recompute = "none"  # enable_recompute(): what the forward keeps for the backward ("none" | "full" | "selective")
         self.lora = None  # add_lora(): {"rank", "alpha", "targets"} of the low-rank adapters on the blocks' q/k/v linears
+        self.frame_band = None  # enable_frame_band(): (chunk, band_chunks) of the blocks' two-sided frame band, or None
         self._lora_frozen: List[str] = []  # names add_lora(freeze_base=True) froze (merge_lora un-freezes exactly these)
 
     def enable_fp8(self, on: bool = True, attention: bool = True, all_linears: bool = True,
@@ -1265,10 +1297,50 @@ class DiT(nn.Module):
             raise NotImplementedError(_FP8_QK_NORM)
         if on and attention and self.frame_causal:
             raise NotImplementedError(_FP8_FRAME_CAUSAL)
+        if on and attention and self.frame_band is not None:
+            raise NotImplementedError(_FP8_FRAME_BAND)
         self.fp8 = bool(on)
         self.fp8_attn = (2 if cross_attention else 1) if (on and attention) else 0  # 0 none, 1 self, 2 self + cross
         self.fp8_lin = bool(on and all_linears)  # attn_proj, q_cross, context_kv, cross_proj too (qkv / MLP always)
         self._fp8_hist = None  # fp8.AmaxHistory: 6 rows per block (gelu(fc1), d fc2-in, xn1, xn3, d mlp-out, d qkv)
+        return self
+
+    def enable_frame_band(self, band, chunk: int = 1):
+        """Frame-band self-attention for the bidirectional model: a token of chunk n -- chunks of `chunk`
+        token-frames, the last one short when the video's frame count is no multiple -- attends the register tokens and
+        the token-frames of chunks n - band // chunk .. n + band // chunk; the register tokens attend, and are attended
+        by, every token.  `band` counts token-frames on EACH side of the token's own chunk: an int >= 0 and a multiple
+        of `chunk` (0: own chunk plus registers); None switches the band off, and the model launches exactly the kernels
+        it launched before.  The mask is symmetric, not causal: there is no cache for it.
+        Every block then runs the frame-major qkv / RoPE kernels and the BAND attention kernels (ops.band_attn_fwd /
+        band_attn_bwd), which skip the key tiles outside a workgroup's band, in forward, backward and recompute replay; its
+        head-major tensors and residual-V's v_0 live in frame-major rows as on a frame_major=True model.  No parameter, no
+        checkpoint key, the same activation_bytes.  Works with residual_v, qk_norm, context_lens, per-frame timesteps,
+        enable_recompute, GraphedTrainStep, train.forward's frame modes (not "teacher"), generate_latents without
+        kv_cache, and LoRA.  Not on a frame_causal model (its masks are causal: frame_window is the bounded one there) and
+        not with fp8 attention (enable_fp8(attention=False) keeps the linears in fp8).  Returns self."""
+        if band is None:
+            self.frame_band = None
+            for blk in self.blocks:
+                blk.frame_band = None
+            return self
+        if self.frame_causal:
+            raise ValueError("enable_frame_band: the frame band is the two-sided mask of the bidirectional model; this model "
+                             "was built with frame_causal=True -- bound its causal attention with frame_window= (with "
+                             "frame_major=True) instead, or build the model without frame_causal")
+        if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+            raise ValueError(f"enable_frame_band: chunk = {chunk!r} must be an int >= 1 (token-frames per chunk)")
+        if isinstance(band, bool) or not isinstance(band, int) or band < 0:
+            raise ValueError(f"enable_frame_band: band = {band!r} must be an int >= 0 (token-frames attended on each side of "
+                             "a token's own chunk; 0: own chunk plus registers) or None (no band)")
+        if band % chunk != 0:
+            raise ValueError(f"enable_frame_band: band={band} must be a multiple of chunk={chunk} -- the band is a whole "
+                             f"number of chunks on each side; pass band={-(-band // chunk) * chunk}")
+        if self.fp8 and self.fp8_attn:
+            raise NotImplementedError(_FP8_FRAME_BAND)
+        self.frame_band = (chunk, band // chunk)
+        for blk in self.blocks:
+            blk.frame_band = self.frame_band
         return self
 
     def enable_recompute(self, mode: str = "selective"):
@@ -1547,6 +1619,10 @@ class DiT(nn.Module):
     def _forward_teacher(self, x, context, timesteps, rope_start, context_lens, register_timesteps, frame_cache,
                          teacher_latents):
         # every refusal before the device is touched
+        if self.frame_band is not None:
+            raise ValueError("DiT: teacher_latents is the training form of the cached causal rollout; a frame-band model is "
+                             "bidirectional and has neither -- drop teacher_latents (train it with frame_mode=None, "
+                             "'first_frame' or 'independent'), or call enable_frame_band(None)")
         if not (self.frame_causal and self.frame_major):
             raise ValueError("DiT: teacher_latents needs the teacher-forcing mask of the frame-major frame-causal "
                              "self-attention -- build the model with frame_causal=True, frame_major=True")
@@ -1639,6 +1715,9 @@ class DiT(nn.Module):
         slots of one chunk of c = frame_chunk token-frames), whatever `frames` is -- `frames` stays the whole video's length
         (the RoPE table depends on it) and may exceed anything seen in training.  A video longer than the ring (frames >
         W*c) must consist of whole chunks: a short last chunk would leave stale rows of chunk n - W in its slot."""
+        if self.frame_band is not None:
+            raise ValueError("DiT.new_frame_cache: " + _BAND_NO_CACHE + " -- run it on whole videos "
+                             "(generate_latents(kv_cache=False))")
         if not self.frame_causal:
             raise ValueError("DiT.new_frame_cache: a frame KV cache needs a model built with frame_causal=True (on any other "
                              "model the K / V rows of finished frames change with the frames after them)")
@@ -1662,6 +1741,9 @@ class DiT(nn.Module):
     def _check_frame_cache(self, cache, b, thw, per_frame, rope_start):
         """the conditions of a cached chunk call, each with its remedy (all before the device is touched)"""
         k, h, w = thw
+        if self.frame_band is not None:
+            raise ValueError("DiT: frame_cache: " + _BAND_NO_CACHE + " -- pass frame_cache=None "
+                             "(generate_latents(kv_cache=False))")
         if not isinstance(cache, FrameKVCache):
             raise ValueError("DiT: frame_cache must be a FrameKVCache -- make one with DiT.new_frame_cache(batch, frames, "
                              "h_tokens, w_tokens)")
@@ -1778,7 +1860,8 @@ class DiT(nn.Module):
         # per-frame timesteps [B, t]: the conditioning path runs on B*G rows, G = 1 + t modulation groups per sample --
         # group 0 (the register rows) on the sample's noisiest frame, group 1 + f (the rows of token-frame f: the token
         # order is (h w t), t fastest) on timesteps[b, f] -- and every modulated kernel looks its row up per group
-        frames = (N_REG, t) if self.frame_causal else None  # [B] and [B, t] timesteps alike
+        # [B] and [B, t] timesteps alike; a frame-band model (enable_frame_band) derives it from the latent shape too
+        frames = (N_REG, t) if (self.frame_causal or self.frame_band is not None) else None
         if teacher:
             frames = TeacherFrames(frames)  # (the blocks' self-attention: the teacher mask over t/2 clean + t/2 noisy frames)
         groups = None

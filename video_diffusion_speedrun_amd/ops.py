@@ -324,6 +324,34 @@ def _teacher(teacher, frame_major, frames, kv_lens, past, window, Lq) -> bool:
     return True
 
 
+def _band(band, frame_major, frames, kv_lens, past, window, teacher, chunk) -> int:
+    """band (chunks on each side of a token's own chunk; the frame band of the bidirectional model) needs frame_major=True
+    and frames=(lead, period), and excludes window, teacher, past and kv_lens: refused here, before anything is launched"""
+    if isinstance(band, bool) or not isinstance(band, int):
+        raise ValueError(f"attention: band = {band!r} must be an int >= 0 (chunks attended on each side of a token's own "
+                         "chunk) or None; pass band=None for the call without a band")
+    if band < 0:
+        raise ValueError(f"attention: band = {band} must be >= 0 -- 0 is 'own chunk plus the lead rows'; pass band=None for "
+                         "the call without a band")
+    if not frame_major or frames is None:
+        raise ValueError(f"attention: band = {band} needs frame_major=True and frames=(lead, period) -- the frame band exists "
+                         "on the frame-major kernels only; pass frame_major=True with frame-major q / k / v rows")
+    if window is not None:
+        raise ValueError(f"attention: band = {band} excludes window = {window} -- the window is the causal mask's, the band "
+                         "is two-sided; pass window=None (or band=None for the sliding-window call)")
+    if teacher:
+        raise ValueError(f"attention: band = {band} excludes teacher=True -- teacher forcing is a causal mask; pass "
+                         "teacher=False (or band=None)")
+    if past:
+        raise ValueError(f"attention: band = {band} excludes past = {past} -- the band call is the full-sequence "
+                         "self-attention and has no cache; pass past=0")
+    if kv_lens is not None:
+        raise ValueError(f"attention: band = {band} is self-attention: pass kv_lens=None")
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+        raise ValueError(f"attention: chunk = {chunk!r} must be an int >= 1 (token-frames per chunk of the band)")
+    return band
+
+
 def _attn_args(q, k, v, o, lse, kv_pad_ones, grads=None, delta=None) -> AttnArgs:
     """vds_attn_args of a call.  Forward: shapes, q / k / v / o with their strides, lse; the backward adds
     grads = (do, dq, dk, dv) with theirs and the delta workspace with its size"""
@@ -408,6 +436,45 @@ def attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=No
     fr = _frames(frames, kv_lens, Lq, Lk, past) if frames is not None else None
     a = _attn_args(q, k, v, o, lse, kv_pad_ones)
     _attn_call("fwd", a, kv_lens, frames, fr, past, fmaj, chunk, window, teacher)
+
+
+def _band_call(direction: str, a: AttnArgs, frames, fr, chunk: int, band: int):
+    name = f"vds_band_attn_{direction}"
+    what = f"{name}(B={a.B},H={a.H},L={a.Lq},hd={a.head_dim},frames={tuple(frames)},chunk={chunk},band={band})"
+    check(getattr(_lib.load(), name)(C.byref(a), fr, chunk, band, _stream()), what)
+
+
+def band_attn_fwd(q, k, v, o, lse, kv_pad_ones: bool = False, kv_lens=None, frames=None, past: int = 0,
+                  frame_major: bool = False, chunk: int = 1, window=None, teacher: bool = False, band=None):
+    """attn_fwd with the trailing keyword band.  band=None: attn_fwd, unchanged.
+    band (with frame_major and frames=(lead, period); not with window / teacher / past / kv_lens; in chunks): the frame
+    band of the bidirectional model, not causal -- a token row of chunk n attends the lead rows and the token rows of
+    chunks n - band .. n + band (frame-major rows [fm_band_lo, fm_band_hi)), a lead row attends every row
+    (vds_band_attn_fwd).  q, k, v and lse rows are frame-major, o token-major, as in every frame_major call."""
+    if band is None:
+        return attn_fwd(q, k, v, o, lse, kv_pad_ones, kv_lens, frames, past, frame_major, chunk, window, teacher)
+    band = _band(band, frame_major, frames, kv_lens, int(past), window, teacher, chunk)
+    Lq, Lk = q.shape[2], k.shape[2]
+    fr = _frames(frames, kv_lens, Lq, Lk)
+    _band_call("fwd", _attn_args(q, k, v, o, lse, kv_pad_ones), frames, fr, chunk, band)
+
+
+def band_attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta=None, kv_pad_ones: bool = False, kv_lens=None, frames=None,
+                  frame_major: bool = False, chunk: int = 1, window=None, teacher: bool = False, band=None):
+    """attn_bwd with the trailing keyword band (band_attn_fwd); band=None: attn_bwd, unchanged.  The workspace is that of
+    the frame_major call (vds_band_attn_bwd)."""
+    if band is None:
+        return attn_bwd(q, k, v, o, lse, do, dq, dk, dv, delta, kv_pad_ones, kv_lens, frames, frame_major, chunk, window,
+                        teacher)
+    band = _band(band, frame_major, frames, kv_lens, 0, window, teacher, chunk)
+    B, H, Lq, hd = q.shape
+    assert lse.is_contiguous()
+    Lk = k.shape[2]
+    fr = _frames(frames, kv_lens, Lq, Lk)
+    if delta is None:
+        delta = torch.empty(attn_bwd_workspace_floats(B, H, Lq, Lk, hd, kv_pad_ones), dtype=f32, device=q.device)
+    assert delta.numel() >= 2 * B * H * Lq and delta.is_contiguous(), "attn_bwd: delta workspace is [2,B,H,Lq] f32"
+    _band_call("bwd", _attn_args(q, k, v, o, lse, kv_pad_ones, (do, dq, dk, dv), delta), frames, fr, chunk, band)
 
 
 def kv_pad_ones(kv: torch.Tensor, B: int, Lk: int, H: int, hd: int, hdp: int, k_col0: int, v_col0: int):
@@ -849,6 +916,25 @@ def fm_query_end(k1: int, lead: int, S: int, chunk: int = 1, window=None, L=None
         return L
     G = chunk * S
     end = lead + ((k1 - 1 - lead) // G + window) * G
+    return end if L is None else min(end, L)
+
+
+def fm_band_lo(x: int, lead: int, S: int, chunk: int = 1, band: int = 0, L=None) -> int:
+    """first frame-major TOKEN row that token row x attends (and is attended by) under a frame band of `band` chunks on
+    each side: lead + max(0, chunk(x) - band) * G with G = chunk * S.  A lead row attends everything: 0"""
+    if x < lead:
+        return 0
+    G = chunk * S
+    return lead + max(0, (x - lead) // G - band) * G
+
+
+def fm_band_hi(x: int, lead: int, S: int, chunk: int = 1, band: int = 0, L=None) -> int:
+    """first frame-major row past the token rows that token row x attends (and is attended by) under the frame band:
+    lead + (chunk(x) + band + 1) * G, clipped to L when given (the last chunk may be short).  A lead row: L"""
+    if x < lead:
+        return L
+    G = chunk * S
+    end = lead + ((x - lead) // G + band + 1) * G
     return end if L is None else min(end, L)
 
 
