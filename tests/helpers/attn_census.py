@@ -248,10 +248,121 @@ def check_zero(tag, got):
 
 
 # -------------------------------------------------- a torch emulation of the kernels ----
-def emulate(q, k, v, do, mask):
+LOG2E, LAZY_THR = 1.4426950408889634, 8.0  # csrc/attention.hip
+
+
+def _any_in_wave(x, rows):
+    """bool [B, H, Lq] -> the ballot of each wave of `rows` queries, on every row of the wave"""
+    B, H, L = x.shape
+    xp = torch.nn.functional.pad(x, (0, (-L) % rows)).view(B, H, -1, rows)
+    return xp.any(-1, keepdim=True).expand_as(xp).reshape(B, H, -1)[..., :L]
+
+
+def emulate_fwd_tiled(q, k, v, mask, own=False, ones=False, rows=32, fault=None):
+    """the forward kernels' evaluation order: 32-key sub-blocks, a running maximum m in the log2 domain that starts at
+    -1e30 and is raised (O and l rescaled) only where the ballot of a wave of `rows` queries finds a sub-block maximum
+    above m + LAZY_THR -- every row of the wave then (lazy_softmax), or only the rows that are over it themselves (own:
+    lazy_softmax<OWN>).  ones (ones_softmax): Q' = bf16(Q scale log2e), m a bf16 value that starts at 0, a row's
+    first sub-block with an attended key always sets it, and the denominator is summed from the bf16 P (it is a row of the O accumulator).
+    fault: one of the defects tests/test_softmax_census_cpu.py injects.  Returns o (bf16), lse (fp32), o unrounded."""
+    B, H, Lq, hd = q.shape
+    Lk = k.shape[2]
+    r = lambda t: t.to(bf16).to(f32)
+    c = torch.tensor(1.0 / math.sqrt(hd), dtype=f32) * torch.tensor(LOG2E, dtype=f32)
+    qf, kf, vf = q.to(f32), k.to(f32), v.to(f32)
+    s_all = (r(qf * c) if ones else qf) @ kf.transpose(-1, -2)
+    if fault == "pad_column":  # a column beyond head_dim meets a 1 in Q and the key's parity in K
+        s_all = s_all + (torch.arange(Lk) % 2).to(f32) * (c if ones else 1.0)
+    m4 = mask[:, None].expand(B, H, Lq, Lk)
+    valid = mask.any(1)[:, None, None, :].expand(B, H, Lq, Lk)  # keys inside the launch's bounds
+    last = (valid[:, 0, 0].long() * torch.arange(Lk)).amax(-1)  # the last valid key of each sample
+    neg = torch.tensor(float("-inf"))
+    m = torch.full((B, H, Lq), 0.0 if ones else -1e30, dtype=f32)
+    m_prev, l, o = m.clone(), torch.zeros(B, H, Lq), torch.zeros(B, H, Lq, hd)
+    pending, seen = None, torch.zeros(B, H, Lq, dtype=torch.bool)
+    for i, k0 in enumerate(range(0, Lk, 32)):
+        sl = slice(k0, min(k0 + 32, Lk))
+        live = m4[..., sl]
+        s = s_all[..., sl] if ones else s_all[..., sl] * c
+        sm = torch.where(live, s, neg)
+        src = sm
+        if fault == "masked_raises_max":
+            src = torch.where(valid[..., sl], s, neg)
+        if fault == "last_key_not_in_max":
+            src = torch.where((torch.arange(sl.start, sl.stop)[None, :] == last[:, None])[:, None, None, :], neg, sm)
+        mx = src.amax(-1)
+        if ones:
+            rel = mx - m
+            fresh = ~seen & torch.isfinite(rel)  # the row's first sub-block with a key it attends sets m, whatever it is
+            seen = seen | fresh
+            m_new = torch.where(_any_in_wave((rel > LAZY_THR) | fresh, rows), r(m + rel.clamp(min=0)), m)
+            m_new = torch.where(fresh, r(m + rel), m_new)
+        else:
+            trig = mx > (m_prev if fault == "stale_threshold" else m) + LAZY_THR
+            m_new = torch.where(trig if own else _any_in_wave(trig, rows), torch.maximum(m, mx), m)
+        alpha = torch.exp2(m - m_new)
+        if ones:
+            alpha = torch.where(fresh, torch.ones(()), alpha)  # (ones_softmax: first -> alpha = 1; O and l are 0)
+        if fault == "neighbour_alpha":
+            alpha = alpha[..., (torch.arange(Lq) ^ 1).clamp(max=Lq - 1)]
+        e = torch.where(live, torch.exp2(s - m_new[..., None]), torch.zeros(()))
+        pv = r(e) @ vf[:, :, sl]
+        l = (l if fault == "l_not_rescaled" else l * alpha) + (r(e) if ones else e).sum(-1)
+        o = o * alpha[..., None]
+        if fault == "p0_after_rescale" and i % 2 == 0:
+            pending = pv  # sub-block 0's product lands after sub-block 1's rescale
+        else:
+            o = o + pv + (0 if pending is None else pending)
+            pending = None
+        m_prev, m = m, m_new
+    if pending is not None:
+        o = o + pending
+    some = (l > 0)
+    m_out = m[..., (torch.arange(Lq) ^ 32).clamp(max=Lq - 1)] if fault == "lse_other_half" else m
+    lse = torch.where(some, (m_out + torch.log2(l.clamp(min=1e-37))) * math.log(2.0), torch.zeros(()))
+    of = torch.where(some[..., None], o / l.clamp(min=1e-37)[..., None], torch.zeros(()))
+    if fault in ("last_key_not_in_max", "masked_raises_max"):  # an overflowed or emptied row stays what the hardware gives
+        lse = torch.where(mask.any(-1)[:, None], (m_out + torch.log2(l)) * math.log(2.0), torch.zeros(()))
+        of = torch.where(mask.any(-1)[:, None, :, None], o / l[..., None], torch.zeros(()))
+    return of.to(bf16), lse, of
+
+
+def emulate_bwd(q, k, v, do, mask, o, lse, ones=False, fault=None, o_unrounded=None):
+    """the backward kernels on a forward's o and lse: P = exp2(s c - lse log2e) recomputed in fp32 (ones: from Q' = bf16(Q c)
+    and -lse log2e as a bf16 (hi, lo) pair), delta from the bf16 o, P and dS rounded to bf16 for their products, fp32
+    sums, bf16 stores.  Returns dq, dk, dv."""
+    hd = q.shape[-1]
+    scale = 1.0 / math.sqrt(hd)
+    r = lambda t: t.to(bf16).to(f32)
+    c = torch.tensor(scale, dtype=f32) * torch.tensor(LOG2E, dtype=f32)
+    qf, kf, vf, dof = q.to(f32), k.to(f32), v.to(f32), do.to(f32)
+    m4 = mask[:, None]
+    lse2 = lse * torch.tensor(LOG2E, dtype=f32)
+    if fault == "lse_bf16":
+        lse2 = r(lse2)
+    elif ones:
+        lse2 = r(lse2) + r(lse2 - r(lse2))
+    s2 = (r(qf * c) @ kf.transpose(-1, -2)) if ones else (qf @ kf.transpose(-1, -2)) * c
+    p = torch.where(m4, torch.exp2(s2 - lse2[..., None]), torch.zeros(()))
+    delta = (dof * (o_unrounded if fault == "delta_unrounded" else o.to(f32))).sum(-1, keepdim=True)
+    ds = r(p * (dof @ vf.transpose(-1, -2) - delta))
+    dv = (r(p).transpose(-1, -2) @ dof).to(bf16)
+    dk = ((ds.transpose(-1, -2) @ qf) * scale).to(bf16)
+    dq = ((ds @ kf) * scale).to(bf16)
+    return dq, dk, dv
+
+
+def emulate(q, k, v, do, mask, tiled=None, bwd_ones=False, fault=None):
     """the kernels' arithmetic on bf16 inputs [B, H, L, hd] under a bool mask [B, Lq, Lk]: fp32 scores, mask, softmax, P and
     dS rounded to bf16 for their products, fp32 sums, bf16 outputs; delta from the bf16 o.  A sample that attends nothing
-    gives zeros.  Returns o, lse and (do given) dq, dk, dv."""
+    gives zeros.  Returns o, lse and (do given) dq, dk, dv.
+    tiled: keywords of emulate_fwd_tiled (own, ones, rows) -- the forward by 32-key sub-blocks with the lazy threshold,
+    the backward by emulate_bwd (bwd_ones: its ones route); fault goes to whichever of the two knows it."""
+    if tiled is not None or bwd_ones or fault is not None:
+        o, lse, of = emulate_fwd_tiled(q, k, v, mask, fault=fault, **(tiled or {}))
+        if do is None:
+            return o, lse
+        return (o, lse) + emulate_bwd(q, k, v, do, mask, o, lse, bwd_ones, fault, of)
     scale = 1.0 / math.sqrt(q.shape[-1])
     r = lambda t: t.to(bf16).to(f32)
     qf, kf, vf = q.to(f32), k.to(f32), v.to(f32)

@@ -274,14 +274,15 @@ def test_past(ops, family, case):
 # --------------------------------------------------------------- per-sample key lengths ----
 def run_kvlen(ops, q, k, v, do, lens, pad_ones=0, variant=None, wide=None, fold=None, dkv16=None, qsplit=None):
     """the launch plumbing of tests/test_attn_kvlen_gpu.py: token-major q / o / dO and a [B*Lk, 2D] kv buffer; pad_ones = 2:
-    k / v through ops.kv_pad_ones (the cross-attention on the ones-column kernels)"""
+    k / v through ops.kv_pad_ones (the cross-attention on the ones-column kernels); lens = None: no key lengths, the
+    unmasked instances"""
     B, H, Lq, hd = q.shape
     Lk = k.shape[2]
     D = H * hd
     qd, kvd = tok(q).cuda(), torch.cat([tok(k), tok(v)], dim=1).cuda()
     o = torch.full((B * Lq, D), NAN, dtype=bf16, device="cuda")
     lse = torch.full((B, H, Lq), NAN, dtype=f32, device="cuda")
-    kvl = torch.tensor(lens, dtype=torch.int32, device="cuda")
+    kvl = None if lens is None else torch.tensor(lens, dtype=torch.int32, device="cuda")
     qv, ov = ops.heads_view(qd, B, Lq, H, hd), ops.heads_view(o, B, Lq, H, hd)
     if pad_ones:
         kp, vp = ops.kv_pad_ones(kvd, B, Lk, H, hd, 96, 0, D)
