@@ -954,6 +954,32 @@ int vds_head_rmsnorm_fwd(void* x, int64_t ldx, float* rstd, int32_t M, int32_t H
 int vds_head_rmsnorm_bwd(void* dy, int64_t lddy, const void* y, int64_t ldy, const float* rstd, int32_t M, int32_t H,
                          int32_t hd, vds_stream_t stream);
 
+/* ------------------------------------------------- row movers of token routing (csrc/route.hip) ----
+ * A routed span of DiT blocks runs on a subset of the sequence's rows (DiT.enable_token_routing): rows are picked out of
+ * [outer, n, row] tensors by an int32 index table ON THE DEVICE (read by the kernel, never by the host: the launches can
+ * be captured in a graph) and put back through its inverse.  Whole rows move in 16-byte pieces; HBM-bound.  No atomics,
+ * no workspace: results are bit-identical run to run, with or without vds_set_deterministic.  Every data pointer is
+ * 16-byte aligned, every table 4-byte aligned, row_bytes a positive multiple of 16.  NULL or misaligned pointers, another
+ * row_bytes, outer <= 0 or a negative count: VDS_ERR_ARG before any launch; rows of 2 GiB or more, or more than 2^31 - 1
+ * workgroups of 1024 pieces per outer slice: VDS_ERR_UNSUPPORTED.  The launches are credited to no profiler class.
+ *
+ * dst[o, i, :] = src[o, idx[i], :]   o < outer, i < n_out; src is [outer, n_in, row_bytes], dst [outer, n_out, row_bytes].
+ * idx int32[n_out]; duplicates allowed; dst must not overlap src.  An index outside [0, n_in) reads nothing: its dst row
+ * is written as zeros.  n_in > 0; n_out == 0: VDS_OK, nothing is launched. */
+int vds_rows_gather(const void* src, void* dst, const int32_t* idx, int32_t outer, int32_t n_in, int32_t n_out,
+                    int64_t row_bytes, vds_stream_t stream);
+/* dst[o, l, :] = (0 <= inv[l] < n_part) ? part[o, inv[l], :] : full[o, l, :]   l < n_full; inv int32[n_full].
+ * dst == full is allowed (every piece is read and written by the same thread; the rows that take no part row are then
+ * left untouched); dst must not overlap part.  n_full > 0; n_part == 0: VDS_OK, nothing is launched and dst is not
+ * written (with dst != full the copy of `full` is the caller's). */
+int vds_rows_merge(const void* full, const void* part, void* dst, const int32_t* inv, int32_t outer, int32_t n_full,
+                   int32_t n_part, int64_t row_bytes, vds_stream_t stream);
+/* acc[o, idx[i], :] += part[o, i, :]   fp32, one add per element; part is [outer, n_part, row_elems], acc [outer, n_full,
+ * row_elems], row_elems a positive multiple of 4.  idx int32[n_part] must be distinct (the caller's contract: a plain
+ * read-add-write, no atomics).  An index outside [0, n_full) is skipped.  n_full > 0; n_part == 0: VDS_OK, no launch. */
+int vds_rows_scatter_add_f32(const float* part, float* acc, const int32_t* idx, int32_t outer, int32_t n_full,
+                             int32_t n_part, int32_t row_elems, vds_stream_t stream);
+
 /* ------------------------------------------------------------------ live profiling ----
  * Per-kernel-class timing with HIP events recorded on the launch stream around each launch of
  * an enabled class (bench.py's roofline leg).  Off by default (no events, no overhead).

@@ -229,6 +229,9 @@ SIGNATURES = {
     "vds_lowrank_chunk": [c_i32, c_i32],
     "vds_head_rmsnorm_fwd": [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp],
     "vds_head_rmsnorm_bwd": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp],
+    "vds_rows_gather": [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i64, c_vp],
+    "vds_rows_merge": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i64, c_vp],
+    "vds_rows_scatter_add_f32": [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp],
     "vds_selftest_lanemaps": [c_vp, c_vp],
     "vds_prof_enable": [C.c_uint32],
     "vds_prof_collect": [c_vp],

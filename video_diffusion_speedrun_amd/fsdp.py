@@ -363,6 +363,9 @@ def apply_fsdp(dit_model, param_dtype=torch.bfloat16, reduce_dtype=torch.float32
     reference's memory-bounded behaviour (model.py:525,541) -- see ReshardRuntime."""
     if param_dtype != torch.bfloat16 or reduce_dtype != torch.float32:
         raise ValueError("apply_fsdp: the HIP path implements param_dtype=bf16, reduce_dtype=fp32 only")
+    if getattr(dit_model, "token_routing", None) is not None:
+        from .model import _ROUTE_FSDP
+        raise NotImplementedError("apply_fsdp: " + _ROUTE_FSDP)
     if getattr(dit_model, "lora", None) is not None:
         raise NotImplementedError("apply_fsdp: a model with LoRA adapters cannot be sharded (the frozen base would be "
                                   "gathered and its gradient buffers reduced for nothing) -- call merge_lora() first, or "

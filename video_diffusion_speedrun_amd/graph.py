@@ -11,6 +11,10 @@ in device memory rather than in kernel arguments:
                             first batch carries it, the int32 `context_lens` the attention kernels read on the device);
   * the RoPE offsets     -> device int32[3] read by `vds_rope_rows_dev` (drawn on the host from the
                             global CPU RNG exactly like the eager path, model.py:224-226);
+  * the token route      -> (a model with enable_token_routing) static device int32 tables idx [Ls] / inv [L] read by the
+                            row movers (`vds_rows_gather` / `_merge` / `_scatter_add_f32`), drawn on the host after the
+                            RoPE offsets exactly like the eager path; Ls is fixed by the shape and `keep`, so every
+                            replay runs a new subset through the same launches;
   * the AdamW bias corrections, LR multiplier and EMA decay -> device float[4] read by `vds_adamw_multi_dev` /
                             `vds_adamw_guarded_multi_dev`; the guarded step's norm, clip coefficient and skip flag never
                             leave the device (optim.py): a replay fed a non-finite batch skips itself;
@@ -70,6 +74,7 @@ class GraphedTrainStep:
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.static: Dict[str, torch.Tensor] = {}
         self.rope_dev = torch.zeros(3, dtype=torch.int32, device=self.device)
+        self.route = None  # model.TokenRoute: the static idx / inv tables of a token-routing model (made on first use)
         self.loss: Optional[torch.Tensor] = None
         self.n_replays = 0
         optimizer.use_device_scalars(self.device)
@@ -105,9 +110,35 @@ class GraphedTrainStep:
         self.rope_dev.copy_(torch.tensor(st, dtype=torch.int32))
         return st
 
-    def _body(self, rope_start):
-        loss, _ = _train.forward(self.model, self.static, None, None, self.device, 0, False, rope_start=rope_start,
-                                 **self.frame_kw)
+    def _draw_route(self, route=None, fill=True):
+        """a token-routing model: draw this step's subset on the host (`route`: pin it instead) and copy its tables into
+        the static buffers the step reads.  Returns them, or None for a step that runs every token -- which steps are
+        routed is DiT.forward's rule: the drawn ones in training mode only, a pinned one always, and a route given to a model
+        without the switch is refused.  fill=False (before the capture): only make sure the buffers exist, no draw."""
+        m = self.model
+        if not m._route_requested(route):
+            return None
+        t, h, w = self._thw(self.static["latent"])
+        N = t * h * w
+        if not fill and self.route is not None:
+            return self.route
+        if not fill:  # identity tables of the step's shapes
+            from .model import route_keep_count
+            route = list(range(route_keep_count(N, m.token_routing[2])))
+        host = m.make_route(m.draw_route(N) if route is None else route, N, "cpu")
+        if self.route is None:
+            self.route = m.make_route(host, N, self.device)
+            return self.route
+        if host.idx.shape != self.route.idx.shape:
+            raise ValueError(f"GraphedTrainStep was set up for routes of {self.route.idx.shape[0] - 16} tokens, got "
+                             f"{host.idx.shape[0] - 16}")
+        self.route.idx.copy_(host.idx)
+        self.route.inv.copy_(host.inv)
+        return self.route
+
+    def _body(self, rope_start, route=None):
+        kw = self.frame_kw if route is None else dict(self.frame_kw, route=route)
+        loss, _ = _train.forward(self.model, self.static, None, None, self.device, 0, False, rope_start=rope_start, **kw)
         self.opt.zero_grad()
         loss.backward()
         self.opt.step()
@@ -120,11 +151,12 @@ class GraphedTrainStep:
         if fs is not None:
             fs.measure = False  # timing events cannot be recorded into a graph
             counts = (fs.n_all_gather, fs.n_reduce_scatter)
+        route = self._draw_route(fill=False)  # (the static tables exist before the capture reads them)
         g = torch.cuda.CUDAGraph()
         torch.cuda.synchronize()
         try:
             with torch.cuda.graph(g):
-                loss = self._body(self.rope_dev)
+                loss = self._body(self.rope_dev, route)
         finally:
             if fs is not None:
                 fs.measure = measure
@@ -136,7 +168,9 @@ class GraphedTrainStep:
         self.graph, self.loss = g, loss
 
     # ------------------------------------------------------------------------------------------
-    def step(self, batch) -> torch.Tensor:
+    def step(self, batch, route=None) -> torch.Tensor:
+        """route (a token-routing model): this step's kept token indices (a list or CPU tensor, DiT.forward(route=)) in
+        place of the draw"""
         if "context" not in batch:
             raise ValueError("GraphedTrainStep takes pre-encoded batches: {'latent', 'context'}")
         self._stage(batch)
@@ -146,11 +180,13 @@ class GraphedTrainStep:
             # fp8: the capture must see delayed scaling armed (a complete recorded step) and the partial-maxima table
             # allocated, or the captured amax roll would differ from the one every later step needs
             self.eager_left = max(0, self.eager_left - 1)
-            loss = self._body(self._draw_rope()).detach().clone()
+            rope = self._draw_rope()
+            loss = self._body(rope, self._draw_route(route)).detach().clone()
         else:
             if self.graph is None:
                 self._capture()
             self._draw_rope()
+            self._draw_route(route)
             self.opt.advance()
             # the captured step holds no fp32 -> bf16 cast (the optimizer kernel writes both copies): parameters
             # written from outside since the last step (load_state_dict, EMA swap, p.mul_()) are re-cast here

@@ -1129,6 +1129,51 @@ class _Saved:
     pass
 
 
+class TokenRoute:
+    """The row tables of one routed call (DiT.enable_token_routing), both int32 on the device: idx [Ls] -- the rows of the
+    full sequence that run the routed span, [0 .. N_REG - 1] ++ (N_REG + the kept token indices), Ls = N_REG + k -- and inv
+    [L], its inverse: inv[idx[i]] = i, -1 for every row that skips the span.  DiT.make_route builds one."""
+    __slots__ = ("idx", "inv")
+
+    def __init__(self, idx: torch.Tensor, inv: torch.Tensor):
+        self.idx, self.inv = idx, inv
+
+
+def route_keep_count(N: int, keep: float) -> int:
+    """tokens of N that run the routed span at keep fraction `keep`: max(1, int(keep * N + 0.5))"""
+    return max(1, int(keep * N + 0.5))
+
+
+def route_tables(route, N: int):
+    """host form of a TokenRoute: route = sorted, distinct token indices in [0, N) (a CPU integer tensor [k]) ->
+    (idx int32 [N_REG + k], inv int32 [N_REG + N]) on the CPU"""
+    k = route.shape[0]
+    idx = torch.cat([torch.arange(N_REG, dtype=torch.int32), route.to(torch.int32) + N_REG])
+    inv = torch.full((N_REG + N,), -1, dtype=torch.int32)
+    inv[idx.long()] = torch.arange(N_REG + k, dtype=torch.int32)
+    return idx, inv
+
+
+_ROUTE_WHAT = ("token routing runs a span of blocks on a subset of the rows, and the rows of a subset have no frame "
+               "structure: ")
+_ROUTE_FRAME_CAUSAL = (_ROUTE_WHAT + "a model built with frame_causal=True (frame_major / frame_chunk / frame_window "
+                       "included) derives its attention mask from a row's index -- build the model without frame_causal to "
+                       "route it, or call enable_token_routing(None)")
+_ROUTE_FRAME_BAND = (_ROUTE_WHAT + "the frame band derives its mask from a row's index -- call enable_frame_band(None) to "
+                     "route the model, or enable_token_routing(None) to run the band")
+_ROUTE_FP8 = ("token routing is not implemented for the fp8 path (the amax tables are sized by the rows of the full "
+              "sequence): call enable_fp8(False) to route the model, or enable_token_routing(None) to run it in fp8")
+_ROUTE_FSDP = ("token routing is not implemented for a model sharded with apply_fsdp (the reshard runtime's lambda snapshot "
+               "interacts with the deferred d v_0 reduction, and no multi-GPU box exists to run it): route an unsharded "
+               "model, or call enable_token_routing(None)")
+_ROUTE_FRAME_TIMESTEPS = (_ROUTE_WHAT + "per-frame timesteps (timesteps [B, t]) make the grouped kernels derive a row's "
+                          "modulation group from its index -- pass timesteps [B], or route=False for this call")
+_ROUTE_TEACHER = (_ROUTE_WHAT + "teacher_latents needs the teacher-forcing mask of a frame-causal model -- drop "
+                  "teacher_latents, or pass route=False for this call")
+_ROUTE_CACHE = (_ROUTE_WHAT + "frame_cache keeps the K / V rows of whole frames -- pass frame_cache=None, or route=False "
+                "for this call (a cached call is inference: call model.eval() and it runs every token)")
+
+
 LORA_TARGETS = ("qkv", "q_cross", "context_kv")  # the linears DiT.add_lora can adapt: plain-store GEMMs, no fused epilogue
 _FP8_LORA = ("LoRA adapters are not implemented for the fp8 linears (the adapter reads the bf16 input of the linear, which "
              "the fp8 path does not keep)")
@@ -1137,7 +1182,7 @@ _FP8_RECOMPUTE = ("enable_fp8() and enable_recompute() cannot be combined: the f
                   "during the forward pass, which a replayed forward would write a second time")
 
 
-def activation_bytes(dit, B: int, latent_shape, Lc: int, mode: str = "none") -> Dict[str, int]:
+def activation_bytes(dit, B: int, latent_shape, Lc: int, mode: str = "none", routing=None) -> Dict[str, int]:
     """Bytes of the tensors a grad-enabled forward of `dit` keeps inside its blocks for the backward pass, from their
     shapes alone (no GPU): latent_shape = (T, H, W) of the input latents, Lc = context length.
       per_block   what ONE block keeps in `mode`
@@ -1149,13 +1194,45 @@ def activation_bytes(dit, B: int, latent_shape, Lc: int, mode: str = "none") -> 
     backward reads the qkv GEMM output (3 D bf16 elements per token row), which every block -- block 0, which mixes no
     v_0, included -- already keeps and this sum already counts.
     A teacher-forcing call (forward(teacher_latents=)) runs the clean and the noisy frames as one sequence: call this with
-    the doubled T, latent_shape = (2 * T, H, W), for its numbers."""
+    the doubled T, latent_shape = (2 * T, H, W), for its numbers.
+    routing = (first_block, last_block, keep), the arguments of DiT.enable_token_routing: the blocks first_block ..
+    last_block keep their tensors at Ls = N_REG + k rows per sample instead of L -- `kept` is then the sum over the blocks
+    of the per-block figure at L or at Ls, `per_block_routed` the figure at Ls (`per_block` and `transient` stay those of a
+    full-length block, the largest), `rows_routed` = B * Ls.  Not counted: the routed call's gathered v_0 (B H Ls hdp bf16)
+    and its two RoPE tables, kept once per call.  None (the default): the numbers of the unrouted model, as before."""
     if mode not in RECOMPUTE_MODES:
         raise ValueError(f"activation_bytes: mode must be one of {RECOMPUTE_MODES}, got {mode!r}")
+    T, Hh, Ww = latent_shape
+    N = (T // dit.time_patch_size) * (Hh // dit.patch_size) * (Ww // dit.patch_size)
+    per_block, full, R = _block_activation_bytes(dit, B, N + N_REG, Lc, mode)
+    out = {"per_block": per_block, "kept": dit.depth * per_block, "transient": 0 if mode == "none" else full, "rows": R}
+    if routing is not None:
+        first, last, keep = check_token_routing(routing[0], routing[1], routing[2], dit.depth)
+        routed, _, Rs = _block_activation_bytes(dit, B, N_REG + route_keep_count(N, keep), Lc, mode)
+        n = last - first + 1
+        out.update(kept=(dit.depth - n) * per_block + n * routed, per_block_routed=routed, rows_routed=Rs)
+    return out
+
+
+def check_token_routing(first_block, last_block, keep, depth: int):
+    """the arguments of DiT.enable_token_routing: (first_block, last_block, keep) checked, or ValueError"""
+    for name, v in (("first_block", first_block), ("last_block", last_block)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"enable_token_routing: {name} = {v!r} must be an int (a block index)")
+    if not 1 <= first_block <= last_block <= depth - 1:
+        raise ValueError(f"enable_token_routing: blocks {first_block} .. {last_block} must satisfy 1 <= first_block <= "
+                         f"last_block <= depth - 1 = {depth - 1} (both inclusive; block 0 is never routed: it produces "
+                         "residual-V's v_0 from every row)")
+    if isinstance(keep, bool) or not isinstance(keep, (int, float)) or not 0.0 < float(keep) < 1.0:
+        raise ValueError(f"enable_token_routing: keep = {keep!r} must be a fraction with 0 < keep < 1 (the share of the "
+                         "video tokens that runs the routed blocks; 0.5 is TREAD's)")
+    return first_block, last_block, float(keep)
+
+
+def _block_activation_bytes(dit, B: int, L: int, Lc: int, mode: str):
+    """(what one block keeps in `mode`, one block's full set of intermediates, B * L) at L rows per sample"""
     D, H, hd = dit.hidden_size, dit.num_heads, dit.head_dim
     hdp = HDP_OF[hd]
-    T, Hh, Ww = latent_shape
-    L = (T // dit.time_patch_size) * (Hh // dit.patch_size) * (Ww // dit.patch_size) + N_REG
     R = B * L
     Dm = int(D * dit.mlp_ratio)
     cross = dit.cross_attn_input_size is not None
@@ -1184,8 +1261,7 @@ def activation_bytes(dit, B: int, latent_shape, Lc: int, mode: str = "none") -> 
                             for t in lora["targets"])
     full += mod
     per_block = {"none": full, "full": 2 * R * D + mod, "selective": 2 * R * D + mod + 2 * R * D + lse}[mode]
-    return {"per_block": per_block, "kept": dit.depth * per_block, "transient": 0 if mode == "none" else full,
-            "rows": R}
+    return per_block, full, R
 
 
 def _offsets(groups):
@@ -1277,6 +1353,109 @@ class DiT(nn.Module):
         self.lora = None  # add_lora(): {"rank", "alpha", "targets"} of the low-rank adapters on the blocks' q/k/v linears
         self.frame_band = None  # enable_frame_band(): (chunk, band_chunks) of the blocks' two-sided frame band, or None
         self._lora_frozen: List[str] = []  # names add_lora(freeze_base=True) froze (merge_lora un-freezes exactly these)
+        self.token_routing = None  # enable_token_routing(): (first_block, last_block, keep) of the routed span, or None
+
+    def enable_token_routing(self, first_block, last_block=None, keep: float = 0.5):
+        """Token routing (TREAD): in training, the blocks first_block .. last_block (both inclusive, 1 <=
+        first_block <= last_block <= depth - 1) run on the 16 register rows and a random subset of k = max(1, int(keep * N +
+        0.5)) of the N video tokens, drawn per call and shared by the batch; the other tokens skip the span -- they enter
+        block last_block + 1 with the value they had before block first_block -- and rejoin at their places.  The routed
+        blocks are the block code at the shorter length Ls = 16 + k with gathered side inputs (v_0, the RoPE rows); the
+        rows move through ops.rows_gather / rows_merge / rows_scatter_add.  enable_token_routing(None) switches it off, and
+        the model launches exactly the kernels it launched before.  No parameter, no checkpoint key.
+        A call is routed when the switch is on, the model is in training mode and gradients are enabled: model.eval() and
+        torch.no_grad() (the sampler) run every token.  forward(route=) overrides that per call.  The subset is
+        torch.randperm(N)[:k].sort() from the global CPU RNG (draw_route), drawn after the RoPE offsets.
+        Works with residual_v, qk_norm, context_lens, enable_recompute, set_deterministic, LoRA, GraphedTrainStep and every
+        optimizer.  Refused -- everything that derives something from a row's index: a frame_causal model, the frame band,
+        timesteps [B, t], teacher_latents, frame_cache; and enable_fp8 and apply_fsdp.  Returns self."""
+        if first_block is None:
+            self.token_routing = None
+            return self
+        args = check_token_routing(first_block, first_block if last_block is None else last_block, keep, self.depth)
+        if self.frame_causal:
+            raise ValueError("enable_token_routing: " + _ROUTE_FRAME_CAUSAL)
+        if self.frame_band is not None:
+            raise ValueError("enable_token_routing: " + _ROUTE_FRAME_BAND)
+        if self.fp8:
+            raise NotImplementedError("enable_token_routing: " + _ROUTE_FP8)
+        if self._fsdp is not None or self._world > 1:
+            raise NotImplementedError("enable_token_routing: " + _ROUTE_FSDP)
+        self.token_routing = args
+        return self
+
+    def draw_route(self, N: int) -> torch.Tensor:
+        """the kept token indices of one routed call on N video tokens: int32 [k], k = max(1, int(keep * N + 0.5)), sorted and
+        distinct -- torch.randperm(N)[:k].sort().values from the global CPU RNG (equal seeds give equal subsets)"""
+        if self.token_routing is None:
+            raise ValueError("draw_route: token routing is off -- call enable_token_routing(first_block, last_block, keep) "
+                             "first")
+        k = route_keep_count(int(N), self.token_routing[2])
+        return torch.randperm(int(N))[:k].sort().values.to(torch.int32)
+
+    def make_route(self, route, N: int, device) -> TokenRoute:
+        """route -> the device tables of a routed call on N video tokens.  route: sorted, distinct token indices in [0, N)
+        as a list or a CPU integer tensor (validated here, on the host; one small copy to the device), or a device int32
+        tensor [k] that is NOT validated (no host sync, so a captured graph can replay it with new contents; the row
+        kernels guard every index they read); a TokenRoute passes through."""
+        device = torch.device(device)
+        if isinstance(route, TokenRoute):  # (host tables are uploaded: one small copy each)
+            return route if route.idx.device == device else TokenRoute(route.idx.to(device), route.inv.to(device))
+        if isinstance(route, torch.Tensor) and route.is_cuda:
+            if route.dtype != torch.int32 or route.dim() != 1 or route.shape[0] < 1:
+                raise ValueError(f"DiT: a device route must be an int32 tensor of shape [k], k >= 1, got {route.dtype} "
+                                 f"{tuple(route.shape)} -- pass route.to(torch.int32), or a list / CPU tensor to have it "
+                                 "checked")
+            k = route.shape[0]
+            idx = torch.cat([torch.arange(N_REG, dtype=torch.int32, device=route.device), route + N_REG])
+            # inv without a scatter (an unchecked index must not address memory): row l = N_REG + tok is routed iff tok is
+            # in the sorted route, at the position a binary search finds
+            tok = torch.arange(N, dtype=torch.int32, device=route.device)
+            pos = torch.searchsorted(route, tok).clamp_(max=k - 1)
+            hit = route[pos] == tok
+            inv_tok = torch.where(hit, (pos + N_REG).to(torch.int32), torch.full_like(tok, -1))
+            inv = torch.cat([torch.arange(N_REG, dtype=torch.int32, device=route.device), inv_tok])
+            return TokenRoute(idx.contiguous(), inv.contiguous())
+        if isinstance(route, torch.Tensor):
+            if route.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or route.dim() != 1:
+                raise ValueError(f"DiT: route must be a 1-D integer tensor of token indices, got {route.dtype} "
+                                 f"{tuple(route.shape)}")
+            vals = [int(v) for v in route.tolist()]
+        else:
+            try:
+                vals = list(route)
+            except TypeError:
+                raise ValueError("DiT: route must be False, None, a sequence of ints or an integer tensor (the kept token "
+                                 "indices)") from None
+            if any(isinstance(v, bool) or not isinstance(v, int) for v in vals):
+                raise ValueError("DiT: route must hold ints (the kept token indices)")
+        if not vals:
+            raise ValueError("DiT: route is empty -- at least one token runs the routed span; pass route=False to run the "
+                             "full model")
+        bad = [v for v in vals if v < 0 or v >= N]
+        if bad:
+            raise ValueError(f"DiT: every route index must be in [0, {N}) (this call has {N} video tokens), got {bad[:8]}")
+        if any(b <= a for a, b in zip(vals, vals[1:])):
+            raise ValueError("DiT: route must be sorted and distinct (strictly increasing token indices) -- pass "
+                             "sorted(set(route))")
+        idx, inv = route_tables(torch.tensor(vals, dtype=torch.int32), N)
+        return TokenRoute(idx.to(device), inv.to(device))  # one small copy each
+
+    def _route_requested(self, route) -> bool:
+        """does this call run the routed span?  (route of DiT.forward; the switch, the mode and the override)"""
+        if self.token_routing is None:
+            if route is not None and route is not False:
+                raise ValueError("DiT: route= given to a model without token routing -- call enable_token_routing("
+                                 "first_block, last_block, keep) first, or drop route")
+            return False
+        if route is False:
+            return False
+        if route is None:
+            return self.training and torch.is_grad_enabled()
+        if isinstance(route, bool):
+            raise ValueError("DiT: route=True is no route -- pass None (routed in training mode, on a drawn subset), False "
+                             "(the full model) or the kept token indices")
+        return True
 
     def enable_fp8(self, on: bool = True, attention: bool = True, all_linears: bool = True,
                    cross_attention: bool = True):
@@ -1289,6 +1468,8 @@ class DiT(nn.Module):
         A model built with qk_norm=True has no fp8 attention producer: `attention=True` raises NotImplementedError there
         (enable_fp8(attention=False) runs its linears in fp8 and the normed attention in bf16).  The same
         holds for a model built with frame_causal=True: the fp8 attention kernels have no masked instance."""
+        if on and self.token_routing is not None:
+            raise NotImplementedError("enable_fp8: " + _ROUTE_FP8)
         if on and self.recompute != "none":
             raise ValueError(_FP8_RECOMPUTE)
         if on and self.lora is not None:
@@ -1324,6 +1505,8 @@ class DiT(nn.Module):
             for blk in self.blocks:
                 blk.frame_band = None
             return self
+        if self.token_routing is not None:
+            raise ValueError("enable_frame_band: " + _ROUTE_FRAME_BAND)
         if self.frame_causal:
             raise ValueError("enable_frame_band: the frame band is the two-sided mask of the bidirectional model; this model "
                              "was built with frame_causal=True -- bound its causal attention with frame_window= (with "
@@ -1582,7 +1765,7 @@ class DiT(nn.Module):
 
     # ------------------------------------------------------------------------ forward ----
     def forward(self, x, context, timesteps, rope_start: Optional[Tuple[int, int, int]] = None, context_lens=None,
-                register_timesteps=None, frame_cache=None, teacher_latents=None):
+                register_timesteps=None, frame_cache=None, route=None, teacher_latents=None):
         """x [B,C,T,H,W], context [B,Lc,Cc], timesteps [B] -> [B,C,T,H,W] bf16 (model.py:358-402).
         timesteps [B, t], t = T // time_patch_size: one noise level per token-frame (image-to-video, video extension,
         diffusion forcing).  The tokens of frame f of sample b are modulated from timesteps[b, f], the register tokens
@@ -1610,11 +1793,40 @@ class DiT(nn.Module):
         sample, the level the cached rollout pins); token-frame t + f takes the RoPE rows of token-frame f; every
         self-attention runs the teacher mask -- a noisy chunk attends the registers, the CLEAN chunks before it and
         itself -- so that each chunk is computed as generate_latents(rollout_frames=frame_chunk, kv_cache=True) computes it.
-        Returns the noisy half, [B,C,T,H,W]; the clean rows get their gradients through K / V."""
+        Returns the noisy half, [B,C,T,H,W]; the clean rows get their gradients through K / V.
+        route (a model with enable_token_routing): None -- the call is routed iff the model is in training mode and
+        gradients are enabled, on a subset drawn from the global CPU RNG after the RoPE offsets (draw_route); False -- the
+        full model; sorted, distinct token indices in [0, N) -- this subset (a list or CPU integer tensor is validated on
+        the host; a device int32 tensor [k] is used unchecked, make_route).  Anything but None / False on a model without
+        token routing: ValueError."""
+        if self._route_requested(route):
+            self._check_routed_call(timesteps, frame_cache, teacher_latents)
+            if route is None:
+                route = True  # drawn in _forward, behind the RoPE offsets
+        else:
+            route = None
         if teacher_latents is not None:
             return self._forward_teacher(x, context, timesteps, rope_start, context_lens, register_timesteps, frame_cache,
                                          teacher_latents)
-        return self._forward(x, context, timesteps, rope_start, context_lens, register_timesteps, frame_cache)
+        return self._forward(x, context, timesteps, rope_start, context_lens, register_timesteps, frame_cache, route=route)
+
+    def _check_routed_call(self, timesteps, frame_cache, teacher_latents):
+        """what a routed call refuses (every refusal before the device is touched); enable_token_routing and the other
+        switches refuse each other where both are set on the model, these show at the call only"""
+        if teacher_latents is not None:
+            raise ValueError("DiT: " + _ROUTE_TEACHER)
+        if frame_cache is not None:
+            raise ValueError("DiT: " + _ROUTE_CACHE)
+        if isinstance(timesteps, torch.Tensor) and timesteps.dim() == 2:
+            raise ValueError("DiT: " + _ROUTE_FRAME_TIMESTEPS)
+        if self.frame_causal:
+            raise ValueError("DiT: " + _ROUTE_FRAME_CAUSAL)
+        if self.frame_band is not None:
+            raise ValueError("DiT: " + _ROUTE_FRAME_BAND)
+        if self.fp8:
+            raise NotImplementedError("DiT: " + _ROUTE_FP8)
+        if self._fsdp is not None or self._world > 1:
+            raise NotImplementedError("DiT: " + _ROUTE_FSDP)
 
     def _forward_teacher(self, x, context, timesteps, rope_start, context_lens, register_timesteps, frame_cache,
                          teacher_latents):
@@ -1655,8 +1867,13 @@ class DiT(nn.Module):
         out = self._forward(x2, context, ts2, rope_start, context_lens, register_timesteps, None, teacher=True)
         return out[:, :, T:]
 
-    def _forward(self, x, context, timesteps, rope_start, context_lens, register_timesteps, frame_cache, teacher=False):
+    def _forward(self, x, context, timesteps, rope_start, context_lens, register_timesteps, frame_cache, teacher=False,
+                 route=None):
+        """route: None (every token runs every block), True (a routed call whose subset is drawn here) or the subset"""
         reg_t = None
+        if route is not None and route is not True:  # a host route is checked before anything else happens
+            n_tok = ((x.shape[2] // self.time_patch_size) * (x.shape[3] // self.patch_size) * (x.shape[4] // self.patch_size))
+            route = self.make_route(route, n_tok, x.device)
         if register_timesteps is not None or frame_cache is not None:  # validated before the device is touched
             b = x.shape[0]
             thw = (x.shape[2] // self.time_patch_size, x.shape[3] // self.patch_size, x.shape[4] // self.patch_size)
@@ -1694,15 +1911,22 @@ class DiT(nn.Module):
             rope_start = self.rope.draw_start(thw)
         if not isinstance(rope_start, torch.Tensor):  # a device int32[3] tensor is read by the kernel (graph.py)
             rope_start = tuple(rope_start)
+        if route is not None:  # (the draw comes after the RoPE offsets': a seeded run draws both in this order)
+            n_tok = thw[0] * thw[1] * thw[2]
+            if route is True:
+                route = self.make_route(self.draw_route(n_tok), n_tok, x.device)
+            if tuple(route.inv.shape) != (N_REG + n_tok,) or not N_REG < route.idx.shape[0] <= N_REG + n_tok:
+                raise ValueError(f"DiT: the route's tables are for {route.inv.shape[0] - N_REG} video tokens, this call has "
+                                 f"{n_tok} -- build them with make_route(route, {n_tok}, device)")
         self._ensure_groups(x.device)
         params = [p for p in self.parameters() if p.requires_grad]
         need_grad = torch.is_grad_enabled() and len(params) > 0
         if kv_lens is not None:
             kv_lens = kv_lens.to(x.device)
         if need_grad:
-            return _DiTFunction.apply(self, x, context, timesteps, rope_start, kv_lens, reg_t, teacher, *params)
+            return _DiTFunction.apply(self, x, context, timesteps, rope_start, kv_lens, reg_t, teacher, route, *params)
         out, _ = self._forward_impl(x, context, timesteps, rope_start, save=False, kv_lens=kv_lens, reg_t=reg_t,
-                                    cache=frame_cache, teacher=teacher)
+                                    cache=frame_cache, teacher=teacher, route=route)
         if frame_cache is not None:
             frame_cache.pending_frames = thw[0]
         return out
@@ -1805,7 +2029,7 @@ class DiT(nn.Module):
             g.gather(ops.cast_f32_bf16, None)
 
     def _forward_impl(self, x, context, timesteps, rope_start, save: bool, kv_lens=None, reg_t=None, cache=None,
-                      teacher=False):
+                      teacher=False, route=None):
         D, H, hd = self.hidden_size, self.num_heads, self.head_dim
         pt, p = self.time_patch_size, self.patch_size
         B, C, T, Hh, Ww = x.shape
@@ -1894,10 +2118,22 @@ class DiT(nn.Module):
         past = cache.past_frames * h * w if cache is not None else 0
         ring_call = cache.ring_call(t) if (cache is not None and cache.ring is not None) else None
         keep = self.recompute if (save and self.recompute != "none") else None  # blocks keep their inputs, not their work
+        # token routing (a TokenRoute): the blocks r_first .. r_last run the block code at Ls = N_REG + k rows -- the
+        # registers and the kept tokens, gathered with residual-V's v_0 rows and the RoPE rows -- and the result goes back
+        # to its rows of the full buffer, whose other rows still hold what they held before block r_first
+        r_first, r_last = self.token_routing[:2] if route is not None else (self.depth, -1)
+        X_full = routed_in = None
         for i in range(self.depth):
             if fs is not None:
                 fs.pre_forward_block(i)
-            X, v, bs = self.blocks[i]._fwd(self.block_group(i), f"blocks.{i}.", X, ctx2d, cvec, v0, cos, sin, B, L, Lc,
+            if i == r_first:
+                Ls = route.idx.shape[0]
+                X_full = X
+                routed_in = (ops.rows_gather(v0, route.idx) if v0 is not None and self.residual_v else None,
+                             ops.rows_gather(cos, route.idx), ops.rows_gather(sin, route.idx), Ls)
+                X = ops.rows_gather(X.view(B, L, D), route.idx).view(B * Ls, D)
+            v0_i, cos_i, sin_i, L_i = routed_in if r_first <= i <= r_last else (v0, cos, sin, L)
+            X, v, bs = self.blocks[i]._fwd(self.block_group(i), f"blocks.{i}.", X, ctx2d, cvec, v0_i, cos_i, sin_i, B, L_i, Lc,
                                            save and keep is None,
                                            (self._fp8_hist, i, self.fp8_attn, self.fp8_lin, q_ctx) if self.fp8 else None,
                                            mods[i] if mods is not None else None, keep=keep, kv_lens=kv_lens,
@@ -1906,11 +2142,16 @@ class DiT(nn.Module):
                                               if ring_call is None else {"cache": (cache.k[i], cache.v[i]) + ring_call}))
             if v0 is None:
                 v0 = v
+            if i == r_last:  # in place: nothing keeps the full buffer (block r_first kept its gathered input)
+                X = ops.rows_merge(X_full.view(B, L, D), X.view(B, L_i, D), route.inv).view(B * L, D)
+                X_full = None
             if save:
                 sv.blocks.append(bs)
             if fs is not None:
                 fs.post_forward_block(i)
         if save:
+            # (the backward and its recompute replay read v_0 / cos / sin at Ls rows: routed_in stays alive)
+            sv.route, sv.route_span, sv.routed_in = route, (r_first, r_last), routed_in
             sv.v0 = v0
             sv.x_last = X
             sv.batched_adaln = mods is not None
@@ -1976,20 +2217,52 @@ class DiT(nn.Module):
         # gathered weights before the deferred reduction reads them (resident and unsharded weights stay where they are)
         snap = sv.dv_terms is not None and fs is not None and fs.releases_params
         sv.lam_snap, sv.lam_used = (torch.empty(self.depth, dtype=bf16, device=dev) if snap else None), 0
+        # token routing: the blocks r_first .. r_last ran at Ls rows.  Their backward runs on a routed view of sv -- the
+        # gathered v_0 / cos / sin, its OWN list of deferred dv terms and its own dv0_started flag (the full-length terms
+        # pending in sv.dv_terms are of another length and stay pending across the span) -- and on an accumulator dv0_r of
+        # Ls rows.  The rows that skipped the span keep the gradient from behind it (dX_full); the routed rows take the
+        # span's input gradient.
+        route = getattr(sv, "route", None)
+        r_first, r_last = sv.route_span
+        rv = dX_full = dv0_r = None
         for i in reversed(range(self.depth)):
             if fs is not None:
                 fs.pre_backward_block(i)
             bs = sv.blocks[i]
+            routed = r_first <= i <= r_last
+            if i == r_last:
+                rv = _Saved()
+                rv.v0, rv.cos, rv.sin, Ls = sv.routed_in
+                rv.ctx2d, rv.cvec, rv.kv_lens = sv.ctx2d, sv.cvec, sv.kv_lens
+                rv.dv_terms = [] if sv.dv_terms is not None else None
+                rv.dv0_started = False
+                dv0_r = torch.zeros(B, H, Ls, hdp, dtype=f32, device=dev) if dv0 is not None else None
+                dX_full = dX
+                dX = ops.rows_gather(dX.view(B, L, D), route.idx).view(B * Ls, D)
+            sv_i, dv0_i, L_i = (rv, dv0_r, Ls) if routed else (sv, dv0, L)
             if sv.recompute:
                 # replay: the block's forward kernels once more, on its kept input and the same conditioning / RoPE rows /
-                # block-0 v (sv.v0 stays the v handed out in the first forward; block 0 makes its own copy again)
+                # block-0 v (sv.v0 stays the v handed out in the first forward; block 0 makes its own copy again); a routed
+                # block on the routed view's rows
                 _, _, bs = self.blocks[i]._fwd(self.block_group(i), f"blocks.{i}.", bs.X, sv.ctx2d, sv.cvec,
-                                               sv.v0 if i > 0 else None, sv.cos, sv.sin, B, L, Lc, True, None, bs.mod,
+                                               sv_i.v0 if i > 0 else None, sv_i.cos, sv_i.sin, B, L_i, Lc, True, None, bs.mod,
                                                replay=bs, kv_lens=sv.kv_lens, groups=groups, frames=sv.frames)
-            dX = self.blocks[i]._bwd(self.block_group(i), f"blocks.{i}.", bs, dX, sv, dc, dv0, B, L, Lc,
+            dX = self.blocks[i]._bwd(self.block_group(i), f"blocks.{i}.", bs, dX, sv_i, dc, dv0_i, B, L_i, Lc,
                                      i == 0, (self._fp8_hist, i, self.fp8_attn, self.fp8_lin, sv.q_ctx) if self.fp8 else None,
                                      dmods[i] if dmods is not None else None, groups=groups)
             sv.blocks[i] = bs = None
+            if i == r_first:
+                if dv0 is not None:
+                    if rv.dv_terms:  # what the span's last chunk left
+                        ops.dv0_reduce([t for t, _ in rv.dv_terms], [l for _, l in rv.dv_terms], dv0_r, B, H, Ls, hd, hdp,
+                                       accumulate=rv.dv0_started)
+                        rv.dv_terms.clear()
+                    ops.rows_scatter_add(dv0_r, dv0, route.idx)
+                    # dv0 now holds the span's share: the first full-length reduction behind it must ADD to it
+                    # (DiTBlock._bwd overwrites while sv.dv0_started is unset)
+                    sv.dv0_started = True
+                dX = ops.rows_merge(dX_full.view(B, L, D), dX.view(B, Ls, D), route.inv).view(B * L, D)
+                rv = dX_full = dv0_r = None
             if fs is not None:
                 fs.post_backward_block(i)
         if dmods is not None:  # adaLN weight / bias gradients of all blocks and their fan-in to dc: one launch each
@@ -2195,9 +2468,9 @@ class _DiTFunction(torch.autograd.Function):
     parameter gradients are written into the flat fp32 gradient buffers that p.grad aliases."""
 
     @staticmethod
-    def forward(ctx, model, x, context, timesteps, rope_start, kv_lens, reg_t, teacher, *params):
+    def forward(ctx, model, x, context, timesteps, rope_start, kv_lens, reg_t, teacher, route, *params):
         out, sv = model._forward_impl(x, context, timesteps, rope_start, save=True, kv_lens=kv_lens, reg_t=reg_t,
-                                      teacher=teacher)
+                                      teacher=teacher, route=route)
         ctx.model, ctx.sv = model, sv
         return out
 
@@ -2206,4 +2479,4 @@ class _DiTFunction(torch.autograd.Function):
         model, sv = ctx.model, ctx.sv
         ctx.sv = None
         model._backward_impl(sv, dout)
-        return (None,) * (8 + len([p for p in model.parameters() if p.requires_grad]))
+        return (None,) * (9 + len([p for p in model.parameters() if p.requires_grad]))

@@ -1081,6 +1081,118 @@ def head_rmsnorm_bwd(dy, y, rstd, H: int, hd: int) -> torch.Tensor:
     return dy
 
 
+# ------------------------------------------------------- row movers of token routing ----
+def _row_tensor(what: str, name: str, t, dtype=None):
+    """a [outer, n, row] operand of the row movers: a contiguous GPU tensor of at least 2 dims (the last is the row, the one
+    before counts the rows, the others multiply to `outer`) whose row is a whole number of 16-byte pieces"""
+    if not isinstance(t, torch.Tensor) or t.dim() < 2 or (dtype is not None and t.dtype != dtype):
+        got = (t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{what}: {name} must be a {'tensor' if dtype is None else dtype} of shape [..., rows, row], got "
+                         f"{got}")
+    if not t.is_cuda:
+        raise ValueError(f"{what}: {name} is on {t.device}; the kernels run on the GPU only -- pass {name}.cuda()")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: {name} {tuple(t.shape)} with strides {t.stride()} is not contiguous -- pass "
+                         f"{name}.contiguous()")
+    row_bytes = t.shape[-1] * t.element_size()
+    if row_bytes == 0 or row_bytes % 16 or t.data_ptr() % 16:
+        raise ValueError(f"{what}: a row of {name} is {row_bytes} bytes at address {t.data_ptr():#x}; rows move in 16-byte "
+                         "pieces -- pad the last dim to a multiple of 16 bytes and pass a 16-byte aligned tensor")
+    outer = 1
+    for s in t.shape[:-2]:
+        outer *= s
+    return outer, t.shape[-2], row_bytes
+
+
+def _row_table(what: str, name: str, t, n: int, like):
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous()
+            or t.device != like.device):
+        got = (t.dtype, tuple(t.shape), str(t.device)) if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{what}: {name} must be a contiguous int32 tensor of shape [{n}] on {like.device} (the kernel reads "
+                         f"it on the device), got {got} -- pass torch.as_tensor({name}, dtype=torch.int32).to(device)")
+
+
+def _row_pair(what: str, a_name: str, a, b_name: str, b):
+    """two row operands that differ in their row count only"""
+    if a.dtype != b.dtype or a.device != b.device or a.shape[:-2] != b.shape[:-2] or a.shape[-1] != b.shape[-1]:
+        raise ValueError(f"{what}: {a_name} {tuple(a.shape)} {a.dtype} on {a.device} and {b_name} {tuple(b.shape)} {b.dtype} "
+                         f"on {b.device} must agree in dtype, device and every dim but the row count (dim -2)")
+
+
+def rows_gather(src, idx, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[..., i, :] = src[..., idx[i], :] (vds_rows_gather): src [..., n_in, row] contiguous, any dtype whose row is a
+    multiple of 16 bytes; idx int32 [n_out] on src's device, duplicates allowed; an index outside [0, n_in) gives a row of
+    zeros.  Returns out [..., n_out, row] (allocated when not given; it must not overlap src)."""
+    what = "rows_gather"
+    outer, n_in, row_bytes = _row_tensor(what, "src", src)
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 1:
+        raise ValueError(f"{what}: idx must be a 1-D int32 tensor on {src.device}")
+    n_out = idx.shape[0]
+    _row_table(what, "idx", idx, n_out, src)
+    if n_in < 1:
+        raise ValueError(f"{what}: src {tuple(src.shape)} has no rows to gather from")
+    if out is None:
+        out = torch.empty(src.shape[:-2] + (n_out, src.shape[-1]), dtype=src.dtype, device=src.device)
+    elif n_out:
+        _row_tensor(what, "out", out)
+        _row_pair(what, "src", src, "out", out)
+        if out.shape[-2] != n_out:
+            raise ValueError(f"{what}: out has {out.shape[-2]} rows, idx {n_out} entries")
+    if n_out == 0 or outer == 0:
+        return out
+    check(_lib.load().vds_rows_gather(_p(src), _p(out), _p(idx), outer, n_in, n_out, row_bytes, _stream()),
+          f"vds_rows_gather(outer={outer},n_in={n_in},n_out={n_out},row_bytes={row_bytes})")
+    return out
+
+
+def rows_merge(full, part, inv, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[..., l, :] = part[..., inv[l], :] where 0 <= inv[l] < n_part, else full[..., l, :] (vds_rows_merge): full
+    [..., n_full, row] and part [..., n_part, row] contiguous with rows of a multiple of 16 bytes, inv int32 [n_full] on
+    their device.  out None: IN PLACE into full (returned); otherwise out gets every row and must not overlap part."""
+    what = "rows_merge"
+    outer, n_full, row_bytes = _row_tensor(what, "full", full)
+    _row_tensor(what, "part", part)
+    _row_pair(what, "full", full, "part", part)
+    _row_table(what, "inv", inv, n_full, full)
+    n_part = part.shape[-2]
+    if out is None:
+        out = full
+    else:
+        _row_tensor(what, "out", out)
+        if out.shape != full.shape or out.dtype != full.dtype or out.device != full.device:
+            raise ValueError(f"{what}: out {tuple(out.shape)} {out.dtype} must have full's shape {tuple(full.shape)}, dtype "
+                             "and device (out=None merges in place into full)")
+    if outer == 0 or n_full == 0:
+        return out
+    if n_part == 0:
+        if out is not full:
+            out.copy_(full)
+        return out
+    check(_lib.load().vds_rows_merge(_p(full), _p(part), _p(out), _p(inv), outer, n_full, n_part, row_bytes, _stream()),
+          f"vds_rows_merge(outer={outer},n_full={n_full},n_part={n_part},row_bytes={row_bytes})")
+    return out
+
+
+def rows_scatter_add(part, acc, idx) -> torch.Tensor:
+    """acc[..., idx[i], :] += part[..., i, :] in fp32, IN PLACE (vds_rows_scatter_add_f32): part [..., n_part, row] and acc
+    [..., n_full, row] contiguous float32 with rows of a multiple of 4 elements, idx int32 [n_part] on their device.  The
+    entries of idx must be DISTINCT (a plain read-add-write: a duplicate would lose an add); an index outside [0, n_full)
+    is skipped.  Returns acc."""
+    what = "rows_scatter_add"
+    outer, n_part, _ = _row_tensor(what, "part", part, f32)
+    _, n_full, _ = _row_tensor(what, "acc", acc, f32)
+    _row_pair(what, "part", part, "acc", acc)
+    _row_table(what, "idx", idx, n_part, part)
+    if outer == 0 or n_part == 0:
+        return acc
+    if n_full < 1:
+        raise ValueError(f"{what}: acc {tuple(acc.shape)} has no rows to add into")
+    check(_lib.load().vds_rows_scatter_add_f32(_p(part), _p(acc), _p(idx), outer, n_full, n_part, part.shape[-1],
+                                               _stream()),
+          f"vds_rows_scatter_add_f32(outer={outer},n_full={n_full},n_part={n_part},row_elems={part.shape[-1]})")
+    return acc
+
+
 def dv0_reduce(dvs, lams, out, B, H, L, hd, hdp, accumulate: bool = False):
     """out[B,H,L,hdp] f32 (+)= sum_i (1 - lam_i) dvs[i][..., :hd]: the residual-V gradient of v_0 from all mixed blocks in one
     pass (vds_dv0_reduce; the blocks' RoPE backward then runs with mix = 2)"""

@@ -173,8 +173,10 @@ def time_shift_from_normal(z: torch.Tensor) -> torch.Tensor:
 
 def forward(dit_model, batch, text_encoder, tokenizer, device, global_step, master_process, generator=None,
             binnings=None, batch_size=None, return_index=-1, rope_start=None, frame_mode=None, cond_prob=0.5,
-            frame_timesteps=None, frame_weights=None):
+            frame_timesteps=None, frame_weights=None, route=None):
     """frame_mode=None (default): one noise level per sample, the reference's step.
+    route: passed to DiT.forward (a model with enable_token_routing routes itself in training mode; this pins the subset
+    or, with False, runs the full model).
     frame_mode="first_frame": one level per sample, and with probability cond_prob token-frame 0 stays clean (t = 0) and
     leaves the loss (image-to-video); "independent": one level per token-frame (diffusion forcing); "chunk": one level
     per chunk of the model's frame_chunk token-frames (what a chunk-at-a-time rollout meets), weights 1.
@@ -205,6 +207,8 @@ def forward(dit_model, batch, text_encoder, tokenizer, device, global_step, mast
             context_lens = torch.where(do_zero_out, torch.zeros((), dtype=torch.int32, device=device), context_lens)
     B = vae_latent.size(0)
     kw = {} if context_lens is None else {"context_lens": context_lens}
+    if route is not None:
+        kw["route"] = route
     if frame_mode is not None or frame_timesteps is not None or frame_weights is not None:
         # per-frame path.  Draw order: levels, noise, conditioning -- "first_frame" consumes the generator exactly as the
         # per-sample path does for its first two draws
@@ -279,10 +283,12 @@ def get_schedule(optimizer, lr_scheduler_type: str = "cosine", num_warmup_steps:
 
 
 def train_step(dit_model, optimizer, lr_scheduler, batch, device, generator=None, rope_start=None, frame_mode=None,
-               cond_prob=0.5):
+               cond_prob=0.5, route=None):
     """train.py:412-434 for one batch with a pre-encoded context; returns the loss tensor.  frame_mode / cond_prob: the
-    per-frame timestep modes of `forward`."""
+    per-frame timestep modes of `forward`; route: its token-routing override."""
     fkw = {} if frame_mode is None else {"frame_mode": frame_mode, "cond_prob": cond_prob}
+    if route is not None:
+        fkw["route"] = route
     total_loss, _ = forward(dit_model, batch, None, None, device, 0, False, generator=generator,
                             rope_start=rope_start, **fkw)
     optimizer.zero_grad()
